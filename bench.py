@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""bench.py -- k-mers/s through hetmers (k=31) on N MI355X GPUs, with roofline + CPU baseline.
+"""bench.py -- k-mers/s through hetmers (k=31) on N MI355X GPUs; with --full also roofline, parity and CPU baseline.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N>1 it is launched under
-torch.distributed.run with one rank per GPU (RCCL).  Rank 0 prints ONE JSON line.
+torch.distributed.run with one rank per GPU (RCCL).  Rank 0 prints ONE JSON line.  Such a plain run does only what the
+headline figure needs: it generates the table, warms up, times the K steps, writes the plot of the last step if
+--dump-outputs DIR is given (DIR/plot.npy, float64) and prints the line (value, ms_per_step, ...).
 
 A "step" = one complete hetmers computation (pass 1 with the symmetry proof -> complement look-ups /
 exchange -> pass 2 -> histogram reduction) over the whole device-resident table.  The table is handed
@@ -13,8 +15,9 @@ Workload at N=1 is BASELINE.json configs[2]: "Synthetic diploid 1 Gbp, 50x cov, 
 hexaploid k=51 (configs[4]) stand-ins (stated in config.workload).
 N>1: STRONG scaling -- the same table, prefix-sharded across the ranks (every rank generates its own shard, none holds
 the whole table); one all_to_all of the complement requests and one all_reduce of the 2-D histogram per step.
-After the timed loop the plot of the last step is rendered as .smu text and compared with the REFERENCE binary's output
-for this very table (tests/golden/bench_<workload>.smu; "parity" in the JSON line); a mismatch exits non-zero.
+With --full, after the timed loop the plot of the last step is rendered as .smu text and compared with the REFERENCE binary's
+output for this very table (tests/golden/bench_<workload>.smu; "parity" in the JSON line); a mismatch exits non-zero.  The
+roofline of the dominant kernel ("roofline") is priced on the HIP events the engine recorded during the timed steps.
 Then, still outside the timed region, the END-TO-END comparison of SURVEY.md section 8d (ii) / BASELINE.md section 3 is run in
 this very process ("e2e" in the JSON line): a ~1e9-entry table of the bench's own generator is written as FastK files, the
 drop-in executable (smudgeplot_amd/bin/hetmers) and the reference binary (oracle/_ref/hetmers_ref) run on those IDENTICAL files,
@@ -91,14 +94,16 @@ def make_table(workload: str, G: int, k: int, dev, seed: int = 1, key_range=None
     return keys, cnt, L, desc
 
 
-def make_shard(workload: str, G: int, k: int, dev, rank: int, world: int, with_index: bool = True, group=None):
+def make_shard(workload: str, G: int, k: int, dev, rank: int, world: int, with_index: bool = True, group=None,
+               with_hash: bool = True):
     """This rank's prefix shard of a bench table and what the sharded run needs to know about the whole of it -- collective when
     world > 1 (any backend: the CPU test-suite runs it under gloo).  Every rank GENERATES its own shard (synth_device
     key_range_of: equal slices of the key space, cut on window-block boundaries), so no rank ever holds the table.
     -> dict: keys, counts, L, desc, sizes (entries of every rank), n_total, first_entry (number of this shard's first entry in
     the whole table), index (the WHOLE table's FastK prefix index, int64[2^24]: bucket counts summed over the ranks -- what the
     stub of a .ktab carries, libfastk.c:841 -- or None), splitters (the cut values: lower bound of the k-mer range of ranks 1 ..
-    world-1, W words each; None for one rank), hk / hc (synth_device.table_hash of the whole table: the shards' sums)."""
+    world-1, W words each; None for one rank), hk / hc (synth_device.table_hash of the whole table: the shards' sums; None
+    with with_hash=False -- only the parity block of --full needs them)."""
     words = (k + 31) // 32
     key_range = synth_device.key_range_of(rank, world) if world > 1 else None
     keys, cnt, L, desc = make_table(workload, G, k, dev, key_range=key_range)
@@ -128,8 +133,10 @@ def make_shard(workload: str, G: int, k: int, dev, rank: int, world: int, with_i
             splitters[r - 1, 0] = np.uint64(synth_device.key_range_of(r, world)[0]) << np.uint64(48)
         splitters = splitters.reshape(-1)
     # checksum of the table (summed over the ranks): what the golden .smu of the parity block was made on
-    hk, hc = synth_device.table_hash(keys, cnt, first_entry=first_entry)
-    if world > 1:
+    hk = hc = None
+    if with_hash:
+        hk, hc = synth_device.table_hash(keys, cnt, first_entry=first_entry)
+    if with_hash and world > 1:
         hv = torch.tensor([hk - (1 << 64) if hk >> 63 else hk, hc - (1 << 64) if hc >> 63 else hc], dtype=torch.int64, device=dev)
         dist.all_reduce(hv, op=dist.ReduceOp.SUM, group=group)
         hk, hc = [int(v) & 0xFFFFFFFFFFFFFFFF for v in hv.cpu().tolist()]
@@ -263,84 +270,17 @@ def end_to_end(workload: str, G: int, k: int, dev, runs: int = 2):
     return e2e, cpu
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--genome", type=float, default=0, help="haploid genome size in bases (default: the workload's, 1e9 for uniform)")
-    ap.add_argument("--k", type=int, default=0, help="default 31 (hexaploid: 51)")
-    ap.add_argument("--symcheck", default="hash", choices=["exact", "hash"])
-    ap.add_argument("--e2e-genome", type=float, default=0, help="genome size of the end-to-end / CPU-baseline table (default: "
-                                                                "4e8 bp = 1.01e9 entries for the diploid workloads)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the end-to-end comparison with the reference binary (e2e, cpu_baseline)")
-    ap.add_argument("--no-index", action="store_true", help="do not hand the table's prefix index to the engine (pass 1 builds "
-                                                            "a directory of its own, as in rounds 1-3)")
-    ap.add_argument("--workload", default="uniform", choices=list(WORKLOADS),
-                    help="uniform: BASELINE configs[2] (uniform random genome); repeats: 5 %% of the genome are dispersed / "
-                         "tandem repeats and homopolymer runs (exercises kf_bigfix and the repeat tail of the plot); "
-                         "octoploid: stand-in for configs[3] (8 graded haplotypes, k=31); hexaploid: for configs[4] (6, k=51)")
-    args = ap.parse_args()
-    if not args.k:
-        args.k = default_k(args.workload)
-    if not args.genome:
-        args.genome = default_genome(args.workload, args.k)
+def dump_outputs(d: str, plot) -> None:
+    """--dump-outputs DIR: what the timed path hands its caller, from the last timed step -- the 2-D histogram of
+    (covB + covA, covB) pair counts, int64[1001, 501] on the device -- as DIR/plot.npy in float64 (exact: every cell is
+    below 2^53; 4 MB).  The table is generated from a fixed seed, so the same arguments give the same inputs on every run."""
+    os.makedirs(d, exist_ok=True)
+    a = plot.reshape(engine.PLOT_ROWS, engine.PLOT_COLS).cpu().numpy().astype(np.float64)
+    np.save(os.path.join(d, "plot.npy"), a)
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the engine has no CPU fallback")
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    force = os.environ.get("SMG_FORCE_EXCHANGE") == "1"     # diagnostics: the N > 1 protocol in a one-rank group
-    if world > 1 or force:
-        if force and "MASTER_ADDR" not in os.environ:
-            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29517", RANK="0", WORLD_SIZE="1")
-        dist.init_process_group("nccl", device_id=dev)
 
-    # ---- workload: every rank generates ITS prefix shard only (the generators cut the key space; no rank holds the table)
-    G = int(args.genome)
-    sh = make_shard(args.workload, G, args.k, dev, rank, world, with_index=not args.no_index)
-    keys, cnt, L, desc = sh["keys"], sh["counts"], sh["L"], sh["desc"]
-    n_local, n_total, sizes, first_entry = cnt.numel(), sh["n_total"], sh["sizes"], sh["first_entry"]
-    index, splitters, hk, hc = sh["index"], sh["splitters"], sh["hk"], sh["hc"]
-    del sh
-    keys = keys.reshape(-1)
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-    eng_stats = []
-    eng = sharded.TorchEngine(dev)        # device buffers are allocated once and reused by every step
-    eng.bind(args.k, keys, cnt, index=index, first_entry=first_entry)       # the table is handed over once, like a file is read once
-    del index
-
-    def step():
-        plot, st = sharded.hetmers_sharded(args.k, keys, cnt, symcheck=args.symcheck, eng=eng, prebound=True,
-                                           splitters=splitters, sizes=sizes if world > 1 else None)
-        st.pop("engine", None)
-        eng_stats.append(st)
-        return plot
-
-    for _ in range(args.warmup):
-        step()
-    eng_stats.clear()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        plot = step()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([dt], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
-
-    # ---- roofline of the dominant kernel, from HIP events recorded by the engine on its stream
+def roofline(args, eng_stats, n_local: int, n_total: int, dt: float, world: int, force: bool) -> dict:
+    """roofline of the dominant kernel, from HIP events recorded by the engine on its stream during the timed steps (--full)"""
     ms = {key: float(np.mean([s[key] for s in eng_stats])) for key in ("ms_pass1", "ms_rclookup", "ms_pass2")}
     nreq = float(np.mean([s.get("nemitted", s["nrequests"]) for s in eng_stats]))   # requests pass 1 emitted
     nkept = float(np.mean([s["nrequests"] for s in eng_stats]))                     # ... and the filter kept
@@ -381,20 +321,110 @@ def main():
             else:
                 traffic_src = "stale: profiles/hbm_traffic.json was measured on code object %s, this library carries %s" % (
                     t.get("code_object_sha256_16"), lib_hash())
+    return {"bound": "hbm", "kernel": single[dom],
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": alg[dom], "kernel_ms": ms,
+            # ms_pass1 brackets kf_pass1_d AND the two short launches behind it (kf_collect, kf_bigfix =
+            # "ms_bigfix" below); `achieved` is priced on the whole bracket, the kernel alone is:
+            "pass1_kernel_alone_ms": ms["ms_pass1"] - float(np.mean([s.get("ms_bigfix", 0.0) for s in eng_stats])),
+            "requests": {"emitted": nreq, "kept_by_filter": nkept, "ms_partition": ms_filter},
+            "deferred_entries": {"count": float(np.mean([s.get("nbig", 0) for s in eng_stats])),
+                                 "ms_bigfix": float(np.mean([s.get("ms_bigfix", 0.0) for s in eng_stats]))},
+            "lookup_phase_GBps": alg["ms_rclookup"] / (ms["ms_rclookup"] * 1e-3) / 1e9
+            if ms["ms_rclookup"] > 0 else 0.0,
+            # whole job against B_alg(k) = 2 x (ceil(k/4) + 2) + 2 bytes per k-mer (22 at k = 31, 32 at k = 51)
+            "whole_job_frac_of_the_B_alg_roofline":
+                (n_total * 2.0 * alg_bytes_per_kmer_pass(args.k) / (dt / args.steps)) / 1e9 / (HBM_PEAK_GBS * world)}
 
-    e2e_failure = None
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--genome", type=float, default=0, help="haploid genome size in bases (default: the workload's, 1e9 for uniform)")
+    ap.add_argument("--k", type=int, default=0, help="default 31 (hexaploid: 51)")
+    ap.add_argument("--symcheck", default="hash", choices=["exact", "hash"])
+    ap.add_argument("--e2e-genome", type=float, default=0, help="genome size of the end-to-end / CPU-baseline table (default: "
+                                                                "4e8 bp = 1.01e9 entries for the diploid workloads)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the "
+                                                        "roofline of the dominant kernel, the parity of the last plot against the "
+                                                        "reference binary's golden, the end-to-end comparison and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the plot of the last timed step to DIR/plot.npy "
+                                                                         "(float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the end-to-end comparison with the reference binary "
+                                                          "(e2e, cpu_baseline)")
+    ap.add_argument("--no-index", action="store_true", help="do not hand the table's prefix index to the engine (pass 1 builds "
+                                                            "a directory of its own, as in rounds 1-3)")
+    ap.add_argument("--workload", default="uniform", choices=list(WORKLOADS),
+                    help="uniform: BASELINE configs[2] (uniform random genome); repeats: 5 %% of the genome are dispersed / "
+                         "tandem repeats and homopolymer runs (exercises kf_bigfix and the repeat tail of the plot); "
+                         "octoploid: stand-in for configs[3] (8 graded haplotypes, k=31); hexaploid: for configs[4] (6, k=51)")
+    args = ap.parse_args()
+    if not args.k:
+        args.k = default_k(args.workload)
+    if not args.genome:
+        args.genome = default_genome(args.workload, args.k)
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: the engine has no CPU fallback")
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    force = os.environ.get("SMG_FORCE_EXCHANGE") == "1"     # diagnostics: the N > 1 protocol in a one-rank group
+    if world > 1 or force:
+        if force and "MASTER_ADDR" not in os.environ:
+            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29517", RANK="0", WORLD_SIZE="1")
+        dist.init_process_group("nccl", device_id=dev)
+
+    # ---- workload: every rank generates ITS prefix shard only (the generators cut the key space; no rank holds the table)
+    G = int(args.genome)
+    sh = make_shard(args.workload, G, args.k, dev, rank, world, with_index=not args.no_index, with_hash=args.full)
+    keys, cnt, L, desc = sh["keys"], sh["counts"], sh["L"], sh["desc"]
+    n_local, n_total, sizes, first_entry = cnt.numel(), sh["n_total"], sh["sizes"], sh["first_entry"]
+    index, splitters, hk, hc = sh["index"], sh["splitters"], sh["hk"], sh["hc"]
+    del sh
+    keys = keys.reshape(-1)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+    eng_stats = []
+    eng = sharded.TorchEngine(dev)        # device buffers are allocated once and reused by every step
+    eng.bind(args.k, keys, cnt, index=index, first_entry=first_entry)       # the table is handed over once, like a file is read once
+    del index
+
+    def step():
+        plot, st = sharded.hetmers_sharded(args.k, keys, cnt, symcheck=args.symcheck, eng=eng, prebound=True,
+                                           splitters=splitters, sizes=sizes if world > 1 else None)
+        st.pop("engine", None)
+        eng_stats.append(st)
+        return plot
+
+    for _ in range(args.warmup):
+        step()
+    eng_stats.clear()
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        plot = step()
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    dt = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([dt], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+
+    e2e_failure = parity = e2e = None
     if rank == 0:
-        parity = parity_against_golden(args.workload, G, args.k, n_total, hk, hc, plot)
-        # the end-to-end comparison and the CPU baseline: rank 0 of the single-GPU run only (the reference takes about a minute)
-        cpu = e2e = None
-        if not (args.no_cpu or world > 1):
-            try:
-                e2e, cpu = end_to_end(args.workload, int(args.e2e_genome) if args.e2e_genome else e2e_genome(args.workload, G), args.k, dev)
-            except SystemExit as ex:
-                # (a missing reference binary or a failing program: the line of the timed region is still printed -- with the
-                #  error in place of the block -- and the process then FAILS with the message: loud, but no measurement is lost)
-                e2e_failure = str(ex)
-                e2e = {"error": e2e_failure, "smu_identical": None}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, plot)
         value = n_total * args.steps / dt
         out = {
             "metric": "k-mers/sec through hetmers (k=%d)" % args.k,
@@ -405,29 +435,26 @@ def main():
                        "symcheck": args.symcheck, "sharding": f"prefix x{world}",
                        "directory": "pass 1 builds its own" if args.no_index else
                                     "the table's FastK prefix index (2^24 buckets, generated with the table as a .ktab stub carries it)"},
-            "roofline": {"bound": "hbm", "kernel": single[dom],
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": alg[dom], "kernel_ms": ms,
-                         # ms_pass1 brackets kf_pass1_d AND the two short launches behind it (kf_collect, kf_bigfix =
-                         # "ms_bigfix" below); `achieved` is priced on the whole bracket, the kernel alone is:
-                         "pass1_kernel_alone_ms": ms["ms_pass1"] - float(np.mean([s.get("ms_bigfix", 0.0) for s in eng_stats])),
-                         "requests": {"emitted": nreq, "kept_by_filter": nkept, "ms_partition": ms_filter},
-                         "deferred_entries": {"count": float(np.mean([s.get("nbig", 0) for s in eng_stats])),
-                                              "ms_bigfix": float(np.mean([s.get("ms_bigfix", 0.0) for s in eng_stats]))},
-                         "lookup_phase_GBps": alg["ms_rclookup"] / (ms["ms_rclookup"] * 1e-3) / 1e9
-                         if ms["ms_rclookup"] > 0 else 0.0,
-                         # whole job against B_alg(k) = 2 x (ceil(k/4) + 2) + 2 bytes per k-mer (22 at k = 31, 32 at k = 51)
-                         "whole_job_frac_of_the_B_alg_roofline":
-                             (n_total * 2.0 * alg_bytes_per_kmer_pass(args.k) / (dt / args.steps)) / 1e9 / (HBM_PEAK_GBS * world)},
-            "cpu_baseline": cpu,
-            # process start -> .smu closed on identical table files: the drop-in executable next to the reference binary
-            "e2e": e2e,
-            # the plot of the last TIMED step against the reference binary's .smu of this very table (outside the timed region)
-            "parity": parity,
             "pairs_in_plot": int(plot.sum().item()),
             "hbm_peak_allocated_by_torch_GB": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),     # (the generator's peak)
         }
+        if args.full:
+            # the end-to-end comparison and the CPU baseline: rank 0 of the single-GPU run only (the reference takes about a minute)
+            cpu = None
+            if not (args.no_cpu or world > 1):
+                try:
+                    e2e, cpu = end_to_end(args.workload, int(args.e2e_genome) if args.e2e_genome else e2e_genome(args.workload, G), args.k, dev)
+                except SystemExit as ex:
+                    # (a missing reference binary or a failing program: the line of the timed region is still printed -- with the
+                    #  error in place of the block -- and the process then FAILS with the message: loud, but no measurement is lost)
+                    e2e_failure = str(ex)
+                    e2e = {"error": e2e_failure, "smu_identical": None}
+            out["roofline"] = roofline(args, eng_stats, n_local, n_total, dt, world, force)
+            out["cpu_baseline"] = cpu
+            # process start -> .smu closed on identical table files: the drop-in executable next to the reference binary
+            out["e2e"] = e2e
+            # the plot of the last TIMED step against the reference binary's .smu of this very table (outside the timed region)
+            parity = out["parity"] = parity_against_golden(args.workload, G, args.k, n_total, hk, hc, plot)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -435,7 +462,7 @@ def main():
         raise SystemExit(e2e_failure)
     if rank == 0 and e2e is not None and not e2e["smu_identical"]:
         raise SystemExit("bench.py: the drop-in executable's .smu differs from the reference binary's on the end-to-end table")
-    if rank == 0 and parity["ok"] is False:
+    if rank == 0 and parity is not None and parity["ok"] is False:
         raise SystemExit("bench.py: the plot of the timed run differs from the reference binary's .smu of this table (%s)"
                          % parity.get("golden"))
 

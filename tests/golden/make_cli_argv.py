@@ -36,6 +36,10 @@ CASES = {
     "hetmers_tmp": ["smudgeplot", "hetmers", "-L", "4", "-o", "OUT", "-tmp", "TMPDIR", "TABLE"],
     "extract_default": ["smudgeplot", "extract", "-o", "OUT", "TABLE.ktab", "SMA.sma"],
     "extract_verbose": ["smudgeplot", "extract", "-o", "OUT", "-t", "8", "--verbose", "TABLE.ktab", "SMA.sma"],
+    # the literal command lines of tests/test_reference_cli.py's runs through the command line
+    "hetmers_pairs_t3_verbose": ["smudgeplot", "hetmers", "-L", "5", "-t", "3", "-o", "pairs", "--verbose", "t.ktab"],
+    "extract_missing_table": ["smudgeplot", "extract", "-o", "x", "missing.ktab", "smudges.sma"],
+    "hetmers_missing_table": ["smudgeplot", "hetmers", "-L", "4", "missing_table"],
 }
 out = {}
 for name, argv in CASES.items():

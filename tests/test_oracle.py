@@ -1,6 +1,8 @@
 """CPU tests: the oracle (C restatement + numpy restatement) against the committed golden
-vectors produced by the reference binary, and -- where the compiled reference is present --
-against the reference itself on fresh random tables."""
+vectors produced by the reference binary, also on fresh random tables (and there -- where the
+compiled reference is present -- against the reference itself)."""
+import hashlib
+import json
 import os
 import subprocess
 
@@ -8,7 +10,7 @@ import numpy as np
 import pytest
 
 import brute
-from conftest import ORACLE_BIN, REF_BIN, golden_names, load_golden
+from conftest import GOLDEN, ORACLE_BIN, REF_BIN, golden_names, load_golden
 from smudgeplot_amd import ktab, synth
 
 
@@ -57,19 +59,25 @@ def test_examine_decisions(tmp_path):
     assert out.strip() == "trim=1 symm=0"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BIN), reason="compiled reference not present")
 @pytest.mark.parametrize("k,ibyte,nparts,L,T,seed", [
     (31, 1, 1, 5, 1, 101), (31, 2, 3, 5, 8, 102), (25, 1, 2, 4, 4, 103), (48, 2, 2, 4, 5, 104),
     (72, 1, 1, 4, 2, 105),
 ])
 def test_reference_live(k, ibyte, nparts, L, T, seed, tmp_path):
-    """three-way on fresh tables: reference binary == C oracle == numpy oracle"""
+    """three-way on fresh tables: reference binary == C oracle == numpy oracle.  The reference's .smu of each table is
+    stored in tests/golden/reference_live.json (tests/golden/make_golden_reference_live.py) together with the table's
+    checksum; where the compiled reference is present it is run live as well and must still write that .smu."""
     packed, cnt = synth.adversarial_table(k, 2000, L, seed, low_complexity=120, dense=2)
+    g = json.load(open(os.path.join(GOLDEN, "reference_live.json")))["k%d_i%d_p%d_L%d_T%d_s%d" % (k, ibyte, nparts, L, T, seed)]
+    assert hashlib.sha256(packed.tobytes() + cnt.astype("<u2").tobytes()).hexdigest() == g["table_sha256"], \
+        "the generator made another table than the one the reference's .smu was recorded for"
     ktab.write_ktab(str(tmp_path / "t"), k, packed, cnt, ibyte=ibyte, nparts=nparts)
-    r = subprocess.run([REF_BIN, f"-e{L}", f"-T{T}", "-oref", "t.ktab"], cwd=tmp_path,
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    ref = open(tmp_path / "ref.smu").read()
+    ref = g["smu"]
+    if os.path.exists(REF_BIN):
+        r = subprocess.run([REF_BIN, f"-e{L}", f"-T{T}", "-oref", "t.ktab"], cwd=tmp_path,
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        assert open(tmp_path / "ref.smu").read() == ref
     subprocess.run([ORACLE_BIN, f"-e{L}", f"-o{tmp_path}/orc", str(tmp_path / "t")], check=True)
     assert open(tmp_path / "orc.smu").read() == ref
     assert brute.smu_text(brute.hetmers_plot(packed, cnt, k)) == ref

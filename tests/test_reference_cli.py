@@ -1,14 +1,16 @@
 """The drop-in boundary, pinned by the REFERENCE's own command line (src/smudgeplot/cli.py:18-72, 348-382).
 
-* In the build container (/root/reference present, no GPU): the reference's `smudgeplot hetmers` / `extract` are run
-  as they are, with smudgeplot_amd/bin first on PATH.  They must find OUR executables, hand them their argument
-  vectors, and surface our exit status the way they surface the reference binary's: the run gets as far as the
-  engine's "no HIP device" (there is no CPU fallback) after the reference's own messages.
-* On the GPU box (/root/reference absent): tests/golden/cli_argv.json holds the argument vectors the reference
-  command line produced (tests/golden/make_cli_argv.py); they are replayed against the drop-in executables and the
-  `.smu` / smudge files are compared with the golden vectors made by the reference binaries."""
+tests/golden/cli_argv.json holds the argument vectors the reference command line hands its executables, recorded from the
+reference's own code (tests/golden/make_cli_argv.py), for the documented grammar and for the literal command lines below.
+* On a machine without a GPU: the command line (smudgeplot_amd/cli.py, which resolves and runs the executables the way
+  the reference's get_binary_path / run_binary do) is run with smudgeplot_amd/bin first on PATH.  It must call OUR
+  executables with exactly the reference's argument vectors, and surface our exit status the way the reference surfaces
+  its binary's: the run gets as far as the engine's "no HIP device" (there is no CPU fallback).
+* On the GPU: the recorded argument vectors are replayed against the drop-in executables and the `.smu` / smudge files
+  are compared with the golden vectors made by the reference binaries."""
 import json
 import os
+import shlex
 import subprocess
 import sys
 
@@ -17,32 +19,31 @@ import pytest
 from conftest import GOLDEN, ROOT, load_golden
 from smudgeplot_amd import ktab
 
-REF_SRC = "/root/reference/src"
 BIN = os.path.join(ROOT, "smudgeplot_amd", "bin")
 ARGV = json.load(open(os.path.join(GOLDEN, "cli_argv.json")))
 
-RUN_REF_CLI = """
-import importlib.metadata, sys
-importlib.metadata.version = lambda name: "0.5.4"
-sys.path.insert(0, %r)
-import smudgeplot.cli as cli
-cli.version = lambda name: "0.5.4"
-sys.argv = ["smudgeplot"] + sys.argv[1:]
-cli.main()
-""" % REF_SRC
+
+def _cli(case, cwd):
+    """the recorded reference command line `case` through the drop-in's command line, the executables first on PATH"""
+    env = dict(os.environ, PATH=BIN + os.pathsep + os.environ.get("PATH", ""), PYTHONPATH=ROOT, MPLBACKEND="Agg")
+    return subprocess.run([sys.executable, "-m", "smudgeplot_amd", *ARGV[case]["cli"]], cwd=cwd, capture_output=True, text=True,
+                          env=env)
 
 
-def _ref_cli(args, cwd):
-    env = dict(os.environ, PATH=BIN + os.pathsep + os.environ.get("PATH", ""), MPLBACKEND="Agg")
-    return subprocess.run([sys.executable, "-c", RUN_REF_CLI, *args], cwd=cwd, capture_output=True, text=True, env=env)
+def _calling(case):
+    """the line the reference's run_binary writes for the recorded argument vector of `case`, our executable resolved"""
+    ex = ARGV[case]["exec"]
+    return "Calling: " + shlex.join([os.path.join(BIN, ex[0])] + ex[1:]) + "\n"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference tree is only present in the build container")
 def test_reference_cli_execs_the_drop_in_hetmers(tmp_path):
     g = load_golden("k31_i1")
+    case = "hetmers_pairs_t3_verbose"
+    assert ARGV[case]["cli"] == ["hetmers", "-L", str(g["L"]), "-t", "3", "-o", "pairs", "--verbose", "t.ktab"]
     ktab.write_ktab(str(tmp_path / "t"), g["k"], g["packed"], g["counts"], ibyte=1, nparts=2)
-    r = _ref_cli(["hetmers", "-L", str(g["L"]), "-t", "3", "-o", "pairs", "--verbose", "t.ktab"], tmp_path)
-    assert f"Calling: {BIN}/hetmers -opairs -e{g['L']} -T3 -v t.ktab" in r.stderr, r.stderr
+    r = _cli(case, tmp_path)
+    assert f"Calling: {BIN}/hetmers -opairs -e{g['L']} -T3 -v t.ktab\n" == _calling(case)
+    assert _calling(case) in r.stderr, r.stderr
     assert "  The input table is trimmed and symmetric\n" in r.stderr          # our executable ran, and read the table
     from smudgeplot_amd import engine
     if engine.device_count() == 0:
@@ -55,12 +56,13 @@ def test_reference_cli_execs_the_drop_in_hetmers(tmp_path):
         assert (tmp_path / "pairs.smu").read_text() == g["smu"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SRC), reason="the reference tree is only present in the build container")
 def test_reference_cli_execs_the_drop_in_extract_and_reports_its_errors(tmp_path):
-    r = _ref_cli(["extract", "-o", "x", "missing.ktab", "smudges.sma"], tmp_path)
-    assert f"Calling: {BIN}/extract_kmer_pairs -ox -T4 missing.ktab smudges" in r.stderr, r.stderr
+    r = _cli("extract_missing_table", tmp_path)
+    assert f"Calling: {BIN}/extract_kmer_pairs -ox -T4 missing.ktab smudges\n" == _calling("extract_missing_table")
+    assert _calling("extract_missing_table") in r.stderr, r.stderr
     assert r.returncode != 0 and "CalledProcessError" in r.stderr
-    r = _ref_cli(["hetmers", "-L", "4", "missing_table"], tmp_path)
+    r = _cli("hetmers_missing_table", tmp_path)
+    assert _calling("hetmers_missing_table") in r.stderr, r.stderr
     assert "hetmers: Cannot open k-mer table missing_table" in r.stderr         # the reference's message, PloidyPlot.c:1351-1354
     assert r.returncode != 0
 

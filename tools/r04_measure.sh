@@ -6,9 +6,9 @@ J=$O/hbm_traffic.json; cp profiles/hbm_traffic.json $J 2>/dev/null
 line() { grep '^{' $1 | python -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(sys.argv[1], "ms/step %.3f" % d["ms_per_step"], {k: round(v,3) for k,v in r["kernel_ms"].items()}, "p1alone %.3f" % r["pass1_kernel_alone_ms"], "frac %.3f" % r["frac"], "traffic", r["traffic"], "cpu", (d.get("cpu_baseline") or {}).get("value"))' $2; }
 prof() {   # prof <tag> <traffic-key> <bench args...>: bench line (with the CPU baseline), kernel stats, PMC passes c + d, traffic entry
   tag=$1; key=$2; shift 2
-  ( timeout 600 python bench.py "$@" ) > $O/bench_$tag.log 2>&1; line $O/bench_$tag.log $tag
+  ( timeout 600 python bench.py --full "$@" ) > $O/bench_$tag.log 2>&1; line $O/bench_$tag.log $tag
   n=$(grep '^{' $O/bench_$tag.log | python -c 'import sys,json,re; d=json.loads(sys.stdin.read()); print(re.search(r": (\d+) table entries", d["config"]["workload"]).group(1))')
-  B="python $R/bench.py --steps 3 --warmup 1 --no-cpu $*"
+  B="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu $*"
   ( cd /tmp && export TMPDIR=/tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$tag -o r04 -- $B > $O/stats_$tag.log 2>&1
     timeout 400 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_${tag}_c -o r04 -- $B > $O/pmc_${tag}_c.log 2>&1
     timeout 400 rocprofv3 --pmc WRITE_SIZE SQ_INSTS_VALU SQ_INSTS_SALU --output-format csv -d $O/pmc_${tag}_d -o r04 -- $B > $O/pmc_${tag}_d.log 2>&1 )
@@ -19,26 +19,26 @@ prof() {   # prof <tag> <traffic-key> <bench args...>: bench line (with the CPU 
 for part in $PARTS; do case $part in
 default)
   prof default k31
-  B="python $R/bench.py --steps 3 --warmup 1 --no-cpu"
+  B="python $R/bench.py --full --steps 3 --warmup 1 --no-cpu"
   ( cd /tmp && export TMPDIR=/tmp
     timeout 300 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $O/pmc_default_a -o r04 -- $B > $O/pmc_default_a.log 2>&1
     timeout 300 rocprofv3 --pmc SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d $O/pmc_default_b -o r04 -- $B > $O/pmc_default_b.log 2>&1 )
   for d in pmc_default_a pmc_default_b; do python tools/pmc_summary.py $O/$d > $O/$d.txt 2>&1; find $O/$d -name '*counter_collection.csv' -delete; done
-  ( timeout 300 python bench.py --no-cpu --no-index ) > $O/bench_default_noindex.log 2>&1; line $O/bench_default_noindex.log default_noindex
-  ( SMG_NO_SPEC=1 timeout 300 python bench.py --no-cpu ) > $O/bench_default_nospec.log 2>&1; line $O/bench_default_nospec.log default_nospec ;;
+  ( timeout 300 python bench.py --full --no-cpu --no-index ) > $O/bench_default_noindex.log 2>&1; line $O/bench_default_noindex.log default_noindex
+  ( SMG_NO_SPEC=1 timeout 300 python bench.py --full --no-cpu ) > $O/bench_default_nospec.log 2>&1; line $O/bench_default_nospec.log default_nospec ;;
 repeats) prof repeats k31_repeats --workload repeats ;;
 k51)     prof k51 k51 --k 51 --genome 5e8 ;;
 oct)     prof octoploid k31_octoploid --workload octoploid ;;
 hex)     prof hexaploid k51_hexaploid --workload hexaploid ;;
-k30)     ( timeout 300 python bench.py --k 30 --no-cpu ) > $O/bench_k30.log 2>&1; line $O/bench_k30.log k30 ;;
-k51big)  ( timeout 900 python bench.py --k 51 --genome 1e9 --no-cpu --steps 5 --warmup 1 ) > $O/bench_k51_G1e9.log 2>&1; line $O/bench_k51_G1e9.log k51_G1e9 ;;
+k30)     ( timeout 300 python bench.py --full --k 30 --no-cpu ) > $O/bench_k30.log 2>&1; line $O/bench_k30.log k30 ;;
+k51big)  ( timeout 900 python bench.py --full --k 51 --genome 1e9 --no-cpu --steps 5 --warmup 1 ) > $O/bench_k51_G1e9.log 2>&1; line $O/bench_k51_G1e9.log k51_G1e9 ;;
 shares)
   for g in 1e9 5e8 2.5e8 1.25e8; do
-    ( SMG_FORCE_EXCHANGE=1 timeout 300 python bench.py --genome $g --no-cpu --steps 10 --warmup 2 ) > $O/forced_$g.log 2>&1
-    ( timeout 300 python bench.py --genome $g --no-cpu --steps 10 --warmup 2 ) > $O/plain_$g.log 2>&1
+    ( SMG_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --genome $g --no-cpu --steps 10 --warmup 2 ) > $O/forced_$g.log 2>&1
+    ( timeout 300 python bench.py --full --genome $g --no-cpu --steps 10 --warmup 2 ) > $O/plain_$g.log 2>&1
     echo "G=$g forced $(grep '^{' $O/forced_$g.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"],3), {k: round(v,3) for k,v in d["roofline"]["kernel_ms"].items()})') plain $(grep '^{' $O/plain_$g.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"],3))')"
   done > $O/rank_share.txt 2>&1
-  ( SMG_BM_BITS=29 SMG_FORCE_EXCHANGE=1 timeout 300 python bench.py --genome 1.25e8 --no-cpu --steps 10 --warmup 2 ) > $O/forced_1.25e8_bm29.log 2>&1
+  ( SMG_BM_BITS=29 SMG_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --genome 1.25e8 --no-cpu --steps 10 --warmup 2 ) > $O/forced_1.25e8_bm29.log 2>&1
   echo "G=1.25e8 forced, 29-bit map (what 8 ranks use) $(grep '^{' $O/forced_1.25e8_bm29.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(round(d["ms_per_step"],3), {k: round(v,3) for k,v in d["roofline"]["kernel_ms"].items()})')" >> $O/rank_share.txt
   cat $O/rank_share.txt ;;
 e2e)
@@ -46,7 +46,7 @@ e2e)
   grep -A3 "end_to_end_T\|reference_T\|byte_identical" $O/e2e_1e9.json | grep -v engine_line | cut -c1-200 ;;
 timeline)   # launch-by-launch timeline of one step (start, duration, idle gap in front of each launch)
   for w in uniform repeats; do
-    ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tl_$w -o r04 -- python $R/bench.py --workload $w --steps 4 --warmup 2 --no-cpu > $O/tl_$w.log 2>&1 )
+    ( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tl_$w -o r04 -- python $R/bench.py --full --workload $w --steps 4 --warmup 2 --no-cpu > $O/tl_$w.log 2>&1 )
     python tools/step_timeline.py $O/tl_$w kf_pass1_d > $O/step_timeline_$w.txt 2>&1; rm -rf $O/tl_$w
     tail -n 2 $O/step_timeline_$w.txt
   done ;;
