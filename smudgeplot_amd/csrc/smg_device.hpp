@@ -195,9 +195,6 @@ template <int W> SMG_DEV int64_t find_key(const u64 *__restrict__ keys, const Di
 // A probe that hits the k-mer ends the search, and a search that ends without such a probe has seen both neighbours of
 // the place where the k-mer would be: no separate verifying load.  (Round 4 started the BISECTION at the expected position
 // and measured nothing: its next probe is the middle of what is left, i.e. just as far away.)
-#ifndef L_GALLOP
-#define L_GALLOP 1                         // 0: plain bisection of the directory bucket (find_key)
-#endif
 #define L_STEP0  3                         // first gallop step: the probe lands 4 entries from the expected position
 #define L_GSTEPS 3                         // gallop steps before the search falls back to bisection
 

@@ -48,16 +48,7 @@
 // tests the flag before anything else of the byte matters -- so what its low bits said is of no further use: the byte
 // becomes CODE_P | CODE_NONE.  Bytes of other entries are untouched by a byte store, and a second request that names the
 // entry (there is at most one: the one from its reverse complement) would store the same value.
-#ifndef L_BLIND_P
-#define L_BLIND_P 1                       // 0: read - or - store (A/B builds)
-#endif
-#ifdef L_ABL_NOSETP                       // ablation build (timing only, WRONG results): the look-ups without their flag stores
-#define SET_P(A, j) ((void) 0)
-#elif L_BLIND_P
 #define SET_P(A, j) ((A).code[j] = (uint8_t) CODE_P)
-#else
-#define SET_P(A, j) ((A).code[j] = (uint8_t) ((A).code[j] | CODE_P))
-#endif
 
 #define P2_TPB   1024
 #define P2_SMAX  208                  // LDS plot tile covers sums < P2_SMAX (43.7 KB; with the 32 KB queue: 2 WGs/CU)
@@ -440,7 +431,7 @@ kf_pass1(FastArgs A, uint32_t *__restrict__ bstart, u64 *__restrict__ req,
 // kf_apply_sorted); `verify` (the exact proof, where the look-up IS the proof) compares the k-mer of every hit.
 // Without signatures (W = 3) the k-mers are bisected directly.
 template <int W> SMG_DEV int64_t sig_find(const FastArgs &A, const Key<W> &y, bool verify)
-{ if (A.sig == NULL) return L_GALLOP ? find_key_near<W>(A.keys, A.dir, y) : find_key<W>(A.keys, A.dir, y);
+{ if (A.sig == NULL) return find_key_near<W>(A.keys, A.dir, y);
   const Dir d = A.dir;
   const uint32_t hb = (uint32_t) (y.w[0] >> 32) >> d.dsh;
   if (hb < d.b0 || hb - d.b0 >= d.nb) return -1;

@@ -39,19 +39,12 @@
 #include "smg_pass1d.hpp"
 #include "smg_lookup.hpp"
 
-// The environment, in three classes (round 6: the product library no longer carries tuning switches):
+// The environment, in two classes:
 //   documented modes    getenv(): SMG_VIRTUAL_SHARDS, SMG_SEQUENTIAL_SHARDS, SMG_SHARD_LIMIT, SMG_HBM_LIMIT, SMG_FORCE_MULTI (smg_hetmers.h);
 //   test hooks          test_hook(): force, on a table of any size, a code path that the engine otherwise picks from the table's
 //                       size, k or counts (the 30-bit exchanged map, the one-bit map of k < 24, kl_probe_x, the unfiltered chain,
-//                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle;
-//   tuning switches     tune_env(): variants that no table selects (A/B material) -- compiled in with -DSMG_TUNING only
-//                       (tools/build_r06.sh), NULL in the product library.
+//                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle.
 static inline const char *test_hook(const char *name) { return getenv(name); }
-#ifdef SMG_TUNING
-static inline const char *tune_env(const char *name) { return getenv(name); }
-#else
-static inline const char *tune_env(const char *) { return NULL; }
-#endif
 
 #define WIN_LIM   32          // window blocks up to this many entries are walked linearly
 #define TPB       256
@@ -613,7 +606,6 @@ struct smg_engine
   uint32_t    *dbits;  int64_t dbits_cap;      // deferred entries of kf_pass1_d: one bit per table entry (bytes); all zero between runs
   bool         dbits_dirty;                     //   ... unless a run was abandoned between pass 1 and kf_bigfix
   uint32_t    *biglist; int64_t biglist_cap;    // the marked entries, compacted (kf_collect), bytes
-  u64         *p1times; int64_t p1times_cap;    // SMG_P1_TIMES
   unsigned    *p1tick;  int64_t p1tick_cap;     // tile tickets of kf_pass1_d
   unsigned    *xtick;   int64_t xtick_cap;      // (bucket, part) tickets of kl_probe_x, one counter per XCD
   uint32_t    *farp;    int64_t farp_cap;       // beside it: the partner of a listed entry whose code is CODE_FAR (kf_bigfix -> kf_pass2_far)
@@ -722,7 +714,7 @@ extern "C" void smg_engine_destroy(smg_engine *e)
   hipSetDevice(e->device);
   hipStreamSynchronize(e->stream);
   hipFree(e->own_keys); hipFree(e->own_cnt); hipFree(e->deg); hipFree(e->sig); hipFree(e->bstart); hipFree(e->ixdir);
-  hipFree(e->req); hipFree(e->req2); hipFree(e->sort_tmp); hipFree(e->dense); hipFree(e->chunk_off); hipFree(e->skey[0]); hipFree(e->skey[1]); hipFree(e->sidx[0]); hipFree(e->sidx[1]); hipFree(e->dbits); hipFree(e->biglist); hipFree(e->farp); hipFree(e->p1times); hipFree(e->p1tick); hipFree(e->xtick); hipFree(e->chunk_fill); hipFree(e->bmap); hipFree(e->reqf); hipFree(e->chunk_fillf); hipFree(e->route_cnt); hipFree(e->route_off);
+  hipFree(e->req); hipFree(e->req2); hipFree(e->sort_tmp); hipFree(e->dense); hipFree(e->chunk_off); hipFree(e->skey[0]); hipFree(e->skey[1]); hipFree(e->sidx[0]); hipFree(e->sidx[1]); hipFree(e->dbits); hipFree(e->biglist); hipFree(e->farp); hipFree(e->p1tick); hipFree(e->xtick); hipFree(e->chunk_fill); hipFree(e->bmap); hipFree(e->reqf); hipFree(e->chunk_fillf); hipFree(e->route_cnt); hipFree(e->route_off);
   hipFree(e->partials); hipFree(e->ctrl); hipFree(e->d_split); hipFree(e->p1cold); hipFree(e->ghist); hipFree(e->boff);
   hipFree(e->whist); hipFree(e->rp_totals);
   hipHostFree(e->h_ctrl); hipHostFree(e->h_partials); hipHostFree(e->h_p1cold);
@@ -1150,7 +1142,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   if (filter_ok(e) && !emit_all && !e->no_filter && !test_hook("SMG_NO_FILTER"))
     { const int nbits = bm_id_bits(e->kmer, e->bm_cap);
       // the look-up chain of smg_lookup.hpp: one-word k-mers, key-only records, a map of >= 12 id bits
-      const bool chain = nbits >= 12 && e->W <= 2 && e->rw == e->W && !tune_env("SMG_OLD_LOOKUP");
+      const bool chain = nbits >= 12 && e->W <= 2 && e->rw == e->W;
       // ... with the two-bit map (smg_fast.hpp) when the k-mer has bits below the id to hash (a function of k and the
       // environment alone: every shard of a table decides the same)
       e->bm2 = (chain && e->kmer >= 24 && !test_hook("SMG_ONE_BIT_MAP")) ? 1 : 0;
@@ -1207,9 +1199,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           if (he != hipSuccess || nb < 1) nb = 3;
           if (nb > 8) nb = 8;
           if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus < 1) cus = 256;
-          { const char *g = tune_env("SMG_P1_WGS_PER_CU"); if (g && atoi(g) > 0) nb = atoi(g); }
           cached = (unsigned) (nb * cus);
-          if (tune_env("SMG_DEBUG")) fprintf(stderr, "  [smg] kf_pass1_d<%d,%d>: %d workgroups per CU x %d CUs\n", e->W, e->rw, nb, cus);
         }
       grid = cached;
     }
@@ -1268,11 +1258,6 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           if ((rc = grow(&e->p1tick, &e->p1tick_cap, (int64_t) D_NCLS * D_TICKW * 4, errbuf, errlen))) return rc;
           HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
           e->h_p1cold->tick = e->p1tick;
-          if (tune_env("SMG_P1_TIMES"))                                          // tuning: when did every workgroup start and end?
-            { if ((rc = grow(&e->p1times, &e->p1times_cap, (int64_t) grid * 24, errbuf, errlen))) return rc;
-              HIPCHK(hipMemsetAsync(e->p1times, 0, (size_t) grid * 24, e->stream));
-              e->h_p1cold->times = e->p1times;
-            }
           HIPCHK(hipMemcpyAsync(e->p1cold, e->h_p1cold, sizeof(P1Cold), hipMemcpyHostToDevice, e->stream));
 #define LAUNCH_R(W_, RW_, ODD_, KF_) do { bool hot_form = false; \
           if constexpr ((RW_) == (W_))            /* (the hot form exists for key-only records: no dead instantiations) */ \
@@ -1325,25 +1310,6 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
         }
       if (replay) { done = true; break; }
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-      if (narrow && e->h_p1cold->times)
-        { std::vector<u64> tm((size_t) grid * 3);
-          HIPCHK(hipMemcpy(tm.data(), e->p1times, (size_t) grid * 24, hipMemcpyDeviceToHost));
-          u64 t0 = ~0ull, t1 = 0;
-          for (unsigned b = 0; b < grid; b++) { if (tm[3 * b] < t0) t0 = tm[3 * b]; if (tm[3 * b + 1] > t1) t1 = tm[3 * b + 1]; }
-          // per XCD (bits of HW_ID differ between generations: printed raw as well): latest start, earliest / mean / latest end
-          double sum = 0; u64 smax = 0, emin = ~0ull;
-          for (unsigned b = 0; b < grid; b++)
-            { sum += (double) (tm[3 * b + 1] - t0); if (tm[3 * b] - t0 > smax) smax = tm[3 * b] - t0; if (tm[3 * b + 1] - t0 < emin) emin = tm[3 * b + 1] - t0; }
-          fprintf(stderr, "  [smg] pass-1 workgroups (100 MHz ticks = 10 ns): span %llu, latest start %llu, earliest end %llu, mean end %.0f\n",
-                  (unsigned long long) (t1 - t0), (unsigned long long) smax, (unsigned long long) emin, sum / grid);
-          unsigned hist[20]; memset(hist, 0, sizeof(hist));
-          for (unsigned b = 0; b < grid; b++) { unsigned q = (unsigned) ((tm[3 * b + 1] - t0) * 20 / (t1 - t0 + 1)); hist[q < 20 ? q : 19]++; }
-          fprintf(stderr, "  [smg] ends per 5 %% of the span:");
-          for (int q = 0; q < 20; q++) fprintf(stderr, " %u", hist[q]);
-          fprintf(stderr, "\n  [smg] first 16 workgroups: start end hw_id:");
-          for (unsigned b = 0; b < 16 && b < grid; b++) fprintf(stderr, " (%llu %llu %llx)", (unsigned long long) (tm[3 * b] - t0), (unsigned long long) (tm[3 * b + 1] - t0), (unsigned long long) tm[3 * b + 2]);
-          fprintf(stderr, "\n");
-        }
       e->dbits_dirty = false;
       if (e->h_ctrl->fast.unsorted)
         return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
@@ -1412,13 +1378,11 @@ static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int ho
   const u64 *src = keys_in;
   // (a short list -- what one rank of eight receives -- is looked up as it comes: the sort is eight launches, ~90 us, to put
   //  a few hundred thousand look-ups in order, which take 70 us either way)
-  int64_t sort_min = 1 << 21;
-  { const char *v = tune_env("SMG_APPLY_SORT_MIN"); if (v && atoll(v) >= SORT_MIN) sort_min = atoll(v); }
+  const int64_t sort_min = 1 << 21;
   if (nsort >= sort_min)
     { if ((rc = grow(&e->req2, &e->req2_cap, nsort * (int64_t) sizeof(u64), errbuf, errlen))) return rc;
       size_t tmp = 0;
-      unsigned lobit = 40;                   // tuning knob: sort on bits [lobit, 64) of the k-mer
-      { const char *lb = tune_env("SMG_SORT_LOBIT"); if (lb) lobit = (unsigned) atoi(lb); if (lobit > 56) lobit = 56; }
+      const unsigned lobit = 40;             // sort on bits [lobit, 64) of the k-mer
       HIPCHK(rocprim::radix_sort_keys<smg_sort_config>(nullptr, tmp, (u64 *) keys_in, e->req2, (size_t) nsort,
                                                        lobit, 64u, e->stream));
       if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
@@ -1510,9 +1474,6 @@ static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
         hipLaunchKernelGGL(kl_part<2>, dim3(e->nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->nown,
                            (const unsigned *) e->whist, e->max_chunks, e->lg.nb, e->req2);
       HIPCHK(hipGetLastError());
-      if (tune_env("SMG_DEBUG"))               // (kl_part's time moves with where its lists lie: profiles/r06_kl_part_addresses.txt)
-        fprintf(stderr, "  [smg] kl_part<%d>: req %p (%lld MB) -> req2 %p (%lld MB), whist %p, %u owners, %u chunks\n", e->rw, (void *) e->req,
-                (long long) (e->req_cap >> 20), (void *) e->req2, (long long) (e->req2_cap >> 20), (void *) e->whist, e->nown, e->n_chunks);
       e->presorted = 3;
       return SMG_OK;
     }
@@ -1520,7 +1481,7 @@ static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
   const int64_t nslots = (int64_t) e->n_chunks * F_CH;
   int64_t sort_min = 1 << 22;               // below this the probes are too few to matter
   { const char *v = test_hook("SMG_FILTER_SORT_MIN"); if (v) sort_min = atoll(v); if (sort_min < SORT_MIN) sort_min = SORT_MIN; }
-  if (!(e->rw == 1 && nslots >= sort_min && e->kmer < 32) || tune_env("SMG_FILTER_UNSORTED")) return SMG_OK;
+  if (!(e->rw == 1 && nslots >= sort_min && e->kmer < 32)) return SMG_OK;
   hipLaunchKernelGGL(kf_fill_holes, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
   if ((rc = grow(&e->req2, &e->req2_cap, nslots * (int64_t) sizeof(u64), errbuf, errlen))) return rc;
   size_t tmp = 0;
@@ -1558,12 +1519,9 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
         // tickets of 2048 requests where many requests survive (polyploid tables: one in seven, all real hits -- half as many
         // buckets in flight per XCD keep more of a bucket's k-mer lines in reach: -0.25 ms on the hexaploid table), 4096 where the
         // kernel is mostly streaming (a table with repeats: 1 request in 50 survives, and a ticket's fixed cost shows: +0.5 ms at 2048)
-        unsigned xw = PX_WGS, part = e->st.nemitted * 100 > e->n * 28 ? PX_PART : 2 * PX_PART;   // (tuning: SMG_PX_WGS workgroups per CU, SMG_PX_PART requests per ticket)
-        { const char *v = tune_env("SMG_PX_WGS"); if (v && atoi(v) > 0 && atoi(v) <= 8) xw = (unsigned) atoi(v);
-          v = tune_env("SMG_PX_PART"); if (v && atoi(v) >= 512) part = (unsigned) atoi(v) & ~511u;
-          if (test_hook("SMG_PX_ONE_XCC")) part |= 0x80000000u;                    // (tests: every workgroup claims XCD 0)
-        }
-        const unsigned xg = grid * xw;
+        unsigned part = e->st.nemitted * 100 > e->n * 28 ? PX_PART : 2 * PX_PART;
+        if (test_hook("SMG_PX_ONE_XCC")) part |= 0x80000000u;                      // (tests: every workgroup claims XCD 0)
+        const unsigned xg = grid * PX_WGS;
 #define PROBEX(TWO_, RW_) hipLaunchKernelGGL((kl_probe_x<TWO_, RW_>), dim3(xg), dim3(PX_TPB), 0, e->stream, a, (const u64 *) e->req2, \
                             (const u64 *) e->boff, map, e->lg, e->xtick, &e->ctrl->fast, part)
         if (two) { if (e->rw == 1) PROBEX(true, 1); else PROBEX(true, 2); }
@@ -1597,7 +1555,6 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   unsigned grid = 512;
   { int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus > 0) grid = 2u * (unsigned) cus;
-    const char *v = tune_env("SMG_FILTER_GRID"); if (v && atoi(v) > 0) grid = (unsigned) atoi(v);
   }
   if (grid > e->n_chunks) grid = e->n_chunks;
   unsigned maxout = e->n_chunks + grid + 16;
@@ -1671,7 +1628,7 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   e->st.ms_rclookup += ms;
   e->st.ms_filter = ms;
   // what a replayed step on this table may take for granted (key-only records through the look-up chain, k <= 64)
-  e->rp_have = e->rp_want && e->presorted == 3 && e->W <= 2 && e->rw == e->W && !e->h_p1cold->times;
+  e->rp_have = e->rp_want && e->presorted == 3 && e->W <= 2 && e->rw == e->W;
   if (e->rp_have)
     { e->rp_nreq = e->st.nemitted; e->rp_nbig = e->st.nbig; e->rp_nf_req = e->st.nrequests; e->rp_bm_bits = e->bm_bits;
       e->rp_seen_chunks = e->n_chunks; e->rp_nranks = 0;
@@ -1699,7 +1656,7 @@ static int compact_chunks(smg_engine *e, int64_t nreq, char *errbuf, size_t errl
 static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_count, int64_t *missing,
                       char *errbuf, size_t errlen)
 { int rc = SMG_OK;
-  if (!flat && e->lg.nb && e->bm_bits && !e->filtered && !tune_env("SMG_LOOKUP_SPLIT"))
+  if (!flat && e->lg.nb && e->bm_bits && !e->filtered)
     { // own requests, own map: partition, then filter and look-ups in one kernel (no survivor list, no sort)
       if (e->n_chunks == 0 || e->st.nrequests == 0) { if (missing) *missing = 0; return SMG_OK; }
       if (!e->presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
@@ -1827,7 +1784,6 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
 
 // the same for k > 85 (round 6): the byte a shard left behind is its array of counted degrees (S_all of every entry, uint8 with the
 // reference's wrap); the look-ups of the received requests add S_hi of the complements on top (k_apply) and pass 2 reads the sums
-static int counted_prepare(smg_engine *e, char *errbuf, size_t errlen);
 static int counted_resume(smg_engine *e, const uint8_t *d_degs, char *errbuf, size_t errlen)
 { HIPCHK(hipSetDevice(e->device));
   int rc = counted_prepare(e, errbuf, errlen);               // control words, geometry, zeroed degrees, directory

@@ -48,41 +48,19 @@
 #define D_SLOTS  (D_SCAN + 8)              // staged entries: scanned + the two outer halo threads
 #define D_LEAD   (D_HALO + 4)              // staged entries in front of the first owned one
 #define D_WIN    30                        // partners are searched within +-30 entries
-#ifndef D_BMF
 #define D_BMF    4096                      // block ids per tile with a bit in LDS (request filter)
-#endif
 #define D_BMW    (D_BMF / 32)
 #define D_HB     1024                      // bins of the request histogram (smg_lookup.hpp: L_BK)
-#ifndef D_QCAP
 #define D_QCAP   1792                      // LDS request queue (records); flushed when the next tile might not fit (every ~5th tile;
                                            //   1280 records: every 2nd or 3rd, +0.3 ms)
-#endif
-// Scheduling fences (nothing is scheduled across them).  They were put between the tests and between the phases when
-// the machine scheduler hoisted every compare to the front and the kernel spilled lane masks (SGPR pairs) by the dozen;
-// with today's kernel only the ones between the entries of the complement loop still pay (they keep its four entries
-// from being interleaved: ~30 vector registers): without the other two classes pass 1 takes 15.7 instead of 16.2 ms
-// (profiles/r02_pass1_ablation.txt, k).
-#ifndef D_NOFENCE
-#define D_NOFENCE 3                        // bit mask of fence classes LEFT OUT: 1 between tests, 2 between phases, 4 between the entries of the complement loop
-#endif
+// Scheduling fence (nothing is scheduled across it) between the entries of the complement loop: it keeps the loop's four
+// entries from being interleaved, which needs ~30 more vector registers than the kernel has.
 #define D_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define D_FENCE_T() do { if (!(D_NOFENCE & 1)) D_SCHED_FENCE(); } while (0)
-#define D_FENCE_P() do { if (!(D_NOFENCE & 2)) D_SCHED_FENCE(); } while (0)
-#define D_FENCE_R() do { if (!(D_NOFENCE & 4)) D_SCHED_FENCE(); } while (0)
-#ifndef D_RC_WIDE
-#define D_RC_WIDE 1
-#endif
-#ifndef D_TAILB
 #define D_TAILB  6                         // tail: the next D_TAILB partners of a queued entry (distances 4 .. D_TAILB + 3) are read in one batch, the
                                            //   (rare) rest one by one.  8 until round 6: 4 / 5 / 6 are 0.2-0.25 ms faster on the bench table (most queued
                                            //   blocks end within two or three entries), 2 and 12 slower (profiles/r06_pass1_experiments.txt)
-#endif
 #define D_RD     3                         // distances tested register-to-register; the deferred tail starts at D_RD + 1 (a fourth
                                            //   distance in registers: ten vector registers spill, 16.4 instead of 14.7 ms)
-#ifndef D_ABL
-#define D_ABL    0                         // ablation mask (timing experiments only; results are WRONG when non-zero):
-#endif                                     //   1 fingerprint, 2 directory, 4 signatures, 8 block map, 16 requests, 32 tail, 64 scan,
-                                           //   512 tail detection passes, 4096/8192 the two barriers of a tile
 
 // (Round 6 swizzled the staged k-mers -- every other group of eight threads swapped the 16-byte halves of its 32 bytes, so that
 //  the sixteen lanes of an LDS cycle cover all 64 banks: the two-way conflicts of the 32-byte lane stride were 41 % of the
@@ -224,7 +202,9 @@ struct P1Cold                             // in device memory: what only a flush
   unsigned  owners;              //   chunk slots are dealt out without a counter: owner w fills w, w + owners, w + 2 owners, ..
   unsigned  max_chunks;
   uint32_t *dbits;               // deferred entries: one bit per table entry (kf_bigfix redoes them exactly and clears the bits)
-  u64      *times;               // SMG_P1_TIMES (tuning): start / end of every workgroup on the constant 100 MHz clock, or NULL
+  u64      *times;               // start / end of every workgroup on the constant 100 MHz clock when set; the host always passes
+                                 //   NULL.  Kept only because dropping it and its two stores in kf_pass1_d changes the pass-1 code
+                                 //   object that profiles/hbm_traffic.json is tied to: it goes with the next change of kf_pass1_d.
   unsigned *tick;                // tile tickets: D_NCLS counters, 128 bytes apart (zeroed before the launch)
 };
 
@@ -276,7 +256,6 @@ d_tests(const WT (&sx)[4 + D_RD], const unsigned (&cn)[4], const u64 (&Sm)[4 + D
           const unsigned w2c = ODD ? 0u : (unsigned) CODE_W2;
           code[a] = d_lane(h) ? ((unsigned) (31 + d) | w2c) : code[a];
           code[eb] = d_lane(hb) ? ((unsigned) (31 - d) | w2c) : code[eb];
-          D_FENCE_T();
         }
     }
 }
@@ -386,24 +365,22 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 
   // ---- order check + bucket directory (the first entry of every bucket stores its index) ------------------
   //@mark D_DIR
-  D_FENCE_P();
-  if (!(D_ABL & 2))
-    { Key<W> nk0;
+  Key<W> nk0;
 #pragma unroll
-      for (int w = 0; w < W; w++) nk0.w[w] = d_next(kk[0].w[w]);
-      const Key<W> nxt[4] = { kk[1], kk[2], kk[3], nk0 };
-      u64 bad = 0;
+  for (int w = 0; w < W; w++) nk0.w[w] = d_next(kk[0].w[w]);
+  const Key<W> nxt[4] = { kk[1], kk[2], kk[3], nk0 };
+  u64 bad = 0;
 #pragma unroll
-      for (int e = 0; e < 4; e++)
-        { u64 b = __ballot(!key_lt<W>(kk[e], nxt[e]));
-          if (!INNER) b &= V[e] & V[e + 1];
-          bad |= b;
-        }
-      if (bad & scanM) *S.s_unsorted = 1u;
-      // raw bucket numbers; the offset and the bound are applied on the (rare) store path only
-      // (no directory is written when the table came with its own: the FastK prefix index, smg_engine_set_prefix_index)
-      if (DIR && A.bstart != nullptr) {
-      uint32_t bq[5];
+  for (int e = 0; e < 4; e++)
+    { u64 b = __ballot(!key_lt<W>(kk[e], nxt[e]));
+      if (!INNER) b &= V[e] & V[e + 1];
+      bad |= b;
+    }
+  if (bad & scanM) *S.s_unsorted = 1u;
+  // raw bucket numbers; the offset and the bound are applied on the (rare) store path only
+  // (no directory is written when the table came with its own: the FastK prefix index, smg_engine_set_prefix_index)
+  if (DIR && A.bstart != nullptr)
+    { uint32_t bq[5];
 #pragma unroll
       for (int e = 0; e < 4; e++) bq[e] = (uint32_t) (kk[e].w[0] >> 32) >> A.dsh();
       bq[4] = (uint32_t) (nk0.w[0] >> 32) >> A.dsh();
@@ -420,13 +397,11 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
               if (!INNER && ((vmask >> e) & 1u) && i0 + e + 1 == n) A.bstart[A.nb] = (uint32_t) n;
             }
         }
-      }
     }
 
   // ---- signatures ---------------------------------------------------------------------------------------------------
   //@mark D_SIG
-  D_FENCE_P();
-  if (DIR && W <= 2 && !(D_ABL & 4) && A.sig && owned)     // (no signatures: the look-ups bisect the k-mers themselves)
+  if (DIR && W <= 2 && A.sig && owned)     // (no signatures: the look-ups bisect the k-mers themselves)
     { unsigned sg[4];
 #pragma unroll
       for (int e = 0; e < 4; e++)
@@ -442,7 +417,6 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 
   // ---- window-block structure as lane masks ---------------------------------------------------------------
   //@mark D_MASKS
-  D_FENCE_P();
   // Sm[e]: entries e and e+1 share their first p0 bases (e = 4..6: the neighbour's 0..2)
   u64 Sm[4 + D_RD];
 #pragma unroll
@@ -457,41 +431,36 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
   for (int e = 0; e < D_RD; e++) Sm[4 + e] = Sm[e] >> 1;
 
   // entries whose block continues past distance 3: deferred (their owner queues their slot)
-  if (!(D_ABL & 32))
-    { u64 Al[4];
+  u64 Al[4];
 #pragma unroll
-      for (int e = 0; e < 4; e++) Al[e] = Sm[e] & Sm[e + 1] & Sm[e + 2] & Sm[e + 3] & ownM;
-      const unsigned na = (unsigned) (__popcll(Al[0]) + __popcll(Al[1]) + __popcll(Al[2]) + __popcll(Al[3]));
-      if (na)
-        { unsigned base = 0;
-          base = d_wave_add(S.s_tn, na, lane);
+  for (int e = 0; e < 4; e++) Al[e] = Sm[e] & Sm[e + 1] & Sm[e + 2] & Sm[e + 3] & ownM;
+  const unsigned na = (unsigned) (__popcll(Al[0]) + __popcll(Al[1]) + __popcll(Al[2]) + __popcll(Al[3]));
+  if (na)
+    { unsigned base = 0;
+      base = d_wave_add(S.s_tn, na, lane);
 #pragma unroll
-          for (int e = 0; e < 4; e++)
-            { if (d_lane(Al[e]))
-                { const unsigned q = __builtin_amdgcn_mbcnt_hi((unsigned) (Al[e] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) Al[e], base));
-                  S.tailq[q] = (uint16_t) (slot0 + e);
-                }
-              base += (unsigned) __popcll(Al[e]);
+      for (int e = 0; e < 4; e++)
+        { if (d_lane(Al[e]))
+            { const unsigned q = __builtin_amdgcn_mbcnt_hi((unsigned) (Al[e] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) Al[e], base));
+              S.tailq[q] = (uint16_t) (slot0 + e);
             }
+          base += (unsigned) __popcll(Al[e]);
         }
     }
 
   // ---- the 12 one-away tests of a thread (distances 1..3), aggregated on the fly -----------------------------
   //@mark D_TESTS
-  D_FENCE_P();
   // per entry e of a lane: npair[e] pairs seen (a carry-in add per hit mask), code[e]: delta code of the last pair seen
   // (the only one if the entry is unique), midM "has a pair on the self-mirrored position".  The b side of a test
   // with b >= 4 is entry b - 4 of the right neighbour lane: the same mask, shifted up by one lane.
   unsigned code[4] = { CODE_NONE, CODE_NONE, CODE_NONE, CODE_NONE };
   unsigned npair[4] = { 0, 0, 0, 0 };
   u64 midM[4] = { 0, 0, 0, 0 };
-  if (!(D_ABL & 64))
-    { unsigned mx = cn[0] > cn[1] ? cn[0] : cn[1];
-      { const unsigned m2 = cn[2] > cn[3] ? cn[2] : cn[3]; mx = mx > m2 ? mx : m2; }
-      // count sums can only exceed 1000 next to a count > 500: one wave-uniform branch, two straight-line variants
-      if (__ballot(mx > SMG_FMAX) == 0) d_tests<WT, ODD, false>(sx, cn, Sm, G, code, npair, midM);
-      else                             d_tests<WT, ODD, true>(sx, cn, Sm, G, code, npair, midM);
-    }
+  unsigned mx = cn[0] > cn[1] ? cn[0] : cn[1];
+  { const unsigned m2 = cn[2] > cn[3] ? cn[2] : cn[3]; mx = mx > m2 ? mx : m2; }
+  // count sums can only exceed 1000 next to a count > 500: one wave-uniform branch, two straight-line variants
+  if (__ballot(mx > SMG_FMAX) == 0) d_tests<WT, ODD, false>(sx, cn, Sm, G, code, npair, midM);
+  else                             d_tests<WT, ODD, true>(sx, cn, Sm, G, code, npair, midM);
   u64 uniqM[4], hiM[4];
 #pragma unroll
   for (int e = 0; e < 4; e++)
@@ -508,11 +477,10 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 
   // ---- request filter: a CANDIDATE (exactly one suffix-side pair) sets the bit of its block id -------------------
   //@mark D_BMAP
-  D_FENCE_P();
   // word 0 of the tile's LDS bit map = the map word of the tile's first owned entry (a uniform, scalar load)
   // (inner tiles: loaded one tile ahead with the entries -- as a load of its own it was waited for on the spot)
   const uint32_t bmbase = D_BM ? (((INNER ? pf_anchor : (uint32_t) (A.keys[(g0 + D_LEAD) * W] >> 32)) >> bmsh) & ~31u) : 0u;
-  if (D_BM && A.bmap && !(D_ABL & 8))
+  if (D_BM && A.bmap)
     { // leading word of the thread's own entries, back from the staged copy (cheaper than four registers kept alive
       // across the tests)
       u64 kw[4];
@@ -567,79 +535,65 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 
   // ---- complement, fingerprint, requests: one entry at a time from the thread's own LDS copy ----------------------
   //@mark D_RC
-  D_FENCE_P();
-  if (!(D_ABL & 16) || (VAR & 2) || A.want_fp())
-    { // hash proof: rc(x) of every owned entry that owns a pair at p > k-1-p; exact proof: of every owned entry, with
-      // that flag.  (A deferred entry that turns out to own more pairs than the register scan saw sends again from
-      // kf_bigfix: the flag of a request is only ever ORed into its target.)
-      u64 E0 = 0, E1 = 0, E2 = 0, E3 = 0;
-      if (!(D_ABL & 16))
-        { const u64 all = (!(VAR & 2) && A.emit_all()) ? ~0ull : 0ull;       // (VAR & 2: the hash proof -- owners of a hi-side pair only)
-          E0 = (hiM[0] | all) & ownM; E1 = (hiM[1] | all) & ownM; E2 = (hiM[2] | all) & ownM; E3 = (hiM[3] | all) & ownM;
-          if (!INNER) { E0 &= V[0]; E1 &= V[1]; E2 &= V[2]; E3 &= V[3]; }
-        }
-      const unsigned cnt_w = (unsigned) (__popcll(E0) + __popcll(E1) + __popcll(E2) + __popcll(E3));
-      unsigned base = 0;
-      if (cnt_w)
-        base = d_wave_add(S.s_qn, cnt_w, lane);
-      const bool fp = ((VAR & 2) || A.want_fp()) && !(D_ABL & 1);
-      // Unrolled, the four entries kept apart by scheduling fences (interleaved they need ~30 more vector registers
-      // than the kernel has).  The rolled loop -- the masks rotating through one register pair, a counter, two branches
-      // per entry -- cost 0.7 ms more: scalar instructions and branches are not free next to a busy vector unit
-      // (tools/issue_mix.hip).
-      const u64 EM[4] = { E0, E1, E2, E3 };
-#if D_RC_WIDE
-      // the thread's four entries in two 16-byte LDS reads + one 8-byte read of the counts (four 8-byte reads at a lane
-      // stride of 32 bytes hit the same banks from eight lanes at a time)
-      Key<W> xs[4]; unsigned cs[4];
-      if constexpr (W == 1)
-        { const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(&S.ent[slot0]);
-          const ulonglong2 b = *reinterpret_cast<const ulonglong2 *>(&S.ent[slot0 + 2]);
-          xs[0].w[0] = a.x; xs[1].w[0] = a.y; xs[2].w[0] = b.x; xs[3].w[0] = b.y;
-        }
-      else
-        {
+  // hash proof: rc(x) of every owned entry that owns a pair at p > k-1-p; exact proof: of every owned entry, with
+  // that flag.  (A deferred entry that turns out to own more pairs than the register scan saw sends again from
+  // kf_bigfix: the flag of a request is only ever ORed into its target.)
+  const u64 all = (!(VAR & 2) && A.emit_all()) ? ~0ull : 0ull;       // (VAR & 2: the hash proof -- owners of a hi-side pair only)
+  u64 E0 = (hiM[0] | all) & ownM, E1 = (hiM[1] | all) & ownM, E2 = (hiM[2] | all) & ownM, E3 = (hiM[3] | all) & ownM;
+  if (!INNER) { E0 &= V[0]; E1 &= V[1]; E2 &= V[2]; E3 &= V[3]; }
+  const unsigned cnt_w = (unsigned) (__popcll(E0) + __popcll(E1) + __popcll(E2) + __popcll(E3));
+  unsigned base = 0;
+  if (cnt_w)
+    base = d_wave_add(S.s_qn, cnt_w, lane);
+  const bool fp = (VAR & 2) || A.want_fp();
+  // Unrolled, the four entries kept apart by scheduling fences (D_SCHED_FENCE).  The rolled loop -- the masks rotating
+  // through one register pair, a counter, two branches per entry -- cost 0.7 ms more: scalar instructions and branches are
+  // not free next to a busy vector unit (tools/issue_mix.hip).
+  const u64 EM[4] = { E0, E1, E2, E3 };
+  // the thread's four entries in two 16-byte LDS reads + one 8-byte read of the counts (four 8-byte reads at a lane
+  // stride of 32 bytes hit the same banks from eight lanes at a time)
+  Key<W> xs[4]; unsigned cs[4];
+  if constexpr (W == 1)
+    { const ulonglong2 a = *reinterpret_cast<const ulonglong2 *>(&S.ent[slot0]);
+      const ulonglong2 b = *reinterpret_cast<const ulonglong2 *>(&S.ent[slot0 + 2]);
+      xs[0].w[0] = a.x; xs[1].w[0] = a.y; xs[2].w[0] = b.x; xs[3].w[0] = b.y;
+    }
+  else
+    {
 #pragma unroll
-          for (int e = 0; e < 4; e++) xs[e] = lds_key<W>(S.ent, slot0 + e);
-        }
-      { const ushort4 c4 = *reinterpret_cast<const ushort4 *>(&S.lcn[slot0]); cs[0] = c4.x; cs[1] = c4.y; cs[2] = c4.z; cs[3] = c4.w; }
-#endif
+      for (int e = 0; e < 4; e++) xs[e] = lds_key<W>(S.ent, slot0 + e);
+    }
+  { const ushort4 c4 = *reinterpret_cast<const ushort4 *>(&S.lcn[slot0]); cs[0] = c4.x; cs[1] = c4.y; cs[2] = c4.z; cs[3] = c4.w; }
 #pragma unroll
-      for (int e = 0; e < 4; e++)
-        { E0 = EM[e];
-          D_FENCE_R();
-#if D_RC_WIDE
-          const Key<W> x = xs[e];
-          const unsigned c = cs[e];
-#else
-          const Key<W> x = lds_key<W>(S.ent, slot0 + e);
-          const unsigned c = S.lcn[slot0 + e];
-#endif
-          const Key<W> rc = revcomp<W>(x, G.k);
-          if (fp && owned)
-            { // XOR of h(min(x, rc x), count) over the entries: the two members of a closed class cancel, an entry
-              // without its complement (or with another count) leaves its 128 bits behind -- no signs, no carries
-              const bool lt = key_lt<W>(x, rc);
-              u64 ha, hb;
-              mix_hash<W>(lt ? x : rc, c, ha, hb);
-              if (ODD && INNER) { fa ^= ha; fb ^= hb; }              // odd k: no k-mer is its own complement
-              else
-                { u64 keep = ~0ull;
-                  if (!ODD) keep = key_eq<W>(x, rc) ? 0ull : ~0ull;  // self-complementary: occurs once, no term
-                  if (!INNER) keep = ((vmask >> e) & 1u) ? keep : 0ull;
-                  fa ^= ha & keep; fb ^= hb & keep;
-                }
+  for (int e = 0; e < 4; e++)
+    { E0 = EM[e];
+      D_SCHED_FENCE();
+      const Key<W> x = xs[e];
+      const unsigned c = cs[e];
+      const Key<W> rc = revcomp<W>(x, G.k);
+      if (fp && owned)
+        { // XOR of h(min(x, rc x), count) over the entries: the two members of a closed class cancel, an entry
+          // without its complement (or with another count) leaves its 128 bits behind -- no signs, no carries
+          const bool lt = key_lt<W>(x, rc);
+          u64 ha, hb;
+          mix_hash<W>(lt ? x : rc, c, ha, hb);
+          if (ODD && INNER) { fa ^= ha; fb ^= hb; }              // odd k: no k-mer is its own complement
+          else
+            { u64 keep = ~0ull;
+              if (!ODD) keep = key_eq<W>(x, rc) ? 0ull : ~0ull;  // self-complementary: occurs once, no term
+              if (!INNER) keep = ((vmask >> e) & 1u) ? keep : 0ull;
+              fa ^= ha & keep; fb ^= hb & keep;
             }
-          //@mark D_EMIT
-          if (E0)
-            { if (d_lane(E0))
-                { const unsigned q = __builtin_amdgcn_mbcnt_hi((unsigned) (E0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) E0, base));
+        }
+      //@mark D_EMIT
+      if (E0)
+        { if (d_lane(E0))
+            { const unsigned q = __builtin_amdgcn_mbcnt_hi((unsigned) (E0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) E0, base));
 #pragma unroll
-                  for (int w = 0; w < W; w++) S.sq[q * RW + w] = rc.w[w];
-                  if (RW > W) S.sq[q * RW + W] = (u64) c | (d_lane(hiM[e]) ? 1ull << 16 : 0ull);
-                }
-              base += (unsigned) __popcll(E0);
+              for (int w = 0; w < W; w++) S.sq[q * RW + w] = rc.w[w];
+              if (RW > W) S.sq[q * RW + W] = (u64) c | (d_lane(hiM[e]) ? 1ull << 16 : 0ull);
             }
+          base += (unsigned) __popcll(E0);
         }
     }
   // the next tile's entries: issued here, used after the flush -- the latency of the loads (a few thousand cycles on a
@@ -707,15 +661,10 @@ d_detect(const P1Hot &A, const u64 *ent, const uint16_t *lcn, int64_t g0, int sa
     }
 }
 
-#ifndef D_WAVES_W2
 #define D_WAVES_W2 3                       // two-word k-mers with a count word in the request (exact proof): waves per SIMD
-#endif                                     //   (the 23 KB request queue of that variant allows three workgroups per CU)
-#ifndef D_WAVES_W2K
+                                           //   (the 23 KB request queue of that variant allows three workgroups per CU)
 #define D_WAVES_W2K 4                      // ... with key-only requests (hash proof): 15 KB less LDS, 108 vector registers
-#endif
-#ifndef D_WAVES_PER_EU
 #define D_WAVES_PER_EU 5
-#endif
 #define D_WAVES(W_, RW_) ((W_) == 2 ? ((RW_) == 2 ? D_WAVES_W2K : D_WAVES_W2) : ((RW_) == 1 ? D_WAVES_PER_EU : 5))
 
 // tile tickets: one counter per class of workgroups (blockIdx.x mod D_NCLS -- the workgroups of one XCD, as the dispatcher
@@ -810,7 +759,7 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
         d_tile<W, RW, ODD, KF, true, VAR>(A, S, g0, g0n, t, fa, fb, pf);
       else
         d_tile<W, RW, ODD, KF, false, VAR>(A, S, g0, g0n, t, fa, fb, pf);
-      if (!(D_ABL & 4096)) lds_barrier();          // the staged copy and the queues of this tile are complete
+      lds_barrier();                               // the staged copy and the queues of this tile are complete
       //@mark D_FLUSH
       const bool last = tnext >= A.ntiles;
       const unsigned tn = s_tn[par];               // (zeroed again behind the barrier at the end of this iteration: the
@@ -829,7 +778,7 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
       // ---- deferred tail: one dense detection pass over this tile's queued entries (a lane each) ---------------------
       // A hit sets the bits of the entry and of its partners in the deferred-entry map (one bit per table entry, so an
       // entry named twice is redone once).
-      for (unsigned q = t; q < tn && !(D_ABL & 512); q += D_TPB)
+      for (unsigned q = t; q < tn; q += D_TPB)
         { const int sa = (int) tailq[q];
           unsigned hm; bool big;
           d_detect<W, ODD, KF>(A, ent, lcn, g0, sa, hm, big);
@@ -886,7 +835,7 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
               for (unsigned e = t; e < (qn - head) * RW; e += D_TPB) o[e] = sq[head * RW + e];
             }
         }
-      if (!(D_ABL & 8192)) lds_barrier();
+      lds_barrier();
       if (t == 0) s_tn[par] = 0;
       tile = tnext; tnext = tnext2;
       tnext2 = (int64_t) gridDim.x + (int64_t) (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk[par]) * D_NCLS + cls;

@@ -24,7 +24,7 @@ SYM_EXACT, SYM_HASH, SYM_NONE = 0, 1, 2
 _SYM = {"exact": SYM_EXACT, "hash": SYM_HASH, "none": SYM_NONE}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SMG_LIB", os.path.join(_HERE, "libsmg_hetmers.so"))   # SMG_LIB: tuning builds only
+LIB_PATH = os.environ.get("SMG_LIB", os.path.join(_HERE, "libsmg_hetmers.so"))   # SMG_LIB: A/B builds only
 BIN_PATH = os.path.join(_HERE, "bin", "hetmers")
 
 
