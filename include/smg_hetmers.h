@@ -327,9 +327,10 @@ int     smg_engine_symhash(smg_engine *e, uint64_t out[4], char *errbuf, size_t 
 int     smg_engine_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen);
 int     smg_engine_stats(smg_engine *e, smg_stats *stats);
 
-/* extract leg on an engine whose run has completed on the symmetric path: d_labels = device
-   uint16[SMG_PLOT_CELLS]; d_out = device buffer of `capacity` records (may be NULL with capacity 0
-   to count only); *nrec = records produced (compare with capacity).                            */
+/* extract leg on an engine whose run has completed, on the symmetric path or on the general path (a
+   table that is not closed under reverse complement: every pair is written once, by its lower member):
+   d_labels = device uint16[SMG_PLOT_CELLS]; d_out = device buffer of `capacity` records (may be NULL
+   with capacity 0 to count only); *nrec = records produced (compare with capacity).              */
 int     smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity,
                            int64_t *nrec, char *errbuf, size_t errlen);
 

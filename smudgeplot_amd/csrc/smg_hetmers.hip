@@ -559,6 +559,109 @@ k_extract(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ out, u64
     }
 }
 
+// ---- extract on the general path (a table that is not closed under reverse complement): the pairs k_pass2<W, false> counts
+// The walk of k_pass2<W, false>: suffix-side partners from the window block, prefix-side partners (p < p0) looked up in the
+// table, or over virtual shards in whichever shard holds them (TabSet).  A pair is written ONCE, by its lower member, with the
+// printed member and the alt base chosen as k_extract chooses them; no mirror image (if the table holds the complement pair,
+// the walk finds it as a pair of its own).  Weight 1 per pair, as in the plot of the general path.
+// Without wrap a degree <= 1 means at most one partner: the walk stops at it, and a wave reserves the slots of its records
+// with one atomic.  A wrapped degree (k > 85: 0 or 1 mod 256) can stand for hundreds of partners: one atomic per record.
+template <int W> __global__ void __launch_bounds__(TPB)
+k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ out, u64 capacity, u64 *__restrict__ total,
+                  const TabSet *__restrict__ set)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  const Geo g = t.g;
+  bool has = false;                          // (no wrap) the one record of this lane
+  Key<W> rk; u64 rmeta = 0;
+#pragma unroll
+  for (int w = 0; w < W; w++) rk.w[w] = 0;
+  unsigned di = 2;
+  if (i < t.n) di = t.deg[i];
+  if (di <= 1 && (di == 1 || g.wrap))        // (lanes without work stay for the wave's ballot below)
+    { const Key<W> x = load_key<W>(t.keys, i);
+      const unsigned c = t.cnt[i];
+      bool done = false;
+      // a partner y > x with count cj and degree dj: -> true when the walk can stop (no wrap: the one partner was found)
+      auto visit = [&](const Key<W> &y, int p, unsigned cj, unsigned dj) -> bool
+      { if (c + cj > SMG_SMAX) return false;                                   // not a pair (nor counted in a degree)
+        const unsigned sum = c + cj, mn = c < cj ? c : cj;
+        const unsigned lab = dj <= 1 ? labels[(size_t) sum * SMG_PLOT_COLS + mn] : 0u;
+        if (lab)
+          { const bool pj = c < cj;                                               // print the larger count; tie: x (smaller base)
+            const Key<W> &who = pj ? y : x;
+            const u64 meta = (u64) p | ((u64) (pj ? base_at<W>(x, p) : base_at<W>(y, p)) << 8) | ((u64) lab << 16);
+            if (!g.wrap) { rk = who; rmeta = meta; has = true; }
+            else
+              { const u64 q = atomicAdd(total, (u64) 1);
+                if (q < capacity)
+                  { u64 *o = out + q * (W + 1);
+#pragma unroll
+                    for (int w = 0; w < W; w++) o[w] = who.w[w];
+                    o[W] = meta;
+                  }
+              }
+          }
+        return !g.wrap;
+      };
+
+      bool big = false;
+      if (i + WIN_LIM < t.n) big = same_block<W>(x, load_key<W>(t.keys, i + WIN_LIM), g);
+      if (!big)
+        { for (int64_t j = i + 1; j < t.n && !done; j++)
+            { const Key<W> y = load_key<W>(t.keys, j);
+              if (!same_block<W>(x, y, g)) break;
+              const int p = pair_pos<W>(x, y);
+              if (p >= 0) done = visit(y, p, t.cnt[j], t.deg[j]);
+            }
+        }
+      else
+        { int64_t a = i + 1, b = t.n;
+          while (a < b)
+            { const int64_t m = (a + b) >> 1;
+              if (!same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
+            }
+          const int64_t bhi = a;
+          for (int p = g.p0; p < g.k && !done; p++)
+            for (int d = 1; d <= 3 && !done; d++)
+              { const Key<W> y = flip_base<W>(x, p, d);
+                if (!key_lt<W>(x, y)) continue;
+                const int64_t j = lower_bound_key<W>(t.keys, i + 1, bhi, y);
+                if (j < bhi && key_eq<W>(load_key<W>(t.keys, j), y)) done = visit(y, p, t.cnt[j], t.deg[j]);
+              }
+        }
+      for (int p = 0; p < g.p0 && !done; p++)
+        for (int d = 1; d <= 3 && !done; d++)
+          { const Key<W> y = flip_base<W>(x, p, d);
+            if (!key_lt<W>(x, y)) continue;
+            if (set)
+              { int64_t j;
+                const int sh = set_find<W>(set, y, j);
+                if (j >= 0) done = visit(y, p, set->shard[sh].cnt[j], set->shard[sh].deg[j]);
+              }
+            else
+              { const int64_t j = find_key<W>(t.keys, t.dir, y);
+                if (j >= 0) done = visit(y, p, t.cnt[j], t.deg[j]);
+              }
+          }
+    }
+  if (g.wrap) return;                        // (uniform over the grid)
+  const u64 mask = __ballot(has);
+  if (!mask) return;
+  const int lead = __ffsll((long long) mask) - 1;
+  u64 base = 0;
+  if ((int) (threadIdx.x & 63) == lead) base = atomicAdd(total, (u64) __popcll(mask));
+  base = __shfl(base, lead, 64);
+  if (has)
+    { const u64 q = base + __builtin_amdgcn_mbcnt_hi((unsigned) (mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) mask, 0u));
+      if (q < capacity)
+        { u64 *o = out + q * (W + 1);
+#pragma unroll
+          for (int w = 0; w < W; w++) o[w] = rk.w[w];
+          o[W] = rmeta;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 //  Host side
 // ------------------------------------------------------------------------------------------
@@ -648,7 +751,10 @@ struct smg_engine
   unsigned     n_chunks;
   u64          fp[4];
   smg_stats    st;
-  hipEvent_t   ev[13];        // 0,1 decode  2,3 pass 1  4,5 look-ups  6,7 pass 2  8,9 whole run  10 between partition and probe  11,12 filter of a replayed step
+  hipEvent_t   ev[15];        // 0,1 decode  2,3 pass 1  4,5 look-ups  6,7 pass 2  8,9 whole run  10 between partition and probe  11,12 filter of a replayed step
+                              // 13,14 extract
+  bool         general_done;  // the general path has run (st.path == 2): deg[] holds the degrees over all positions
+  float        ms_extract;    // device time of the last extract launch
 };
 
 static int fail(char *errbuf, size_t errlen, int code, const char *fmt, const char *a = "")
@@ -705,7 +811,7 @@ extern "C" smg_engine *smg_engine_create(int device, void *stream, char *errbuf,
     { fail(errbuf, errlen, SMG_ENOMEM, "cannot allocate the control block%s");
       delete e; return NULL;
     }
-  for (int i = 0; i < 13; i++) hipEventCreate(&e->ev[i]);
+  for (int i = 0; i < 15; i++) hipEventCreate(&e->ev[i]);
   return e;
 }
 
@@ -718,7 +824,7 @@ extern "C" void smg_engine_destroy(smg_engine *e)
   hipFree(e->partials); hipFree(e->ctrl); hipFree(e->d_split); hipFree(e->p1cold); hipFree(e->ghist); hipFree(e->boff);
   hipFree(e->whist); hipFree(e->rp_totals);
   hipHostFree(e->h_ctrl); hipHostFree(e->h_partials); hipHostFree(e->h_p1cold);
-  for (int i = 0; i < 13; i++) hipEventDestroy(e->ev[i]);
+  for (int i = 0; i < 15; i++) hipEventDestroy(e->ev[i]);
   delete e;
 }
 
@@ -730,7 +836,7 @@ static int set_table(smg_engine *e, int kmer, int64_t nels, char *errbuf, size_t
   e->kmer = kmer;
   e->W = (kmer + 31) / 32;
   e->n = nels;
-  e->prepared = false; e->counted_done = false; e->lookup_pending = false;
+  e->prepared = false; e->counted_done = false; e->general_done = false; e->lookup_pending = false;
   e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;        // (properties of the table that was bound before)
   e->rp_have = false; e->rp_active = false;
   memset(&e->st, 0, sizeof(e->st));
@@ -917,7 +1023,7 @@ static Tab make_tab(smg_engine *e)
 static int counted_prepare(smg_engine *e, char *errbuf, size_t errlen)
 { HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
-  e->fast = false; e->counted_done = false;
+  e->fast = false; e->counted_done = false; e->general_done = false;
   const int64_t dbytes = ((e->n + 3) & ~3ll) + 4;
   int rc = grow(&e->deg, &e->deg_cap, dbytes, errbuf, errlen);
   if (rc) return rc;
@@ -1047,6 +1153,7 @@ static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errl
   hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 += ms;
   hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->st.ms_pass2 = ms;
   e->st.path = 2;
+  e->general_done = true;
   return SMG_OK;
 }
 
@@ -1093,7 +1200,7 @@ static int general_shard_pass(smg_engine *e, const TabSet *d_set, int pass, int6
   if (e->h_ctrl->unsorted) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
   float ms = 0;
   if (pass == 1) { hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 += ms; }
-  else { hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->st.ms_pass2 = ms; e->st.path = 2; }
+  else { hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->st.ms_pass2 = ms; e->st.path = 2; e->general_done = true; }
   return SMG_OK;
 }
 
@@ -1128,7 +1235,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
-  e->fast = true; e->counted_done = false;
+  e->fast = true; e->counted_done = false; e->general_done = false;
   if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
   const int64_t pbytes = ((e->n + 15) & ~15ll) + 32;
   e->use_sig = e->W <= 2;
@@ -1758,7 +1865,7 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
-  e->fast = true; e->counted_done = false; e->lookup_pending = false;
+  e->fast = true; e->counted_done = false; e->general_done = false; e->lookup_pending = false;
   if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
   if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_codes, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
   e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
@@ -2330,7 +2437,7 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
 #undef CCHK
 #undef CRC
   e->n = n;
-  e->prepared = false; e->counted_done = false;
+  e->prepared = false; e->counted_done = false; e->general_done = false;
   e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;      // (another table now: its index and ends are gone)
   e->rp_have = false; e->rp_active = false;
   e->st.nels = n;
@@ -2657,7 +2764,7 @@ extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int
       if (rc) return rc;
     }
   e->n = kept;
-  e->prepared = false; e->counted_done = false;
+  e->prepared = false; e->counted_done = false; e->general_done = false;
   e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
   e->st.nels = kept;
   if (new_nels) *new_nels = kept;
@@ -2666,17 +2773,27 @@ extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int
 
 // ---- extract: the unique pairs of the labelled pixels (next row of the scope table: extract_kmer_pairs) ------
 
-extern "C" int smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity,
-                                  int64_t *nrec, char *errbuf, size_t errlen)
+// d_set: the shard set of a general run over virtual shards (smg_multi.hpp), NULL otherwise
+static int engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity, int64_t *nrec,
+                          const TabSet *d_set, char *errbuf, size_t errlen)
 { if (!e || !d_labels || !nrec) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
+  const bool general = e->general_done && !e->fast && e->st.path == 2;        // the table failed the proof: all positions
   const bool counted = e->counted_done && !e->fast && e->st.path == 1;        // k > 85: degrees instead of code bytes
-  if (!counted && (!e->prepared || !e->fast || e->st.path != 1))
-    return fail(errbuf, errlen, SMG_EINVAL,
-                "extract needs a completed run on a conditioned (reverse-complement closed) table%s");
+  if (!general && !counted && (!e->prepared || !e->fast || e->st.path != 1))
+    return fail(errbuf, errlen, SMG_EINVAL, "extract needs a completed run on the engine's current table%s");
   HIPCHK(hipSetDevice(e->device));
   u64 *d_total = &e->ctrl->plot_sum;
   HIPCHK(hipMemsetAsync(d_total, 0, sizeof(u64), e->stream));
-  if (e->n > 0 && counted)
+  hipEventRecord(e->ev[13], e->stream);
+  if (e->n > 0 && general)
+    { Tab t = make_tab(e);
+      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+#define CALL(WW) hipLaunchKernelGGL(k_extract_general<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out, \
+                   (u64) (d_out ? capacity : 0), d_total, d_set)
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  else if (e->n > 0 && counted)
     { Tab t = make_tab(e);
       const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
 #define CALL(WW) hipLaunchKernelGGL(k_extract<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out, \
@@ -2693,12 +2810,18 @@ extern "C" int smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint6
       DISPATCH_W3(e, CALL)
 #undef CALL
     }
+  hipEventRecord(e->ev[14], e->stream);
   HIPCHK(hipGetLastError());
   int rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
+  hipEventElapsedTime(&e->ms_extract, e->ev[13], e->ev[14]);
   *nrec = (int64_t) e->h_ctrl->plot_sum;
   return SMG_OK;
 }
+
+extern "C" int smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity,
+                                  int64_t *nrec, char *errbuf, size_t errlen)
+{ return engine_extract(e, d_labels, d_out, capacity, nrec, NULL, errbuf, errlen); }
 
 #include "smg_ingest.hpp"
 #include "smg_multi.hpp"
@@ -2845,9 +2968,8 @@ static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *p
   if (hipMemcpy(plot, d_plot, sizeof(int64_t) * SMG_PLOT_CELLS, hipMemcpyDeviceToHost) != hipSuccess)
     BAIL(SMG_ENODEV, "device to host copy failed")
   if (labels)
-    { // exact record count = plot weight on the labelled pixels (the plot counts a mirrored pair twice)
-      if (e->st.path != 1)
-        BAIL(SMG_EINVAL, "extract needs a trimmed, reverse-complement closed table")
+    { // exact record count = plot weight on the labelled pixels (path 1 counts a mirrored pair twice and writes it twice,
+      // path 2 counts and writes every pair once)
       int64_t want = 0, got = 0;
       for (int c = 0; c < SMG_PLOT_CELLS; c++) if (labels[c]) want += plot[c];
       const int rw = e->W + 1;
@@ -2874,6 +2996,8 @@ static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *p
               e->st.ms_h2d, h2d_s > 0 ? (double) tv->nels * pbyte / h2d_s / 1e9 : 0.0, tv->host_threads > 0 ? tv->host_threads : 4,
               e->st.ms_pass1, e->st.ms_rclookup, e->st.ms_pass2,
               e->st.ms_total, e->st.ms_total > 0 ? e->st.nels / (e->st.ms_total * 1e-3) : 0.0);
+      if (labels)
+        fprintf(stderr, "  [smg] extract %.2f ms (device), %lld records\n", e->ms_extract, (long long) *nrec);
       // where the wall time of this call went (the process adds its own start-up, the table probe and the .smu writer)
       fprintf(stderr, "  [smg] wall %.1f ms: runtime start-up + code object %.1f, allocations + index %.1f, read+h2d+decode %.1f, "
               "conditioning %.1f, passes + host round trips %.1f, results %.1f\n",

@@ -360,8 +360,7 @@ static void *multi_worker(void *argp)
       if (MOK && (c->rc[r] = general_shard_pass(e, c->d_set, 1, d_plot, eb, el))) c->failed = 1;
       pthread_barrier_wait(&c->bar);                                                     // G3: all degrees final
       if (MOK && (c->rc[r] = general_shard_pass(e, c->d_set, 2, d_plot, eb, el))) c->failed = 1;
-      pthread_barrier_wait(&c->bar);                                                     // G4: nobody reads the set any more
-      if (r == 0 && c->d_set) { hipFree(c->d_set); c->d_set = NULL; }
+      // (the set stays until barrier E: the extract leg looks partners up through it too)
     }
   else if (go_pass2 && MOK && (c->rc[r] = smg_engine_pass2(e, d_plot, eb, el))) c->failed = 1;
   const bool go_reduce = multi_agree(c);                                                 // C2: all in, or all out
@@ -396,16 +395,16 @@ static void *multi_worker(void *argp)
     { uint16_t *d_labels = NULL; uint64_t *d_out = NULL;
       int64_t cnt = 0, got = 0;
       const int rw = W + 1;
-      if (c->general) MFAIL(SMG_EINVAL, "extract needs a trimmed, reverse-complement closed table");
+      const TabSet *set = c->general ? c->d_set : NULL;     // (general path: a prefix-side partner may live in another shard)
       if (MOK && (hipMalloc(&d_labels, sizeof(uint16_t) * SMG_PLOT_CELLS) != hipSuccess
                   || hipMemcpy(d_labels, c->labels, sizeof(uint16_t) * SMG_PLOT_CELLS, hipMemcpyHostToDevice) != hipSuccess))
         MFAIL(SMG_ENOMEM, "out of device memory for the pair list");
-      if (MOK && (c->rc[r] = smg_engine_extract(e, d_labels, NULL, 0, &cnt, eb, el))) c->failed = 1;       // count first
+      if (MOK && (c->rc[r] = engine_extract(e, d_labels, NULL, 0, &cnt, set, eb, el))) c->failed = 1;       // count first
       if (MOK && cnt > 0)
         { c->h_rec[r] = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) cnt * rw);
           if (!c->h_rec[r] || hipMalloc(&d_out, sizeof(uint64_t) * (size_t) cnt * rw) != hipSuccess)
             MFAIL(SMG_ENOMEM, "out of memory for the pair list");
-          if (MOK && (c->rc[r] = smg_engine_extract(e, d_labels, d_out, cnt, &got, eb, el))) c->failed = 1;
+          if (MOK && (c->rc[r] = engine_extract(e, d_labels, d_out, cnt, &got, set, eb, el))) c->failed = 1;
           if (MOK && got != cnt) MFAIL(SMG_ENODEV, "internal error: the pair list changed between two passes");
           if (MOK && hipMemcpy(c->h_rec[r], d_out, sizeof(uint64_t) * (size_t) cnt * rw, hipMemcpyDeviceToHost) != hipSuccess)
             MFAIL(SMG_ENODEV, "device to host copy failed");
@@ -414,7 +413,8 @@ static void *multi_worker(void *argp)
       if (d_labels) hipFree(d_labels);
       if (d_out) hipFree(d_out);
     }
-  pthread_barrier_wait(&c->bar);                                                         // E: done with h_plot
+  pthread_barrier_wait(&c->bar);                                                         // E: done with h_plot and the shard set
+  if (r == 0 && c->d_set) { hipFree(c->d_set); c->d_set = NULL; }
   free(c->h_plot[r]); c->h_plot[r] = NULL;
   if (d_plot) hipFree(d_plot);
   if (e) smg_engine_destroy(e);
