@@ -1,0 +1,85 @@
+/* smg_count.h -- C ABI of the k-mer counter (libsmg_count.so, gfx950).
+ *
+ * Reads in, canonical k-mer table out: what FastK does in front of `hetmers`, on one MI355X.
+ *   - input: plain FASTA / FASTQ (first byte '>' or '@'); gzip is refused;
+ *   - bases ACGTacgt code to 0..3, every other byte ends the current stretch, no k-mer spans two records;
+ *   - every window of k bases counts once for the smaller of the k-mer and its reverse complement
+ *     (left-aligned big-endian words, the order of the FastK table);
+ *   - counts saturate at 32767; the table holds the k-mers with count >= t, sorted, one entry each;
+ *   - hist[c] = number of distinct canonical k-mers with count c BEFORE trimming, c = 1..32767
+ *     (the last bin holds the saturated ones, hist[0] is 0).
+ * The result does not depend on the number of host threads, the batch size or the order of the files.
+ * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
+ * return SMG_ENODEV; smg_count_parse and smg_count_version need no device.
+ */
+#ifndef SMG_COUNT_H
+#define SMG_COUNT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef SMG_OK
+#define SMG_OK        0
+#define SMG_ENODEV   -1      /* no usable HIP device / HIP runtime error                     */
+#define SMG_EINVAL   -2      /* bad argument (k out of range, unreadable or compressed file)  */
+#define SMG_ENOMEM   -3      /* device or host allocation failed, distinct k-mers do not fit  */
+#define SMG_EFORMAT  -4
+#define SMG_ENOTSYM  -5
+#endif
+#ifndef SMG_MAX_KMER
+#define SMG_MAX_KMER  128
+#endif
+
+#define SMG_COUNT_MIN_KMER   13        /* ibyte = 3: kbyte must exceed it              */
+#define SMG_COUNT_MAX_COUNT  32767
+#define SMG_COUNT_HIST       32768     /* hist[0 .. 32767]                              */
+#define SMG_COUNT_SEPARATOR  '\n'      /* the byte between two records of a stripped stream */
+
+typedef struct smg_count_opts
+{ int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
+  int32_t minval;        /* t: keep the k-mers with count >= t (>= 1)            */
+  int32_t device;        /* HIP device ordinal                                   */
+  int32_t host_threads;  /* reader threads, one file each, at most 16 are used  */
+  int32_t verbose;
+} smg_count_opts;
+
+typedef struct smg_count_stats
+{ int64_t bases;         /* sequence bytes read (separators not counted)         */
+  int64_t windows;       /* k-mer instances counted                              */
+  int64_t distinct;      /* distinct canonical k-mers                            */
+  int64_t kept;          /* entries with count >= t                              */
+  int64_t batches;
+  double  ms_read;       /* start until the last reader delivered its last block (overlaps the device work) */
+  double  ms_extract;    /* device events, summed over the batches               */
+  double  ms_sort;
+  double  ms_reduce;     /* runs of the batch + merge into the distinct list     */
+  double  ms_finish;     /* histogram, clamp, trim                               */
+  double  ms_wall;
+} smg_count_stats;
+
+/* *keys: malloc'ed *nels * *key_words uint64, left aligned, sorted; *counts: malloc'ed uint16[*nels];
+   hist: caller's uint64[SMG_COUNT_HIST] or NULL; stats may be NULL.  Release with smg_count_free.  */
+int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *opts,
+                    uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
+                    uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+
+/* the same from a host buffer of sequence bytes in which any byte outside ACGTacgt separates */
+int smg_count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts,
+                    uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
+                    uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+
+/* host only: the stripped byte stream of one file, the sequence of every record with line ends removed
+   and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).            */
+int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen);
+
+void smg_count_free(void *p);
+const char *smg_count_version(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,140 @@
+"""ctypes binding of the k-mer counter (include/smg_count.h, libsmg_count.so, built in-tree).
+
+Reads in, canonical FastK-style k-mer table out: the step in front of `hetmers`.  There is no CPU
+fallback: the counting calls raise `CountError` without a HIP device; `parse` needs none.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import ktab
+
+MIN_KMER, MAX_KMER, MAX_COUNT, HIST = 13, 128, 32767, 32768
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
+BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
+
+EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_parse", "smg_count_free", "smg_count_version"]
+
+
+class CountError(RuntimeError):
+    def __init__(self, code: int, msg: str):
+        super().__init__(f"smg_count error {code}: {msg}")
+        self.code = code
+
+
+class Opts(C.Structure):
+    _fields_ = [("kmer", C.c_int32), ("minval", C.c_int32), ("device", C.c_int32),
+                ("host_threads", C.c_int32), ("verbose", C.c_int32)]
+
+
+class Stats(C.Structure):
+    _fields_ = [("bases", C.c_int64), ("windows", C.c_int64), ("distinct", C.c_int64), ("kept", C.c_int64),
+                ("batches", C.c_int64), ("ms_read", C.c_double), ("ms_extract", C.c_double), ("ms_sort", C.c_double),
+                ("ms_reduce", C.c_double), ("ms_finish", C.c_double), ("ms_wall", C.c_double)]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+_lib = None
+
+
+def load_library():
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise CountError(-1, f"{LIB_PATH} is missing: run __graft_entry__.build() (there is no CPU fallback)")
+    from .engine import _share_torch_hip_runtime      # one HIP runtime per process, torch's if torch is installed
+    _share_torch_hip_runtime()
+    lib = C.CDLL(LIB_PATH)
+    vp = C.c_void_p
+    tail = [C.POINTER(Opts), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), vp,
+            C.POINTER(Stats), C.c_char_p, C.c_size_t]
+    lib.smg_count_files.argtypes = [C.POINTER(C.c_char_p), C.c_int] + tail
+    lib.smg_count_files.restype = C.c_int
+    lib.smg_count_bases.argtypes = [vp, C.c_int64] + tail
+    lib.smg_count_bases.restype = C.c_int
+    lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_parse.restype = C.c_int
+    lib.smg_count_free.argtypes = [vp]
+    lib.smg_count_free.restype = None
+    lib.smg_count_version.restype = C.c_char_p
+    _lib = lib
+    return lib
+
+
+def version() -> str:
+    return load_library().smg_count_version().decode()
+
+
+def keys_to_packed(keys: np.ndarray, k: int) -> np.ndarray:
+    """[N,W] uint64 left-aligned words -> [N,kbyte] uint8 packed (the layout of ktab.KTable.packed)."""
+    n = keys.shape[0]
+    kb = ktab.kbyte_of(k)
+    return np.ascontiguousarray(keys.astype(">u8").view(np.uint8).reshape(n, 8 * keys.shape[1])[:, :kb])
+
+
+def _table(k, t, keys, counts):
+    packed = keys_to_packed(keys, k)
+    pre = np.zeros(len(counts), dtype=np.int64)
+    for j in range(3):
+        pre = (pre << 8) | packed[:, j].astype(np.int64)
+    index = np.cumsum(np.bincount(pre, minlength=1 << 24)).astype(np.int64)
+    return ktab.KTable(k, 3, 1, t, packed, counts, index, np.array([len(counts)], np.int64))
+
+
+def _run(call, k, t, device, threads):
+    lib = load_library()
+    opts = Opts(int(k), int(t), int(device), int(threads), 0)
+    keys, cnt = C.c_void_p(), C.c_void_p()
+    nels, words = C.c_int64(0), C.c_int(0)
+    hist = np.zeros(HIST, dtype=np.uint64)
+    st = Stats()
+    err = C.create_string_buffer(1024)
+    rc = call(lib, C.byref(opts), C.byref(keys), C.byref(cnt), C.byref(nels), C.byref(words),
+              hist.ctypes.data_as(C.c_void_p), C.byref(st), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        n, w = nels.value, words.value
+        k64 = np.ctypeslib.as_array(C.cast(keys, C.POINTER(C.c_uint64)), shape=(max(n, 1) * w,))[: n * w].copy().reshape(n, w)
+        c16 = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint16)), shape=(max(n, 1),))[:n].copy()
+    finally:
+        lib.smg_count_free(keys)
+        lib.smg_count_free(cnt)
+    return _table(int(k), int(t), k64, c16), hist, st.asdict()
+
+
+def count_files(paths, k, t=4, device=0, threads=4):
+    """-> (ktab.KTable of the canonical k-mers with count >= t, hist uint64[32768], stats dict)"""
+    paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
+    arr = (C.c_char_p * len(paths))(*paths)
+    return _run(lambda lib, *a: lib.smg_count_files(arr, len(paths), *a), k, t, device, threads)
+
+
+def count_bases(seq, k, t=4, device=0, threads=4):
+    """The same from sequence bytes (bytes or a uint8 array) in which any byte outside ACGTacgt separates."""
+    buf = np.ascontiguousarray(np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray, memoryview)) else seq,
+                               dtype=np.uint8)
+    return _run(lambda lib, *a: lib.smg_count_bases(buf.ctypes.data_as(C.c_void_p), buf.size, *a), k, t, device, threads)
+
+
+def parse(path) -> bytes:
+    """Host only: the stripped byte stream of one FASTA / FASTQ file, one '\\n' between two records."""
+    lib = load_library()
+    seq, n = C.c_void_p(), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_parse(os.fsencode(path), C.byref(seq), C.byref(n), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(seq, n.value)
+    finally:
+        lib.smg_count_free(seq)

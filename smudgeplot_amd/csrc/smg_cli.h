@@ -50,7 +50,7 @@ __attribute__((unused)) static void system_x(const char *command)       /* Syste
 static int Load_Threads = 1;           /* -T: host threads that read the part files */
 static int Load_Lazy = 0;              /* 1: leave the records on disk (smg_ktab_open), the engine pulls them */
 
-static void load_or_die(const char *name, smg_ktab *T)
+__attribute__((unused)) static void load_or_die(const char *name, smg_ktab *T)
 { char what[4096];
   switch (Load_Lazy ? smg_ktab_open(name, T, what) : smg_ktab_load_mt(name, T, what, Load_Threads))
   { case SMG_KTAB_OK:
@@ -259,6 +259,87 @@ __attribute__((unused)) static void smg_cli_table_view(const smg_ktab *T, smg_ta
   tv->part_data = (const uint8_t *const *) T->part;
   tv->part_nels = T->part_nels;
   tv->prefix_index = T->index;
+}
+
+static int smg_cli_write_all(FILE *f, const void *p, size_t n) { return fwrite(p, 1, n, f) == n ? 0 : -1; }
+
+/* Write a sorted, duplicate-free table as format F (libfastk.c:786-908 reads it back): stub = kmer, nparts, minval,
+   ibyte, index[]; part p = kmer, n_p, n_p records of (hbyte suffix bytes + uint16 count).  keys: n entries of W
+   left-aligned 64-bit words.  target: root name, with or without ".ktab".  0, or -1 after a message on stderr.   */
+__attribute__((unused)) static int smg_cli_write_ktab(const char *target, int kmer, int ibyte, int nparts_in, int minval,
+                                                      const uint64_t *keys, const uint16_t *cnt, int64_t n, int W)
+{ const int kbyte = (kmer + 3) >> 2, hbyte = kbyte - ibyte, pbyte = hbyte + 2;
+  const int nparts = nparts_in > 0 ? nparts_in : 1;
+  const int64_t ixlen = (int64_t) 1 << (8 * ibyte);
+  int64_t *index = (int64_t *) calloc((size_t) ixlen, sizeof(int64_t));
+  int64_t *cut = (int64_t *) malloc(sizeof(int64_t) * (size_t) (nparts + 1));
+  uint8_t *rec = (uint8_t *) malloc((size_t) (n > 0 ? n : 1) * pbyte);
+  char *root = path_n_root(target, ".ktab");
+  const char *slash = root ? strrchr(root, '/') : NULL;
+  char *dir = root == NULL ? NULL : slash ? strndup(root, (size_t) (slash - root)) : strdup(".");
+  const char *base = slash ? slash + 1 : root;
+  char *path = root ? (char *) malloc(strlen(root) + 64) : NULL;
+  int64_t e, p;
+  int32_t hdr[4];
+  int rc = 0;
+  FILE *f;
+  if (!index || !cut || !rec || !root || !dir || !path)
+    { fprintf(stderr, "%s: Out of memory (Allocating k-mer table)\n", Prog_Name); rc = -1; }
+  if (rc == 0)
+    { for (e = 0; e < n; e++)
+        { uint8_t kb[SMG_MAX_KMER / 4 + 8];
+          int64_t pre = 0;
+          int b;
+          for (b = 0; b < kbyte; b++) kb[b] = (uint8_t) (keys[e * W + (b >> 3)] >> (56 - 8 * (b & 7)));
+          for (b = 0; b < ibyte; b++) pre = (pre << 8) | kb[b];
+          index[pre] += 1;
+          memcpy(rec + (size_t) e * pbyte, kb + ibyte, (size_t) hbyte);
+          rec[(size_t) e * pbyte + hbyte] = (uint8_t) (cnt[e] & 0xFF);
+          rec[(size_t) e * pbyte + hbyte + 1] = (uint8_t) (cnt[e] >> 8);
+        }
+      for (p = 1; p < ixlen; p++) index[p] += index[p - 1];            /* cumulative END offsets */
+      cut[0] = 0; cut[nparts] = n;
+      for (p = 1; p < nparts; p++)                                      /* parts break on prefix boundaries */
+        { const int64_t want = n / nparts * p;
+          int64_t lo = 0, hi = ixlen - 1;
+          while (lo < hi) { const int64_t m = (lo + hi) >> 1; if (index[m] < want) lo = m + 1; else hi = m; }
+          cut[p] = index[lo] > cut[p - 1] ? index[lo] : cut[p - 1];
+        }
+      sprintf(path, "%s/%s.ktab", dir, base);
+      f = fopen(path, "wb");
+      hdr[0] = kmer; hdr[1] = nparts; hdr[2] = minval; hdr[3] = ibyte;
+      if (f == NULL || smg_cli_write_all(f, hdr, sizeof(hdr)) || smg_cli_write_all(f, index, sizeof(int64_t) * (size_t) ixlen) || fclose(f))
+        { fprintf(stderr, "%s: Cannot write %s\n", Prog_Name, path); rc = -1; }
+      for (p = 0; p < nparts && rc == 0; p++)
+        { const int64_t np = cut[p + 1] - cut[p];
+          const int32_t km = kmer;
+          sprintf(path, "%s/.%s.ktab.%d", dir, base, (int) p + 1);
+          f = fopen(path, "wb");
+          if (f == NULL || smg_cli_write_all(f, &km, 4) || smg_cli_write_all(f, &np, 8)
+              || smg_cli_write_all(f, rec + (size_t) cut[p] * pbyte, (size_t) np * pbyte) || fclose(f))
+            { fprintf(stderr, "%s: Cannot write %s\n", Prog_Name, path); rc = -1; }
+        }
+    }
+  free(index); free(cut); free(rec); free(root); free(dir); free(path);
+  return rc;
+}
+
+/* remove the stub and the part files 1..nparts of a table (a run that failed half way leaves none behind) */
+__attribute__((unused)) static void smg_cli_remove_ktab(const char *target, int nparts)
+{ char *root = path_n_root(target, ".ktab");
+  const char *slash = root ? strrchr(root, '/') : NULL;
+  char *path = root ? (char *) malloc(2 * strlen(root) + 64) : NULL;
+  int p;
+  if (path != NULL)
+    { sprintf(path, "%s.ktab", root);
+      remove(path);
+      for (p = 1; p <= nparts; p++)
+        { if (slash) sprintf(path, "%.*s/.%s.ktab.%d", (int) (slash - root), root, slash + 1, p);
+          else sprintf(path, ".%s.ktab.%d", root, p);
+          remove(path);
+        }
+    }
+  free(root); free(path);
 }
 
 __attribute__((unused)) static void smg_cli_remove_temp(char *input)

@@ -1,0 +1,918 @@
+// smg_count.hip -- k-mer counter for one MI355X (gfx950, wave64): FASTA / FASTQ in, canonical k-mer table out.
+//
+// What FastK does in front of `hetmers`, on the device (include/smg_count.h is the contract):
+//   host    reader threads (one file each) strip records to sequence bytes, one separator byte between records, into
+//           pinned blocks; the consumer copies them into the batch buffer on the device
+//   batch   kc_extract<W>  bases -> canonical k-mers (left aligned, W = ceil(k/32) words), compacted
+//           rocPRIM radix sort (W = 1: the keys themselves; W > 1: word by word, least significant first)
+//           kc_flag_heads + scan + kc_runs + kc_run_counts: (k-mer, uint32 count) per distinct k-mer of the batch
+//   merge   the batch list and the running distinct list are both duplicate free: after sorting their concatenation
+//           a k-mer occurs at most twice and kc_merge_write adds the right-hand neighbour (uint32, saturating)
+//   finish  kc_finish_flag (histogram, trim flag) + scan + kc_finish_compact (k-mers, uint16 counts clamped to 32767)
+// A batch boundary never loses or doubles a window: a piece that does not continue the byte in front of it in the
+// batch buffer is preceded by a separator and the last k-1 bytes of its file's stream (no whole window fits in those).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <rocprim/rocprim.hpp>
+
+#include <fcntl.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <condition_variable>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <deque>
+#include <mutex>
+#include <new>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "smg_count.h"
+#include "smg_device.hpp"
+
+#define KC_TPB   256
+#define KC_TILE  4096                    // positions per workgroup: 16 bytes per thread
+#define KC_HALO  128                     // >= SMG_MAX_KMER - 1, a multiple of 16
+#define KC_CHUNKS ((KC_TILE + KC_HALO) / 16)
+#define KC_HBINS 8192                    // counts below this go through per-workgroup LDS bins
+
+// ---------------------------------------------------------------------------------------------------------------
+//  device code
+// ---------------------------------------------------------------------------------------------------------------
+
+// 64 bits of a big-endian bit stream kept in 64-bit words, from bit `pos` on (reads s[pos/64] and the word behind it)
+SMG_DEV u64 kc_take64(const u64 *s, int pos)
+{ const int q = pos >> 6, sh = pos & 63;
+  const u64 a = s[q], b = s[q + 1];
+  return sh ? (a << sh) | (b >> (64 - sh)) : a;
+}
+
+// four sequence bytes -> 2-bit codes (first byte in the top bits of an 8-bit group) and one validity bit each
+SMG_DEV void kc_code4(unsigned v, unsigned &code, unsigned &valid)
+{
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    { const unsigned b = (v >> (8 * j)) & 0xFFu, u = b & 0xDFu;
+      const unsigned ok = (u == 'A') | (u == 'C') | (u == 'G') | (u == 'T');
+      code = (code << 2) | ((((b >> 1) & 3u) ^ ((b >> 2) & 1u)) & (0u - ok));   // a c g t -> 0 1 2 3 (ktab.pack_bases)
+      valid = (valid << 1) | ok;
+    }
+}
+
+template <int W> SMG_DEV bool kc_all_ones(const Key<W> &x)
+{ bool e = true;
+#pragma unroll
+  for (int w = 0; w < W; w++) e &= (x.w[w] == ~0ull);
+  return e;
+}
+
+// One workgroup per tile of KC_TILE sequence bytes plus a halo of k-1.  The bytes are coded into two LDS bit streams
+// (2-bit codes, validity), both big endian so that one funnel shift serves both; position p starts a window when the
+// k validity bits from p on are all set.  The canonical k-mers of the tile go out in position order behind ONE atomic
+// per workgroup (64 ballot counts, scanned by the first wavefront): 1 byte in per position, 8 W bytes out per window.
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_extract(const uint8_t *__restrict__ seq, int64_t n, int k, u64 *__restrict__ out, unsigned long long *__restrict__ nout)
+{ __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
+  __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
+  __shared__ unsigned s_cnt[64];
+  __shared__ unsigned long long s_base;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int64_t tile0 = (int64_t) blockIdx.x * KC_TILE;
+  unsigned *c32 = reinterpret_cast<unsigned *>(s_code);
+  uint16_t *v16 = reinterpret_cast<uint16_t *>(s_val);
+
+  if (t < 4) c32[(KC_CHUNKS + t) ^ 1] = 0;
+  if (t < 8) v16[(KC_CHUNKS + t) ^ 3] = 0;
+  for (int c = t; c < KC_CHUNKS; c += KC_TPB)
+    { const int64_t g = tile0 + 16 * (int64_t) c;
+      uint4 v = make_uint4(0, 0, 0, 0);                      // (byte 0 is no base: past the end nothing is valid)
+      if (g + 16 <= n) v = *reinterpret_cast<const uint4 *>(seq + g);
+      else if (g < n)
+        { unsigned d[4] = { 0, 0, 0, 0 };
+          for (int b = 0; b < 16 && g + b < n; b++) d[b >> 2] |= (unsigned) seq[g + b] << (8 * (b & 3));
+          v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+      unsigned code = 0, valid = 0;
+      kc_code4(v.x, code, valid); kc_code4(v.y, code, valid); kc_code4(v.z, code, valid); kc_code4(v.w, code, valid);
+      c32[c ^ 1] = code;                                     // (^1, ^3: the first chunk of a 64-bit word in its top bits)
+      v16[c ^ 3] = (uint16_t) valid;
+    }
+  __syncthreads();
+
+  // which of this thread's 16 positions (p = j * 256 + t: neighbouring lanes, neighbouring windows) start a window
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < KC_TILE / KC_TPB; j++)
+    { const int p = j * KC_TPB + t;
+      const u64 x0 = kc_take64(s_val, p);
+      bool ok = tile0 + p + k <= n;
+      if (k <= 64) ok &= (~x0 >> (64 - k)) == 0;
+      else
+        { const u64 x1 = kc_take64(s_val, p + 64);
+          ok &= (x0 == ~0ull) & ((~x1 >> (128 - k)) == 0);
+        }
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0) s_cnt[j * 4 + wave] = (unsigned) __popcll(bal);
+      mine |= (unsigned) ok << j;
+    }
+  __syncthreads();
+  if (wave == 0)
+    { const unsigned own = s_cnt[lane];
+      unsigned inc = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1)
+        { const unsigned up = __shfl_up(inc, o, 64);
+          if (lane >= o) inc += up;
+        }
+      s_cnt[lane] = inc - own;
+      if (lane == 63) s_base = inc ? atomicAdd(nout, (unsigned long long) inc) : 0ull;
+    }
+  __syncthreads();
+  const unsigned long long base = s_base;
+  const int rem = 2 * k - 64 * (W - 1);                      // bits of the last word that belong to the k-mer
+  const u64 lastmask = ~0ull << (64 - rem);
+  for (int j = 0; j < KC_TILE / KC_TPB; j++)                 // (the trip count is uniform: every lane meets every ballot)
+    { const bool ok = (mine >> j) & 1u;
+      const unsigned long long bal = __ballot(ok);
+      if (ok)
+        { const int p = j * KC_TPB + t;
+          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned) (bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) bal, 0u));
+          Key<W> x;
+#pragma unroll
+          for (int w = 0; w < W; w++) x.w[w] = kc_take64(s_code, 2 * p + 64 * w);
+          x.w[W - 1] &= lastmask;
+          const Key<W> r = revcomp<W>(x, k);
+          const bool lt = key_lt<W>(r, x);
+          u64 *o = out + (size_t) (base + s_cnt[j * 4 + wave] + rank) * W;
+#pragma unroll
+          for (int w = 0; w < W; w++) o[w] = lt ? r.w[w] : x.w[w];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(KC_TPB) kc_iota(uint32_t *__restrict__ p, int64_t n)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i < n) p[i] = (uint32_t) i;
+}
+
+__global__ void __launch_bounds__(KC_TPB)
+kc_gather_word(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, int W, int w, int64_t n, u64 *__restrict__ o)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i < n) o[i] = keys[(size_t) perm[i] * W + w];
+}
+
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_gather_entries(const u64 *__restrict__ keys, const uint32_t *__restrict__ val, const uint32_t *__restrict__ perm, int64_t n,
+                  u64 *__restrict__ okeys, uint32_t *__restrict__ oval)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t s = perm[i];
+  const Key<W> x = load_key<W>(keys, s);
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[(size_t) i * W + w] = x.w[w];
+  if (val) oval[i] = val[s];
+}
+
+// head flags on sorted keys; an all-ones key is no k-mer (never canonical: the complement of t..t is a..a, pad bits are 0)
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_flag_heads(const u64 *__restrict__ keys, int64_t n, uint32_t *__restrict__ flag)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  bool head = !kc_all_ones<W>(x);
+  if (head && i > 0) head = !key_eq<W>(x, load_key<W>(keys, i - 1));
+  flag[i] = head;
+}
+
+// run j starts at start[j]; start[number of runs] = number of k-mers
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_runs(const u64 *__restrict__ keys, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
+        u64 *__restrict__ ukeys, uint32_t *__restrict__ start)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  if (kc_all_ones<W>(x)) return;
+  const uint32_t f = flag[i], q = pos[i];
+  if (f)
+    {
+#pragma unroll
+      for (int w = 0; w < W; w++) ukeys[(size_t) q * W + w] = x.w[w];
+      start[q] = (uint32_t) i;
+    }
+  if (i == n - 1 || kc_all_ones<W>(load_key<W>(keys, i + 1))) start[q + f] = (uint32_t) (i + 1);
+}
+
+__global__ void __launch_bounds__(KC_TPB)
+kc_run_counts(const uint32_t *__restrict__ start, int64_t nruns, uint32_t *__restrict__ cnt)
+{ const int64_t j = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (j < nruns) cnt[j] = start[j + 1] - start[j];
+}
+
+// both merged lists were duplicate free: a k-mer occurs once or twice, the head takes its right-hand neighbour's count
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_merge_write(const u64 *__restrict__ keys, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ flag,
+               const uint32_t *__restrict__ pos, int64_t n, u64 *__restrict__ okeys, uint32_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const Key<W> x = load_key<W>(keys, i);
+  uint32_t c = cnt[i];
+  if (i + 1 < n && key_eq<W>(x, load_key<W>(keys, i + 1)))
+    { const uint32_t s = c + cnt[i + 1];
+      c = s < c ? 0xFFFFFFFFu : s;
+    }
+  const uint32_t q = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[(size_t) q * W + w] = x.w[w];
+  ocnt[q] = c;
+}
+
+// histogram of the clamped counts (LDS bins below KC_HBINS, flushed once per workgroup; the rare larger counts go
+// straight to the global bins) and the trim flag
+__global__ void __launch_bounds__(KC_TPB)
+kc_finish_flag(const uint32_t *__restrict__ cnt, int64_t n, unsigned t, unsigned long long *__restrict__ hist, uint32_t *__restrict__ flag)
+{ __shared__ unsigned h[KC_HBINS];
+  for (int b = threadIdx.x; b < KC_HBINS; b += KC_TPB) h[b] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x; i < n; i += (int64_t) gridDim.x * KC_TPB)
+    { unsigned c = cnt[i];
+      if (c > SMG_COUNT_MAX_COUNT) c = SMG_COUNT_MAX_COUNT;
+      flag[i] = c >= t;
+      if (c < KC_HBINS) atomicAdd(&h[c], 1u); else atomicAdd(&hist[c], 1ull);
+    }
+  __syncthreads();
+  for (int b = threadIdx.x; b < KC_HBINS; b += KC_TPB)
+    if (h[b]) atomicAdd(&hist[b], (unsigned long long) h[b]);
+}
+
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_finish_compact(const u64 *__restrict__ keys, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ flag,
+                  const uint32_t *__restrict__ pos, int64_t n, u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const Key<W> x = load_key<W>(keys, i);
+  const uint32_t q = pos[i], c = cnt[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[(size_t) q * W + w] = x.w[w];
+  ocnt[q] = (uint16_t) (c > SMG_COUNT_MAX_COUNT ? SMG_COUNT_MAX_COUNT : c);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+//  host: errors, parser
+// ---------------------------------------------------------------------------------------------------------------
+
+static int fail(char *errbuf, size_t errlen, int code, const char *fmt, ...)
+{ if (errbuf && errlen)
+    { va_list ap;
+      va_start(ap, fmt);
+      vsnprintf(errbuf, errlen, fmt, ap);
+      va_end(ap);
+    }
+  return code;
+}
+
+static double now_ms()
+{ return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+struct Sink
+{ virtual bool put(const uint8_t *p, size_t n) = 0;          // false: the consumer gave up
+  virtual ~Sink() {}
+};
+
+// Line-wise state machine over the bytes of one file, fed in arbitrary pieces.  A '\r' is dropped only in front of a
+// '\n' or at the end of the file; anywhere else it is a byte like any other (and ends a stretch).
+struct Parser
+{ Sink &out;
+  int fmt = 0, phase = 0, kind = 0;                           // fmt 1 FASTA, 2 FASTQ; kind 0 skip, 1 sequence, 2 blank
+  bool bol = true, first = true, pending_cr = false, started = false;
+  int64_t bases = 0;
+  explicit Parser(Sink &s) : out(s) {}
+
+  bool emit(const uint8_t *p, size_t n) { bases += (int64_t) n; return n == 0 || out.put(p, n); }
+  bool record() { const uint8_t sep = SMG_COUNT_SEPARATOR; const bool ok = first || out.put(&sep, 1); first = false; return ok; }
+
+  // 0 ok, 1 the consumer gave up, SMG_EINVAL with a message
+  int feed(const uint8_t *p, size_t n, const char *path, char *errbuf, size_t errlen)
+  { size_t i = 0;
+    if (n == 0) return 0;
+    if (!started)
+      { started = true;
+        if (p[0] == 0x1f && (n < 2 || p[1] == 0x8b))
+          return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
+        if (p[0] == '>') fmt = 1;
+        else if (p[0] == '@') fmt = 2;
+        else return fail(errbuf, errlen, SMG_EINVAL, "%s is neither FASTA nor FASTQ (first byte 0x%02x)", path, p[0]);
+      }
+    if (pending_cr)
+      { const uint8_t cr = '\r';
+        pending_cr = false;
+        if (p[0] != '\n' && !emit(&cr, 1)) return 1;
+      }
+    while (i < n)
+      { if (bol)
+          { const uint8_t c = p[i];
+            bol = false;
+            if (fmt == 1)
+              { kind = c != '>';
+                if (c == '>' && !record()) return 1;
+              }
+            else if (phase == 0)
+              { kind = (c == '\n' || c == '\r') ? 2 : 0;     // (blank lines between records are passed over)
+                if (kind == 0 && !record()) return 1;
+              }
+            else kind = phase == 1;
+          }
+        const uint8_t *nl = (const uint8_t *) memchr(p + i, '\n', n - i);
+        const size_t end = nl ? (size_t) (nl - p) : n;
+        if (kind == 1)
+          { size_t e = end;
+            if (e > i && p[e - 1] == '\r') { e--; if (!nl) pending_cr = true; }
+            if (!emit(p + i, e - i)) return 1;
+          }
+        if (nl)
+          { bol = true;
+            if (fmt == 2 && kind != 2) phase = (phase + 1) & 3;
+            i = end + 1;
+          }
+        else i = n;
+      }
+    return 0;
+  }
+};
+
+static int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases, char *errbuf, size_t errlen)
+{ std::vector<uint8_t> buf((size_t) 4 << 20);
+  Parser ps(sink);
+  for (;;)
+    { const ssize_t got = read(fd, buf.data(), buf.size());
+      if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+      if (got == 0) break;
+      const int rc = ps.feed(buf.data(), (size_t) got, path, errbuf, errlen);
+      if (rc) return rc;
+    }
+  if (bases) *bases = ps.bases;
+  return 0;
+}
+
+struct GrowSink : Sink
+{ uint8_t *p = nullptr; size_t len = 0, cap = 0;
+  bool put(const uint8_t *s, size_t n) override
+  { if (len + n > cap)
+      { size_t nc = cap ? cap * 2 : (size_t) 1 << 16;
+        while (nc < len + n) nc *= 2;
+        uint8_t *q = (uint8_t *) realloc(p, nc);
+        if (!q) throw std::bad_alloc();
+        p = q; cap = nc;
+      }
+    memcpy(p + len, s, n); len += n;
+    return true;
+  }
+  ~GrowSink() override { free(p); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+//  host: the device side of a run
+// ---------------------------------------------------------------------------------------------------------------
+
+#define DCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) \
+    return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (" #call ")", hipGetErrorString(_e)); } while (0)
+#define RCHK(call) do { const int _rc = (call); if (_rc) return _rc; } while (0)
+#define DISPATCH_W(CALL) switch (W) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; default: CALL(4); break; }
+
+struct Dev                                                     // a device allocation that frees itself
+{ void *p = nullptr;
+  ~Dev() { if (p) (void) hipFree(p); }
+  void reset() { if (p) (void) hipFree(p); p = nullptr; }
+  void take(Dev &o) { reset(); p = o.p; o.p = nullptr; }
+  template <class T> T *as() const { return (T *) p; }
+};
+
+static unsigned nblk(int64_t n) { return (unsigned) ((n + KC_TPB - 1) / KC_TPB); }
+
+struct Counter
+{ int k = 0, W = 1, t = 1;
+  char *errbuf = nullptr; size_t errlen = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int64_t cap = 0;                                             // bytes of sequence a batch holds
+  int64_t fill = 0;                                            // bytes in the batch buffer
+  int last_file = -1;                                          // the file whose stream ends at `fill`
+  std::vector<std::vector<uint8_t>> tails;                     // per file: the last k-1 bytes handed over
+  Dev seq, ka, kb, flag, pos, start, tmp, ctr, dk, dc;         // dk, dc: the running distinct list (k-mers, uint32 counts)
+  size_t tmp_cap = 0;
+  int64_t nd = 0;
+  smg_count_stats st;
+
+  ~Counter()
+  { if (ev0) (void) hipEventDestroy(ev0);
+    if (ev1) (void) hipEventDestroy(ev1);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
+
+  int alloc(Dev &d, size_t bytes)
+  { d.reset();
+    const hipError_t e = hipMalloc(&d.p, bytes ? bytes : 16);
+    if (e != hipSuccess)
+      { d.p = nullptr;
+        return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV,
+                    "cannot allocate %.3f GB of device memory: %s", (double) bytes * 1e-9, hipGetErrorString(e));
+      }
+    return 0;
+  }
+
+  int need_tmp(size_t bytes)
+  { if (bytes <= tmp_cap) return 0;
+    RCHK(alloc(tmp, bytes + 256));
+    tmp_cap = bytes + 256;
+    return 0;
+  }
+
+  void tic() { (void) hipEventRecord(ev0, stream); }
+  int toc(double *acc)
+  { float ms = 0;
+    DCHK(hipEventRecord(ev1, stream));
+    DCHK(hipEventSynchronize(ev1));
+    DCHK(hipEventElapsedTime(&ms, ev0, ev1));
+    *acc += ms;
+    return 0;
+  }
+
+  // Memory plan, before the first allocation: a third of what is free goes to the batch (sequence, two key buffers,
+  // flags, positions, run starts, and the word sort's scratch for W > 1), the rest is left to the distinct list and
+  // its merge.  `bound` is the most sequence the input can hold.
+  int init(const smg_count_opts *o, int64_t bound, int nfiles, char *eb, size_t el)
+  { errbuf = eb; errlen = el;
+    memset(&st, 0, sizeof(st));
+    k = o->kmer; t = o->minval; W = (k + 31) / 32;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+      return fail(errbuf, errlen, SMG_ENODEV, "no HIP device: the k-mer counter has no CPU fallback%s", "");
+    if (o->device < 0 || o->device >= ndev) return fail(errbuf, errlen, SMG_EINVAL, "device %d of %d", o->device, ndev);
+    DCHK(hipSetDevice(o->device));
+    size_t free_b = 0, total_b = 0;
+    DCHK(hipMemGetInfo(&free_b, &total_b));
+    const int64_t per = 1 + 16 * W + 12 + (W > 1 ? 24 : 0);
+    int64_t c = (int64_t) (free_b / 3) / per;
+    if (c > ((int64_t) 1 << 30)) c = (int64_t) 1 << 30;
+    const char *hook = getenv("SMG_COUNT_BATCH_BASES");
+    if (hook && atoll(hook) > 0) c = atoll(hook) + k;
+    if (c > bound + k + 1) c = bound + k + 1;
+    if (c < k + 1) c = k + 1;
+    if (c * per > (int64_t) free_b)
+      return fail(errbuf, errlen, SMG_ENOMEM, "a batch of %lld bases needs %.3f GB, %.3f GB of device memory are free",
+                  (long long) c, (double) (c * per) * 1e-9, (double) free_b * 1e-9);
+    cap = c;
+    tails.assign((size_t) (nfiles > 0 ? nfiles : 1), std::vector<uint8_t>());
+    DCHK(hipStreamCreate(&stream));
+    DCHK(hipEventCreate(&ev0));
+    DCHK(hipEventCreate(&ev1));
+    RCHK(alloc(seq, (size_t) cap + 16));
+    RCHK(alloc(ka, sizeof(u64) * (size_t) cap * W));
+    RCHK(alloc(kb, sizeof(u64) * (size_t) cap * W));
+    RCHK(alloc(flag, sizeof(uint32_t) * (size_t) cap));
+    RCHK(alloc(pos, sizeof(uint32_t) * (size_t) cap));
+    RCHK(alloc(start, sizeof(uint32_t) * ((size_t) cap + 1)));
+    RCHK(alloc(ctr, 16));
+    return 0;
+  }
+
+  // bytes of one file's stream, in order; pieces go into the batch buffer, full batches are counted
+  int add(const uint8_t *p, int64_t n, int file)
+  { std::vector<uint8_t> &tail = tails[(size_t) file];
+    while (n > 0)
+      { const bool joined = last_file == file && fill > 0;
+        const int64_t lead = joined ? 0 : 1 + (int64_t) tail.size();
+        if (cap - fill < lead + 1) { RCHK(flush()); continue; }
+        if (!joined)
+          { uint8_t head[SMG_MAX_KMER + 1];
+            head[0] = SMG_COUNT_SEPARATOR;
+            if (!tail.empty()) memcpy(head + 1, tail.data(), tail.size());
+            DCHK(hipMemcpy(seq.as<uint8_t>() + fill, head, (size_t) lead, hipMemcpyHostToDevice));
+            fill += lead;
+          }
+        const int64_t m = n < cap - fill ? n : cap - fill;
+        DCHK(hipMemcpy(seq.as<uint8_t>() + fill, p, (size_t) m, hipMemcpyHostToDevice));
+        fill += m;
+        last_file = file;
+        if (m >= k - 1) tail.assign(p + m - (k - 1), p + m);      // the last k-1 bytes of (tail + piece)
+        else
+          { tail.insert(tail.end(), p, p + m);
+            if ((int64_t) tail.size() > k - 1) tail.erase(tail.begin(), tail.end() - (k - 1));
+          }
+        p += m; n -= m;
+      }
+    return 0;
+  }
+
+  // sorts n entries (W-word k-mers, optional uint32 values) that lie in (a, va); (b, vb) are buffers of the same size.
+  // The result is in (*ko, *vo), one of the two.
+  int sort_entries(u64 *a, u64 *b, uint32_t *va, uint32_t *vb, int64_t n, u64 **ko, uint32_t **vo)
+  { if (W == 1)
+      { rocprim::double_buffer<u64> dk2(a, b);
+        rocprim::double_buffer<uint32_t> dv2(va, vb);
+        // All 64 bits, not 64-2k .. 64: the pad bits are zero, so the order is the same, and rocPRIM's merge-sort path
+        // (inputs below its radix threshold) left runs of 1024 keys unmerged when given a begin bit above 0.
+        const unsigned b0 = 0u;
+        size_t bytes = 0;
+        if (va) { DCHK(rocprim::radix_sort_pairs(nullptr, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
+        else { DCHK(rocprim::radix_sort_keys(nullptr, bytes, dk2, (size_t) n, b0, 64u, stream)); }
+        RCHK(need_tmp(bytes));
+        if (va) { DCHK(rocprim::radix_sort_pairs(tmp.p, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
+        else { DCHK(rocprim::radix_sort_keys(tmp.p, bytes, dk2, (size_t) n, b0, 64u, stream)); }
+        *ko = dk2.current();
+        if (vo) *vo = va ? dv2.current() : nullptr;
+        return 0;
+      }
+    // W > 1: stable sorts of (word, permutation), least significant word first, then one gather
+    Dev w1, w2, p1, p2;
+    RCHK(alloc(w1, sizeof(u64) * (size_t) n)); RCHK(alloc(w2, sizeof(u64) * (size_t) n));
+    RCHK(alloc(p1, sizeof(uint32_t) * (size_t) n)); RCHK(alloc(p2, sizeof(uint32_t) * (size_t) n));
+    rocprim::double_buffer<uint32_t> perm(p1.as<uint32_t>(), p2.as<uint32_t>());
+    hipLaunchKernelGGL(kc_iota, dim3(nblk(n)), dim3(KC_TPB), 0, stream, perm.current(), n);
+    for (int w = W - 1; w >= 0; w--)
+      { rocprim::double_buffer<u64> word(w1.as<u64>(), w2.as<u64>());
+        hipLaunchKernelGGL(kc_gather_word, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, perm.current(), W, w, n, word.current());
+        size_t bytes = 0;
+        DCHK(rocprim::radix_sort_pairs(nullptr, bytes, word, perm, (size_t) n, 0u, 64u, stream));
+        RCHK(need_tmp(bytes));
+        DCHK(rocprim::radix_sort_pairs(tmp.p, bytes, word, perm, (size_t) n, 0u, 64u, stream));
+      }
+#define CALL(WW) hipLaunchKernelGGL(kc_gather_entries<WW>, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, va, perm.current(), n, b, vb)
+    DISPATCH_W(CALL)
+#undef CALL
+    DCHK(hipStreamSynchronize(stream));                        // (the scratch is freed on return)
+    *ko = b;
+    if (vo) *vo = va ? vb : nullptr;
+    return 0;
+  }
+
+  // exclusive scan of fl[0..n) into ps[], the total to the host
+  int scan(uint32_t *fl, uint32_t *ps, int64_t n, int64_t *total)
+  { size_t bytes = 0;
+    DCHK(rocprim::exclusive_scan(nullptr, bytes, fl, ps, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
+    RCHK(need_tmp(bytes));
+    DCHK(rocprim::exclusive_scan(tmp.p, bytes, fl, ps, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
+    uint32_t last[2] = { 0, 0 };
+    DCHK(hipMemcpyAsync(&last[0], fl + n - 1, 4, hipMemcpyDeviceToHost, stream));
+    DCHK(hipMemcpyAsync(&last[1], ps + n - 1, 4, hipMemcpyDeviceToHost, stream));
+    DCHK(hipStreamSynchronize(stream));
+    *total = (int64_t) last[0] + last[1];
+    return 0;
+  }
+
+  // the batch buffer -> (k-mer, count) runs -> merged into the distinct list
+  int flush()
+  { const int64_t n = fill;
+    fill = 0; last_file = -1;
+    if (n < k) return 0;
+    st.batches++;
+    tic();
+    DCHK(hipMemsetAsync(ctr.p, 0, 16, stream));
+    const unsigned ntiles = (unsigned) ((n + KC_TILE - 1) / KC_TILE);
+#define CALL(WW) hipLaunchKernelGGL(kc_extract<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, seq.as<uint8_t>(), n, k, ka.as<u64>(), \
+                                    ctr.as<unsigned long long>())
+    DISPATCH_W(CALL)
+#undef CALL
+    DCHK(hipGetLastError());
+    unsigned long long nwin = 0;
+    DCHK(hipMemcpyAsync(&nwin, ctr.p, 8, hipMemcpyDeviceToHost, stream));
+    RCHK(toc(&st.ms_extract));
+    if (nwin == 0) return 0;
+    if ((int64_t) nwin > cap) return fail(errbuf, errlen, SMG_ENODEV, "internal error: %llu windows from %lld bytes", nwin, (long long) n);
+    st.windows += (int64_t) nwin;
+    u64 *sorted = nullptr;
+    tic();
+    RCHK(sort_entries(ka.as<u64>(), kb.as<u64>(), nullptr, nullptr, (int64_t) nwin, &sorted, nullptr));
+    RCHK(toc(&st.ms_sort));
+    u64 *uk = sorted == ka.as<u64>() ? kb.as<u64>() : ka.as<u64>();
+    int64_t nruns = 0;
+    tic();
+#define CALL(WW) hipLaunchKernelGGL(kc_flag_heads<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, (int64_t) nwin, flag.as<uint32_t>())
+    DISPATCH_W(CALL)
+#undef CALL
+    RCHK(scan(flag.as<uint32_t>(), pos.as<uint32_t>(), (int64_t) nwin, &nruns));
+#define CALL(WW) hipLaunchKernelGGL(kc_runs<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, flag.as<uint32_t>(), pos.as<uint32_t>(), \
+                                    (int64_t) nwin, uk, start.as<uint32_t>())
+    DISPATCH_W(CALL)
+#undef CALL
+    uint32_t *rc = flag.as<uint32_t>();                        // (the flags are spent: the run counts take their place)
+    hipLaunchKernelGGL(kc_run_counts, dim3(nblk(nruns)), dim3(KC_TPB), 0, stream, start.as<uint32_t>(), nruns, rc);
+    DCHK(hipGetLastError());
+    RCHK(merge(uk, rc, nruns));
+    RCHK(toc(&st.ms_reduce));
+    return 0;
+  }
+
+  int merge(const u64 *uk, const uint32_t *rc, int64_t nr)
+  { if (nd == 0)
+      { Dev nk, nc;
+        RCHK(alloc(nk, sizeof(u64) * (size_t) nr * W)); RCHK(alloc(nc, sizeof(uint32_t) * (size_t) nr));
+        DCHK(hipMemcpyAsync(nk.p, uk, sizeof(u64) * (size_t) nr * W, hipMemcpyDeviceToDevice, stream));
+        DCHK(hipMemcpyAsync(nc.p, rc, sizeof(uint32_t) * (size_t) nr, hipMemcpyDeviceToDevice, stream));
+        DCHK(hipStreamSynchronize(stream));
+        dk.take(nk); dc.take(nc); nd = nr;
+        return 0;
+      }
+    const int64_t m = nd + nr;
+    if (m >= 0xFFFFFFF0ll)
+      return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 distinct k-mers (%lld): partitioned counting is not implemented", (long long) m);
+    const size_t ent = sizeof(u64) * W + sizeof(uint32_t);
+    const size_t want = (size_t) m * (3 * ent + 8 + (W > 1 ? 24 : 0)) + ((size_t) 64 << 20);
+    size_t free_b = 0, total_b = 0;
+    DCHK(hipMemGetInfo(&free_b, &total_b));
+    if (want > free_b)
+      return fail(errbuf, errlen, SMG_ENOMEM, "the distinct k-mers of this data set do not fit the device: merging %lld entries needs "
+                  "%.3f GB, %.3f GB are free", (long long) m, (double) want * 1e-9, (double) free_b * 1e-9);
+    Dev ck, cc, ak, ac, mf, mp, nk, nc;
+    RCHK(alloc(ck, sizeof(u64) * (size_t) m * W)); RCHK(alloc(cc, sizeof(uint32_t) * (size_t) m));
+    RCHK(alloc(ak, sizeof(u64) * (size_t) m * W)); RCHK(alloc(ac, sizeof(uint32_t) * (size_t) m));
+    DCHK(hipMemcpyAsync(ck.p, dk.p, sizeof(u64) * (size_t) nd * W, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipMemcpyAsync(ck.as<u64>() + (size_t) nd * W, uk, sizeof(u64) * (size_t) nr * W, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipMemcpyAsync(cc.p, dc.p, sizeof(uint32_t) * (size_t) nd, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipMemcpyAsync(cc.as<uint32_t>() + nd, rc, sizeof(uint32_t) * (size_t) nr, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipStreamSynchronize(stream));
+    dk.reset(); dc.reset(); nd = 0;
+    u64 *sk = nullptr; uint32_t *sc = nullptr;
+    RCHK(sort_entries(ck.as<u64>(), ak.as<u64>(), cc.as<uint32_t>(), ac.as<uint32_t>(), m, &sk, &sc));
+    RCHK(alloc(mf, sizeof(uint32_t) * (size_t) m)); RCHK(alloc(mp, sizeof(uint32_t) * (size_t) m));
+#define CALL(WW) hipLaunchKernelGGL(kc_flag_heads<WW>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, m, mf.as<uint32_t>())
+    DISPATCH_W(CALL)
+#undef CALL
+    int64_t nn = 0;
+    RCHK(scan(mf.as<uint32_t>(), mp.as<uint32_t>(), m, &nn));
+    RCHK(alloc(nk, sizeof(u64) * (size_t) nn * W)); RCHK(alloc(nc, sizeof(uint32_t) * (size_t) nn));
+#define CALL(WW) hipLaunchKernelGGL(kc_merge_write<WW>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, sc, mf.as<uint32_t>(), mp.as<uint32_t>(), m, \
+                                    nk.as<u64>(), nc.as<uint32_t>())
+    DISPATCH_W(CALL)
+#undef CALL
+    DCHK(hipGetLastError());
+    DCHK(hipStreamSynchronize(stream));
+    dk.take(nk); dc.take(nc); nd = nn;
+    return 0;
+  }
+
+  // the last batch, then histogram, clamp, trim; the table goes to malloc'ed host arrays
+  int finish(uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist)
+  { RCHK(flush());
+    seq.reset(); ka.reset(); kb.reset(); start.reset();
+    st.distinct = nd;
+    int64_t kept = 0;
+    Dev dh, ok, oc;
+    tic();
+    RCHK(alloc(dh, sizeof(uint64_t) * SMG_COUNT_HIST));
+    DCHK(hipMemsetAsync(dh.p, 0, sizeof(uint64_t) * SMG_COUNT_HIST, stream));
+    if (nd > 0)
+      { RCHK(alloc(flag, sizeof(uint32_t) * (size_t) nd)); RCHK(alloc(pos, sizeof(uint32_t) * (size_t) nd));
+        const unsigned g = nblk(nd) < 2048u ? nblk(nd) : 2048u;
+        hipLaunchKernelGGL(kc_finish_flag, dim3(g), dim3(KC_TPB), 0, stream, dc.as<uint32_t>(), nd, (unsigned) t,
+                           dh.as<unsigned long long>(), flag.as<uint32_t>());
+        RCHK(scan(flag.as<uint32_t>(), pos.as<uint32_t>(), nd, &kept));
+        RCHK(alloc(ok, sizeof(u64) * (size_t) kept * W)); RCHK(alloc(oc, sizeof(uint16_t) * (size_t) kept));
+#define CALL(WW) hipLaunchKernelGGL(kc_finish_compact<WW>, dim3(nblk(nd)), dim3(KC_TPB), 0, stream, dk.as<u64>(), dc.as<uint32_t>(), \
+                                    flag.as<uint32_t>(), pos.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>())
+        DISPATCH_W(CALL)
+#undef CALL
+        DCHK(hipGetLastError());
+      }
+    RCHK(toc(&st.ms_finish));
+    st.kept = kept;
+    uint64_t *hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (kept > 0 ? kept : 1) * W);
+    uint16_t *hc = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1));
+    if (!hk || !hc) { free(hk); free(hc); return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory for %lld k-mers", (long long) kept); }
+    hipError_t e = hipSuccess;
+    if (kept > 0)
+      { e = hipMemcpy(hk, ok.p, sizeof(uint64_t) * (size_t) kept * W, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(hc, oc.p, sizeof(uint16_t) * (size_t) kept, hipMemcpyDeviceToHost);
+      }
+    if (e == hipSuccess && hist) e = hipMemcpy(hist, dh.p, sizeof(uint64_t) * SMG_COUNT_HIST, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { free(hk); free(hc); return fail(errbuf, errlen, SMG_ENODEV, "HIP error: %s", hipGetErrorString(e)); }
+    *keys = hk; *counts = hc; *nels = kept; *key_words = W;
+    return 0;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+//  host: reader threads and the pinned ring
+// ---------------------------------------------------------------------------------------------------------------
+
+#define RING_BLOCK ((size_t) 8 << 20)
+
+struct Block { uint8_t *p; size_t len; int file; };
+
+struct Ring
+{ std::mutex m;
+  std::condition_variable cv_ready, cv_free;
+  std::deque<Block> ready;
+  std::vector<uint8_t *> idle;
+  int live = 0;                                                // readers still at work
+  bool abort = false;
+  int rc = 0;
+  char err[512] = { 0 };
+  int64_t bases = 0;
+  double t_last = 0;
+};
+
+struct RingSink : Sink
+{ Ring &r; int file; uint8_t *cur = nullptr; size_t len = 0;
+  RingSink(Ring &ring, int f) : r(ring), file(f) {}
+  bool push()
+  { std::unique_lock<std::mutex> lk(r.m);
+    if (r.abort) return false;
+    r.ready.push_back(Block{ cur, len, file });
+    cur = nullptr; len = 0;
+    r.cv_ready.notify_one();
+    return true;
+  }
+  bool put(const uint8_t *p, size_t n) override
+  { while (n)
+      { if (!cur)
+          { std::unique_lock<std::mutex> lk(r.m);
+            r.cv_free.wait(lk, [&] { return r.abort || !r.idle.empty(); });
+            if (r.abort) return false;
+            cur = r.idle.back(); r.idle.pop_back();
+          }
+        const size_t m = n < RING_BLOCK - len ? n : RING_BLOCK - len;
+        memcpy(cur + len, p, m);
+        len += m; p += m; n -= m;
+        if (len == RING_BLOCK && !push()) return false;
+      }
+    return true;
+  }
+  void done()
+  { if (cur && len) push();
+    else if (cur) { std::unique_lock<std::mutex> lk(r.m); r.idle.push_back(cur); cur = nullptr; r.cv_free.notify_one(); }
+  }
+};
+
+static void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step)
+{ for (int f = first; f < npaths; f += step)
+    { char eb[512]; eb[0] = 0;
+      int rc = 0;
+      int64_t bases = 0;
+      try
+        { RingSink sink(*r, f);
+          const int fd = open(paths[f], O_RDONLY);
+          if (fd < 0) rc = fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f]);
+          else
+            { rc = parse_fd(fd, paths[f], sink, &bases, eb, sizeof(eb));
+              close(fd);
+            }
+          if (rc == 0) sink.done();
+        }
+      catch (...) { rc = fail(eb, sizeof(eb), SMG_ENOMEM, "out of host memory while reading %s", paths[f]); }
+      std::unique_lock<std::mutex> lk(r->m);
+      r->bases += bases;
+      if (rc < 0 && !r->rc) { r->rc = rc; memcpy(r->err, eb, sizeof(eb)); r->abort = true; r->cv_free.notify_all(); }
+      if (rc != 0 || r->abort) break;
+    }
+  std::unique_lock<std::mutex> lk(r->m);
+  r->live--;
+  r->t_last = now_ms();
+  r->cv_ready.notify_all();
+}
+
+static int check_opts(const smg_count_opts *o, char *errbuf, size_t errlen)
+{ if (!o) return fail(errbuf, errlen, SMG_EINVAL, "null options%s", "");
+  if (o->kmer < SMG_COUNT_MIN_KMER || o->kmer > SMG_MAX_KMER)
+    return fail(errbuf, errlen, SMG_EINVAL, "k = %d is out of range: the table has a 3-byte prefix index, so k must be %d .. %d",
+                o->kmer, SMG_COUNT_MIN_KMER, SMG_MAX_KMER);
+  if (o->minval < 1 || o->minval > SMG_COUNT_MAX_COUNT)
+    return fail(errbuf, errlen, SMG_EINVAL, "count threshold %d is out of range 1 .. %d", o->minval, SMG_COUNT_MAX_COUNT);
+  return 0;
+}
+
+static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+                       int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+{ const double t0 = now_ms();
+  RCHK(check_opts(opts, errbuf, errlen));
+  if (!paths || npaths < 1 || !keys || !counts || !nels || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  int64_t bound = 0;
+  for (int f = 0; f < npaths; f++)                             // refuse what cannot be read before the device is touched
+    { uint8_t magic[2] = { 0, 0 };
+      const int fd = open(paths[f], O_RDONLY);
+      if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
+      const ssize_t got = read(fd, magic, 2);
+      const off_t size = lseek(fd, 0, SEEK_END);
+      close(fd);
+      if (got < 0 || size < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
+      if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
+        return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", paths[f]);
+      bound += (int64_t) size + opts->kmer + 1;
+    }
+  Counter c;
+  RCHK(c.init(opts, bound, npaths, errbuf, errlen));
+
+  int nthr = opts->host_threads < 1 ? 1 : opts->host_threads > 16 ? 16 : opts->host_threads;
+  if (nthr > npaths) nthr = npaths;
+  Ring ring;
+  std::vector<uint8_t *> pinned;
+  struct Unpin { std::vector<uint8_t *> &v; ~Unpin() { for (uint8_t *p : v) (void) hipHostFree(p); } } unpin{ pinned };
+  pinned.reserve((size_t) (2 * nthr + 2));
+  for (int b = 0; b < 2 * nthr + 2; b++)
+    { uint8_t *p = nullptr;
+      if (hipHostMalloc((void **) &p, RING_BLOCK, hipHostMallocDefault) != hipSuccess)
+        return fail(errbuf, errlen, SMG_ENOMEM, "cannot pin %zu bytes of host memory", RING_BLOCK);
+      pinned.push_back(p); ring.idle.push_back(p);
+    }
+  std::vector<std::thread> thr;
+  thr.reserve((size_t) nthr);
+  int rc = 0;
+  for (int j = 0; j < nthr && rc == 0; j++)
+    { try
+        { { std::unique_lock<std::mutex> lk(ring.m); ring.live++; }
+          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr);
+        }
+      catch (...)
+        { std::unique_lock<std::mutex> lk(ring.m);
+          ring.live--; ring.abort = true; ring.cv_free.notify_all();
+          rc = fail(errbuf, errlen, SMG_ENOMEM, "cannot start reader thread %d", j);
+        }
+    }
+  for (;;)
+    { Block b{ nullptr, 0, 0 };
+      { std::unique_lock<std::mutex> lk(ring.m);
+        ring.cv_ready.wait(lk, [&] { return !ring.ready.empty() || ring.live == 0; });
+        if (ring.ready.empty()) break;
+        b = ring.ready.front(); ring.ready.pop_front();
+      }
+      if (rc == 0) rc = c.add(b.p, (int64_t) b.len, b.file);
+      std::unique_lock<std::mutex> lk(ring.m);
+      ring.idle.push_back(b.p);
+      if (rc) ring.abort = true;
+      ring.cv_free.notify_all();
+    }
+  for (std::thread &th : thr) th.join();
+  if (ring.rc) { snprintf(errbuf, errlen, "%s", ring.err); return ring.rc; }
+  if (rc) return rc;
+  c.st.bases = ring.bases;
+  c.st.ms_read = ring.t_last - t0;
+  RCHK(c.finish(keys, counts, nels, key_words, hist));
+  c.st.ms_wall = now_ms() - t0;
+  if (stats) *stats = c.st;
+  return 0;
+}
+
+static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+                       int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+{ const double t0 = now_ms();
+  RCHK(check_opts(opts, errbuf, errlen));
+  if (n < 0 || (n > 0 && !seq) || !keys || !counts || !nels || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  Counter c;
+  RCHK(c.init(opts, n, 1, errbuf, errlen));
+  const int64_t piece = (int64_t) 256 << 20;
+  for (int64_t o = 0; o < n; o += piece) RCHK(c.add(seq + o, n - o < piece ? n - o : piece, 0));
+  c.st.bases = n;
+  c.st.ms_read = now_ms() - t0;
+  RCHK(c.finish(keys, counts, nels, key_words, hist));
+  c.st.ms_wall = now_ms() - t0;
+  if (stats) *stats = c.st;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+//  C ABI: no C++ exception crosses it
+// ---------------------------------------------------------------------------------------------------------------
+
+#define GUARD(expr) \
+  try { return (expr); } \
+  catch (const std::bad_alloc &) { return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", ""); } \
+  catch (const std::exception &x) { return fail(errbuf, errlen, SMG_ENODEV, "internal error: %s", x.what()); } \
+  catch (...) { return fail(errbuf, errlen, SMG_ENODEV, "internal error%s", ""); }
+
+extern "C" int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+                               int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+{ GUARD(count_files(paths, npaths, opts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" int smg_count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+                               int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+{ GUARD(count_bases(seq, n, opts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+static int parse_path(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
+{ if (!path || !seq || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  GrowSink sink;
+  int rc;
+  try { rc = parse_fd(fd, path, sink, nullptr, errbuf, errlen); }
+  catch (...) { close(fd); throw; }
+  close(fd);
+  if (rc) return rc;
+  if (!sink.p) sink.p = (uint8_t *) malloc(1);
+  *seq = sink.p; *n = (int64_t) sink.len;
+  sink.p = nullptr;
+  return 0;
+}
+
+extern "C" int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
+{ GUARD(parse_path(path, seq, n, errbuf, errlen)) }
+
+extern "C" void smg_count_free(void *p) { free(p); }
+
+extern "C" const char *smg_count_version(void) { return "smudgeplot_amd 0.4 (k-mer counter, gfx950)"; }
