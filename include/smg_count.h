@@ -8,7 +8,8 @@
  *   - counts saturate at 32767; the table holds the k-mers with count >= t, sorted, one entry each;
  *   - hist[c] = number of distinct canonical k-mers with count c BEFORE trimming, c = 1..32767
  *     (the last bin holds the saturated ones, hist[0] is 0).
- * The result does not depend on the number of host threads, the batch size or the order of the files.
+ * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
+ * key ranges the run is partitioned into.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
  * return SMG_ENODEV; smg_count_parse and smg_count_version need no device.
  */
@@ -38,6 +39,8 @@ extern "C" {
 #define SMG_COUNT_MAX_COUNT  32767
 #define SMG_COUNT_HIST       32768     /* hist[0 .. 32767]                              */
 #define SMG_COUNT_SEPARATOR  '\n'      /* the byte between two records of a stripped stream */
+#define SMG_COUNT_BIN_BITS   12        /* key ranges are cut between bins of the leading 12 bits  */
+#define SMG_COUNT_BINS       4096      /* of the canonical k-mer                                  */
 
 typedef struct smg_count_opts
 { int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
@@ -61,6 +64,21 @@ typedef struct smg_count_stats
   double  ms_wall;
 } smg_count_stats;
 
+/* Counting by key range.  Where one merge is not guaranteed to hold the distinct k-mers of the input, the input is
+   read once, kept on the device at 3 bits per base, and counted one contiguous range of canonical k-mers at a time;
+   the result is that of one pass.  partitions = 1 is today's single pass and refuses (SMG_ENOMEM) what does not fit. */
+typedef struct smg_count_parts
+{ int32_t partitions;    /* in: 0 automatic (one pass where the size of the input guarantees that it fits, else ranges
+                                cut so that none can overflow a merge), 1 one pass, 2 .. SMG_COUNT_BINS that many ranges
+                                of equal window share                                                               */
+  int64_t max_entries;   /* in: test hook, plan and refuse as if one merge held only this many entries; 0: the device's
+                                own limit                                                                           */
+  int32_t used;          /* out: ranges the run was cut into (1: one pass, nothing was packed)                      */
+  int64_t store_bytes;   /* out: device memory of the packed input                                                  */
+  double  ms_pack;       /* out: device events, packing the batches into the store                                  */
+  double  ms_plan;       /* out: host clock, window histogram over the store and the choice of the cuts            */
+} smg_count_parts;
+
 /* *keys: malloc'ed *nels * *key_words uint64, left aligned, sorted; *counts: malloc'ed uint16[*nels];
    hist: caller's uint64[SMG_COUNT_HIST] or NULL; stats may be NULL.  Release with smg_count_free.  */
 int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *opts,
@@ -71,6 +89,24 @@ int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *
 int smg_count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts,
                     uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
                     uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+
+/* the same two with the partitioning under the caller's control; parts may be NULL (automatic).  stats->batches counts
+   the sorted batches of all ranges and the stage times sum over the ranges.                                          */
+int smg_count_files_parts(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts,
+                          uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
+                          uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+int smg_count_bases_parts(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts,
+                          uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
+                          uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+
+/* host only: the cuts of a partitioned run.  windows[SMG_COUNT_BINS] = windows per bin of the leading bits of the
+   canonical k-mer.  partitions = 0: the fewest contiguous ranges none of which holds more than `budget` windows
+   (greedy; a single bin above the budget is refused with SMG_ENOMEM and named in the message); 1: one range;
+   2 .. SMG_COUNT_BINS: that many non-empty ranges of bins, as close to an equal share of the windows as the bins allow
+   (budget is not looked at).  Range r is bins cuts[r] .. cuts[r + 1] - 1; cuts has room for SMG_COUNT_BINS + 1 values,
+   cuts[0] = 0 and cuts[*nranges] = SMG_COUNT_BINS.                                                                  */
+int smg_count_plan(const uint64_t *windows, int64_t budget, int32_t partitions, int32_t *cuts, int32_t *nranges,
+                   char *errbuf, size_t errlen);
 
 /* host only: the stripped byte stream of one file, the sequence of every record with line ends removed
    and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).            */

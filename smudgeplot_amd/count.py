@@ -13,13 +13,14 @@ import numpy as np
 
 from . import ktab
 
-MIN_KMER, MAX_KMER, MAX_COUNT, HIST = 13, 128, 32767, 32768
+MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
 BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 
-EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_parse", "smg_count_free", "smg_count_version"]
+EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
+           "smg_count_parse", "smg_count_free", "smg_count_version"]
 
 
 class CountError(RuntimeError):
@@ -42,6 +43,11 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Parts(C.Structure):
+    _fields_ = [("partitions", C.c_int32), ("max_entries", C.c_int64), ("used", C.c_int32), ("store_bytes", C.c_int64),
+                ("ms_pack", C.c_double), ("ms_plan", C.c_double)]
+
+
 _lib = None
 
 
@@ -61,6 +67,13 @@ def load_library():
     lib.smg_count_files.restype = C.c_int
     lib.smg_count_bases.argtypes = [vp, C.c_int64] + tail
     lib.smg_count_bases.restype = C.c_int
+    ptail = [tail[0], C.POINTER(Parts)] + tail[1:]
+    lib.smg_count_files_parts.argtypes = [C.POINTER(C.c_char_p), C.c_int] + ptail
+    lib.smg_count_files_parts.restype = C.c_int
+    lib.smg_count_bases_parts.argtypes = [vp, C.c_int64] + ptail
+    lib.smg_count_bases_parts.restype = C.c_int
+    lib.smg_count_plan.argtypes = [vp, C.c_int64, C.c_int32, vp, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
+    lib.smg_count_plan.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_parse.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
@@ -90,15 +103,16 @@ def _table(k, t, keys, counts):
     return ktab.KTable(k, 3, 1, t, packed, counts, index, np.array([len(counts)], np.int64))
 
 
-def _run(call, k, t, device, threads):
+def _run(call, k, t, device, threads, partitions, max_entries):
     lib = load_library()
     opts = Opts(int(k), int(t), int(device), int(threads), 0)
+    parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
     keys, cnt = C.c_void_p(), C.c_void_p()
     nels, words = C.c_int64(0), C.c_int(0)
     hist = np.zeros(HIST, dtype=np.uint64)
     st = Stats()
     err = C.create_string_buffer(1024)
-    rc = call(lib, C.byref(opts), C.byref(keys), C.byref(cnt), C.byref(nels), C.byref(words),
+    rc = call(lib, C.byref(opts), C.byref(parts), C.byref(keys), C.byref(cnt), C.byref(nels), C.byref(words),
               hist.ctypes.data_as(C.c_void_p), C.byref(st), err, len(err))
     if rc != 0:
         raise CountError(rc, err.value.decode(errors="replace"))
@@ -109,21 +123,45 @@ def _run(call, k, t, device, threads):
     finally:
         lib.smg_count_free(keys)
         lib.smg_count_free(cnt)
-    return _table(int(k), int(t), k64, c16), hist, st.asdict()
+    stats = st.asdict()
+    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan)
+    return _table(int(k), int(t), k64, c16), hist, stats
 
 
-def count_files(paths, k, t=4, device=0, threads=4):
-    """-> (ktab.KTable of the canonical k-mers with count >= t, hist uint64[32768], stats dict)"""
+def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
+    """-> (ktab.KTable of the canonical k-mers with count >= t, hist uint64[32768], stats dict)
+
+    partitions: 0 lets the library count by key range where one pass is not guaranteed to fit, 1 is one pass,
+    2 .. 4096 that many ranges; max_entries (test hook) plans as if one merge held only that many entries.
+    The stats carry `used` (ranges), `store_bytes`, `ms_pack` and `ms_plan` of a partitioned run."""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
-    return _run(lambda lib, *a: lib.smg_count_files(arr, len(paths), *a), k, t, device, threads)
+    return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries)
 
 
-def count_bases(seq, k, t=4, device=0, threads=4):
+def count_bases(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
     """The same from sequence bytes (bytes or a uint8 array) in which any byte outside ACGTacgt separates."""
     buf = np.ascontiguousarray(np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray, memoryview)) else seq,
                                dtype=np.uint8)
-    return _run(lambda lib, *a: lib.smg_count_bases(buf.ctypes.data_as(C.c_void_p), buf.size, *a), k, t, device, threads)
+    return _run(lambda lib, *a: lib.smg_count_bases_parts(buf.ctypes.data_as(C.c_void_p), buf.size, *a), k, t, device, threads,
+                partitions, max_entries)
+
+
+def plan(windows, budget, partitions=0):
+    """Host only: the cuts of a partitioned run over the 4096-bin window histogram -> int32 array, range r is bins
+    cuts[r] .. cuts[r + 1] - 1.  Raises CountError (-3) with the bin named when one bin alone is above the budget."""
+    lib = load_library()
+    w = np.ascontiguousarray(windows, dtype=np.uint64)
+    if w.shape != (BINS,):
+        raise ValueError(f"windows must have {BINS} entries")
+    cuts = np.zeros(BINS + 1, dtype=np.int32)
+    n = C.c_int32(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_plan(w.ctypes.data_as(C.c_void_p), int(budget), int(partitions), cuts.ctypes.data_as(C.c_void_p), C.byref(n),
+                            err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    return cuts[: n.value + 1].copy()
 
 
 def parse(path) -> bytes:

@@ -11,6 +11,15 @@
 //   finish  kc_finish_flag (histogram, trim flag) + scan + kc_finish_compact (k-mers, uint16 counts clamped to 32767)
 // A batch boundary never loses or doubles a window: a piece that does not continue the byte in front of it in the
 // batch buffer is preceded by a separator and the last k-1 bytes of its file's stream (no whole window fits in those).
+//
+// Where one merge cannot be guaranteed to hold the distinct k-mers of the input, the run is partitioned by key range:
+//   pack    kc_pack  every batch of bytes -> 3 bits per position (2-bit codes, validity) appended to a resident store
+//   plan    kc_bins  windows per bin of the leading 12 bits of the canonical k-mer; smg_count_plan cuts the 4096 bins
+//           into contiguous ranges whose windows (an upper bound of their distinct k-mers) stay within one sorted
+//           batch or, where a single bin is larger than that, within one merge
+//   range   kc_extract_packed<W>  the store -> canonical k-mers of ONE range, the key buffer filled across the store
+//           and sorted when full; then batch / merge / finish as above, the kept entries appended to the host table
+// Every instance of a k-mer lies in one range, so ranges in ascending order give the sorted table.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -74,17 +83,98 @@ template <int W> SMG_DEV bool kc_all_ones(const Key<W> &x)
   return e;
 }
 
-// One workgroup per tile of KC_TILE sequence bytes plus a halo of k-1.  The bytes are coded into two LDS bit streams
-// (2-bit codes, validity), both big endian so that one funnel shift serves both; position p starts a window when the
-// k validity bits from p on are all set.  The canonical k-mers of the tile go out in position order behind ONE atomic
-// per workgroup (64 ballot counts, scanned by the first wavefront): 1 byte in per position, 8 W bytes out per window.
+// The leading SMG_COUNT_BIN_BITS bits of the canonical k-mer of the window at position p of the LDS code stream:
+// top(min(x, rc x)) = min(top x, top rc x), and top rc x is the complement of the window's last bases in reverse
+// order, so two short reads of the stream give the bin and the k-mer itself is never built.
+#define KC_BIN_BASES (SMG_COUNT_BIN_BITS / 2)
+SMG_DEV unsigned kc_bin(const u64 *s_code, int p, int k)
+{ const unsigned f = (unsigned) (kc_take64(s_code, 2 * p) >> (64 - SMG_COUNT_BIN_BITS));
+  const u64 l = kc_take64(s_code, 2 * (p + k - KC_BIN_BASES)) & (~0ull << (64 - SMG_COUNT_BIN_BITS));
+  const unsigned r = (unsigned) rev2_comp_word(l) & (SMG_COUNT_BINS - 1u);
+  return f < r ? f : r;
+}
+
+// does a window of k valid bases start at position p of the LDS validity stream?
+SMG_DEV bool kc_window(const u64 *s_val, int p, int k)
+{ const u64 x0 = kc_take64(s_val, p);
+  if (k <= 64) return (~x0 >> (64 - k)) == 0;
+  const u64 x1 = kc_take64(s_val, p + 64);
+  return (x0 == ~0ull) & ((~x1 >> (128 - k)) == 0);
+}
+
+// The back half of both extract kernels.  The two LDS bit streams of a tile (2-bit codes, validity; both big endian so
+// that one funnel shift serves both) are in place.  Position p of the tile starts a window when the k validity bits
+// from p on are all set, its global position lies in [p0, p1) and, with FILTER, the bin of its canonical k-mer lies in
+// [lo, hi): the predicate is complete BEFORE the ballot, so a rejected window never builds, reverse-complements or
+// compares its k-mer.  The canonical k-mers go out in position order behind ONE atomic per workgroup (64 ballot
+// counts, scanned by the first wavefront): 8 W bytes out per accepted window.
+template <int W, bool FILTER> SMG_DEV void
+kc_emit(const u64 *s_code, const u64 *s_val, unsigned *s_cnt, unsigned long long *s_base, int64_t tile0, int64_t p0, int64_t p1, int k,
+        unsigned lo, unsigned hi, u64 *__restrict__ out, unsigned long long limit, unsigned long long *__restrict__ nout)
+{ const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  // which of this thread's 16 positions (p = j * 256 + t: neighbouring lanes, neighbouring windows) start a window
+  unsigned mine = 0;
+#pragma unroll
+  for (int j = 0; j < KC_TILE / KC_TPB; j++)
+    { const int p = j * KC_TPB + t;
+      bool ok = (tile0 + p >= p0) & (tile0 + p < p1);
+      ok &= kc_window(s_val, p, k);
+      if (FILTER)
+        { const unsigned b = kc_bin(s_code, p, k);               // (garbage where ok is false already: ANDed away)
+          ok &= (b >= lo) & (b < hi);
+        }
+      const unsigned long long bal = __ballot(ok);
+      if (lane == 0) s_cnt[j * 4 + wave] = (unsigned) __popcll(bal);
+      mine |= (unsigned) ok << j;
+    }
+  __syncthreads();
+  if (wave == 0)
+    { const unsigned own = s_cnt[lane];
+      unsigned inc = own;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1)
+        { const unsigned up = __shfl_up(inc, o, 64);
+          if (lane >= o) inc += up;
+        }
+      s_cnt[lane] = inc - own;
+      if (lane == 63) *s_base = inc ? atomicAdd(nout, (unsigned long long) inc) : 0ull;
+    }
+  __syncthreads();
+  const unsigned long long base = *s_base;
+  const int rem = 2 * k - 64 * (W - 1);                      // bits of the last word that belong to the k-mer
+  const u64 lastmask = ~0ull << (64 - rem);
+  for (int j = 0; j < KC_TILE / KC_TPB; j++)                 // (the trip count is uniform: every lane meets every ballot)
+    { const bool ok = (mine >> j) & 1u;
+      const unsigned long long bal = __ballot(ok);
+      if (ok)
+        { const int p = j * KC_TPB + t;
+          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned) (bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) bal, 0u));
+          Key<W> x;
+#pragma unroll
+          for (int w = 0; w < W; w++) x.w[w] = kc_take64(s_code, 2 * p + 64 * w);
+          x.w[W - 1] &= lastmask;
+          const Key<W> r = revcomp<W>(x, k);
+          const bool lt = key_lt<W>(r, x);
+          const unsigned long long q = base + s_cnt[j * 4 + wave] + rank;
+          u64 *o = out + (size_t) q * W;
+          if (q < limit)                                       // (never false: the host sizes the span; it reads *nout and would say so)
+            {
+#pragma unroll
+              for (int w = 0; w < W; w++) o[w] = lt ? r.w[w] : x.w[w];
+            }
+        }
+    }
+}
+
+// One workgroup per tile of KC_TILE sequence bytes plus a halo of k-1.  The bytes are coded into the two LDS bit streams,
+// kc_emit does the rest: 1 byte in per position, 8 W bytes out per window.
 template <int W> __global__ void __launch_bounds__(KC_TPB)
 kc_extract(const uint8_t *__restrict__ seq, int64_t n, int k, u64 *__restrict__ out, unsigned long long *__restrict__ nout)
 { __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
   __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
   __shared__ unsigned s_cnt[64];
   __shared__ unsigned long long s_base;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int64_t tile0 = (int64_t) blockIdx.x * KC_TILE;
   unsigned *c32 = reinterpret_cast<unsigned *>(s_code);
   uint16_t *v16 = reinterpret_cast<uint16_t *>(s_val);
@@ -106,56 +196,95 @@ kc_extract(const uint8_t *__restrict__ seq, int64_t n, int k, u64 *__restrict__ 
       v16[c ^ 3] = (uint16_t) valid;
     }
   __syncthreads();
+  kc_emit<W, false>(s_code, s_val, s_cnt, &s_base, tile0, 0, n - k + 1, k, 0u, 0u, out, (unsigned long long) n, nout);
+}
 
-  // which of this thread's 16 positions (p = j * 256 + t: neighbouring lanes, neighbouring windows) start a window
-  unsigned mine = 0;
+// ---- the resident store of a partitioned run: the two bit streams of kc_extract's LDS, kept in device memory -----------
+// code[p / 32] holds position p in bits 63 - 2 (p % 32) and the one below, val[p / 64] in bit 63 - p % 64.  Batches are
+// appended at multiples of 64 positions; the filler in between is invalid, like a separator.
+
+// One thread per 64 positions of a batch: four 16-byte loads in, one 16-byte and one 8-byte store out (3 bits a base).
+// at = the store position the batch goes to (a multiple of 64); npad = n rounded up to 64.
+__global__ void __launch_bounds__(KC_TPB)
+kc_pack(const uint8_t *__restrict__ seq, int64_t n, int64_t npad, int64_t at, u64 *__restrict__ code, u64 *__restrict__ val)
+{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
+  if (64 * i >= npad) return;
+  unsigned cw[4], vw[4];
 #pragma unroll
-  for (int j = 0; j < KC_TILE / KC_TPB; j++)
-    { const int p = j * KC_TPB + t;
-      const u64 x0 = kc_take64(s_val, p);
-      bool ok = tile0 + p + k <= n;
-      if (k <= 64) ok &= (~x0 >> (64 - k)) == 0;
-      else
-        { const u64 x1 = kc_take64(s_val, p + 64);
-          ok &= (x0 == ~0ull) & ((~x1 >> (128 - k)) == 0);
+  for (int c = 0; c < 4; c++)
+    { const int64_t g = 64 * i + 16 * c;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (g + 16 <= n) v = *reinterpret_cast<const uint4 *>(seq + g);
+      else if (g < n)
+        { unsigned d[4] = { 0, 0, 0, 0 };
+          for (int b = 0; b < 16 && g + b < n; b++) d[b >> 2] |= (unsigned) seq[g + b] << (8 * (b & 3));
+          v = make_uint4(d[0], d[1], d[2], d[3]);
         }
-      const unsigned long long bal = __ballot(ok);
-      if (lane == 0) s_cnt[j * 4 + wave] = (unsigned) __popcll(bal);
-      mine |= (unsigned) ok << j;
+      unsigned co = 0, va = 0;
+      kc_code4(v.x, co, va); kc_code4(v.y, co, va); kc_code4(v.z, co, va); kc_code4(v.w, co, va);
+      cw[c] = co; vw[c] = va;
     }
-  __syncthreads();
-  if (wave == 0)
-    { const unsigned own = s_cnt[lane];
-      unsigned inc = own;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1)
-        { const unsigned up = __shfl_up(inc, o, 64);
-          if (lane >= o) inc += up;
-        }
-      s_cnt[lane] = inc - own;
-      if (lane == 63) s_base = inc ? atomicAdd(nout, (unsigned long long) inc) : 0ull;
+  const int64_t q = at / 64 + i;
+  ulonglong2 cc;
+  cc.x = ((u64) cw[0] << 32) | cw[1];
+  cc.y = ((u64) cw[2] << 32) | cw[3];
+  *reinterpret_cast<ulonglong2 *>(code + 2 * q) = cc;
+  val[q] = ((u64) vw[0] << 48) | ((u64) vw[1] << 32) | ((u64) vw[2] << 16) | vw[3];
+}
+
+// the tile at position tile0 (a multiple of KC_TILE) and its halo from the store into the LDS streams; npos = positions
+// in the store (a multiple of 64), beyond them nothing is valid
+SMG_DEV void kc_load_tile(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos, int64_t tile0, u64 *s_code, u64 *s_val)
+{ const int t = threadIdx.x;
+  const int NC = KC_CHUNKS / 2 + 2, NV = KC_CHUNKS / 4 + 2;
+  if (t < NC)
+    { const int64_t g = tile0 / 32 + t;
+      s_code[t] = (t < NC - 2 && g < npos / 32) ? code[g] : 0ull;
     }
-  __syncthreads();
-  const unsigned long long base = s_base;
-  const int rem = 2 * k - 64 * (W - 1);                      // bits of the last word that belong to the k-mer
-  const u64 lastmask = ~0ull << (64 - rem);
-  for (int j = 0; j < KC_TILE / KC_TPB; j++)                 // (the trip count is uniform: every lane meets every ballot)
-    { const bool ok = (mine >> j) & 1u;
-      const unsigned long long bal = __ballot(ok);
-      if (ok)
+  else if (t < NC + NV)
+    { const int v = t - NC;
+      const int64_t g = tile0 / 64 + v;
+      s_val[v] = (v < NV - 2 && g < npos / 64) ? val[g] : 0ull;
+    }
+}
+
+// windows per bin of the leading bits of the canonical k-mer: LDS bins, flushed once per workgroup (grid-stride over tiles)
+__global__ void __launch_bounds__(KC_TPB)
+kc_bins(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos, int k, unsigned long long *__restrict__ bins)
+{ __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
+  __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
+  __shared__ unsigned h[SMG_COUNT_BINS];
+  const int t = threadIdx.x;
+  for (int b = t; b < SMG_COUNT_BINS; b += KC_TPB) h[b] = 0;
+  const int64_t ntiles = (npos + KC_TILE - 1) / KC_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)     // (at most 2^32 / KC_TILE tiles per workgroup: host)
+    { __syncthreads();
+      kc_load_tile(code, val, npos, tile * KC_TILE, s_code, s_val);
+      __syncthreads();
+#pragma unroll 4
+      for (int j = 0; j < KC_TILE / KC_TPB; j++)
         { const int p = j * KC_TPB + t;
-          const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned) (bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) bal, 0u));
-          Key<W> x;
-#pragma unroll
-          for (int w = 0; w < W; w++) x.w[w] = kc_take64(s_code, 2 * p + 64 * w);
-          x.w[W - 1] &= lastmask;
-          const Key<W> r = revcomp<W>(x, k);
-          const bool lt = key_lt<W>(r, x);
-          u64 *o = out + (size_t) (base + s_cnt[j * 4 + wave] + rank) * W;
-#pragma unroll
-          for (int w = 0; w < W; w++) o[w] = lt ? r.w[w] : x.w[w];
+          if (kc_window(s_val, p, k)) atomicAdd(&h[kc_bin(s_code, p, k)], 1u);
         }
     }
+  __syncthreads();
+  for (int b = t; b < SMG_COUNT_BINS; b += KC_TPB)
+    if (h[b]) atomicAdd(&bins[b], (unsigned long long) h[b]);
+}
+
+// kc_extract with its front half replaced by loads of the two streams from the store: the windows that start in
+// [p0, p1) and whose bin lies in [lo, hi).  The grid starts at the tile that holds p0; 0.375 bytes in per position.
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_extract_packed(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos, int64_t p0, int64_t p1, int k,
+                  unsigned lo, unsigned hi, u64 *__restrict__ out, unsigned long long limit, unsigned long long *__restrict__ nout)
+{ __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
+  __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
+  __shared__ unsigned s_cnt[64];
+  __shared__ unsigned long long s_base;
+  const int64_t tile0 = (p0 / KC_TILE + blockIdx.x) * KC_TILE;
+  kc_load_tile(code, val, npos, tile0, s_code, s_val);
+  __syncthreads();
+  kc_emit<W, true>(s_code, s_val, s_cnt, &s_base, tile0, p0, p1, k, lo, hi, out, limit, nout);
 }
 
 __global__ void __launch_bounds__(KC_TPB) kc_iota(uint32_t *__restrict__ p, int64_t n)
@@ -409,9 +538,19 @@ struct Counter
   size_t tmp_cap = 0;
   int64_t nd = 0;
   smg_count_stats st;
+  // a partitioned run: the packed input (positions; store_n is a multiple of 64), the bins, the host table so far
+  bool parted = false;
+  int req_parts = 0;
+  int64_t max_entries = 0;
+  Dev scode, sval, dh;
+  int64_t store_cap = 0, store_n = 0;
+  smg_count_parts pt;
+  uint64_t *hk = nullptr; uint16_t *hc = nullptr;
+  int64_t hn = 0, hcap = 0;
 
   ~Counter()
-  { if (ev0) (void) hipEventDestroy(ev0);
+  { free(hk); free(hc);
+    if (ev0) (void) hipEventDestroy(ev0);
     if (ev1) (void) hipEventDestroy(ev1);
     if (stream) (void) hipStreamDestroy(stream);
   }
@@ -444,12 +583,35 @@ struct Counter
     return 0;
   }
 
+  size_t merge_price() const { return 3 * (sizeof(u64) * W + sizeof(uint32_t)) + 8 + (W > 1 ? 24 : 0); }   // bytes per merged entry
+
+  // positions a batch holds when `avail` bytes are there to share between the batch and the merges
+  int64_t batch_cap(size_t avail, int64_t per, int64_t bound) const
+  { int64_t c = (int64_t) (avail / 3) / per;
+    if (c > ((int64_t) 1 << 30)) c = (int64_t) 1 << 30;
+    const char *hook = getenv("SMG_COUNT_BATCH_BASES");
+    if (hook && atoll(hook) > 0) c = atoll(hook) + k;
+    if (c > bound + k + 1) c = bound + k + 1;
+    if (c < k + 1) c = k + 1;
+    return c;
+  }
+
   // Memory plan, before the first allocation: a third of what is free goes to the batch (sequence, two key buffers,
   // flags, positions, run starts, and the word sort's scratch for W > 1), the rest is left to the distinct list and
-  // its merge.  `bound` is the most sequence the input can hold.
-  int init(const smg_count_opts *o, int64_t bound, int nfiles, char *eb, size_t el)
+  // its merge.  `bound` is the most sequence the input can hold, hence a bound on its windows and its distinct k-mers:
+  // where a merge of that many entries fits next to the batch, the run is one pass; otherwise (or when the caller asks
+  // for ranges) the batches are packed into a store that comes off the top, and the ranges are planned in finish().
+  int init(const smg_count_opts *o, const smg_count_parts *parts, int64_t bound, int nfiles, char *eb, size_t el)
   { errbuf = eb; errlen = el;
     memset(&st, 0, sizeof(st));
+    memset(&pt, 0, sizeof(pt));
+    if (parts)
+      { if (parts->partitions < 0 || parts->partitions > SMG_COUNT_BINS)
+          return fail(errbuf, errlen, SMG_EINVAL, "partitions = %d is out of range 0 .. %d", parts->partitions, SMG_COUNT_BINS);
+        if (parts->max_entries < 0) return fail(errbuf, errlen, SMG_EINVAL, "max_entries = %lld is negative", (long long) parts->max_entries);
+        req_parts = parts->partitions; max_entries = parts->max_entries;
+      }
+    pt.used = 1;
     k = o->kmer; t = o->minval; W = (k + 31) / 32;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
@@ -459,12 +621,22 @@ struct Counter
     size_t free_b = 0, total_b = 0;
     DCHK(hipMemGetInfo(&free_b, &total_b));
     const int64_t per = 1 + 16 * W + 12 + (W > 1 ? 24 : 0);
-    int64_t c = (int64_t) (free_b / 3) / per;
-    if (c > ((int64_t) 1 << 30)) c = (int64_t) 1 << 30;
-    const char *hook = getenv("SMG_COUNT_BATCH_BASES");
-    if (hook && atoll(hook) > 0) c = atoll(hook) + k;
-    if (c > bound + k + 1) c = bound + k + 1;
-    if (c < k + 1) c = k + 1;
+    int64_t c = batch_cap(free_b, per, bound);
+    parted = req_parts > 1;
+    if (req_parts == 0)
+      { const bool fits = bound < 0xFFFFFFF0ll &&
+                          (size_t) (c * per) + (size_t) bound * merge_price() + ((size_t) 64 << 20) <= free_b;
+        parted = !(fits && (max_entries == 0 || bound <= max_entries));
+      }
+    if (parted)
+      { store_cap = ((bound + bound / 32 + ((int64_t) 1 << 16)) + KC_TILE - 1) / KC_TILE * KC_TILE;
+        const size_t need = (size_t) store_cap / 8 * 3;
+        if (need + ((size_t) 64 << 20) > free_b)
+          return fail(errbuf, errlen, SMG_ENOMEM, "the packed input does not fit the device: a store of %lld positions needs %.3f GB, "
+                      "%.3f GB of device memory are free", (long long) store_cap, (double) need * 1e-9, (double) free_b * 1e-9);
+        free_b -= need;
+        c = batch_cap(free_b, per, bound);
+      }
     if (c * per > (int64_t) free_b)
       return fail(errbuf, errlen, SMG_ENOMEM, "a batch of %lld bases needs %.3f GB, %.3f GB of device memory are free",
                   (long long) c, (double) (c * per) * 1e-9, (double) free_b * 1e-9);
@@ -480,6 +652,43 @@ struct Counter
     RCHK(alloc(pos, sizeof(uint32_t) * (size_t) cap));
     RCHK(alloc(start, sizeof(uint32_t) * ((size_t) cap + 1)));
     RCHK(alloc(ctr, 16));
+    if (parted)
+      { RCHK(alloc(scode, (size_t) store_cap / 4)); RCHK(alloc(sval, (size_t) store_cap / 8));
+        pt.store_bytes = store_cap / 8 * 3;
+      }
+    return 0;
+  }
+
+  // room for `more` positions behind store_n (the size bound of the input does not count the separators and re-prefixed
+  // tails that batches and interleaved files add, so the store may have to grow)
+  int need_store(int64_t more)
+  { if (store_n + more <= store_cap) return 0;
+    int64_t nc = store_cap + store_cap / 2;
+    if (nc < store_n + more) nc = store_n + more;
+    nc = (nc + KC_TILE - 1) / KC_TILE * KC_TILE;
+    Dev c2, v2;
+    RCHK(alloc(c2, (size_t) nc / 4)); RCHK(alloc(v2, (size_t) nc / 8));
+    DCHK(hipMemcpyAsync(c2.p, scode.p, (size_t) store_n / 4, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipMemcpyAsync(v2.p, sval.p, (size_t) store_n / 8, hipMemcpyDeviceToDevice, stream));
+    DCHK(hipStreamSynchronize(stream));
+    scode.take(c2); sval.take(v2);
+    store_cap = nc; pt.store_bytes = nc / 8 * 3;
+    return 0;
+  }
+
+  // the batch buffer -> 3 bits per position behind the store
+  int pack()
+  { const int64_t n = fill;
+    fill = 0; last_file = -1;
+    if (n < k) return 0;
+    const int64_t npad = (n + 63) / 64 * 64;
+    RCHK(need_store(npad));
+    tic();
+    hipLaunchKernelGGL(kc_pack, dim3(nblk(npad / 64)), dim3(KC_TPB), 0, stream, seq.as<uint8_t>(), n, npad, store_n,
+                       scode.as<u64>(), sval.as<u64>());
+    DCHK(hipGetLastError());
+    RCHK(toc(&pt.ms_pack));
+    store_n += npad;
     return 0;
   }
 
@@ -567,9 +776,10 @@ struct Counter
     return 0;
   }
 
-  // the batch buffer -> (k-mer, count) runs -> merged into the distinct list
+  // the batch buffer -> (k-mer, count) runs -> merged into the distinct list (a partitioned run packs it instead)
   int flush()
-  { const int64_t n = fill;
+  { if (parted) return pack();
+    const int64_t n = fill;
     fill = 0; last_file = -1;
     if (n < k) return 0;
     st.batches++;
@@ -586,7 +796,12 @@ struct Counter
     RCHK(toc(&st.ms_extract));
     if (nwin == 0) return 0;
     if ((int64_t) nwin > cap) return fail(errbuf, errlen, SMG_ENODEV, "internal error: %llu windows from %lld bytes", nwin, (long long) n);
-    st.windows += (int64_t) nwin;
+    return count_keys((int64_t) nwin);
+  }
+
+  // nwin canonical k-mers in ka -> sorted -> (k-mer, count) runs -> merged into the distinct list
+  int count_keys(int64_t nwin)
+  { st.windows += nwin;
     u64 *sorted = nullptr;
     tic();
     RCHK(sort_entries(ka.as<u64>(), kb.as<u64>(), nullptr, nullptr, (int64_t) nwin, &sorted, nullptr));
@@ -611,7 +826,10 @@ struct Counter
   }
 
   int merge(const u64 *uk, const uint32_t *rc, int64_t nr)
-  { if (nd == 0)
+  { if (max_entries && nd + nr > max_entries)
+      return fail(errbuf, errlen, SMG_ENOMEM, "the distinct k-mers of this data set do not fit the device: merging %lld entries, "
+                  "one merge holds %lld (max_entries)", (long long) (nd + nr), (long long) max_entries);
+    if (nd == 0)
       { Dev nk, nc;
         RCHK(alloc(nk, sizeof(u64) * (size_t) nr * W)); RCHK(alloc(nc, sizeof(uint32_t) * (size_t) nr));
         DCHK(hipMemcpyAsync(nk.p, uk, sizeof(u64) * (size_t) nr * W, hipMemcpyDeviceToDevice, stream));
@@ -622,9 +840,9 @@ struct Counter
       }
     const int64_t m = nd + nr;
     if (m >= 0xFFFFFFF0ll)
-      return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 distinct k-mers (%lld): partitioned counting is not implemented", (long long) m);
-    const size_t ent = sizeof(u64) * W + sizeof(uint32_t);
-    const size_t want = (size_t) m * (3 * ent + 8 + (W > 1 ? 24 : 0)) + ((size_t) 64 << 20);
+      return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 - 16 entries in one merge (%lld): this many distinct k-mers need more than one "
+                  "key range", (long long) m);
+    const size_t want = (size_t) m * merge_price() + ((size_t) 64 << 20);
     size_t free_b = 0, total_b = 0;
     DCHK(hipMemGetInfo(&free_b, &total_b));
     if (want > free_b)
@@ -658,42 +876,145 @@ struct Counter
     return 0;
   }
 
-  // the last batch, then histogram, clamp, trim; the table goes to malloc'ed host arrays
-  int finish(uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist)
-  { RCHK(flush());
-    seq.reset(); ka.reset(); kb.reset(); start.reset();
-    st.distinct = nd;
-    int64_t kept = 0;
-    Dev dh, ok, oc;
+  // histogram, clamp and trim of the distinct list, which is final; its kept entries go behind the host table
+  int finish_range()
+  { int64_t kept = 0;
+    Dev ff, fp, ok, oc;
     tic();
-    RCHK(alloc(dh, sizeof(uint64_t) * SMG_COUNT_HIST));
-    DCHK(hipMemsetAsync(dh.p, 0, sizeof(uint64_t) * SMG_COUNT_HIST, stream));
     if (nd > 0)
-      { RCHK(alloc(flag, sizeof(uint32_t) * (size_t) nd)); RCHK(alloc(pos, sizeof(uint32_t) * (size_t) nd));
+      { RCHK(alloc(ff, sizeof(uint32_t) * (size_t) nd)); RCHK(alloc(fp, sizeof(uint32_t) * (size_t) nd));
         const unsigned g = nblk(nd) < 2048u ? nblk(nd) : 2048u;
         hipLaunchKernelGGL(kc_finish_flag, dim3(g), dim3(KC_TPB), 0, stream, dc.as<uint32_t>(), nd, (unsigned) t,
-                           dh.as<unsigned long long>(), flag.as<uint32_t>());
-        RCHK(scan(flag.as<uint32_t>(), pos.as<uint32_t>(), nd, &kept));
+                           dh.as<unsigned long long>(), ff.as<uint32_t>());
+        RCHK(scan(ff.as<uint32_t>(), fp.as<uint32_t>(), nd, &kept));
         RCHK(alloc(ok, sizeof(u64) * (size_t) kept * W)); RCHK(alloc(oc, sizeof(uint16_t) * (size_t) kept));
 #define CALL(WW) hipLaunchKernelGGL(kc_finish_compact<WW>, dim3(nblk(nd)), dim3(KC_TPB), 0, stream, dk.as<u64>(), dc.as<uint32_t>(), \
-                                    flag.as<uint32_t>(), pos.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>())
+                                    ff.as<uint32_t>(), fp.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>())
         DISPATCH_W(CALL)
 #undef CALL
         DCHK(hipGetLastError());
       }
     RCHK(toc(&st.ms_finish));
-    st.kept = kept;
-    uint64_t *hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (kept > 0 ? kept : 1) * W);
-    uint16_t *hc = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1));
-    if (!hk || !hc) { free(hk); free(hc); return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory for %lld k-mers", (long long) kept); }
-    hipError_t e = hipSuccess;
-    if (kept > 0)
-      { e = hipMemcpy(hk, ok.p, sizeof(uint64_t) * (size_t) kept * W, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hc, oc.p, sizeof(uint16_t) * (size_t) kept, hipMemcpyDeviceToHost);
+    st.distinct += nd;
+    st.kept += kept;
+    if (hn + kept > hcap || !hk)
+      { int64_t nc = hcap + hcap / 2;
+        if (nc < hn + kept) nc = hn + kept;
+        if (nc < 1) nc = 1;
+        uint64_t *k2 = (uint64_t *) realloc(hk, sizeof(uint64_t) * (size_t) nc * W);
+        if (k2) hk = k2;
+        uint16_t *c2 = (uint16_t *) realloc(hc, sizeof(uint16_t) * (size_t) nc);
+        if (c2) hc = c2;
+        if (!k2 || !c2) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory for %lld k-mers", (long long) nc);
+        hcap = nc;
       }
-    if (e == hipSuccess && hist) e = hipMemcpy(hist, dh.p, sizeof(uint64_t) * SMG_COUNT_HIST, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(hk); free(hc); return fail(errbuf, errlen, SMG_ENODEV, "HIP error: %s", hipGetErrorString(e)); }
-    *keys = hk; *counts = hc; *nels = kept; *key_words = W;
+    if (kept > 0)
+      { DCHK(hipMemcpy(hk + (size_t) hn * W, ok.p, sizeof(uint64_t) * (size_t) kept * W, hipMemcpyDeviceToHost));
+        DCHK(hipMemcpy(hc + hn, oc.p, sizeof(uint16_t) * (size_t) kept, hipMemcpyDeviceToHost));
+      }
+    hn += kept;
+    dk.reset(); dc.reset(); nd = 0;
+    return 0;
+  }
+
+  // Entries one merge is guaranteed to hold, now that the store and the batch buffers are allocated: the smaller of the
+  // uint32 limit of the scans and what is free, priced as merge() prices it (less a reserve for the sort's scratch).
+  int merge_budget(int64_t *budget)
+  { size_t free_b = 0, total_b = 0;
+    DCHK(hipMemGetInfo(&free_b, &total_b));
+    const size_t reserve = (size_t) 320 << 20;
+    int64_t b = free_b > reserve ? (int64_t) ((free_b - reserve) / merge_price()) : 0;
+    if (b > 0xFFFFFFEFll) b = 0xFFFFFFEFll;
+    if (max_entries && b > max_entries) b = max_entries;
+    if (b < 1)
+      return fail(errbuf, errlen, SMG_ENOMEM, "no device memory is left for a merge: %.3f GB are free next to the packed input (%.3f GB) "
+                  "and the batch buffers", (double) free_b * 1e-9, (double) pt.store_bytes * 1e-9);
+    *budget = b;
+    return 0;
+  }
+
+  // the ranges of a partitioned run, in ascending order
+  int run_ranges()
+  { const double t0 = now_ms();
+    Dev db;
+    std::vector<uint64_t> bins(SMG_COUNT_BINS, 0);
+    std::vector<int32_t> cuts(SMG_COUNT_BINS + 1, 0);
+    int32_t nranges = 1;
+    RCHK(alloc(db, sizeof(uint64_t) * SMG_COUNT_BINS));
+    DCHK(hipMemsetAsync(db.p, 0, sizeof(uint64_t) * SMG_COUNT_BINS, stream));
+    if (store_n > 0)
+      { const int64_t ntiles = (store_n + KC_TILE - 1) / KC_TILE;
+        hipLaunchKernelGGL(kc_bins, dim3((unsigned) (ntiles < 2048 ? ntiles : 2048)), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(),
+                           store_n, k, db.as<unsigned long long>());
+        DCHK(hipGetLastError());
+      }
+    DCHK(hipMemcpyAsync(bins.data(), db.p, sizeof(uint64_t) * SMG_COUNT_BINS, hipMemcpyDeviceToHost, stream));
+    DCHK(hipStreamSynchronize(stream));
+    int64_t budget = 0;
+    RCHK(merge_budget(&budget));
+    // Automatic mode: ranges of one sorted batch each, which never merge (an extra pass over the store costs less than the
+    // merge it saves, profiles/count_partitioned.md); where a single bin is above a batch, the merge limit is the budget.
+    int rc = SMG_ENOMEM;
+    if (req_parts == 0 && cap < budget) rc = smg_count_plan(bins.data(), cap, 0, cuts.data(), &nranges, errbuf, errlen);
+    if (rc == SMG_ENOMEM) rc = smg_count_plan(bins.data(), budget, req_parts, cuts.data(), &nranges, errbuf, errlen);
+    RCHK(rc);
+    pt.used = nranges;
+    pt.ms_plan = now_ms() - t0;
+
+    for (int r = 0; r < nranges; r++)
+      { const unsigned lo = (unsigned) cuts[(size_t) r], hi = (unsigned) cuts[(size_t) r + 1];
+        int64_t left = 0;                                      // windows of the range not yet in the key buffer
+        for (unsigned b = lo; b < hi; b++) left += (int64_t) bins[b];
+        if (left == 0) continue;
+        int64_t p = 0, have = 0;                               // next store position, keys in the buffer
+        DCHK(hipMemsetAsync(ctr.p, 0, 16, stream));
+        while (left > 0 && p < store_n)
+          { // a span of s positions holds at most s windows: all that is left of the store if the rest of the range fits
+            const int64_t room = cap - have;
+            const int64_t p1 = left <= room ? store_n : (p + room < store_n ? p + room : store_n);
+            const unsigned ntiles = (unsigned) ((p1 - 1) / KC_TILE - p / KC_TILE + 1);
+            tic();
+#define CALL(WW) hipLaunchKernelGGL(kc_extract_packed<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n, \
+                                    p, p1, k, lo, hi, ka.as<u64>(), (unsigned long long) cap, ctr.as<unsigned long long>())
+            DISPATCH_W(CALL)
+#undef CALL
+            DCHK(hipGetLastError());
+            unsigned long long now = 0;
+            DCHK(hipMemcpyAsync(&now, ctr.p, 8, hipMemcpyDeviceToHost, stream));
+            RCHK(toc(&st.ms_extract));
+            if ((int64_t) now > cap || (int64_t) now - have > left)
+              return fail(errbuf, errlen, SMG_ENODEV, "internal error: %llu keys of range %d in a buffer of %lld, %lld were left",
+                          now, r, (long long) cap, (long long) left);
+            left -= (int64_t) now - have;
+            have = (int64_t) now;
+            p = p1;
+            if (left > 0 && cap - have < (cap / 8 > 1 ? cap / 8 : 1))       // full (or nearly): sort it
+              { st.batches++;
+                RCHK(count_keys(have));
+                have = 0;
+                DCHK(hipMemsetAsync(ctr.p, 0, 16, stream));
+              }
+          }
+        if (left != 0) return fail(errbuf, errlen, SMG_ENODEV, "internal error: %lld windows of range %d were not found again", (long long) left, r);
+        if (have > 0) { st.batches++; RCHK(count_keys(have)); }
+        RCHK(finish_range());
+      }
+    return 0;
+  }
+
+  // the last batch, then histogram, clamp, trim; the table goes to malloc'ed host arrays
+  int finish(uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_parts *parts)
+  { RCHK(flush());
+    seq.reset();
+    RCHK(alloc(dh, sizeof(uint64_t) * SMG_COUNT_HIST));
+    DCHK(hipMemsetAsync(dh.p, 0, sizeof(uint64_t) * SMG_COUNT_HIST, stream));
+    if (parted) RCHK(run_ranges());
+    ka.reset(); kb.reset(); start.reset(); flag.reset(); pos.reset(); scode.reset(); sval.reset();
+    if (!parted || !hk) RCHK(finish_range());                 // (also the empty table of a run without any window)
+    if (hist) DCHK(hipMemcpy(hist, dh.p, sizeof(uint64_t) * SMG_COUNT_HIST, hipMemcpyDeviceToHost));
+    *keys = hk; *counts = hc; *nels = hn; *key_words = W;
+    hk = nullptr; hc = nullptr;
+    if (parts) { parts->used = pt.used; parts->store_bytes = pt.store_bytes; parts->ms_pack = pt.ms_pack; parts->ms_plan = pt.ms_plan; }
     return 0;
   }
 };
@@ -788,7 +1109,7 @@ static int check_opts(const smg_count_opts *o, char *errbuf, size_t errlen)
   return 0;
 }
 
-static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys, uint16_t **counts,
                        int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
 { const double t0 = now_ms();
   RCHK(check_opts(opts, errbuf, errlen));
@@ -807,7 +1128,7 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
       bound += (int64_t) size + opts->kmer + 1;
     }
   Counter c;
-  RCHK(c.init(opts, bound, npaths, errbuf, errlen));
+  RCHK(c.init(opts, parts, bound, npaths, errbuf, errlen));
 
   int nthr = opts->host_threads < 1 ? 1 : opts->host_threads > 16 ? 16 : opts->host_threads;
   if (nthr > npaths) nthr = npaths;
@@ -853,24 +1174,24 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
   if (rc) return rc;
   c.st.bases = ring.bases;
   c.st.ms_read = ring.t_last - t0;
-  RCHK(c.finish(keys, counts, nels, key_words, hist));
+  RCHK(c.finish(keys, counts, nels, key_words, hist, parts));
   c.st.ms_wall = now_ms() - t0;
   if (stats) *stats = c.st;
   return 0;
 }
 
-static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
+static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys, uint16_t **counts,
                        int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
 { const double t0 = now_ms();
   RCHK(check_opts(opts, errbuf, errlen));
   if (n < 0 || (n > 0 && !seq) || !keys || !counts || !nels || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
   Counter c;
-  RCHK(c.init(opts, n, 1, errbuf, errlen));
+  RCHK(c.init(opts, parts, n, 1, errbuf, errlen));
   const int64_t piece = (int64_t) 256 << 20;
   for (int64_t o = 0; o < n; o += piece) RCHK(c.add(seq + o, n - o < piece ? n - o : piece, 0));
   c.st.bases = n;
   c.st.ms_read = now_ms() - t0;
-  RCHK(c.finish(keys, counts, nels, key_words, hist));
+  RCHK(c.finish(keys, counts, nels, key_words, hist, parts));
   c.st.ms_wall = now_ms() - t0;
   if (stats) *stats = c.st;
   return 0;
@@ -888,11 +1209,71 @@ static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts
 
 extern "C" int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
                                int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
-{ GUARD(count_files(paths, npaths, opts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_files(paths, npaths, opts, nullptr, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
 
 extern "C" int smg_count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
                                int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
-{ GUARD(count_bases(seq, n, opts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_bases(seq, n, opts, nullptr, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" int smg_count_files_parts(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys,
+                                     uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
+                                     size_t errlen)
+{ GUARD(count_files(paths, npaths, opts, parts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" int smg_count_bases_parts(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys,
+                                     uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
+                                     size_t errlen)
+{ GUARD(count_bases(seq, n, opts, parts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+// The cuts of a partitioned run (host only).  Greedy over the bins: a range takes bins while its windows stay within the
+// budget, which gives the fewest contiguous ranges; the windows of a range bound its distinct k-mers and every merge of
+// it, so a plan made this way cannot overflow.  A requested number of ranges gets cuts at the equal shares of the
+// windows instead, moved where needed so that every range has a bin.
+static int plan(const uint64_t *windows, int64_t budget, int32_t partitions, int32_t *cuts, int32_t *nranges, char *errbuf, size_t errlen)
+{ if (!windows || !cuts || !nranges) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  if (partitions < 0 || partitions > SMG_COUNT_BINS)
+    return fail(errbuf, errlen, SMG_EINVAL, "partitions = %d is out of range 0 .. %d", partitions, SMG_COUNT_BINS);
+  int32_t n = 0;
+  cuts[0] = 0;
+  if (partitions == 0)
+    { if (budget < 1) return fail(errbuf, errlen, SMG_EINVAL, "budget = %lld is not positive", (long long) budget);
+      uint64_t sum = 0;
+      for (int b = 0; b < SMG_COUNT_BINS; b++)
+        { if (windows[b] > (uint64_t) budget)
+            { char lead[KC_BIN_BASES + 1];
+              for (int j = 0; j < KC_BIN_BASES; j++) lead[j] = "acgt"[(b >> (2 * (KC_BIN_BASES - 1 - j))) & 3];
+              lead[KC_BIN_BASES] = 0;
+              return fail(errbuf, errlen, SMG_ENOMEM, "bin %d (canonical k-mers that begin with %s) holds %llu windows, one merge holds %lld "
+                          "entries: a single bin cannot be split", b, lead, (unsigned long long) windows[b], (long long) budget);
+            }
+          if (sum + windows[b] > (uint64_t) budget) { cuts[++n] = b; sum = 0; }
+          sum += windows[b];
+        }
+      cuts[++n] = SMG_COUNT_BINS;
+    }
+  else
+    { uint64_t total = 0, cum = 0;
+      for (int b = 0; b < SMG_COUNT_BINS; b++) total += windows[b];
+      int b = 0;
+      for (int j = 1; j < partitions; j++)                         // cut j: the first bin boundary with j / P of the windows below it
+        { const uint64_t want = (uint64_t) (((unsigned __int128) total * (unsigned) j + (unsigned) partitions - 1) / (unsigned) partitions);
+          while (b < SMG_COUNT_BINS && cum < want) cum += windows[b++];
+          int c = b;
+          if (c <= cuts[j - 1]) c = cuts[j - 1] + 1;
+          if (c > SMG_COUNT_BINS - (partitions - j)) c = SMG_COUNT_BINS - (partitions - j);
+          while (b < c) cum += windows[b++];
+          cuts[j] = c;
+        }
+      n = partitions;
+      cuts[n] = SMG_COUNT_BINS;
+    }
+  *nranges = n;
+  return 0;
+}
+
+extern "C" int smg_count_plan(const uint64_t *windows, int64_t budget, int32_t partitions, int32_t *cuts, int32_t *nranges, char *errbuf,
+                              size_t errlen)
+{ GUARD(plan(windows, budget, partitions, cuts, nranges, errbuf, errlen)) }
 
 static int parse_path(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { if (!path || !seq || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
@@ -915,4 +1296,4 @@ extern "C" int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char
 
 extern "C" void smg_count_free(void *p) { free(p); }
 
-extern "C" const char *smg_count_version(void) { return "smudgeplot_amd 0.4 (k-mer counter, gfx950)"; }
+extern "C" const char *smg_count_version(void) { return "smudgeplot_amd 0.5 (k-mer counter, gfx950)"; }
