@@ -46,6 +46,7 @@
 
 #include "smg_count.h"
 #include "smg_device.hpp"
+#include "smg_keysort.hpp"
 
 #define KC_TPB   256
 #define KC_TILE  4096                    // positions per workgroup: 16 bytes per thread
@@ -287,17 +288,6 @@ kc_extract_packed(const u64 *__restrict__ code, const u64 *__restrict__ val, int
   kc_emit<W, true>(s_code, s_val, s_cnt, &s_base, tile0, p0, p1, k, lo, hi, out, limit, nout);
 }
 
-__global__ void __launch_bounds__(KC_TPB) kc_iota(uint32_t *__restrict__ p, int64_t n)
-{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
-  if (i < n) p[i] = (uint32_t) i;
-}
-
-__global__ void __launch_bounds__(KC_TPB)
-kc_gather_word(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, int W, int w, int64_t n, u64 *__restrict__ o)
-{ const int64_t i = (int64_t) blockIdx.x * KC_TPB + threadIdx.x;
-  if (i < n) o[i] = keys[(size_t) perm[i] * W + w];
-}
-
 template <int W> __global__ void __launch_bounds__(KC_TPB)
 kc_gather_entries(const u64 *__restrict__ keys, const uint32_t *__restrict__ val, const uint32_t *__restrict__ perm, int64_t n,
                   u64 *__restrict__ okeys, uint32_t *__restrict__ oval)
@@ -515,14 +505,6 @@ struct GrowSink : Sink
 #define RCHK(call) do { const int _rc = (call); if (_rc) return _rc; } while (0)
 #define DISPATCH_W(CALL) switch (W) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; default: CALL(4); break; }
 
-struct Dev                                                     // a device allocation that frees itself
-{ void *p = nullptr;
-  ~Dev() { if (p) (void) hipFree(p); }
-  void reset() { if (p) (void) hipFree(p); p = nullptr; }
-  void take(Dev &o) { reset(); p = o.p; o.p = nullptr; }
-  template <class T> T *as() const { return (T *) p; }
-};
-
 static unsigned nblk(int64_t n) { return (unsigned) ((n + KC_TPB - 1) / KC_TPB); }
 
 struct Counter
@@ -535,7 +517,7 @@ struct Counter
   int last_file = -1;                                          // the file whose stream ends at `fill`
   std::vector<std::vector<uint8_t>> tails;                     // per file: the last k-1 bytes handed over
   Dev seq, ka, kb, flag, pos, start, tmp, ctr, dk, dc;         // dk, dc: the running distinct list (k-mers, uint32 counts)
-  size_t tmp_cap = 0;
+  int64_t tmp_cap = 0;                                         // bytes behind tmp, the grow-only rocPRIM scratch
   int64_t nd = 0;
   smg_count_stats st;
   // a partitioned run: the packed input (positions; store_n is a multiple of 64), the bins, the host table so far
@@ -556,20 +538,10 @@ struct Counter
   }
 
   int alloc(Dev &d, size_t bytes)
-  { d.reset();
-    const hipError_t e = hipMalloc(&d.p, bytes ? bytes : 16);
+  { const hipError_t e = dev_alloc(d, bytes);
     if (e != hipSuccess)
-      { d.p = nullptr;
-        return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV,
-                    "cannot allocate %.3f GB of device memory: %s", (double) bytes * 1e-9, hipGetErrorString(e));
-      }
-    return 0;
-  }
-
-  int need_tmp(size_t bytes)
-  { if (bytes <= tmp_cap) return 0;
-    RCHK(alloc(tmp, bytes + 256));
-    tmp_cap = bytes + 256;
+      return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV,
+                  "cannot allocate %.3f GB of device memory: %s", (double) bytes * 1e-9, hipGetErrorString(e));
     return 0;
   }
 
@@ -726,53 +698,28 @@ struct Counter
   { if (W == 1)
       { rocprim::double_buffer<u64> dk2(a, b);
         rocprim::double_buffer<uint32_t> dv2(va, vb);
-        // All 64 bits, not 64-2k .. 64: the pad bits are zero, so the order is the same, and rocPRIM's merge-sort path
-        // (inputs below its radix threshold) left runs of 1024 keys unmerged when given a begin bit above 0.
+        // All 64 bits, not 64-2k .. 64: the pad bits are zero, so the order is the same, and a partial bit range is not
+        // safe on rocPRIM's merge-sort path (sort_permutation, smg_keysort.hpp).
         const unsigned b0 = 0u;
         size_t bytes = 0;
         if (va) { DCHK(rocprim::radix_sort_pairs(nullptr, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
         else { DCHK(rocprim::radix_sort_keys(nullptr, bytes, dk2, (size_t) n, b0, 64u, stream)); }
-        RCHK(need_tmp(bytes));
+        DCHK(ks_scratch(&tmp.p, &tmp_cap, bytes));
         if (va) { DCHK(rocprim::radix_sort_pairs(tmp.p, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
         else { DCHK(rocprim::radix_sort_keys(tmp.p, bytes, dk2, (size_t) n, b0, 64u, stream)); }
         *ko = dk2.current();
         if (vo) *vo = va ? dv2.current() : nullptr;
         return 0;
       }
-    // W > 1: stable sorts of (word, permutation), least significant word first, then one gather
-    Dev w1, w2, p1, p2;
-    RCHK(alloc(w1, sizeof(u64) * (size_t) n)); RCHK(alloc(w2, sizeof(u64) * (size_t) n));
-    RCHK(alloc(p1, sizeof(uint32_t) * (size_t) n)); RCHK(alloc(p2, sizeof(uint32_t) * (size_t) n));
-    rocprim::double_buffer<uint32_t> perm(p1.as<uint32_t>(), p2.as<uint32_t>());
-    hipLaunchKernelGGL(kc_iota, dim3(nblk(n)), dim3(KC_TPB), 0, stream, perm.current(), n);
-    for (int w = W - 1; w >= 0; w--)
-      { rocprim::double_buffer<u64> word(w1.as<u64>(), w2.as<u64>());
-        hipLaunchKernelGGL(kc_gather_word, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, perm.current(), W, w, n, word.current());
-        size_t bytes = 0;
-        DCHK(rocprim::radix_sort_pairs(nullptr, bytes, word, perm, (size_t) n, 0u, 64u, stream));
-        RCHK(need_tmp(bytes));
-        DCHK(rocprim::radix_sort_pairs(tmp.p, bytes, word, perm, (size_t) n, 0u, 64u, stream));
-      }
-#define CALL(WW) hipLaunchKernelGGL(kc_gather_entries<WW>, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, va, perm.current(), n, b, vb)
+    // W > 1: the sorted order as a permutation (smg_keysort.hpp), then one gather
+    Dev perm;
+    DCHK(sort_permutation(a, W, n, stream, &tmp.p, &tmp_cap, perm));
+#define CALL(WW) hipLaunchKernelGGL(kc_gather_entries<WW>, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, va, perm.as<uint32_t>(), n, b, vb)
     DISPATCH_W(CALL)
 #undef CALL
-    DCHK(hipStreamSynchronize(stream));                        // (the scratch is freed on return)
+    DCHK(hipStreamSynchronize(stream));                        // (the permutation is freed on return)
     *ko = b;
     if (vo) *vo = va ? vb : nullptr;
-    return 0;
-  }
-
-  // exclusive scan of fl[0..n) into ps[], the total to the host
-  int scan(uint32_t *fl, uint32_t *ps, int64_t n, int64_t *total)
-  { size_t bytes = 0;
-    DCHK(rocprim::exclusive_scan(nullptr, bytes, fl, ps, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
-    RCHK(need_tmp(bytes));
-    DCHK(rocprim::exclusive_scan(tmp.p, bytes, fl, ps, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
-    uint32_t last[2] = { 0, 0 };
-    DCHK(hipMemcpyAsync(&last[0], fl + n - 1, 4, hipMemcpyDeviceToHost, stream));
-    DCHK(hipMemcpyAsync(&last[1], ps + n - 1, 4, hipMemcpyDeviceToHost, stream));
-    DCHK(hipStreamSynchronize(stream));
-    *total = (int64_t) last[0] + last[1];
     return 0;
   }
 
@@ -812,7 +759,7 @@ struct Counter
 #define CALL(WW) hipLaunchKernelGGL(kc_flag_heads<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, (int64_t) nwin, flag.as<uint32_t>())
     DISPATCH_W(CALL)
 #undef CALL
-    RCHK(scan(flag.as<uint32_t>(), pos.as<uint32_t>(), (int64_t) nwin, &nruns));
+    DCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), (int64_t) nwin, stream, &tmp.p, &tmp_cap, &nruns));
 #define CALL(WW) hipLaunchKernelGGL(kc_runs<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, flag.as<uint32_t>(), pos.as<uint32_t>(), \
                                     (int64_t) nwin, uk, start.as<uint32_t>())
     DISPATCH_W(CALL)
@@ -864,7 +811,7 @@ struct Counter
     DISPATCH_W(CALL)
 #undef CALL
     int64_t nn = 0;
-    RCHK(scan(mf.as<uint32_t>(), mp.as<uint32_t>(), m, &nn));
+    DCHK(scan_flags(mf.as<uint32_t>(), mp.as<uint32_t>(), m, stream, &tmp.p, &tmp_cap, &nn));
     RCHK(alloc(nk, sizeof(u64) * (size_t) nn * W)); RCHK(alloc(nc, sizeof(uint32_t) * (size_t) nn));
 #define CALL(WW) hipLaunchKernelGGL(kc_merge_write<WW>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, sc, mf.as<uint32_t>(), mp.as<uint32_t>(), m, \
                                     nk.as<u64>(), nc.as<uint32_t>())
@@ -886,7 +833,7 @@ struct Counter
         const unsigned g = nblk(nd) < 2048u ? nblk(nd) : 2048u;
         hipLaunchKernelGGL(kc_finish_flag, dim3(g), dim3(KC_TPB), 0, stream, dc.as<uint32_t>(), nd, (unsigned) t,
                            dh.as<unsigned long long>(), ff.as<uint32_t>());
-        RCHK(scan(ff.as<uint32_t>(), fp.as<uint32_t>(), nd, &kept));
+        DCHK(scan_flags(ff.as<uint32_t>(), fp.as<uint32_t>(), nd, stream, &tmp.p, &tmp_cap, &kept));
         RCHK(alloc(ok, sizeof(u64) * (size_t) kept * W)); RCHK(alloc(oc, sizeof(uint16_t) * (size_t) kept));
 #define CALL(WW) hipLaunchKernelGGL(kc_finish_compact<WW>, dim3(nblk(nd)), dim3(KC_TPB), 0, stream, dk.as<u64>(), dc.as<uint32_t>(), \
                                     ff.as<uint32_t>(), fp.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>())

@@ -35,6 +35,7 @@
 
 #include "smg_hetmers.h"
 #include "smg_device.hpp"
+#include "smg_keysort.hpp"
 #include "smg_fast.hpp"
 #include "smg_pass1d.hpp"
 #include "smg_lookup.hpp"
@@ -1048,25 +1049,74 @@ static int plot_sum(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
   return SMG_OK;
 }
 
-// symmetric half-scan with counted degrees (exact uint8 wrap emulation), k > 85
-static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool *symmetric,
-                             char *errbuf, size_t errlen)
+__global__ void __launch_bounds__(TPB) kc_fill_u32(uint32_t *__restrict__ p, int64_t n, uint32_t v, uint32_t last)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i < n) p[i] = i == n - 1 ? last : v;
+}
+
+// The launches of both paths, each over the whole table, between its pair of events and dispatched on W.  What the
+// one-shot run and the phase API do differently (emit_all, the first size of the record list, k_verify) is their callers'.
+
+// k_pass1<W, SYM>: events 2, 3
+template <bool SYM> static void launch_pass1(smg_engine *e, int emit_all, int want_fp, u64 *req, int64_t cap, const TabSet *d_set)
+{ const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+  Tab t = make_tab(e);
+  hipEventRecord(e->ev[2], e->stream);
+  if (e->n > 0)
+    {
+#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
+                   (int64_t) 0, e->n, emit_all, want_fp, req, cap, e->ctrl, d_set)
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  hipEventRecord(e->ev[3], e->stream);
+}
+
+// k_apply<W> over nrec records, then (verify) k_verify<W> over the table: events 4, 5
+static void launch_apply(smg_engine *e, const u64 *rec, int64_t nrec, bool verify)
+{ Tab t = make_tab(e);
+  hipEventRecord(e->ev[4], e->stream);
+  if (nrec > 0)
+    { const unsigned rb = (unsigned) ((nrec + TPB - 1) / TPB);
+#define CALL(WW) hipLaunchKernelGGL(k_apply<WW>, dim3(rb), dim3(TPB), 0, e->stream, t, rec, nrec, e->ctrl)
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  if (verify && e->n > 0)
+    { const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+#define CALL(WW) hipLaunchKernelGGL(k_verify<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, (int64_t) 0, e->n, e->ctrl)
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  hipEventRecord(e->ev[5], e->stream);
+}
+
+// the plot cleared, then k_pass2<W, SYM>: events 6, 7
+template <bool SYM> static int launch_pass2(smg_engine *e, int64_t *d_plot, const TabSet *d_set, char *errbuf, size_t errlen)
+{ HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
+  hipEventRecord(e->ev[6], e->stream);
+  if (e->n > 0)
+    { Tab t = make_tab(e);
+      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
+                   (int64_t) 0, e->n, (u64 *) d_plot, d_set)
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  hipEventRecord(e->ev[7], e->stream);
+  HIPCHK(hipGetLastError());
+  return SMG_OK;
+}
+
+// Pass 1 of the symmetric half-scan = k_pass1<W, true>: S_all into deg[], records (rc(x), count | S_hi << 16) from the
+// owners of a hi-side pair (emit_all: from every entry) into the flat list e->req, which holds `cap` records at first and,
+// where pass 1 counted more, that many on the second attempt.
+static int counted_pass1(smg_engine *e, int emit_all, int symcheck, int64_t cap, char *errbuf, size_t errlen)
 { int rc;
   if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
-  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  int64_t cap = e->n / 4 + 1024;
   for (int attempt = 0; attempt < 2; attempt++)
     { if ((rc = grow(&e->req, &e->req_cap, cap * (int64_t) sizeof(u64) * (e->W + 1), errbuf, errlen))) return rc;
-      Tab t = make_tab(e);
-      hipEventRecord(e->ev[2], e->stream);
-      if (e->n > 0)
-        {
-#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, true>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, 0, symcheck == SMG_SYM_HASH, e->req, cap, e->ctrl)
-          DISPATCH_W(e, CALL)
-#undef CALL
-        }
-      hipEventRecord(e->ev[3], e->stream);
+      launch_pass1<true>(e, emit_all, symcheck == SMG_SYM_HASH, e->req, cap, NULL);
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       if (e->h_ctrl->unsorted)
         return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
@@ -1077,41 +1127,24 @@ static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool 
     }
   float ms = 0; hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
   e->st.ms_pass1 = ms;
-  const int64_t nreq = (int64_t) e->h_ctrl->nreq;
-  e->st.nrequests = nreq;
-  hipEventRecord(e->ev[4], e->stream);
-  { Tab t = make_tab(e);
-    if (nreq > 0)
-      { const unsigned rb = (unsigned) ((nreq + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_apply<WW>, dim3(rb), dim3(TPB), 0, e->stream, t, e->req, nreq, e->ctrl)
-        DISPATCH_W(e, CALL)
-#undef CALL
-      }
-    if (symcheck == SMG_SYM_EXACT && e->n > 0)
-      {
-#define CALL(WW) hipLaunchKernelGGL(k_verify<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, (int64_t) 0, e->n, e->ctrl)
-        DISPATCH_W(e, CALL)
-#undef CALL
-      }
-  }
-  hipEventRecord(e->ev[5], e->stream);
+  e->st.nrequests = (int64_t) e->h_ctrl->nreq;
+  return SMG_OK;
+}
+
+// symmetric half-scan with counted degrees (exact uint8 wrap emulation), k > 85
+static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool *symmetric,
+                             char *errbuf, size_t errlen)
+{ int rc;
+  if ((rc = counted_pass1(e, 0, symcheck, e->n / 4 + 1024, errbuf, errlen))) return rc;
+  launch_apply(e, e->req, e->st.nrequests, symcheck == SMG_SYM_EXACT);
   if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-  hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
+  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
   e->st.ms_rclookup = ms;
   *symmetric = e->h_ctrl->missing == 0;
   if (*symmetric && symcheck == SMG_SYM_HASH)
     *symmetric = e->h_ctrl->fp[0] == e->h_ctrl->fp[2] && e->h_ctrl->fp[1] == e->h_ctrl->fp[3];
   if (!*symmetric) return SMG_OK;
-  HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
-  hipEventRecord(e->ev[6], e->stream);
-  if (e->n > 0)
-    { Tab t = make_tab(e);
-#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, true>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, (u64 *) d_plot)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[7], e->stream);
+  if ((rc = launch_pass2<true>(e, d_plot, NULL, errbuf, errlen))) return rc;
   if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
   hipEventElapsedTime(&ms, e->ev[6], e->ev[7]);
   e->st.ms_pass2 = ms;
@@ -1120,32 +1153,55 @@ static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool 
   return SMG_OK;
 }
 
+// The same in the steps of the phase API (sharded runs): the flat list is presented to the router as full chunks of F_CH
+// records; a received record adds S_hi to the degree of its k-mer (the uint8 wrap of PloidyPlot.c:163 emulated by deg_add)
+// and proves that the k-mer is there with the same count.  The exact proof emits from every entry instead of k_verify.
+static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
+{ const int emit_all = symcheck == SMG_SYM_EXACT;
+  e->rw = e->W + 1;
+  int rc = counted_pass1(e, emit_all, symcheck, (emit_all ? e->n : e->n / 4) + 1024, errbuf, errlen);
+  if (rc) return rc;
+  const int64_t nreq = e->st.nrequests;
+  for (int i = 0; i < 4; i++) e->fp[i] = e->h_ctrl->fp[i];
+  const int64_t nc = (nreq + F_CH - 1) / F_CH;
+  if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large%s");
+  if ((rc = grow(&e->chunk_fill, &e->chunk_cap, nc * 4 + 4, errbuf, errlen))) return rc;
+  if (nc > 0)
+    hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->chunk_fill, nc, (uint32_t) F_CH,
+                       (uint32_t) (nreq - (nc - 1) * F_CH));
+  HIPCHK(hipGetLastError());
+  e->n_chunks = (unsigned) nc; e->bm_bits = 0; e->filtered = false; e->presorted = false;
+  e->st.path = 1; e->st.ms_filter = 0;
+  e->prepared = true;                     // (with e->fast == false: the counted steps)
+  return SMG_OK;
+}
+
+static int counted_phase_apply(smg_engine *e, const u64 *rec, int64_t nrec, int64_t *missing, char *errbuf, size_t errlen)
+{ launch_apply(e, rec, nrec, false);
+  HIPCHK(hipGetLastError());
+  if (!missing) { e->lookup_pending = true; return SMG_OK; }
+  const int rc = read_ctrl(e, errbuf, errlen);
+  if (rc) return rc;
+  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
+  e->st.ms_rclookup += ms;
+  *missing = (int64_t) e->h_ctrl->missing;
+  return SMG_OK;
+}
+
+static int counted_phase_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
+{ const int rc = launch_pass2<true>(e, d_plot, NULL, errbuf, errlen);
+  if (rc) return rc;
+  e->st.path = 1; e->st.npairs = 0; e->st.ms_pass2 = -1.0;      // (no host wait: smg_engine_stats resolves the events)
+  e->counted_done = true;
+  return SMG_OK;
+}
+
 // general (assumption-free) path: both passes over every position
 static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
 { int rc;
   if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
-  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  Tab t = make_tab(e);
-  hipEventRecord(e->ev[2], e->stream);
-  if (e->n > 0)
-    {
-#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, false>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, 0, 0, (u64 *) NULL, (int64_t) 0, e->ctrl)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[3], e->stream);
-  HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
-  hipEventRecord(e->ev[6], e->stream);
-  if (e->n > 0)
-    {
-#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, false>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, (u64 *) d_plot)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[7], e->stream);
-  HIPCHK(hipGetLastError());
+  launch_pass1<false>(e, 0, 0, NULL, 0, NULL);
+  if ((rc = launch_pass2<false>(e, d_plot, NULL, errbuf, errlen))) return rc;
   if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
   if (e->h_ctrl->unsorted)
     return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
@@ -1169,34 +1225,12 @@ static int general_shard_prepare(smg_engine *e, Tab *out, char *errbuf, size_t e
 }
 
 static int general_shard_pass(smg_engine *e, const TabSet *d_set, int pass, int64_t *d_plot, char *errbuf, size_t errlen)
-{ const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  Tab t = make_tab(e);
-  if (pass == 1)
-    { hipEventRecord(e->ev[2], e->stream);
-      if (e->n > 0)
-        {
-#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, false>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, 0, 0, (u64 *) NULL, (int64_t) 0, e->ctrl, d_set)
-          DISPATCH_W(e, CALL)
-#undef CALL
-        }
-      hipEventRecord(e->ev[3], e->stream);
-    }
-  else
-    { HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
-      hipEventRecord(e->ev[6], e->stream);
-      if (e->n > 0)
-        {
-#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, false>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, (u64 *) d_plot, d_set)
-          DISPATCH_W(e, CALL)
-#undef CALL
-        }
-      hipEventRecord(e->ev[7], e->stream);
-    }
-  HIPCHK(hipGetLastError());
-  int rc = read_ctrl(e, errbuf, errlen);
+{ int rc = SMG_OK;
+  if (pass == 1) launch_pass1<false>(e, 0, 0, NULL, 0, d_set);
+  else rc = launch_pass2<false>(e, d_plot, d_set, errbuf, errlen);
   if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
   if (e->h_ctrl->unsorted) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
   float ms = 0;
   if (pass == 1) { hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 += ms; }
@@ -1905,7 +1939,7 @@ static int counted_resume(smg_engine *e, const uint8_t *d_degs, char *errbuf, si
 }
 
 // ---- public phase API (sharded runs) ------------------------------------------------------------
-// k <= 85: the fast path.  k > 85: the counted path in the same steps (counted_phase_* below) -- pass 1 leaves ONE flat
+// k <= 85: the fast path.  k > 85: the counted path in the same steps (counted_phase_* above) -- pass 1 leaves ONE flat
 // list of (rc(x), count | S_hi << 16) records, presented to the router as full chunks; no block map, nothing is filtered.
 
 #define NEED_FAST(e)                                                                          \
@@ -1913,10 +1947,6 @@ static int counted_resume(smg_engine *e, const uint8_t *d_degs, char *errbuf, si
   if ((e)->kmer > FAST_MAX_K)                                                                 \
     return fail(errbuf, errlen, SMG_EINVAL, "no block map and no request filter above k = 85%s");
 #define NEED_ENGINE(e)  if (!(e)) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-
-static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen);
-static int counted_phase_apply(smg_engine *e, const u64 *rec, int64_t nrec, int64_t *missing, char *errbuf, size_t errlen);
-static int counted_phase_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen);
 
 extern "C" int smg_engine_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
@@ -2294,10 +2324,7 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
 //   symmetrise  : add rc(x) with the count of x for every entry x, sort, keep one copy of a k-mer that
 //                 occurs twice (a self-complementary k-mer, or -- only on input that is neither canonical
 //                 nor symmetric -- a k-mer whose complement was already present: the original entry wins)
-// Sorting is an LSD radix sort over the 64-bit words of the k-mer (stable, rocPRIM Onesweep).
-
-typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                   rocprim::default_config, 0> smg_pair_sort_config;
+// The sort, the scans and the buffers are those of the k-mer counter (smg_keysort.hpp).
 
 template <int W> __global__ void __launch_bounds__(TPB)
 kc_append_rc(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k,
@@ -2309,18 +2336,6 @@ kc_append_rc(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int
 #pragma unroll
   for (int w = 0; w < W; w++) { okeys[i * W + w] = x.w[w]; okeys[(n + i) * W + w] = r.w[w]; }
   ocnt[i] = cnt[i]; ocnt[n + i] = cnt[i];
-}
-
-__global__ void __launch_bounds__(TPB) kc_iota(uint32_t *__restrict__ p, int64_t n)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i < n) p[i] = (uint32_t) i;
-}
-
-__global__ void __launch_bounds__(TPB)
-kc_gather_word(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, int W, int w, int64_t n,
-               u64 *__restrict__ out)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i < n) out[i] = keys[(int64_t) perm[i] * W + w];
 }
 
 // flag[i] = 1 when the i-th entry in sorted order survives (first of its k-mer)
@@ -2354,24 +2369,76 @@ kc_compact(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const
   ocnt[dst] = cnt[src];
 }
 
-// flag -> positions + survivor count (exclusive scan); tmp is engine scratch
-static int cond_scan(smg_engine *e, uint32_t *flag, uint32_t *pos, int64_t n, int64_t *kept,
-                     char *errbuf, size_t errlen)
-{ size_t tmp = 0;
-  int rc;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tmp, flag, pos, 0u, (size_t) n, rocprim::plus<uint32_t>(), e->stream));
-  if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
-  HIPCHK(rocprim::exclusive_scan(e->sort_tmp, tmp, flag, pos, 0u, (size_t) n, rocprim::plus<uint32_t>(), e->stream));
-  uint32_t lastp = 0, lastf = 0;
-  HIPCHK(hipMemcpyAsync(&lastp, pos + (n - 1), 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(&lastf, flag + (n - 1), 4, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  *kept = (int64_t) lastp + lastf;
-  return SMG_OK;
+// like kc_compact, for a sorted permutation in which a k-mer occurs at most twice (once as an entry, once as a
+// complement): the survivor is the first of the two, its count the ENTRY's
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_compact_pref(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint8_t *__restrict__ copy,
+                const uint32_t *__restrict__ perm, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                int64_t n, u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t src = perm[i];
+  int64_t csrc = src;
+  if (copy[src] && i + 1 < n && !flag[i + 1]) csrc = perm[i + 1];        // (the next one is the same k-mer: the entry)
+  const int64_t dst = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
+  ocnt[dst] = cnt[csrc];
 }
 
+// the engine's table has n entries now and is another table: what a run, the prefix index and the ends said is gone
+static void table_changed(smg_engine *e, int64_t n)
+{ e->n = n;
+  e->prepared = false; e->counted_done = false; e->general_done = false;
+  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
+  e->st.nels = n;
+}
+
+// (k, c), n finished entries, leave their buffers and become the engine's own table.  The stream is idle: the old one is freed.
+static void adopt_table(smg_engine *e, Dev &k, Dev &c, int64_t n)
+{ hipFree(e->own_keys); hipFree(e->own_cnt);
+  e->own_keys = (u64 *) k.release(); e->own_cnt = (uint16_t *) c.release();
+  e->keys = e->own_keys; e->cnt = e->own_cnt;
+  table_changed(e, n);
+}
+
+// sorted, duplicate-free table from 2-copies-at-most material: keys[n2 * W], counts, copy flags (NULL: the first of two
+// equal k-mers in INPUT order wins, as the stable sort leaves it) -> the engine's own table.  Frees nothing of the caller's.
 static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, const uint8_t *copy, int64_t n2,
-                            int64_t *kept_out, char *errbuf, size_t errlen);
+                            int64_t *kept_out, char *errbuf, size_t errlen)
+{ const int W = e->W;
+  if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
+  const unsigned nblk2 = (unsigned) ((n2 + TPB - 1) / TPB);
+  Dev perm, flag, pos, ko, co;
+  int64_t kept = 0;
+  HIPCHK(sort_permutation(k2, W, n2, e->stream, &e->sort_tmp, &e->sort_tmp_cap, perm));
+  HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n2));
+  HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n2));
+#define CALL(WW) hipLaunchKernelGGL(kc_flag_first<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm.as<uint32_t>(), n2, flag.as<uint32_t>())
+  DISPATCH_W(e, CALL)
+#undef CALL
+  HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n2, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &kept));
+  HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
+  HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
+  if (copy)
+    {
+#define CALL(WW) hipLaunchKernelGGL(kc_compact_pref<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm.as<uint32_t>(), \
+                   flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>())
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  else
+    {
+#define CALL(WW) hipLaunchKernelGGL(kc_compact<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm.as<uint32_t>(), \
+                   flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>())
+      DISPATCH_W(e, CALL)
+#undef CALL
+    }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  adopt_table(e, ko, co, kept);
+  *kept_out = kept;
+  return SMG_OK;
+}
 
 extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
                                     int64_t *new_nels, char *errbuf, size_t errlen)
@@ -2381,68 +2448,56 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
   const int W = e->W;
   int rc;
   int64_t n = e->n;
-  hipEvent_t c0, c1;
-  hipEventCreate(&c0); hipEventCreate(&c1);
-  hipEventRecord(c0, e->stream);
-  uint32_t *flag = NULL, *pos = NULL, *perm = NULL, *perm2 = NULL;
-  u64 *k2 = NULL, *wk = NULL, *wk2 = NULL, *ko = NULL;
-  uint16_t *c2 = NULL, *co = NULL;
-#define CFREE() { hipFree(flag); hipFree(pos); hipFree(perm); hipFree(perm2); hipFree(k2); hipFree(wk); \
-                  hipFree(wk2); hipFree(c2); hipFree(ko); hipFree(co); hipEventDestroy(c0); hipEventDestroy(c1); }
-#define CCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { CFREE(); \
-                     return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, \
-                                 "HIP error while conditioning: %s", hipGetErrorString(_e)); } } while (0)
-#define CRC(call) do { if ((rc = (call))) { CFREE(); return rc; } } while (0)
+  hipEventRecord(e->ev[0], e->stream);                 // (the decode pair: conditioning is booked under ms_decode)
 
   if (do_trim && n > 0)
     { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
-      CCHK(hipMalloc(&flag, sizeof(uint32_t) * (size_t) n));
-      CCHK(hipMalloc(&pos, sizeof(uint32_t) * (size_t) n));
-      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->cnt, n, (unsigned) ethresh, flag);
+      Dev flag, pos, ko, co;
+      HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n));
+      HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n));
+      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->cnt, n, (unsigned) ethresh, flag.as<uint32_t>());
       int64_t kept = 0;
-      CRC(cond_scan(e, flag, pos, n, &kept, errbuf, errlen));
-      CCHK(hipMalloc(&ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
-      CCHK(hipMalloc(&co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
+      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &kept));
+      HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
+      HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
 #define CALL(WW) hipLaunchKernelGGL(kc_compact<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, \
-                   (const uint32_t *) NULL, flag, pos, n, ko, co)
+                   (const uint32_t *) NULL, flag.as<uint32_t>(), pos.as<uint32_t>(), n, ko.as<u64>(), co.as<uint16_t>())
       DISPATCH_W(e, CALL)
 #undef CALL
-      CCHK(hipStreamSynchronize(e->stream));
-      hipFree(e->own_keys); hipFree(e->own_cnt);
-      e->own_keys = ko; e->own_cnt = co; ko = NULL; co = NULL;
-      e->keys = e->own_keys; e->cnt = e->own_cnt;
+      HIPCHK(hipStreamSynchronize(e->stream));
+      adopt_table(e, ko, co, kept);
       n = kept;
-      hipFree(flag); hipFree(pos); flag = pos = NULL;
     }
 
   if (do_symm && n > 0)
     { const int64_t n2 = 2 * n;
-      if (n2 >= 0xFFFFFFF0ll) { CFREE(); return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s"); }
+      if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
       const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
-      CCHK(hipMalloc(&k2, sizeof(u64) * (size_t) n2 * W));
-      CCHK(hipMalloc(&c2, sizeof(uint16_t) * (size_t) n2));
-#define CALL(WW) hipLaunchKernelGGL(kc_append_rc<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, n, e->kmer, k2, c2)
+      Dev k2, c2;
+      HIPCHK(dev_alloc(k2, sizeof(u64) * (size_t) n2 * W));
+      HIPCHK(dev_alloc(c2, sizeof(uint16_t) * (size_t) n2));
+#define CALL(WW) hipLaunchKernelGGL(kc_append_rc<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, n, e->kmer, \
+                   k2.as<u64>(), c2.as<uint16_t>())
       DISPATCH_W(e, CALL)
 #undef CALL
-      int64_t kept = 0;
       // (entries first, complements behind them: the stable sort keeps the entry in front of an equal complement)
-      CRC(cond_sort_dedupe(e, k2, c2, NULL, n2, &kept, errbuf, errlen));
-      n = kept;
+      if ((rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), NULL, n2, &n, errbuf, errlen))) return rc;
     }
-  hipEventRecord(c1, e->stream);
-  CCHK(hipStreamSynchronize(e->stream));
-  float ms = 0; hipEventElapsedTime(&ms, c0, c1);
-  CFREE();
-#undef CFREE
-#undef CCHK
-#undef CRC
-  e->n = n;
-  e->prepared = false; e->counted_done = false; e->general_done = false;
-  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;      // (another table now: its index and ends are gone)
+  hipEventRecord(e->ev[1], e->stream);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  float ms = 0; hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
+  table_changed(e, n);                                 // (also where nothing was asked for, or of an empty table)
   e->rp_have = false; e->rp_active = false;
-  e->st.nels = n;
   e->st.ms_decode += ms;
   if (new_nels) *new_nels = n;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
+{ if (!e) return SMG_EINVAL;
+  if (nels) *nels = e->n;
+  if (d_keys) *d_keys = (const uint64_t *) e->keys;
+  if (d_counts) *d_counts = e->cnt;
   return SMG_OK;
 }
 
@@ -2491,99 +2546,6 @@ kc_symm_records(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, 
   b[W] = (u64) cnt[i] | (1ull << 16);
 }
 
-__global__ void __launch_bounds__(TPB) kc_fill_u32(uint32_t *__restrict__ p, int64_t n, uint32_t v, uint32_t last)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i < n) p[i] = i == n - 1 ? last : v;
-}
-
-// ---- the counted path (k > 85) in the steps of the phase API ---------------------------------------------------
-// Pass 1 = k_pass1<W, true>: S_all into deg[], records (rc(x), count | S_hi << 16) from the owners of a hi-side pair (from
-// every entry for the exact proof) into one flat list, which the router reads as full chunks of F_CH records; a received
-// record adds S_hi to the degree of its k-mer (the uint8 wrap of PloidyPlot.c:163 emulated by deg_add) and proves that
-// the k-mer is there with the same count; pass 2 = k_pass2<W, true>.
-static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
-{ int rc;
-  if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
-  const int emit_all = symcheck == SMG_SYM_EXACT;
-  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  int64_t cap = (emit_all ? e->n : e->n / 4) + 1024;
-  e->rw = e->W + 1;
-  for (int attempt = 0; attempt < 2; attempt++)
-    { if ((rc = grow(&e->req, &e->req_cap, cap * (int64_t) sizeof(u64) * e->rw, errbuf, errlen))) return rc;
-      Tab t = make_tab(e);
-      hipEventRecord(e->ev[2], e->stream);
-      if (e->n > 0)
-        {
-#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, true>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, emit_all, symcheck == SMG_SYM_HASH, e->req, cap, e->ctrl)
-          DISPATCH_W(e, CALL)
-#undef CALL
-        }
-      hipEventRecord(e->ev[3], e->stream);
-      if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-      if (e->h_ctrl->unsorted)
-        return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
-      if ((int64_t) e->h_ctrl->nreq <= cap) break;
-      cap = (int64_t) e->h_ctrl->nreq;
-      HIPCHK(hipMemsetAsync(&e->ctrl->nreq, 0, sizeof(u64), e->stream));
-      HIPCHK(hipMemsetAsync(e->ctrl->fp, 0, sizeof(u64) * 4, e->stream));
-    }
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
-  e->st.ms_pass1 = ms;
-  const int64_t nreq = (int64_t) e->h_ctrl->nreq;
-  e->st.nrequests = nreq;
-  for (int i = 0; i < 4; i++) e->fp[i] = e->h_ctrl->fp[i];
-  const int64_t nc = (nreq + F_CH - 1) / F_CH;
-  if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large%s");
-  if ((rc = grow(&e->chunk_fill, &e->chunk_cap, nc * 4 + 4, errbuf, errlen))) return rc;
-  if (nc > 0)
-    hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->chunk_fill, nc, (uint32_t) F_CH,
-                       (uint32_t) (nreq - (nc - 1) * F_CH));
-  HIPCHK(hipGetLastError());
-  e->n_chunks = (unsigned) nc; e->bm_bits = 0; e->filtered = false; e->presorted = false;
-  e->st.path = 1; e->st.ms_filter = 0;
-  e->prepared = true;                     // (with e->fast == false: the counted steps)
-  return SMG_OK;
-}
-
-static int counted_phase_apply(smg_engine *e, const u64 *rec, int64_t nrec, int64_t *missing, char *errbuf, size_t errlen)
-{ hipEventRecord(e->ev[4], e->stream);
-  if (nrec > 0)
-    { Tab t = make_tab(e);
-      const unsigned rb = (unsigned) ((nrec + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_apply<WW>, dim3(rb), dim3(TPB), 0, e->stream, t, rec, nrec, e->ctrl)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[5], e->stream);
-  HIPCHK(hipGetLastError());
-  if (!missing) { e->lookup_pending = true; return SMG_OK; }
-  const int rc = read_ctrl(e, errbuf, errlen);
-  if (rc) return rc;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
-  e->st.ms_rclookup += ms;
-  *missing = (int64_t) e->h_ctrl->missing;
-  return SMG_OK;
-}
-
-static int counted_phase_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
-{ HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
-  hipEventRecord(e->ev[6], e->stream);
-  if (e->n > 0)
-    { Tab t = make_tab(e);
-      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, true>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, (u64 *) d_plot)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[7], e->stream);
-  HIPCHK(hipGetLastError());
-  e->st.path = 1; e->st.npairs = 0; e->st.ms_pass2 = -1.0;      // (no host wait: smg_engine_stats resolves the events)
-  e->counted_done = true;
-  return SMG_OK;
-}
-
 // records -> separate k-mer / count / is-a-complement arrays
 template <int W> __global__ void __launch_bounds__(TPB)
 kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, uint16_t *__restrict__ cnt, uint8_t *__restrict__ copy)
@@ -2596,51 +2558,25 @@ kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, u
   copy[i] = (uint8_t) ((q[W] >> 16) & 1u);
 }
 
-// like kc_compact, for a sorted permutation in which a k-mer occurs at most twice (once as an entry, once as a
-// complement): the survivor is the first of the two, its count the ENTRY's
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_compact_pref(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint8_t *__restrict__ copy,
-                const uint32_t *__restrict__ perm, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
-                int64_t n, u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const int64_t src = perm[i];
-  int64_t csrc = src;
-  if (copy[src] && i + 1 < n && !flag[i + 1]) csrc = perm[i + 1];        // (the next one is the same k-mer: the entry)
-  const int64_t dst = pos[i];
-#pragma unroll
-  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
-  ocnt[dst] = cnt[csrc];
-}
-
-extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
-{ if (!e) return SMG_EINVAL;
-  if (nels) *nels = e->n;
-  if (d_keys) *d_keys = (const uint64_t *) e->keys;
-  if (d_counts) *d_counts = e->cnt;
-  return SMG_OK;
-}
-
 extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
 { if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
   if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
   if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
   const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
-  u64 *d = NULL;
-  HIPCHK(hipMalloc(&d, bytes));
-  hipError_t he = hipMemsetAsync(d, 0, bytes, e->stream);
+  Dev d;
+  HIPCHK(dev_alloc(d, bytes));
+  hipError_t he = hipMemsetAsync(d.p, 0, bytes, e->stream);
   if (he == hipSuccess && e->n > 0)
     { int64_t nb = (e->n + TPB - 1) / TPB;
       if (nb > 2048) nb = 2048;
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_hist<WW>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->keys, e->n, e->kmer, bits, d)
+#define CALL(WW) hipLaunchKernelGGL(kc_symm_hist<WW>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->keys, e->n, e->kmer, bits, d.as<u64>())
       DISPATCH_W(e, CALL)
 #undef CALL
       he = hipGetLastError();
     }
-  if (he == hipSuccess) he = hipMemcpyAsync(hist, d, bytes, hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(hist, d.p, bytes, hipMemcpyDeviceToHost, e->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  hipFree(d);
   if (he != hipSuccess) return fail(errbuf, errlen, SMG_ENODEV, "symm_hist: %s", hipGetErrorString(he));
   return SMG_OK;
 }
@@ -2657,84 +2593,20 @@ extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, i
   const int rw = e->W + 1;
   const int64_t nc = (n2 + F_CH - 1) / F_CH;
   if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: shard too large%s");
-  u64 *rec = NULL; uint32_t *fill = NULL;
+  Dev rec, fill;
   int rc = SMG_OK;
-  if (hipMalloc(&rec, sizeof(u64) * (size_t) n2 * rw) != hipSuccess || hipMalloc(&fill, sizeof(uint32_t) * (size_t) nc) != hipSuccess)
-    { hipFree(rec); hipFree(fill); return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s"); }
+  if (dev_alloc(rec, sizeof(u64) * (size_t) n2 * rw) != hipSuccess || dev_alloc(fill, sizeof(uint32_t) * (size_t) nc) != hipSuccess)
+    return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
   const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_records<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, e->n, e->kmer, rec)
+#define CALL(WW) hipLaunchKernelGGL(kc_symm_records<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, e->n, e->kmer, rec.as<u64>())
   DISPATCH_W(e, CALL)
 #undef CALL
-  hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill, nc, (uint32_t) F_CH,
+  hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill.as<uint32_t>(), nc, (uint32_t) F_CH,
                      (uint32_t) (n2 - (nc - 1) * F_CH));
   if (hipGetLastError() != hipSuccess) rc = fail(errbuf, errlen, SMG_ENODEV, "symm_route: launch failed%s");
-  if (rc == SMG_OK) rc = route_records(e, rec, fill, (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
-  hipStreamSynchronize(e->stream);
-  hipFree(rec); hipFree(fill);
+  if (rc == SMG_OK) rc = route_records(e, rec.as<u64>(), fill.as<uint32_t>(), (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
+  hipStreamSynchronize(e->stream);                     // (the records are freed on return)
   return rc;
-}
-
-// sorted, duplicate-free table from 2-copies-at-most material: keys[n2 * W], counts, copy flags (NULL: the first of two
-// equal k-mers in INPUT order wins, as the stable sort leaves it) -> the engine's own table.  Frees nothing of the caller's.
-static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, const uint8_t *copy, int64_t n2,
-                            int64_t *kept_out, char *errbuf, size_t errlen)
-{ const int W = e->W;
-  int rc = SMG_OK;
-  uint32_t *flag = NULL, *pos = NULL, *perm = NULL, *perm2 = NULL;
-  u64 *wk = NULL, *wk2 = NULL, *ko = NULL;
-  uint16_t *co = NULL;
-  int64_t kept = 0;
-  if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
-  const unsigned nblk2 = (unsigned) ((n2 + TPB - 1) / TPB);
-#define SFREE() { hipFree(flag); hipFree(pos); hipFree(perm); hipFree(perm2); hipFree(wk); hipFree(wk2); hipFree(ko); hipFree(co); }
-#define SCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { SFREE(); \
-                     return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, \
-                                 "HIP error while conditioning: %s", hipGetErrorString(_e)); } } while (0)
-#define SRC(call) do { if ((rc = (call))) { SFREE(); return rc; } } while (0)
-  SCHK(hipMalloc(&perm, sizeof(uint32_t) * (size_t) n2));
-  SCHK(hipMalloc(&perm2, sizeof(uint32_t) * (size_t) n2));
-  SCHK(hipMalloc(&wk, sizeof(u64) * (size_t) n2));
-  SCHK(hipMalloc(&wk2, sizeof(u64) * (size_t) n2));
-  hipLaunchKernelGGL(kc_iota, dim3(nblk2), dim3(TPB), 0, e->stream, perm, n2);
-  for (int w = W - 1; w >= 0; w--)              // LSD over the words, stable
-    { hipLaunchKernelGGL(kc_gather_word, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm, W, w, n2, wk);
-      size_t tmp = 0;
-      SCHK(rocprim::radix_sort_pairs<smg_pair_sort_config>(nullptr, tmp, wk, wk2, perm, perm2, (size_t) n2, 0u, 64u, e->stream));
-      SRC(grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen));
-      SCHK(rocprim::radix_sort_pairs<smg_pair_sort_config>(e->sort_tmp, tmp, wk, wk2, perm, perm2, (size_t) n2, 0u, 64u, e->stream));
-      uint32_t *sw = perm; perm = perm2; perm2 = sw;
-    }
-  hipFree(wk); hipFree(wk2); hipFree(perm2); wk = wk2 = NULL; perm2 = NULL;
-  SCHK(hipMalloc(&flag, sizeof(uint32_t) * (size_t) n2));
-  SCHK(hipMalloc(&pos, sizeof(uint32_t) * (size_t) n2));
-#define CALL(WW) hipLaunchKernelGGL(kc_flag_first<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm, n2, flag)
-  DISPATCH_W(e, CALL)
-#undef CALL
-  SRC(cond_scan(e, flag, pos, n2, &kept, errbuf, errlen));
-  SCHK(hipMalloc(&ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
-  SCHK(hipMalloc(&co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
-  if (copy)
-    {
-#define CALL(WW) hipLaunchKernelGGL(kc_compact_pref<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm, flag, pos, n2, ko, co)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  else
-    {
-#define CALL(WW) hipLaunchKernelGGL(kc_compact<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm, flag, pos, n2, ko, co)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  SCHK(hipStreamSynchronize(e->stream));
-  hipFree(e->own_keys); hipFree(e->own_cnt);
-  e->own_keys = ko; e->own_cnt = co; ko = NULL; co = NULL;
-  e->keys = e->own_keys; e->cnt = e->own_cnt;
-  SFREE();
-#undef SFREE
-#undef SCHK
-#undef SRC
-  *kept_out = kept;
-  return SMG_OK;
 }
 
 extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int64_t nrecv, int64_t *new_nels,
@@ -2744,29 +2616,24 @@ extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int
   HIPCHK(hipSetDevice(e->device));
   int64_t kept = 0;
   if (nrecv == 0)
-    { hipFree(e->own_keys); hipFree(e->own_cnt); e->own_keys = NULL; e->own_cnt = NULL;
-      HIPCHK(hipMalloc(&e->own_keys, sizeof(u64) * e->W)); HIPCHK(hipMalloc(&e->own_cnt, 16));
-      e->keys = e->own_keys; e->cnt = e->own_cnt;
+    { Dev ko, co;
+      HIPCHK(dev_alloc(ko, sizeof(u64) * e->W)); HIPCHK(dev_alloc(co, 16));
+      adopt_table(e, ko, co, 0);
     }
   else
     { if (nrecv >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
-      u64 *k2 = NULL; uint16_t *c2 = NULL; uint8_t *cp = NULL;
-      if (hipMalloc(&k2, sizeof(u64) * (size_t) nrecv * e->W) != hipSuccess || hipMalloc(&c2, sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
-          || hipMalloc(&cp, (size_t) nrecv + 16) != hipSuccess)
-        { hipFree(k2); hipFree(c2); hipFree(cp); return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s"); }
+      Dev k2, c2, cp;
+      if (dev_alloc(k2, sizeof(u64) * (size_t) nrecv * e->W) != hipSuccess || dev_alloc(c2, sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
+          || dev_alloc(cp, (size_t) nrecv + 16) != hipSuccess)
+        return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
       const unsigned nblk = (unsigned) ((nrecv + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_unpack<WW>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2, c2, cp)
+#define CALL(WW) hipLaunchKernelGGL(kc_symm_unpack<WW>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2.as<u64>(), \
+                   c2.as<uint16_t>(), cp.as<uint8_t>())
       DISPATCH_W(e, CALL)
 #undef CALL
-      const int rc = cond_sort_dedupe(e, k2, c2, cp, nrecv, &kept, errbuf, errlen);
-      hipStreamSynchronize(e->stream);
-      hipFree(k2); hipFree(c2); hipFree(cp);
+      const int rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), cp.as<uint8_t>(), nrecv, &kept, errbuf, errlen);
       if (rc) return rc;
     }
-  e->n = kept;
-  e->prepared = false; e->counted_done = false; e->general_done = false;
-  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
-  e->st.nels = kept;
   if (new_nels) *new_nels = kept;
   return SMG_OK;
 }

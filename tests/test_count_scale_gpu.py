@@ -7,8 +7,8 @@ regime it is there for, so that a change of a generator cannot quietly turn it b
 Size thresholds the assertions rely on, and where each comes from (retune one, move the assertion named with it):
   ONE_SWEEP = 2^20   rocPRIM's default radix_sort_config (rocprim/device/device_radix_sort.hpp): one block sorts up to 1024
                      items, a merge sort up to merge_sort_limit = 1024 * 1024, the one-sweep radix sort above.  Cases a, b, c
-                     put more than 2^20 items into the key sort, into every word pass of the k > 32 sort (kc_iota,
-                     kc_gather_word, stable pair sorts, kc_gather_entries) and into the (k-mer, count) pair sort of merge().
+                     put more than 2^20 items into the key sort, into every word pass of the k > 32 sort (ks_iota,
+                     ks_gather_word, stable pair sorts, kc_gather_entries) and into the (k-mer, count) pair sort of merge().
   KC_TILE = 4096     positions per workgroup of the extract kernels (smg_count.hip); GRID = 2048 is the most workgroups
                      kc_bins (one tile each per trip) and kc_finish_flag (256 entries each per trip) are launched with, so
                      their grid-stride loops take a second trip above 2048 * 4096 store positions and 2048 * 256 distinct
