@@ -224,6 +224,9 @@ int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int64_t nrecv,
                            char *errbuf, size_t errlen);
 /* the engine's current table (bound, decoded or conditioned): entries, device pointers (any may be NULL)         */
 int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts);
+/* the same table copied into HOST buffers of `capacity` entries: keys[nels * W] (W = ceil(kmer / 32) words per k-mer,
+   left aligned), counts[nels].  Waits for the engine's stream; launches nothing.                                    */
+int smg_engine_table_host(smg_engine *e, uint64_t *keys, uint16_t *counts, int64_t capacity, char *errbuf, size_t errlen);
 
 /* Whole single-GPU computation on the bound/decoded table; d_plot = int64[SMG_PLOT_CELLS]
    in device memory, overwritten.  Asynchronous on the engine's stream except for the small

@@ -2501,6 +2501,20 @@ extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d
   return SMG_OK;
 }
 
+// the same table copied to the host (tests and tools that want to look at a conditioned table): two copies and a wait
+extern "C" int smg_engine_table_host(smg_engine *e, uint64_t *keys, uint16_t *counts, int64_t capacity, char *errbuf, size_t errlen)
+{ NEED_ENGINE(e)
+  if (capacity < e->n || (e->n > 0 && (!keys || !counts)))
+    return fail(errbuf, errlen, SMG_EINVAL, "table_host: the buffers must hold every entry of the table%s");
+  if (e->n == 0) return SMG_OK;
+  if (!e->keys || !e->cnt) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMemcpyAsync(keys, e->keys, sizeof(u64) * (size_t) e->n * e->W, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(counts, e->cnt, sizeof(uint16_t) * (size_t) e->n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return SMG_OK;
+}
+
 // ---- symmetrising a table that is cut into prefix shards (several GPUs, or one device and more than 2^32 entries) -----
 // The reference's Symmex has no size limit (PloidyPlot.c:1395-1414 hands it any table).  Here every shard
 //   1. counts its own entries and their reverse complements per leading `bits` k-mer bits (smg_engine_symm_hist): the

@@ -66,6 +66,7 @@ EXPORTS = [
     "smg_engine_symhash", "smg_engine_pass2", "smg_engine_stats", "smg_engine_proof",
     "smg_engine_set_replay", "smg_engine_replay_state", "smg_engine_replay_done", "smg_engine_proof_tail",
     "smg_engine_symm_hist", "smg_engine_symm_route", "smg_engine_symm_finish", "smg_engine_table",
+    "smg_engine_table_host",
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
 ]
 
@@ -144,6 +145,7 @@ def load_library():
     lib.smg_engine_symm_route.argtypes = [vp, vp, i32, vp, i64, C.POINTER(i64), *err]
     lib.smg_engine_symm_finish.argtypes = [vp, vp, i64, C.POINTER(i64), *err]
     lib.smg_engine_table.argtypes = [vp, C.POINTER(i64), C.POINTER(vp), C.POINTER(vp)]
+    lib.smg_engine_table_host.argtypes = [vp, vp, vp, i64, *err]
     lib.smg_engine_pass2.argtypes = [vp, vp, *err]
     lib.smg_engine_stats.argtypes = [vp, C.POINTER(Stats)]
     lib.smg_engine_extract.argtypes = [vp, vp, vp, i64, C.POINTER(i64), *err]
@@ -271,6 +273,7 @@ class Engine:
         if not self.h:
             raise EngineError(-1, self._buf.value.decode(errors="replace"))
         self.device = device
+        self.k = None                      # set by bind() / decode(): table_host() takes the words per k-mer from it
 
     def close(self):
         if getattr(self, "h", None):
@@ -280,6 +283,7 @@ class Engine:
     __del__ = close
 
     def bind(self, k: int, nels: int, keys_ptr: int, counts_ptr: int):
+        self.k = k
         _check(self.lib.smg_engine_bind(self.h, k, nels, keys_ptr, counts_ptr, self._buf, 512), self._buf)
 
     def set_prefix_index(self, index_ptr: int, ibyte: int = 3, first_entry: int = 0):
@@ -287,6 +291,7 @@ class Engine:
         _check(self.lib.smg_engine_set_prefix_index(self.h, index_ptr, ibyte, first_entry, self._buf, 512), self._buf)
 
     def decode(self, k: int, ibyte: int, nels: int, records_ptr: int, index_ptr: int):
+        self.k = k
         _check(self.lib.smg_engine_decode(self.h, k, ibyte, nels, records_ptr, index_ptr, self._buf, 512),
                self._buf)
 
@@ -320,6 +325,17 @@ class Engine:
         n, pk, pc = C.c_int64(0), C.c_void_p(0), C.c_void_p(0)
         self.lib.smg_engine_table(self.h, C.byref(n), C.byref(pk), C.byref(pc))
         return int(n.value), pk.value or 0, pc.value or 0
+
+    def table_host(self):
+        """the engine's current table on the host: (k-mers uint64[n, W], left aligned words; counts uint16[n])"""
+        if self.k is None:
+            raise EngineError(-2, "table_host: no table was bound or decoded through this object")
+        n = self.table()[0]
+        words = (self.k + 31) // 32
+        keys = np.empty((n, words), dtype=np.uint64)
+        counts = np.empty(n, dtype=np.uint16)
+        _check(self.lib.smg_engine_table_host(self.h, keys.ctypes.data, counts.ctypes.data, n, self._buf, 512), self._buf)
+        return keys, counts
 
     def run(self, plot_ptr: int, symcheck: str = "exact") -> dict:
         st = Stats()

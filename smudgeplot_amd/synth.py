@@ -7,7 +7,8 @@ Two generators:
   * `adversarial_table`  -- small, any k: random k-mers with 1..3 single-base variants at random
     positions (unique pairs AND non-unique groups of 3-4), counts drawn from values that sit on
     the SMAX=1000 / FMAX=500 edges, low-complexity (poly-A like) seeds that create dense local
-    neighbourhoods, optional palindromes for even k.
+    neighbourhoods.  It makes no self-complementary k-mers (for even k >= 12 a random k-mer essentially never is
+    one); tests/condition_oracle.py generates tables that hold them.
   * `diploid_table_u64`  -- large, k <= 32, vectorised on uint64: a "diploid genome" stand-in where
     a fraction of k-mers has exactly one one-away partner; Poisson coverage.
 """
