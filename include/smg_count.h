@@ -99,6 +99,20 @@ int smg_count_bases_parts(const uint8_t *seq, int64_t n, const smg_count_opts *o
                           uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words,
                           uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
 
+/* the same two with the table left in DEVICE memory, for a consumer on the same device (smg_engine_bind,
+   smg_hetmers_run_device of smg_hetmers.h): *d_keys = *nels * *key_words uint64 and *d_counts = uint16[*nels] are device
+   pointers, each a whole hipMalloc allocation (never NULL on success, also for an empty table) -- release both with
+   smg_count_device_free.  hist, stats and parts as above.  A partitioned run appends the kept entries of every range to the
+   table on the device, which grows as the packed input does; a table that does not fit there next to the input is refused
+   with SMG_ENOMEM, both sizes in the message, and never moved to the host behind the caller's back.                  */
+int smg_count_files_device(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts,
+                           uint64_t **d_keys, uint16_t **d_counts, int64_t *nels, int *key_words,
+                           uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+int smg_count_bases_device(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts,
+                           uint64_t **d_keys, uint16_t **d_counts, int64_t *nels, int *key_words,
+                           uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen);
+void smg_count_device_free(void *d);
+
 /* host only: the cuts of a partitioned run.  windows[SMG_COUNT_BINS] = windows per bin of the leading bits of the
    canonical k-mer.  partitions = 0: the fewest contiguous ranges none of which holds more than `budget` windows
    (greedy; a single bin above the budget is refused with SMG_ENOMEM and named in the message); 1: one range;

@@ -128,6 +128,20 @@ int smg_hetmers_run(const smg_table_view *table, const smg_opts *opts, int64_t *
 int smg_hetmers_run_source(const smg_table_source *source, const smg_opts *opts, int64_t *plot,
                            smg_stats *stats, char *errbuf, size_t errlen);
 
+/* the same from a table that is ALREADY IN DEVICE MEMORY, decoded: what the k-mer counter's _device entries leave there
+   (smg_count.h), or any sorted, duplicate-free table in the layout of smg_engine_bind -- d_keys = nels * ceil(kmer / 32)
+   words, 16-byte aligned; d_counts = nels uint16, 8-byte aligned.  The table is borrowed and not changed.  opts->condition:
+   SMG_COND_TRIM keeps the entries with count >= opts->ethresh; SMG_COND_SYMM closes the table under reverse complement,
+   by smg_engine_close_canonical where the table is canonical and by the generic closure of smg_engine_condition where
+   it is not, so the answer is right for either (a build-time switch in smg_hetmers.hip takes the generic closure
+   always: the same closed table).  Whatever conditioning is asked for, the engine works on a table of its
+   own from there on: the caller may free d_keys and d_counts as soon as the call returns.
+   One device (opts->ngpus > 1: SMG_EINVAL), in core only: a table that does not fit next to the buffers of its closure and
+   of a run is refused with SMG_ENOMEM and the advice to write it to disk and run `hetmers` on the file, which does run
+   out of core.                                                                                                     */
+int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
+                           const smg_opts *opts, int64_t *plot, smg_stats *stats, char *errbuf, size_t errlen);
+
 /* ---- extract: the pairs behind the labelled pixels ----------------------------------------
    Replaces the compute section of extract_kmer_pairs, src/lib/PloidyList.c:1207-1583 (same two
    passes as hetmers; the pass-2 sink prints the pair instead of counting it, PloidyList.c:424-448).
@@ -201,6 +215,16 @@ int smg_engine_set_prefix_index(smg_engine *e, const int64_t *d_prefix_index, in
    Replaces the Logex / Symmex / Fastrm shell-outs, PloidyPlot.c:1381-1414, 1584-1592.        */
 int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
                          int64_t *new_nels, char *errbuf, size_t errlen);
+
+/* Close a CANONICAL table under reverse complement: a table in which every entry is at most its reverse complement, as
+   the k-mer counter writes it (bound or decoded, sorted, duplicate free).  The complements of its entries are then no
+   entries themselves, so they are sorted on their own -- half the k-mers the generic closure sorts -- and merged with the
+   table (ks_merge, a merge-path kernel).  The result is entry for entry that of smg_engine_condition with do_symm alone,
+   and engine-owned.  A table that is not canonical is refused with SMG_EINVAL ("table is not canonical") and left as it
+   was.  *new_nels may be NULL.  An empty table and a table of self-complementary k-mers only are valid.               */
+int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char *errbuf, size_t errlen);
+/* outputs per workgroup of that merge for k-mers of key_words words, 1 .. 4 (0 otherwise): where its tiles end        */
+int smg_engine_merge_tile(int key_words);
 
 /* ---- symmetrising a table that is cut into prefix shards (several GPUs, or more than 2^32 entries) --------------
    The reference hands a table of any size to Symmex (PloidyPlot.c:1395-1414).  Sharded, the same closure takes one

@@ -20,7 +20,8 @@ LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
 BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
-           "smg_count_parse", "smg_count_free", "smg_count_version"]
+           "smg_count_parse", "smg_count_free", "smg_count_version",
+           "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free"]
 
 
 class CountError(RuntimeError):
@@ -72,6 +73,12 @@ def load_library():
     lib.smg_count_files_parts.restype = C.c_int
     lib.smg_count_bases_parts.argtypes = [vp, C.c_int64] + ptail
     lib.smg_count_bases_parts.restype = C.c_int
+    lib.smg_count_files_device.argtypes = [C.POINTER(C.c_char_p), C.c_int] + ptail
+    lib.smg_count_files_device.restype = C.c_int
+    lib.smg_count_bases_device.argtypes = [vp, C.c_int64] + ptail
+    lib.smg_count_bases_device.restype = C.c_int
+    lib.smg_count_device_free.argtypes = [vp]
+    lib.smg_count_device_free.restype = None
     lib.smg_count_plan.argtypes = [vp, C.c_int64, C.c_int32, vp, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
     lib.smg_count_plan.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
@@ -145,6 +152,98 @@ def count_bases(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
                                dtype=np.uint8)
     return _run(lambda lib, *a: lib.smg_count_bases_parts(buf.ctypes.data_as(C.c_void_p), buf.size, *a), k, t, device, threads,
                 partitions, max_entries)
+
+
+class DeviceTable:
+    """A counted table that stayed in device memory: k, t, nels, words (64-bit words per k-mer) and the two device pointers
+    keys_ptr (uint64[nels * words], left aligned, sorted) and counts_ptr (uint16[nels]), in the layout of engine.Engine.bind.
+    close() -- or leaving the `with` block -- frees them."""
+
+    def __init__(self, k, t, nels, words, keys_ptr, counts_ptr, device=0):
+        self.k, self.t, self.nels, self.words, self.device = int(k), int(t), int(nels), int(words), int(device)
+        self.keys_ptr, self.counts_ptr = keys_ptr, counts_ptr
+
+    def close(self):
+        for name in ("keys_ptr", "counts_ptr"):
+            if getattr(self, name, None) and _lib is not None:
+                _lib.smg_count_device_free(getattr(self, name))
+            setattr(self, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    __del__ = close
+
+    def to_host(self):
+        """(k-mers uint64[nels, words], counts uint16[nels]) copied from the device"""
+        from . import engine
+        e = engine.Engine(self.device)
+        try:
+            e.bind(self.k, self.nels, self.keys_ptr, self.counts_ptr)
+            return e.table_host()
+        finally:
+            e.close()
+
+
+def _run_device(call, k, t, device, threads, partitions, max_entries):
+    lib = load_library()
+    opts = Opts(int(k), int(t), int(device), int(threads), 0)
+    parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
+    keys, cnt = C.c_void_p(), C.c_void_p()
+    nels, words = C.c_int64(0), C.c_int(0)
+    hist = np.zeros(HIST, dtype=np.uint64)
+    st = Stats()
+    err = C.create_string_buffer(1024)
+    rc = call(lib, C.byref(opts), C.byref(parts), C.byref(keys), C.byref(cnt), C.byref(nels), C.byref(words),
+              hist.ctypes.data_as(C.c_void_p), C.byref(st), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    stats = st.asdict()
+    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan)
+    return DeviceTable(k, t, nels.value, words.value, keys.value, cnt.value, device), hist, stats
+
+
+def _as_bases(seq):
+    return np.ascontiguousarray(np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray, memoryview)) else seq,
+                                dtype=np.uint8)
+
+
+def count_files_device(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
+    """count_files with the table left on the device -> (DeviceTable, hist uint64[32768], stats dict)"""
+    paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
+    arr = (C.c_char_p * len(paths))(*paths)
+    return _run_device(lambda lib, *a: lib.smg_count_files_device(arr, len(paths), *a), k, t, device, threads, partitions, max_entries)
+
+
+def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
+    """count_bases with the table left on the device -> (DeviceTable, hist uint64[32768], stats dict)"""
+    buf = _as_bases(seq)
+    return _run_device(lambda lib, *a: lib.smg_count_bases_device(buf.ctypes.data_as(C.c_void_p), buf.size, *a), k, t, device, threads,
+                       partitions, max_entries)
+
+
+def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash"):
+    """Reads to the het-mer plot in one process: count on the device (k-mers with count >= t), hand the table over where
+    it lies, trim at e, close under reverse complement, run -> (plot int64[1001, 501], hist uint64[32768], stats dict).
+    paths_or_bases: sequence bytes (bytes, bytearray, memoryview or a uint8 array) or one path or a list of paths.
+    e < t cannot be honoured (the entries below t are gone) and raises ValueError.  The stats are the counter's, with the
+    engine's under "hetmers"."""
+    from . import engine
+    if int(e) < int(t):
+        raise ValueError(f"e = {e} is below t = {t}: the k-mers with a count below t are not in the table")
+    if isinstance(paths_or_bases, (bytes, bytearray, memoryview, np.ndarray)):
+        got = count_bases_device(paths_or_bases, k, t, device, threads, partitions, max_entries)
+    else:
+        got = count_files_device(paths_or_bases, k, t, device, threads, partitions, max_entries)
+    table, hist, stats = got
+    with table:
+        plot, est = engine.hetmers_run_device(k, table.nels, table.keys_ptr, table.counts_ptr, device=device, symcheck=symcheck,
+                                              condition=engine.COND_TRIM | engine.COND_SYMM, ethresh=int(e))
+    stats["hetmers"] = est
+    return plot, hist, stats
 
 
 def plan(windows, budget, partitions=0):

@@ -4,15 +4,20 @@
  *               k-mer table (format F: stub + one hidden part file, 3-byte prefix index), plus the
  *               k-mer count histogram that `smudgeplot cutoff` reads.
  *
- *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.
+ *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.  With -e it is
+ *  that step and `hetmers` in one process: the counted table stays in device memory and is trimmed, closed under reverse
+ *  complement and scanned for het-mer pairs there (smg_hetmers_run_device), and <output>.smu is written as `hetmers -e`
+ *  writes it from the table on disk.
  *
- *  Usage: smg_count [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-o<output>] <reads> ...
+ *  Usage: smg_count [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
  *           -k: k-mer length, 13 .. 128          -t: keep the k-mers with count >= t
  *           -H: also write <output>.hist.txt     -T: reader threads (one input file each, at most 16)
  *           -o: root name of the table; default is the root of the first input
  *           -p: key ranges to count in: 0 as many as the data need, 1 one pass, 2 .. 4096 that many
+ *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device, in core
+ *           -n: write no table (with -e or -H only)
  *
- *  SMUDGEPLOT_GPU picks the device.  No CPU fallback.  A failed run leaves no table files behind.
+ *  SMUDGEPLOT_GPU picks the device.  No CPU fallback.  A failed run leaves no table, histogram or .smu file behind.
  *
  ********************************************************************************************/
 
@@ -20,12 +25,15 @@
 #include "smg_count.h"
 
 static void usage(void)
-{ fprintf(stderr, "\nUsage: %s [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-o<output>] <reads> ...\n", Prog_Name);
+{ fprintf(stderr, "\nUsage: %s [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...\n", Prog_Name);
   fprintf(stderr, "\n");
   fprintf(stderr, "      -k: k-mer length (13 .. %d)\n", SMG_MAX_KMER);
   fprintf(stderr, "      -t: keep the k-mers that occur at least t times\n");
   fprintf(stderr, "      -p: count in this many ranges of canonical k-mers (0 .. %d): 0 as many as the data need, 1 one pass\n", SMG_COUNT_BINS);
   fprintf(stderr, "      -H: write the k-mer count histogram to <output>.hist.txt\n");
+  fprintf(stderr, "      -e: write the het-mer pairs of the k-mers that occur at least e times to <output>.smu (e >= t),\n");
+  fprintf(stderr, "            from the table in device memory: what hetmers -e writes from the table file\n");
+  fprintf(stderr, "      -n: write no table (with -e or -H)\n");
   fprintf(stderr, "      -o: root name for the output table\n");
   fprintf(stderr, "            default is root of the first <reads> argument\n");
   fprintf(stderr, "      -v: verbose mode\n");
@@ -44,9 +52,18 @@ static char *default_root(const char *name)
   return strdup(name);
 }
 
+/* remove what a run that fails half way has written */
+static void remove_outputs(const char *root, int table, const char *hname, const char *sname)
+{ if (table) smg_cli_remove_ktab(root, 1);
+  if (hname != NULL) remove(hname);
+  if (sname != NULL) remove(sname);
+}
+
 int main(int argc, char *argv[])
-{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0;
-  char *out = NULL, *root, *hname = NULL;
+{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0, ethresh = 0, no_table = 0;
+  char *out = NULL, *root, *hname = NULL, *sname = NULL;
+  int64_t *plot = NULL;
+  smg_stats hst;
   int i, j;
   smg_count_opts opts;
   smg_count_stats st;
@@ -64,6 +81,8 @@ int main(int argc, char *argv[])
       switch (argv[i][1])
       { case 'v': verbose = 1; break;
         case 'H': do_hist = 1; break;
+        case 'n': no_table = 1; break;
+        case 'e': ethresh = arg_positive(argv[i], "Error-mer threshold"); break;
         case 'k': kmer = arg_positive(argv[i], "K-mer length"); break;
         case 'p':
           { char *eptr;
@@ -92,6 +111,13 @@ int main(int argc, char *argv[])
     }
   if (minval > SMG_COUNT_MAX_COUNT)
     { fprintf(stderr, "%s: Count threshold must be at most %d (%d)\n", Prog_Name, SMG_COUNT_MAX_COUNT, minval); exit(1); }
+  if (no_table && !do_hist && ethresh == 0)
+    { fprintf(stderr, "%s: -n leaves nothing to write: give -e or -H with it\n", Prog_Name); usage(); }
+  if (ethresh > 0 && ethresh < minval)
+    { fprintf(stderr, "%s: -e%d is below -t%d: the k-mers that occur less than %d times are not counted into the table\n", Prog_Name,
+              ethresh, minval, minval);
+      exit(1);
+    }
   for (i = 1; i < j; i++)
     { FILE *f = fopen(argv[i], "rb");
       if (f == NULL) { fprintf(stderr, "%s: Cannot open %s for reading\n", Prog_Name, argv[i]); exit(1); }
@@ -107,16 +133,51 @@ int main(int argc, char *argv[])
   memset(&parts, 0, sizeof(parts));
   parts.partitions = nparts;
   errbuf[0] = 0;
-  if (smg_count_files_parts((const char *const *) (argv + 1), j - 1, &opts, &parts, &keys, &cnt, &n, &W, hist, &st, errbuf, sizeof(errbuf)) != SMG_OK)
-    { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed"); exit(1); }
+  memset(&hst, 0, sizeof(hst));
+  if (ethresh == 0)
+    { if (smg_count_files_parts((const char *const *) (argv + 1), j - 1, &opts, &parts, &keys, &cnt, &n, &W, hist, &st, errbuf, sizeof(errbuf)) != SMG_OK)
+        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed"); exit(1); }
+    }
+  else
+    { /* the table stays where it was counted; everything is computed before the first file is written */
+      uint64_t *d_keys = NULL;
+      uint16_t *d_cnt = NULL;
+      smg_opts ho;
+      int rc;
+      if (smg_count_files_device((const char *const *) (argv + 1), j - 1, &opts, &parts, &d_keys, &d_cnt, &n, &W, hist, &st, errbuf, sizeof(errbuf)) != SMG_OK)
+        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed"); exit(1); }
+      plot = (int64_t *) malloc(sizeof(int64_t) * SMG_PLOT_CELLS);
+      rc = plot == NULL ? SMG_ENOMEM : SMG_OK;
+      if (rc == SMG_OK && !no_table)                              /* a host copy for the table file, through an engine */
+        { smg_engine *e = smg_engine_create(opts.device, NULL, errbuf, sizeof(errbuf));
+          keys = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (n > 0 ? n : 1) * (size_t) W);
+          cnt = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (n > 0 ? n : 1));
+          if (e == NULL) rc = SMG_ENODEV;
+          else if (keys == NULL || cnt == NULL) rc = SMG_ENOMEM;
+          else if ((rc = smg_engine_bind(e, kmer, n, d_keys, d_cnt, errbuf, sizeof(errbuf))) == SMG_OK)
+            rc = smg_engine_table_host(e, keys, cnt, n, errbuf, sizeof(errbuf));
+          smg_engine_destroy(e);
+        }
+      if (rc == SMG_OK)
+        { memset(&ho, 0, sizeof(ho));
+          ho.device = opts.device; ho.symcheck = SMG_SYM_HASH; ho.verbose = verbose; ho.ethresh = ethresh;
+          ho.condition = SMG_COND_SYMM | (ethresh > minval ? SMG_COND_TRIM : 0);      /* (nothing below t is left to trim) */
+          rc = smg_hetmers_run_device(kmer, n, d_keys, d_cnt, &ho, plot, &hst, errbuf, sizeof(errbuf));
+        }
+      smg_count_device_free(d_keys); smg_count_device_free(d_cnt);
+      if (rc != SMG_OK)
+        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : rc == SMG_ENOMEM ? "Out of memory" : "GPU engine failed");
+          exit(1);
+        }
+    }
 
-  if (smg_cli_write_ktab(root, kmer, 3, 1, minval, keys, cnt, n, W))
+  if (!no_table && smg_cli_write_ktab(root, kmer, 3, 1, minval, keys, cnt, n, W))
     { smg_cli_remove_ktab(root, 1); exit(1); }
   if (do_hist)
     { int64_t c, top = 0;
       FILE *f;
       hname = (char *) malloc(strlen(root) + 16);
-      if (hname == NULL) { smg_cli_remove_ktab(root, 1); fprintf(stderr, "%s: Out of memory\n", Prog_Name); exit(1); }
+      if (hname == NULL) { remove_outputs(root, !no_table, NULL, NULL); fprintf(stderr, "%s: Out of memory\n", Prog_Name); exit(1); }
       sprintf(hname, "%s.hist.txt", root);
       for (c = 1; c < SMG_COUNT_HIST; c++) if (hist[c]) top = c;
       f = fopen(hname, "w");
@@ -124,7 +185,16 @@ int main(int argc, char *argv[])
         if (fprintf(f, "%lld\t%llu\n", (long long) c, (unsigned long long) hist[c]) < 0) { fclose(f); f = NULL; }
       if (f == NULL || fclose(f))
         { fprintf(stderr, "%s: Cannot write %s\n", Prog_Name, hname);
-          remove(hname); smg_cli_remove_ktab(root, 1);
+          remove_outputs(root, !no_table, hname, NULL);
+          exit(1);
+        }
+    }
+  if (ethresh > 0)
+    { sname = (char *) malloc(strlen(root) + 16);
+      if (sname != NULL) sprintf(sname, "%s.smu", root);
+      if (sname == NULL || smg_cli_write_smu(sname, plot, NULL))
+        { fprintf(stderr, "%s: Cannot write %s.smu\n", Prog_Name, root);
+          remove_outputs(root, !no_table, hname, sname);
           exit(1);
         }
     }
@@ -136,8 +206,13 @@ int main(int argc, char *argv[])
               parts.used == 1 ? "" : "s", (double) parts.store_bytes * 1e-9, parts.ms_pack, parts.ms_plan);
       fprintf(stderr, "  ms: read %.1f  extract %.3f  sort %.3f  reduce+merge %.3f  finish %.3f  wall %.1f\n", st.ms_read, st.ms_extract,
               st.ms_sort, st.ms_reduce, st.ms_finish, st.ms_wall);
+      if (ethresh > 0)
+        fprintf(stderr, "  het-mers at -e%d: %lld entries in the closed table, %lld pairs; ms: conditioning %.3f  pairs %.3f\n", ethresh,
+                (long long) hst.nels, (long long) hst.npairs, hst.ms_decode, hst.ms_total);
     }
-  smg_count_free(keys); smg_count_free(cnt);
+  if (ethresh == 0) { smg_count_free(keys); smg_count_free(cnt); }
+  else { free(keys); free(cnt); }
+  free(plot); free(sname);
   free(hist); free(root); free(out); free(hname);
   exit(0);
 }

@@ -102,7 +102,7 @@ static int run(const smg_cli *c, const char *OUT, smg_ktab *Tp, const smg_opts *
   smg_table_source src;
   int64_t *plot;
   char  errbuf[512];
-  int   rc, i;
+  int   rc;
   double t_engine;
 
   if (c->verbose)
@@ -126,24 +126,15 @@ static int run(const smg_cli *c, const char *OUT, smg_ktab *Tp, const smg_opts *
   if (c->verbose)
     { fprintf(stderr, "\n  Count complete, outputting table\n"); fflush(stderr); }
 
-  /* writer, PloidyPlot.c:1603-1617: sum ascending, min ascending, min == 500 never printed */
+  /* writer, PloidyPlot.c:1603-1617 (smg_cli_write_smu: sum ascending, min ascending, min == 500 never printed) */
   { char *fname = (char *) malloc(strlen(OUT) + 8);
-    FILE *f;
-    int   a;
     sprintf(fname, "%s.smu", OUT);
     snprintf(Smu_Path, sizeof(Smu_Path), "%s", strlen(fname) < sizeof(Smu_Path) ? fname : "");
-    f = fopen(fname, "w");
-    if (f == NULL)
-      { fprintf(stderr, "Could not open %s.smu\n", OUT);
+    const int wrc = smg_cli_write_smu(fname, plot, smu_mark);
+    if (wrc != 0)                /* (a short write is a failure too: disk full) */
+      { fprintf(stderr, wrc == -1 ? "Could not open %s.smu\n" : "Could not write %s.smu\n", OUT);
         return 1;
       }
-    smu_mark(1);
-    for (a = 0; a <= SMG_SMAX; a++)
-      for (i = 0; i < SMG_FMAX; i++)
-        if (plot[a * SMG_PLOT_COLS + i] > 0)
-          fprintf(f, "%i\t%i\t%lld\n", i, a - i, (long long) plot[a * SMG_PLOT_COLS + i]);
-    fclose(f);
-    smu_mark(2);
     free(fname);
   }
   free(plot);

@@ -342,6 +342,24 @@ __attribute__((unused)) static void smg_cli_remove_ktab(const char *target, int 
   free(root); free(path);
 }
 
+/* The .smu writer, PloidyPlot.c:1603-1617: rows "min <tab> sum - min <tab> pairs" of the non-empty cells, sum ascending, min
+   ascending, min == 500 never printed.  mark (may be NULL) is told 1 once the file is open and 2 once it is closed: a program
+   that can be signalled over its output keeps track with it.  0; -1 when fname cannot be opened (the caller says so in its own
+   words), -2 when a row or the close failed.                                                                          */
+__attribute__((unused)) static int smg_cli_write_smu(const char *fname, const int64_t *plot, void (*mark)(int))
+{ FILE *f = fopen(fname, "w");
+  int a, i, bad = 0;
+  if (f == NULL) return -1;
+  if (mark != NULL) mark(1);
+  for (a = 0; a <= SMG_SMAX; a++)
+    for (i = 0; i < SMG_FMAX; i++)
+      if (plot[a * SMG_PLOT_COLS + i] > 0)
+        bad |= fprintf(f, "%i\t%i\t%lld\n", i, a - i, (long long) plot[a * SMG_PLOT_COLS + i]) < 0;
+  bad |= fclose(f) != 0;
+  if (mark != NULL) mark(2);
+  return bad ? -2 : 0;
+}
+
 __attribute__((unused)) static void smg_cli_remove_temp(char *input)
 { if (input != NULL)
     { char *command = (char *) malloc(strlen(input) + 100);

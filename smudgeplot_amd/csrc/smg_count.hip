@@ -20,6 +20,9 @@
 //   range   kc_extract_packed<W>  the store -> canonical k-mers of ONE range, the key buffer filled across the store
 //           and sorted when full; then batch / merge / finish as above, the kept entries appended to the host table
 // Every instance of a k-mer lies in one range, so ranges in ascending order give the sorted table.
+//
+// The _device entries leave the table where it was made: the kept entries of a range are appended to a table in device
+// memory instead (two whole allocations, which the caller hands to smg_engine_bind / smg_hetmers_run_device and frees).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -529,6 +532,10 @@ struct Counter
   smg_count_parts pt;
   uint64_t *hk = nullptr; uint16_t *hc = nullptr;
   int64_t hn = 0, hcap = 0;
+  // the _device entries: the table so far stays in device memory (tk, tc: whole allocations of tcap entries, tn in use)
+  bool dev_out = false;
+  Dev tk, tc;
+  int64_t tn = 0, tcap = 0;
 
   ~Counter()
   { free(hk); free(hc);
@@ -844,6 +851,11 @@ struct Counter
     RCHK(toc(&st.ms_finish));
     st.distinct += nd;
     st.kept += kept;
+    if (dev_out)
+      { RCHK(append_device(ok, oc, kept));
+        dk.reset(); dc.reset(); nd = 0;
+        return 0;
+      }
     if (hn + kept > hcap || !hk)
       { int64_t nc = hcap + hcap / 2;
         if (nc < hn + kept) nc = hn + kept;
@@ -861,6 +873,39 @@ struct Counter
       }
     hn += kept;
     dk.reset(); dc.reset(); nd = 0;
+    return 0;
+  }
+
+  // the kept entries of a range (ok, oc: whole allocations, or empty) behind the device table.  The first range's buffers
+  // become the table as they are; from then on it grows by half, like the store, with a device-to-device copy.
+  int append_device(Dev &ok, Dev &oc, int64_t kept)
+  { if (!tk.p && ok.p && oc.p) { tk.take(ok); tc.take(oc); tn = tcap = kept; return 0; }
+    if (tn + kept > tcap || !tk.p)
+      { int64_t nc = tcap + tcap / 2;
+        if (nc < tn + kept) nc = tn + kept;
+        if (nc < 1) nc = 1;
+        const size_t want = (sizeof(u64) * W + sizeof(uint16_t)) * (size_t) nc + ((size_t) 64 << 20);
+        size_t free_b = 0, total_b = 0;
+        DCHK(hipMemGetInfo(&free_b, &total_b));
+        if (want > free_b)
+          return fail(errbuf, errlen, SMG_ENOMEM, "the counted table does not fit the device next to the input: room for %lld entries needs "
+                      "%.3f GB, %.3f GB are free (count to a table on disk instead: the entries that return host arrays)", (long long) nc,
+                      (double) want * 1e-9, (double) free_b * 1e-9);
+        Dev k2, c2;
+        RCHK(alloc(k2, sizeof(u64) * (size_t) nc * W)); RCHK(alloc(c2, sizeof(uint16_t) * (size_t) nc));
+        if (tn > 0)
+          { DCHK(hipMemcpyAsync(k2.p, tk.p, sizeof(u64) * (size_t) tn * W, hipMemcpyDeviceToDevice, stream));
+            DCHK(hipMemcpyAsync(c2.p, tc.p, sizeof(uint16_t) * (size_t) tn, hipMemcpyDeviceToDevice, stream));
+            DCHK(hipStreamSynchronize(stream));
+          }
+        tk.take(k2); tc.take(c2); tcap = nc;
+      }
+    if (kept > 0)
+      { DCHK(hipMemcpyAsync(tk.as<u64>() + (size_t) tn * W, ok.p, sizeof(u64) * (size_t) kept * W, hipMemcpyDeviceToDevice, stream));
+        DCHK(hipMemcpyAsync(tc.as<uint16_t>() + tn, oc.p, sizeof(uint16_t) * (size_t) kept, hipMemcpyDeviceToDevice, stream));
+        DCHK(hipStreamSynchronize(stream));                        // (ok and oc are freed on return)
+      }
+    tn += kept;
     return 0;
   }
 
@@ -949,7 +994,7 @@ struct Counter
     return 0;
   }
 
-  // the last batch, then histogram, clamp, trim; the table goes to malloc'ed host arrays
+  // the last batch, then histogram, clamp, trim; the table goes to malloc'ed host arrays, or (dev_out) stays in device memory
   int finish(uint64_t **keys, uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_parts *parts)
   { RCHK(flush());
     seq.reset();
@@ -957,10 +1002,16 @@ struct Counter
     DCHK(hipMemsetAsync(dh.p, 0, sizeof(uint64_t) * SMG_COUNT_HIST, stream));
     if (parted) RCHK(run_ranges());
     ka.reset(); kb.reset(); start.reset(); flag.reset(); pos.reset(); scode.reset(); sval.reset();
-    if (!parted || !hk) RCHK(finish_range());                 // (also the empty table of a run without any window)
+    if (!parted || !(dev_out ? tk.p : (void *) hk)) RCHK(finish_range());       // (also the empty table of a run without any window)
     if (hist) DCHK(hipMemcpy(hist, dh.p, sizeof(uint64_t) * SMG_COUNT_HIST, hipMemcpyDeviceToHost));
-    *keys = hk; *counts = hc; *nels = hn; *key_words = W;
-    hk = nullptr; hc = nullptr;
+    if (dev_out)
+      { DCHK(hipStreamSynchronize(stream));
+        *keys = (uint64_t *) tk.release(); *counts = (uint16_t *) tc.release(); *nels = tn; *key_words = W;
+      }
+    else
+      { *keys = hk; *counts = hc; *nels = hn; *key_words = W;
+        hk = nullptr; hc = nullptr;
+      }
     if (parts) { parts->used = pt.used; parts->store_bytes = pt.store_bytes; parts->ms_pack = pt.ms_pack; parts->ms_plan = pt.ms_plan; }
     return 0;
   }
@@ -1056,8 +1107,8 @@ static int check_opts(const smg_count_opts *o, char *errbuf, size_t errlen)
   return 0;
 }
 
-static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys, uint16_t **counts,
-                       int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, bool dev_out, uint64_t **keys,
+                       uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
 { const double t0 = now_ms();
   RCHK(check_opts(opts, errbuf, errlen));
   if (!paths || npaths < 1 || !keys || !counts || !nels || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
@@ -1075,6 +1126,7 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
       bound += (int64_t) size + opts->kmer + 1;
     }
   Counter c;
+  c.dev_out = dev_out;
   RCHK(c.init(opts, parts, bound, npaths, errbuf, errlen));
 
   int nthr = opts->host_threads < 1 ? 1 : opts->host_threads > 16 ? 16 : opts->host_threads;
@@ -1127,12 +1179,13 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
   return 0;
 }
 
-static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys, uint16_t **counts,
-                       int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
+static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, bool dev_out, uint64_t **keys,
+                       uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
 { const double t0 = now_ms();
   RCHK(check_opts(opts, errbuf, errlen));
   if (n < 0 || (n > 0 && !seq) || !keys || !counts || !nels || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
   Counter c;
+  c.dev_out = dev_out;
   RCHK(c.init(opts, parts, n, 1, errbuf, errlen));
   const int64_t piece = (int64_t) 256 << 20;
   for (int64_t o = 0; o < n; o += piece) RCHK(c.add(seq + o, n - o < piece ? n - o : piece, 0));
@@ -1156,21 +1209,33 @@ static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts
 
 extern "C" int smg_count_files(const char *const *paths, int npaths, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
                                int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
-{ GUARD(count_files(paths, npaths, opts, nullptr, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_files(paths, npaths, opts, nullptr, false, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
 
 extern "C" int smg_count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, uint64_t **keys, uint16_t **counts,
                                int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf, size_t errlen)
-{ GUARD(count_bases(seq, n, opts, nullptr, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_bases(seq, n, opts, nullptr, false, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
 
 extern "C" int smg_count_files_parts(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys,
                                      uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
                                      size_t errlen)
-{ GUARD(count_files(paths, npaths, opts, parts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_files(paths, npaths, opts, parts, false, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
 
 extern "C" int smg_count_bases_parts(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **keys,
                                      uint16_t **counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
                                      size_t errlen)
-{ GUARD(count_bases(seq, n, opts, parts, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+{ GUARD(count_bases(seq, n, opts, parts, false, keys, counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" int smg_count_files_device(const char *const *paths, int npaths, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **d_keys,
+                                      uint16_t **d_counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
+                                      size_t errlen)
+{ GUARD(count_files(paths, npaths, opts, parts, true, d_keys, d_counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" int smg_count_bases_device(const uint8_t *seq, int64_t n, const smg_count_opts *opts, smg_count_parts *parts, uint64_t **d_keys,
+                                      uint16_t **d_counts, int64_t *nels, int *key_words, uint64_t *hist, smg_count_stats *stats, char *errbuf,
+                                      size_t errlen)
+{ GUARD(count_bases(seq, n, opts, parts, true, d_keys, d_counts, nels, key_words, hist, stats, errbuf, errlen)) }
+
+extern "C" void smg_count_device_free(void *d) { if (d) (void) hipFree(d); }
 
 // The cuts of a partitioned run (host only).  Greedy over the bins: a range takes bins while its windows stay within the
 // budget, which gives the fewest contiguous ranges; the windows of a range bound its distinct k-mers and every merge of

@@ -2493,6 +2493,118 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
   return SMG_OK;
 }
 
+// ---- closure of a CANONICAL table by merge ------------------------------------------------------------------------------
+// A table as the k-mer counter leaves it holds, of every k-mer and its reverse complement, the smaller one only (x <= rc x),
+// sorted.  The complements R of its entries that are not their own complement are then disjoint from the table C (were
+// rc x = y in C, y <= rc y = x and x <= rc x = y would make them equal), so the closure is C merged with sorted R: one sort
+// of m <= n k-mers where smg_engine_condition sorts 2 n, nothing to de-duplicate, no count to choose.  Entry for entry the
+// table smg_engine_condition(e, 0, 0, 1) leaves.
+
+// rc[i] = the reverse complement of entry i, flag[i] = it is another k-mer; *bad is set where it is the SMALLER one
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_rc_flag(const u64 *__restrict__ keys, int64_t n, int k, u64 *__restrict__ rc, uint32_t *__restrict__ flag, uint32_t *__restrict__ bad)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  const Key<W> r = revcomp<W>(x, k);
+#pragma unroll
+  for (int w = 0; w < W; w++) rc[i * W + w] = r.w[w];
+  flag[i] = !key_eq<W>(x, r);
+  if (key_lt<W>(r, x)) *bad = 1u;
+}
+
+// the flagged complements, compacted, and the entry each came from
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_rc_compact(const u64 *__restrict__ rc, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
+              u64 *__restrict__ okeys, uint32_t *__restrict__ osrc)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t dst = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[dst * W + w] = rc[i * W + w];
+  osrc[dst] = (uint32_t) i;
+}
+
+extern "C" int smg_engine_merge_tile(int key_words)
+{ return key_words >= 1 && key_words <= 4 ? ks_merge_tile(key_words) : 0; }
+
+// *not_canonical tells that refusal (SMG_EINVAL like the others, the table untouched) from every other one
+static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical, char *errbuf, size_t errlen)
+{ *not_canonical = false;
+  if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
+  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  const int W = e->W;
+  const int64_t n = e->n;
+  int64_t m = 0;
+  hipEventRecord(e->ev[0], e->stream);                 // (booked under ms_decode, like smg_engine_condition)
+  if (n > 0)
+    { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
+      Dev rc, flag, pos, bad, rk, rsrc, perm, split, ko, co;
+      uint32_t h_bad = 0;
+      HIPCHK(dev_alloc(rc, sizeof(u64) * (size_t) n * W));
+      HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n));
+      HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n));
+      HIPCHK(dev_alloc(bad, 16));
+      HIPCHK(hipMemsetAsync(bad.p, 0, 16, e->stream));
+#define CALL(WW) hipLaunchKernelGGL(kc_rc_flag<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, n, e->kmer, rc.as<u64>(), \
+                   flag.as<uint32_t>(), bad.as<uint32_t>())
+      DISPATCH_W(e, CALL)
+#undef CALL
+      HIPCHK(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &m));    // (waits)
+      if (h_bad)
+        { *not_canonical = true;
+          return fail(errbuf, errlen, SMG_EINVAL, "table is not canonical: an entry is larger than its reverse complement "
+                      "(smg_engine_condition closes any sorted table)%s");
+        }
+      if (n + m >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
+      HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (n + m) * W));
+      HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (n + m) + 16));
+      if (m == 0)                                      // every entry is its own complement: the closure is a copy
+        { HIPCHK(hipMemcpyAsync(ko.p, e->keys, sizeof(u64) * (size_t) n * W, hipMemcpyDeviceToDevice, e->stream));
+          HIPCHK(hipMemcpyAsync(co.p, e->cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToDevice, e->stream));
+        }
+      else
+        { HIPCHK(dev_alloc(rk, sizeof(u64) * (size_t) m * W));
+          HIPCHK(dev_alloc(rsrc, sizeof(uint32_t) * (size_t) m));
+#define CALL(WW) hipLaunchKernelGGL(kc_rc_compact<WW>, dim3(nblk), dim3(TPB), 0, e->stream, rc.as<u64>(), flag.as<uint32_t>(), \
+                   pos.as<uint32_t>(), n, rk.as<u64>(), rsrc.as<uint32_t>())
+          DISPATCH_W(e, CALL)
+#undef CALL
+          HIPCHK(hipStreamSynchronize(e->stream));
+          rc.reset(); flag.reset(); pos.reset();
+          HIPCHK(sort_permutation(rk.as<u64>(), W, m, e->stream, &e->sort_tmp, &e->sort_tmp_cap, perm));
+          const int64_t ntiles = (n + m + ks_merge_tile(W) - 1) / ks_merge_tile(W);
+          HIPCHK(dev_alloc(split, sizeof(uint32_t) * (size_t) (ntiles + 1)));
+#define CALL(WW) hipLaunchKernelGGL(ks_merge_split<WW>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, e->keys, n, \
+                   rk.as<u64>(), perm.as<uint32_t>(), m, ntiles, split.as<uint32_t>())
+          DISPATCH_W(e, CALL)
+#undef CALL
+#define CALL(WW) hipLaunchKernelGGL(ks_merge<WW>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, e->keys, e->cnt, n, rk.as<u64>(), \
+                   perm.as<uint32_t>(), rsrc.as<uint32_t>(), m, split.as<uint32_t>(), ko.as<u64>(), co.as<uint16_t>())
+          DISPATCH_W(e, CALL)
+#undef CALL
+          HIPCHK(hipGetLastError());
+        }
+      HIPCHK(hipStreamSynchronize(e->stream));
+      adopt_table(e, ko, co, n + m);
+    }
+  hipEventRecord(e->ev[1], e->stream);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  float ms = 0; hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
+  table_changed(e, n + m);
+  e->rp_have = false; e->rp_active = false;
+  e->st.ms_decode += ms;
+  if (new_nels) *new_nels = n + m;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char *errbuf, size_t errlen)
+{ bool not_canonical;
+  return close_canonical(e, new_nels, &not_canonical, errbuf, errlen);
+}
+
 extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
 { if (!e) return SMG_EINVAL;
   if (nels) *nels = e->n;
@@ -2907,6 +3019,77 @@ extern "C" int smg_hetmers_run(const smg_table_view *tv, const smg_opts *opts, i
 extern "C" int smg_hetmers_run_source(const smg_table_source *src, const smg_opts *opts, int64_t *plot,
                                       smg_stats *stats, char *errbuf, size_t errlen)
 { return host_run(src, opts, plot, stats, NULL, NULL, NULL, NULL, errbuf, errlen); }
+
+// ---- one-shot entry: a table that is already on the device -> plot ------------------------------------------------------
+// What smg_hetmers_run does behind its ingest, for the table the k-mer counter left in device memory (smg_count.h, the
+// _device entries): bind, trim, close, run.  One device, in core.
+// 1: a canonical table is closed by smg_engine_close_canonical, any other by the generic closure (same table either way).
+// profiles/reads_to_smu.md: at 1e8 entries the merge takes 17.0 against 24.0 ms at k = 31 and 27.4 against 43.1 ms at k = 51;
+// at 1e6 entries it is 0.1 - 0.2 ms behind.  0 takes the generic closure always.
+#define RUN_DEVICE_CLOSE_BY_MERGE 1
+
+extern "C" int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts, const smg_opts *opts,
+                                      int64_t *plot, smg_stats *stats, char *errbuf, size_t errlen)
+{ if (!plot) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
+  const int device = opts ? opts->device : 0;
+  const int symcheck = opts ? opts->symcheck : SMG_SYM_HASH;
+  const int cond = opts ? opts->condition : 0;
+  static const char *two_step = ": write the table (smg_count without -e) and run hetmers on it, which runs out of core";
+  if (opts && opts->ngpus > 1)
+    return fail(errbuf, errlen, SMG_EINVAL, "a table that is already on one device runs on that device only (ngpus > 1)%s");
+  if (kmer < 1 || kmer > SMG_MAX_KMER) return fail(errbuf, errlen, SMG_EINVAL, "k-mer length out of range (1..128)%s");
+  if (nels < 0) return fail(errbuf, errlen, SMG_EINVAL, "negative number of entries%s");
+  { // in core or not at all: the closed table next to the lists of a run, or next to the buffers of its own closure
+    // (host_run's prices per entry); the table handed in is in device memory already and not part of what is free
+    const int W = (kmer + 31) / 32;
+    const double ne = (double) nels * ((cond & SMG_COND_SYMM) ? 2.0 : 1.0);
+    if (ne >= (double) (0xFFFFFFF0ll - 16))
+      return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 - 32 entries in the closed table: one engine does not address them%s", two_step);
+    size_t fr = 0, tot = 0;
+    double limit = 0;
+    { const char *hl = getenv("SMG_HBM_LIMIT"); if (hl && atof(hl) > 0) limit = atof(hl); }
+    if (limit <= 0)
+      { if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess)
+          return fail(errbuf, errlen, SMG_ENODEV, "no usable HIP device%s");
+        limit = 0.9 * (double) fr;
+      }
+    const double per_run = 10.6 * W + 5.5, per_cond = cond ? ((cond & SMG_COND_SYMM) ? 24.0 * W + 30.0 : 8.0 * W + 12.0) : 0.0;
+    const double need = ne * (per_run > per_cond ? per_run : per_cond) + 1.1e9 - (cond ? 0.0 : (double) nels * (8.0 * W + 2.0));
+    if (need > limit)
+      { char msg[256];
+        snprintf(msg, sizeof(msg), "the table does not fit the device in core: %lld entries need %.3f GB, %.3f GB are free",
+                 (long long) nels, need * 1e-9, limit * 1e-9);
+        if (errbuf && errlen) snprintf(errbuf, errlen, "%s%s", msg, two_step);
+        return SMG_ENOMEM;
+      }
+  }
+  smg_engine *e = smg_engine_create(device, NULL, errbuf, errlen);
+  if (!e) return SMG_ENODEV;
+  int rc = SMG_OK;
+  int64_t *d_plot = NULL;
+  if (hipMalloc(&d_plot, sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess)
+    { rc = fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the plot%s"); goto done; }
+  if ((rc = smg_engine_bind(e, kmer, nels, d_keys, d_counts, errbuf, errlen))) goto done;
+  if ((cond & SMG_COND_TRIM) && (rc = smg_engine_condition(e, opts->ethresh, 1, 0, NULL, errbuf, errlen))) goto done;
+  if (cond & SMG_COND_SYMM)
+    { bool generic = !RUN_DEVICE_CLOSE_BY_MERGE;
+      if (!generic) rc = close_canonical(e, NULL, &generic, errbuf, errlen);     // (not canonical: left as it was, the generic closure takes it)
+      if (generic) rc = smg_engine_condition(e, 0, 0, 1, NULL, errbuf, errlen);
+      if (rc) goto done;
+    }
+  if ((rc = smg_engine_run(e, symcheck, d_plot, NULL, errbuf, errlen))) goto done;
+  if (hipMemcpy(plot, d_plot, sizeof(int64_t) * SMG_PLOT_CELLS, hipMemcpyDeviceToHost) != hipSuccess)
+    { rc = fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s"); goto done; }
+  if (stats) *stats = e->st;
+  if (opts && opts->verbose)
+    fprintf(stderr, "  [smg] n=%lld k=%d path=%s  conditioning %.2f ms, pass1 %.2f, rc-lookup %.2f, pass2 %.2f, total(device) %.2f ms\n",
+            (long long) e->st.nels, kmer, e->st.path == 1 ? "rc-half-scan" : "general", e->st.ms_decode, e->st.ms_pass1,
+            e->st.ms_rclookup, e->st.ms_pass2, e->st.ms_total);
+done:
+  if (d_plot) hipFree(d_plot);
+  smg_engine_destroy(e);
+  return rc;
+}
 
 extern "C" int smg_hetmers_extract(const smg_table_view *tv, const smg_opts *opts, const uint16_t *labels,
                                    int64_t *plot, uint64_t **records, int64_t *nrec, int *rec_words,

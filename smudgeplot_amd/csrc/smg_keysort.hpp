@@ -1,6 +1,6 @@
 // smg_keysort.hpp -- what the k-mer counter (smg_count.hip) and table conditioning (smg_hetmers.hip) share: a device
-// buffer that frees itself, the stable sort of W-word k-mers as a permutation, and the scan that turns flags into
-// positions.  No state of its own; every function returns the HIP error and the caller gives it its own code and message.
+// buffer that frees itself, the stable sort of W-word k-mers as a permutation, the scan that turns flags into
+// positions, and the merge of two sorted lists of k-mers.  No state of its own; every function returns the HIP error and the caller gives it its own code and message.
 
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +8,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "smg_device.hpp"
+#include "smg_mergepath.hpp"
 
 #define KS_TPB 256
 #define KS_TRY(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
@@ -90,6 +91,91 @@ static inline hipError_t scan_flags(uint32_t *flag, uint32_t *pos, int64_t n, hi
   KS_TRY(hipStreamSynchronize(stream));
   *total = (int64_t) last[0] + last[1];
   return hipSuccess;
+}
+
+// ---- merge path: two sorted lists of W-word k-mers with no k-mer in common -> one ----------------------------------------
+// A is a table (k-mers a[na * W], counts acnt[na]).  B is given unsorted with its order beside it: its j-th k-mer in sorted
+// order is b[bperm[j]], and it carries the count of A's entry bsrc[bperm[j]] (B holds reverse complements of entries of A:
+// smg_engine_close_canonical).  Output tile t is the outputs [t * T, (t + 1) * T): ks_merge_split finds with one diagonal
+// search per tile (mp_split, smg_mergepath.hpp, on the k-mers in device memory) how many of the outputs in front of it come
+// from A.  ks_merge stages the tile's two input spans -- T items together -- in LDS, A's span in front of B's, with their
+// counts; every thread searches its own diagonal there, merges its T / 256 items into registers, and after a barrier the
+// merged tile replaces the spans in LDS and leaves in coalesced stores.
+// T per key width: 8 W + 2 bytes of LDS per item, 20 / 36 / 26 / 34 KiB per workgroup for W = 1 .. 4, so that four
+// workgroups (16 wavefronts) fit the 160 KiB of a CU at every width, and 8 / 8 / 4 / 4 items per thread in registers.
+// (KsMergeTile<W>, ks_merge_tile: smg_mergepath.hpp, where the host check reads them too)
+// Where its time is expected to go: B is never written out in sorted order, so its span is staged by one random gather per
+// item through bperm (8 W bytes out of a cache line each, and a second gather for the count), and every step of a tile's
+// search in ks_merge_split is a dependent gather of the same kind (about log2 T .. log2 nb of them in a row per tile).
+static_assert(KS_TPB == MP_TPB, "ks_merge runs with the threads smg_mergepath.hpp cuts its tiles for");
+
+// split[t] = items of A among the first min(t * T, na + nb) outputs, t = 0 .. ntiles
+template <int W> __global__ void __launch_bounds__(KS_TPB)
+ks_merge_split(const u64 *__restrict__ a, int64_t na, const u64 *__restrict__ b, const uint32_t *__restrict__ bperm, int64_t nb,
+               int64_t ntiles, uint32_t *__restrict__ split)
+{ const int64_t t = (int64_t) blockIdx.x * KS_TPB + threadIdx.x;
+  if (t > ntiles) return;
+  int64_t diag = t * KsMergeTile<W>::value;
+  if (diag > na + nb) diag = na + nb;
+  split[t] = (uint32_t) mp_split(diag, na, nb, [&](int64_t j, int64_t i) { return mp_key_lt<W>(b + (size_t) bperm[j] * W, a + (size_t) i * W); });
+}
+
+template <int W> __global__ void __launch_bounds__(KS_TPB)
+ks_merge(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t na, const u64 *__restrict__ b,
+         const uint32_t *__restrict__ bperm, const uint32_t *__restrict__ bsrc, int64_t nb, const uint32_t *__restrict__ split,
+         u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ constexpr int T = KsMergeTile<W>::value, IPT = T / KS_TPB;
+  __shared__ __attribute__((aligned(16))) u64 s_key[T * W];
+  __shared__ __attribute__((aligned(16))) uint16_t s_cnt[T];
+  const int t = threadIdx.x;
+  const int64_t d0 = (int64_t) blockIdx.x * T, d1 = d0 + T < na + nb ? d0 + T : na + nb;
+  const int64_t a0 = split[blockIdx.x], a1 = split[blockIdx.x + 1], b0 = d0 - a0, b1 = d1 - a1;
+  // mp_split keeps every split within both lists; on sorted lists the splits ascend as well.  Lists that are not sorted can
+  // give spans of negative length: such a tile is left unwritten (the whole workgroup leaves), nothing is read out of bounds
+  if (a1 < a0 || b1 < b0) return;
+  const int ca = (int) (a1 - a0), cb = (int) (b1 - b0), ct = ca + cb;       // ct = d1 - d0 <= T
+
+  for (int x = t; x < ca * W; x += KS_TPB) s_key[x] = a[(size_t) a0 * W + x];
+  for (int x = t; x < ca; x += KS_TPB) s_cnt[x] = acnt[a0 + x];
+  for (int x = t; x < cb; x += KS_TPB)
+    { const uint32_t p = bperm[b0 + x];
+      const Key<W> y = load_key<W>(b, p);
+#pragma unroll
+      for (int w = 0; w < W; w++) s_key[(ca + x) * W + w] = y.w[w];
+      s_cnt[ca + x] = acnt[bsrc[p]];
+    }
+  __syncthreads();
+
+  const u64 *sa = s_key, *sb = s_key + ca * W;
+  const auto b_before_a = [&](int64_t j, int64_t i) { return mp_key_lt<W>(sb + j * W, sa + i * W); };
+  const int diag = t * IPT < ct ? t * IPT : ct;
+  const int mine = ct - diag < IPT ? ct - diag : IPT;
+  const int64_t i0 = mp_split(diag, ca, cb, b_before_a);
+  u64 rk[IPT][W];
+  uint16_t rc[IPT];
+  mp_merge_run<IPT>(i0, diag - i0, ca, cb, mine, b_before_a, [&](int c, bool from_a, int64_t x)
+    { const int s = (int) (from_a ? x : ca + x);
+#pragma unroll
+      for (int w = 0; w < W; w++) rk[c][w] = s_key[s * W + w];
+      rc[c] = s_cnt[s];
+    });
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < IPT; c++)
+    if (c < mine)
+      {
+#pragma unroll
+        for (int w = 0; w < W; w++) s_key[(diag + c) * W + w] = rk[c][w];
+        s_cnt[diag + c] = rc[c];
+      }
+  __syncthreads();
+
+  for (int x = t; x < ct * W; x += KS_TPB) okeys[(size_t) d0 * W + x] = s_key[x];
+  // (d0 is a multiple of T: the counts of a tile begin on a 4-byte boundary of a hipMalloc'ed array and leave two at a time)
+  const uint32_t *c2 = reinterpret_cast<const uint32_t *>(s_cnt);
+  uint32_t *o2 = reinterpret_cast<uint32_t *>(ocnt + d0);
+  for (int x = t; x < ct / 2; x += KS_TPB) o2[x] = c2[x];
+  if (t == 0 && (ct & 1)) ocnt[d0 + ct - 1] = s_cnt[ct - 1];
 }
 
 #undef KS_TRY

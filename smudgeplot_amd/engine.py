@@ -68,6 +68,7 @@ EXPORTS = [
     "smg_engine_symm_hist", "smg_engine_symm_route", "smg_engine_symm_finish", "smg_engine_table",
     "smg_engine_table_host",
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
+    "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device",
 ]
 
 _lib = None
@@ -120,6 +121,9 @@ def load_library():
     lib.smg_engine_bind.argtypes = [vp, i32, i64, vp, vp, *err]
     lib.smg_engine_set_prefix_index.argtypes = [vp, vp, i32, i64, *err]
     lib.smg_engine_condition.argtypes = [vp, i32, i32, i32, C.POINTER(i64), *err]
+    lib.smg_engine_close_canonical.argtypes = [vp, C.POINTER(i64), *err]
+    lib.smg_engine_merge_tile.argtypes = [i32]
+    lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
     lib.smg_engine_nreq.restype = i64
@@ -188,6 +192,25 @@ def hetmers_run(table, device: int = 0, symcheck: str = "exact", verbose: int = 
     rc = lib.smg_hetmers_run(C.byref(tv), C.byref(opts), plot.ctypes.data, C.byref(st), buf, 512)
     _check(rc, buf)
     return plot.reshape(PLOT_ROWS, PLOT_COLS), st.asdict()
+
+
+def hetmers_run_device(k: int, nels: int, keys_ptr: int, counts_ptr: int, device: int = 0, symcheck: str = "hash",
+                       verbose: int = 0, condition: int = 0, ethresh: int = 0):
+    """A decoded table in device memory (the layout of Engine.bind; borrowed) -> (plot int64[1001,501], stats dict).
+    condition as for hetmers_run; COND_SYMM closes a canonical table by merge and any other table the generic way."""
+    lib = load_library()
+    opts = Opts(device, _SYM[symcheck], verbose, condition, ethresh, 0)
+    plot = np.zeros(PLOT_CELLS, dtype=np.int64)
+    st = Stats()
+    buf = C.create_string_buffer(512)
+    rc = lib.smg_hetmers_run_device(k, nels, keys_ptr or None, counts_ptr or None, C.byref(opts), plot.ctypes.data, C.byref(st), buf, 512)
+    _check(rc, buf)
+    return plot.reshape(PLOT_ROWS, PLOT_COLS), st.asdict()
+
+
+def merge_tile(words: int) -> int:
+    """outputs per workgroup of the merge kernel behind Engine.close_canonical for k-mers of `words` 64-bit words"""
+    return int(load_library().smg_engine_merge_tile(words))
 
 
 def _table_view(table):
@@ -299,6 +322,13 @@ class Engine:
         n = C.c_int64(0)
         _check(self.lib.smg_engine_condition(self.h, ethresh, int(trim), int(symm), C.byref(n), self._buf, 512),
                self._buf)
+        return int(n.value)
+
+    def close_canonical(self) -> int:
+        """close a canonical table (every entry <= its reverse complement) under reverse complement by one sort of the
+        complements and a merge; raises EngineError (-2, "table is not canonical") and changes nothing otherwise"""
+        n = C.c_int64(0)
+        _check(self.lib.smg_engine_close_canonical(self.h, C.byref(n), self._buf, 512), self._buf)
         return int(n.value)
 
     # ---- symmetrising across shards (smg_hetmers.h) ----------------------------------------
