@@ -66,6 +66,7 @@ struct FastArgs
   uint32_t       *bmap;          // candidate block map (or NULL): bit (hi32(kmer) >> bmsh) is set when a window block
   int             bmsh;          //   (coarsened to <= 32 leading bits) holds an entry with exactly one suffix-side pair
   int             bm2;           // two-bit map (below): 64-bit map words
+  int             ow;            // one-way requests (below): this engine's own requests carry a flag in bit 0 of their last word
 };
 
 // code byte (P flag masked off) -> "owns a pair at p > k-1-p": several pairs, or one that is not self-mirrored
@@ -80,6 +81,38 @@ SMG_DEV bool code_hi(unsigned c) { return c - 63u < 65u; }                    //
 // word, so marking is one atomic and probing one load.
 SMG_DEV unsigned bm2_pos(uint32_t lo) { return (lo * 0x9E3779B1u) >> 27; }
 SMG_DEV u64 bm2_bits(uint32_t id, uint32_t lo) { return (u64) (1u << (id & 31u)) | ((u64) (1u << bm2_pos(lo)) << 32); }
+
+// ONE-WAY REQUESTS (odd k <= 63, hash proof, key-only records, an engine that looks up its own requests).
+// With m = (k - 1) / 2, A(x) = pairs of x at p >= m, H(x) = pairs at p > m:  P(x) = [H(rc x) > 0], read only where A(x) = 1.
+// The two-way protocol lets every entry with H > 0 tell its complement -- both members of a class {x, rc x}, independently.
+// Both halves of a class's knowledge meet at the target, so one message per class is enough.  The middle base of rc x is the
+// complement of the middle base of x, so the high bit of the middle base (bit 64 - k of the leading word) picks exactly one
+// member of every class: the LOWER one (bit clear).
+//   send     a lower entry x with A(x) >= 1 sends rc(x) with the flag f = [H(x) > 0] in bit 0 of the record's last word
+//            (free: 2k <= 64 W - 2); upper entries never send;
+//   mark     only upper entries are targets, so only they mark the map: the id bit as ever, and in the high half of the
+//            64-bit map word two PLANES of 16 hashed positions: plane C (bits 0..15) when A(y) = 1, plane H (bits 16..31)
+//            when H(y) > 0;
+//   filter   f = 1 passes on id and (C or H), f = 0 (the sender's only pairs sit on the middle position) on id and H;
+//   look up  the target j: c = code[j] is read BEFORE any store; f sets P(j); where c says H(j) > 0 the sender -- the entry
+//            rc(record) -- is looked up and gets its flag.  Both stores are true whatever A says.  Nobody else names j or
+//            the sender but a duplicate from kf_bigfix; a duplicate that reads 0x80 skips the reverse step its first reader
+//            has done.
+SMG_DEV unsigned bm2_pos16(uint32_t lo) { return (lo * 0x9E3779B1u) >> 28; }
+// (uq: A = 1, hi: H > 0; at least one of them)
+SMG_DEV u64 bm2_planes(uint32_t id, uint32_t lo, bool uq, bool hi)
+{ const unsigned pl = (uq ? 1u : 0u) | (hi ? 0x10000u : 0u);
+  return (u64) (1u << (id & 31u)) | ((u64) (pl << bm2_pos16(lo)) << 32);
+}
+// second test of a request against the high half `hw` of its target's map word (the id bit has been tested); lo = the 32 k-mer
+// bits below the id, the flag bit masked off
+SMG_DEV bool bm2_pass(unsigned hw, uint32_t lo, unsigned f, int ow)
+{ if (!ow) return ((hw >> bm2_pos(lo)) & 1u) != 0;
+  const unsigned pl = (hw >> 16) | (f ? hw : 0u);
+  return ((pl >> bm2_pos16(lo)) & 1u) != 0;
+}
+// the lower member of {x, rc x} (odd k <= 63: the middle base is base (k - 1) / 2 <= 31 of the leading word)
+template <int W> SMG_DEV bool key_lower(const Key<W> &x, int k) { return ((x.w[0] >> (64 - k)) & 1ull) == 0; }
 
 struct FastCtl                    // device control words of the fast path
 { unsigned n_chunks;             // chunks handed out (may exceed max_chunks => rerun)
@@ -461,6 +494,21 @@ template <int W> SMG_DEV int64_t sig_find(const FastArgs &A, const Key<W> &y, bo
   return j;
 }
 
+// One request of the one-way protocol (above): flag off, target, its code byte, then the stores.
+template <int W> SMG_DEV void apply_one_way(const FastArgs &A, Key<W> y, FastCtl *__restrict__ ctl)
+{ const unsigned f = (unsigned) y.w[W - 1] & 1u;
+  y.w[W - 1] &= ~1ull;
+  const int64_t j = sig_find<W>(A, y, false);
+  if (j < 0) { if (ctl->missing == 0) ctl->missing = 1; return; }
+  const unsigned c = A.code[j];
+  if (f) SET_P(A, j);
+  if (code_hi(c))                                      // (a byte that is 0x80 already: the first reader has told the sender)
+    { const int64_t i = sig_find<W>(A, revcomp<W>(y, A.g.k), false);
+      if (i < 0) { if (ctl->missing == 0) ctl->missing = 1; return; }
+      SET_P(A, i);
+    }
+}
+
 // ---- apply: set the P bit of every requested complement ---------------------------------------
 // chunk_fill != NULL : one workgroup per chunk of the local request list
 // chunk_fill == NULL : flat list of nflat records (received from other ranks), grid-stride
@@ -482,6 +530,7 @@ kf_apply(FastArgs A, const u64 *__restrict__ req, const uint32_t *__restrict__ c
       Key<W> y;
 #pragma unroll
       for (int w = 0; w < W; w++) y.w[w] = q[w];
+      if constexpr (W <= 2) if (A.ow) { apply_one_way<W>(A, y, ctl); continue; }
       const u64 meta = rw > W ? q[W] : 1ull << 16;
       const bool cc = check_count && rw > W;
       const int64_t j = sig_find<W>(A, y, cc);
@@ -642,7 +691,8 @@ kf_apply_sorted(FastArgs A, const u64 *__restrict__ keys_sorted, int64_t nreq, i
     { Key<W> y;
 #pragma unroll
       for (int w = 0; w < W; w++) y.w[w] = keys_sorted[r * W + w];
-      if (skip_sentinels && y.w[0] == ~0ull) continue;
+      if (skip_sentinels && y.w[0] == ~0ull) continue;       // (before the flag bit of a one-way record is looked at)
+      if (A.ow) { apply_one_way<W>(A, y, ctl); continue; }
       const int64_t j = sig_find<W>(A, y, false);
       if (j < 0) { if (ctl->missing == 0) ctl->missing = 1; continue; }
       SET_P(A, j);
@@ -670,6 +720,7 @@ kf_apply_indexed(FastArgs A, const u64 *__restrict__ rec, const uint32_t *__rest
       Key<W> y;
 #pragma unroll
       for (int w = 0; w < W; w++) y.w[w] = q[w];
+      if constexpr (W <= 2) if (A.ow) { apply_one_way<W>(A, y, ctl); continue; }
       const u64 meta = rw > W ? q[W] : 1ull << 16;
       const bool cc = check_count && rw > W;
       const int64_t j = sig_find<W>(A, y, cc);
@@ -1206,6 +1257,7 @@ kf_bigfix(FastArgs A, const uint32_t *__restrict__ biglist, const unsigned *__re
           uint32_t *__restrict__ farp /* [cap]: the partner of a listed entry whose code says "out of reach" */)
 { constexpr int rw = RW;
   __shared__ uint32_t slist[BF_SLAB];   // entries of the slab that owe a request
+  __shared__ unsigned sflag[BF_SLAB / 32];      // one-way: the flag of the request in that slot (s_hi > 0)
   __shared__ unsigned hist[1024];       // requests of this workgroup per look-up bucket (a row of whist, like pass 1's)
   __shared__ unsigned s_nl, s_next, s_slab, s_chunk, s_used;
   __shared__ u64      s_base, s_total;
@@ -1221,6 +1273,7 @@ kf_bigfix(FastArgs A, const uint32_t *__restrict__ biglist, const unsigned *__re
   for (;;)
     { __syncthreads();
       if (t == 0) { s_slab = atomicAdd(&ctl->bf_next, slab); s_next = 0; s_nl = 0; }
+      if (t < BF_SLAB / 32) sflag[t] = 0;
       __syncthreads();
       const unsigned slab0 = s_slab;
       if (slab0 >= nbig) break;
@@ -1239,12 +1292,24 @@ kf_bigfix(FastArgs A, const uint32_t *__restrict__ biglist, const unsigned *__re
               const unsigned code = make_code(s_all, partner - i, w2);
               A.code[i] = (uint8_t) code;
               if ((code & 63) == CODE_FAR) farp[r] = (uint32_t) partner;
-              if (W <= 2 && A.bmap && s_all == 1)             // a candidate: mark its block for the request filter
+              // one-way requests (W <= 2): a lower entry with a pair sends, with its exact flag; an upper entry marks
+              const bool lower = W <= 2 && A.ow && ((A.keys[i * W] >> (64 - A.g.k)) & 1ull) == 0;
+              const bool mark = A.ow ? (!lower && s_all >= 1) : s_all == 1;       // two-way: a candidate marks its block
+              if (W <= 2 && A.bmap && mark)
                 { const uint32_t id = (uint32_t) (A.keys[i * W] >> 32) >> A.bmsh;
-                  if (A.bm2) atomicOr(reinterpret_cast<u64 *>(A.bmap) + (id >> 5), bm2_bits(id, (uint32_t) A.keys[i * W]));
+                  if (A.bm2)
+                    { const uint32_t lo = (uint32_t) A.keys[i * W];
+                      if (!A.ow) atomicOr(reinterpret_cast<u64 *>(A.bmap) + (id >> 5), bm2_bits(id, lo));
+                      else if (s_all == 1 || s_hi > 0)
+                        atomicOr(reinterpret_cast<u64 *>(A.bmap) + (id >> 5), bm2_planes(id, lo, s_all == 1, s_hi > 0));
+                    }
                   else atomicOr(&A.bmap[id >> 5], 1u << (id & 31));
                 }
-              if (s_hi > 0) slist[atomicAdd(&s_nl, 1u)] = (uint32_t) i;
+              if (A.ow ? (lower && s_all >= 1) : s_hi > 0)
+                { const unsigned sl = atomicAdd(&s_nl, 1u);
+                  slist[sl] = (uint32_t) i;
+                  if (A.ow && s_hi > 0) atomicOr(&sflag[sl >> 5], 1u << (sl & 31));
+                }
             }
         }
       __syncthreads();
@@ -1266,7 +1331,8 @@ kf_bigfix(FastArgs A, const uint32_t *__restrict__ biglist, const unsigned *__re
           __syncthreads();
           if ((unsigned) t < qn)
             { const int64_t i = slist[q0 + t];
-              const Key<W> rc = revcomp<W>(load_key<W>(A.keys, i), A.g.k);
+              Key<W> rc = revcomp<W>(load_key<W>(A.keys, i), A.g.k);
+              if (A.ow) rc.w[W - 1] |= (u64) ((sflag[(q0 + t) >> 5] >> ((q0 + t) & 31)) & 1u);
               if (s_chunk < max_chunks)
                 { u64 *o = req + (s_base + t) * rw;
 #pragma unroll

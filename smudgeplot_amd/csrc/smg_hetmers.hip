@@ -44,7 +44,8 @@
 //   documented modes    getenv(): SMG_VIRTUAL_SHARDS, SMG_SEQUENTIAL_SHARDS, SMG_SHARD_LIMIT, SMG_HBM_LIMIT, SMG_FORCE_MULTI (smg_hetmers.h);
 //   test hooks          test_hook(): force, on a table of any size, a code path that the engine otherwise picks from the table's
 //                       size, k or counts (the 30-bit exchanged map, the one-bit map of k < 24, kl_probe_x, the unfiltered chain,
-//                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle.
+//                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle;
+//                       SMG_TWO_WAY=1 keeps the two-way request protocol where one-way would be chosen (tests/test_one_way_gpu.py).
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
 #define WIN_LIM   32          // window blocks up to this many entries are walked linearly
@@ -736,6 +737,7 @@ struct smg_engine
   bool         lookup_pending; // look-ups of received requests were queued without a host wait (their time is read later)
   bool         use_sig;    // pass 1 writes the 2-byte look-up signatures (not worth their 5 GB when the filter leaves 1 request in 115)
   int          bm2;        //   the map is a two-bit map (smg_fast.hpp): 64-bit words, private to this engine
+  int          one_way;    //   this run's requests are one-way (smg_fast.hpp): set by fast_pass1 for smg_engine_run, never by the phase API
   int          bm_cap;     //   id bits of the block map: 32 on one GPU, 30 when the maps of several shards are exchanged
   int          bm_want;    //   ... as asked for by smg_engine_set_blockmap_bits (0: default)
   P1Cold      *p1cold;     // rarely used arguments of kf_pass1_d (device copy)
@@ -1249,6 +1251,7 @@ static FastArgs make_fast(smg_engine *e)
   a.bmap = e->bm_bits ? e->bmap : NULL;
   a.bmsh = 32 - e->bm_bits;
   a.bm2 = e->bm2;
+  a.ow = e->one_way;
   return a;
 }
 
@@ -1261,12 +1264,18 @@ static bool filter_ok(const smg_engine *e)
 // nothing is read back here: the lists are as large as last time, the counts that later launches take from the host (requests,
 // deferred entries) are the recorded step's -- they are functions of the table -- and the device checks all of it against the
 // control words at the end of the step (k_proof_replay).
-static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, char *errbuf, size_t errlen, bool replay = false)
+// one_way_ok: the caller looks this engine's requests up itself, with this engine's map (smg_engine_run): odd k <= 63 with key-only
+// records under the hash proof then sends one request per complement class (smg_fast.hpp); the test hook SMG_TWO_WAY=1 keeps the
+// two-way protocol.  The phase API never passes it: its requests leave the engine, and the sender is not local to the look-up.
+static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, char *errbuf, size_t errlen, bool replay = false,
+                      bool one_way_ok = false)
 { int rc;
   // record = the complement k-mer (W words) [+ one word: count | has-hi-pair << 16]
   // (two-word k-mers send key-only records for the hash proof as one-word ones do: 16 instead of 24 bytes for 21.6 % of
   //  the entries at k = 51; three-word k-mers go through the generic kernel, whose records always carry the count word)
   e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
+  e->one_way = (one_way_ok && (e->kmer & 1) && e->kmer >= 3 && e->kmer <= 63 && e->W <= 2 && e->rw == e->W && want_fp && !emit_all
+                && !test_hook("SMG_TWO_WAY")) ? 1 : 0;
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
   e->fast = true; e->counted_done = false; e->general_done = false;
@@ -1349,7 +1358,8 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   // a chunk is closed as soon as the next tile's batch (<= one tile of records) does not fit, so
   // chunks fill to >= 75 %: size the list for that, and never below what is already allocated
   // (an engine that is reused on the same table must not redo pass 1 every time)
-  int64_t want_rec = (emit_all ? e->n + e->n / 24 : e->n / 4) + (int64_t) (grid + 16 + 256) * F_CH;
+  // (one-way requests: half the senders)
+  int64_t want_rec = (emit_all ? e->n + e->n / 24 : e->one_way ? e->n / 8 : e->n / 4) + (int64_t) (grid + 16 + 256) * F_CH;
   const int64_t dwords = ((((e->n + 31) >> 5) + 2) + 3) & ~3ll;          // (kf_bigfix reads the map four words at a time)
   if (narrow)
     { if (e->dbits_cap < dwords * 4) e->dbits_dirty = true;                 // (fresh memory)
@@ -1389,13 +1399,13 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           P1Hot hot;
           hot.keys = a.keys; hot.cnt = a.cnt; hot.n = a.n; hot.code = a.code; hot.sig = a.sig; hot.bstart = e->dir_preset ? (uint32_t *) NULL : e->bstart;
           hot.bmap = a.bmap; hot.b0 = e->dir.b0; hot.nb = e->dir.nb; hot.shifts = (unsigned) e->dir.dsh | ((unsigned) a.sigsh << 6) | (((unsigned) a.bmsh & 31u) << 12)
-                       | ((emit_all ? 1u : 0u) << 18) | ((want_fp ? 1u : 0u) << 19) | ((unsigned) e->lg.nb << 20) | ((unsigned) e->bm2 << 24);
+                       | ((emit_all ? 1u : 0u) << 18) | ((want_fp ? 1u : 0u) << 19) | ((unsigned) e->lg.nb << 20) | ((unsigned) e->bm2 << 24)
+                       | ((unsigned) e->one_way << 25);
           hot.G = gr; hot.ntiles = ntiles;
           e->h_p1cold->req = e->req; e->h_p1cold->chunk_fill = e->chunk_fill; e->h_p1cold->dbits = e->dbits;
           e->dbits_dirty = true;                                               // until kf_bigfix has cleared the bits again
           e->h_p1cold->partials = e->partials; e->h_p1cold->ctl = &e->ctrl->fast; e->h_p1cold->max_chunks = maxc;
           e->h_p1cold->whist = e->whist; e->h_p1cold->owners = grid + BF_MAXGRID;
-          e->h_p1cold->times = NULL;
           if ((rc = grow(&e->p1tick, &e->p1tick_cap, (int64_t) D_NCLS * D_TICKW * 4, errbuf, errlen))) return rc;
           HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
           e->h_p1cold->tick = e->p1tick;
@@ -1652,7 +1662,9 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
   { const char *px = test_hook("SMG_PROBE_X");
     // ... and so does the share of entries that sent a request: 17.5 % on the diploid tables, a third on the polyploid ones, where
     // one request in seven survives the filter (2.5e7 look-ups at 6.4e8 entries) and kl_probe_x is 7-8 % ahead as well
-    const bool auto_x = (e->st.nbig > 0 && e->st.nbig * 400 > e->n) || e->st.nemitted * 100 > e->n * 28;
+    // (a one-way run sends one request per complement class: half the share says the same about the table)
+    const int64_t share = e->one_way ? 14 : 28;
+    const bool auto_x = (e->st.nbig > 0 && e->st.nbig * 400 > e->n) || e->st.nemitted * 100 > e->n * share;
     if (!list && e->lg.nb >= 3 && (px ? atoi(px) != 0 : auto_x))
       { int rc2;
         if ((rc2 = grow(&e->xtick, &e->xtick_cap, (int64_t) PX_NXCD * PX_TICKW * 4, errbuf, errlen))) return rc2;
@@ -1660,7 +1672,7 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
         // tickets of 2048 requests where many requests survive (polyploid tables: one in seven, all real hits -- half as many
         // buckets in flight per XCD keep more of a bucket's k-mer lines in reach: -0.25 ms on the hexaploid table), 4096 where the
         // kernel is mostly streaming (a table with repeats: 1 request in 50 survives, and a ticket's fixed cost shows: +0.5 ms at 2048)
-        unsigned part = e->st.nemitted * 100 > e->n * 28 ? PX_PART : 2 * PX_PART;
+        unsigned part = e->st.nemitted * 100 > e->n * share ? PX_PART : 2 * PX_PART;
         if (test_hook("SMG_PX_ONE_XCC")) part |= 0x80000000u;                      // (tests: every workgroup claims XCD 0)
         const unsigned xg = grid * PX_WGS;
 #define PROBEX(TWO_, RW_) hipLaunchKernelGGL((kl_probe_x<TWO_, RW_>), dim3(xg), dim3(PX_TPB), 0, e->stream, a, (const u64 *) e->req2, \
@@ -1903,7 +1915,7 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
   if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
   if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_codes, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
   e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
-  e->use_sig = false; e->bm_bits = 0; e->bm2 = 0; e->lg.nb = 0;
+  e->use_sig = false; e->bm_bits = 0; e->bm2 = 0; e->lg.nb = 0; e->one_way = 0;
   e->filtered = false; e->presorted = 0; e->n_chunks = 0; e->far_listed = false;
   e->st.nrequests = 0; e->st.ms_rclookup = 0;
   memset(e->fp, 0, sizeof(e->fp));
@@ -2229,6 +2241,7 @@ extern "C" int smg_engine_route(smg_engine *e, const uint64_t *splitters, int nr
   if (!counts || nranks < 1 || nranks > 16)
     return fail(errbuf, errlen, SMG_EINVAL, "bad route arguments (1..16 ranks)%s");
   if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
+  if (e->one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
   HIPCHK(hipSetDevice(e->device));
   if (e->st.nrequests > capacity) return fail(errbuf, errlen, SMG_EINVAL, "send buffer too small%s");
   return route_records(e, e->req, e->chunk_fill, e->n_chunks, e->rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
@@ -2240,6 +2253,7 @@ extern "C" int smg_engine_route_device(smg_engine *e, const uint64_t *splitters,
   if (!d_counts || nranks < 1 || nranks > 16)
     return fail(errbuf, errlen, SMG_EINVAL, "bad route arguments (1..16 ranks)%s");
   if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
+  if (e->one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
   HIPCHK(hipSetDevice(e->device));
   if (e->st.nrequests > capacity) return fail(errbuf, errlen, SMG_EINVAL, "send buffer too small%s");
   int rc = route_records(e, e->req, e->chunk_fill, e->n_chunks, e->rw, splitters, nranks, d_send, capacity, NULL, errbuf, errlen, d_counts);
@@ -2297,7 +2311,7 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
       // (Rounds 3-5 queued a re-run on the same table from the counts of the run before -- "run_speculative", one host wait
       //  instead of four.  Measured twice without a gain, 17.94 against 17.7-18.0 ms per step, profiles/r05_lookup_experiments.txt:
       //  taken out in round 6.  The one mechanism of that kind left is the replayed step of the phase API, for sharded runs.)
-      rc = fast_pass1(e, exact, exact, symcheck == SMG_SYM_HASH, errbuf, errlen);
+      rc = fast_pass1(e, exact, exact, symcheck == SMG_SYM_HASH, errbuf, errlen, false, symcheck == SMG_SYM_HASH);
       if (rc) return rc;
       int64_t missing = 0;
       if ((rc = fast_apply(e, NULL, 0, exact, &missing, errbuf, errlen))) return rc;

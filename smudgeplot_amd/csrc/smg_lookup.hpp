@@ -52,8 +52,10 @@ static inline LookupGeo lookup_geo(int fb)
 // (Tried in round 4: turning the question round on a single shard -- the CANDIDATES send, the owners of a pair at p > k-1-p
 //  mark the map, the look-up reads the answer from the complement's code byte.  Correct, and no gain: on the bench table
 //  18.7 % of the entries are candidates, 17.5 % own such a pair -- the two streams are the same size.)
+// One-way requests (A.ow; smg_fast.hpp): the record carries a flag, and the sender may get its own flag from the target's byte.
 template <int W> SMG_DEV void lookup_one(const FastArgs &A, const Key<W> &y, FastCtl *__restrict__ ctl)
-{ const int64_t i = sig_find<W>(A, y, false);          // (no signatures bound: find_key_near, smg_device.hpp)
+{ if (A.ow) { apply_one_way<W>(A, y, ctl); return; }
+  const int64_t i = sig_find<W>(A, y, false);          // (no signatures bound: find_key_near, smg_device.hpp)
   if (i < 0) { if (ctl->missing == 0) ctl->missing = 1; return; }
   SET_P(A, i);
 }
@@ -377,7 +379,15 @@ kl_probe(FastArgs A, const u64 *__restrict__ recs, const u64 *__restrict__ boff,
           for (int j = 0; j < PB_PER; j++)
             { const unsigned fid = (unsigned) (y[j] >> (64 - g.fb));
               keep[j] = keep[j] && ((fwd[j] >> (fid & 31)) & 1u);
-              if (TWO) keep[j] = keep[j] && ((fw2[j] >> bm2_pos((uint32_t) y[j])) & 1u);
+              if (TWO)
+                { // one-way records: the flag is bit 0 of the last word (RW = 2: of the second word, in the line just read)
+                  unsigned f = 0; uint32_t lo = (uint32_t) y[j];
+                  if (A.ow)
+                    { if (RW == 1) { f = lo & 1u; lo &= ~1u; }
+                      else if (keep[j]) f = (unsigned) recs[(i0 + (u64) j * 64 + lane) * RW + 1] & 1u;
+                    }
+                  keep[j] = keep[j] && bm2_pass(fw2[j], lo, f, A.ow);
+                }
             }
 #pragma unroll
           for (int j = 0; j < PB_PER; j += 2)                  // queue two wave-instructions' worth, drain to below 64
@@ -493,7 +503,15 @@ kl_probe_x(FastArgs A, const u64 *__restrict__ recs, const u64 *__restrict__ bof
           for (int j = 0; j < PX_PER; j++)
             { const unsigned fid = (unsigned) (y[j] >> (64 - g.fb));
               keep[j] = keep[j] && ((fwd[j] >> (fid & 31)) & 1u);
-              if (TWO) keep[j] = keep[j] && ((fw2[j] >> bm2_pos((uint32_t) y[j])) & 1u);
+              if (TWO)
+                { // one-way records: the flag is bit 0 of the last word (RW = 2: of the second word, in the line just read)
+                  unsigned f = 0; uint32_t lo = (uint32_t) y[j];
+                  if (A.ow)
+                    { if (RW == 1) { f = lo & 1u; lo &= ~1u; }
+                      else if (keep[j]) f = (unsigned) recs[(i0 + (u64) j * 64 + lane) * RW + 1] & 1u;
+                    }
+                  keep[j] = keep[j] && bm2_pass(fw2[j], lo, f, A.ow);
+                }
             }
 #pragma unroll
           for (int j = 0; j < PX_PER; j += 2)

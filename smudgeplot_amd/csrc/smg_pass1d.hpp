@@ -180,7 +180,7 @@ struct P1Hot                              // kernel argument: what every tile to
   uint32_t       *bstart;        // bucket directory: bucket(x) = (hi32(x) >> dsh) - b0; NULL: the table came with its prefix index, none is built
   uint32_t       *bmap;          // candidate block map (or NULL): bit (hi32(x) >> bmsh)
   uint32_t        b0, nb;
-  unsigned        shifts;        // dsh | sigsh << 6 | bmsh << 12 | emit_all << 18 | want_fp << 19 | hbits << 20 | two << 24  (one register)
+  unsigned        shifts;        // dsh | sigsh << 6 | bmsh << 12 | emit_all << 18 | want_fp << 19 | hbits << 20 | two << 24 | ow << 25  (one register)
   GeoR            G;
   int64_t         ntiles;
   SMG_DEV int dsh() const { return (int) (shifts & 63u); }
@@ -190,6 +190,7 @@ struct P1Hot                              // kernel argument: what every tile to
   SMG_DEV bool want_fp() const { return (shifts >> 19 & 1u) != 0; }
   SMG_DEV int hbits() const { return (int) ((shifts >> 20) & 15u); }    // request histogram on the leading hbits bits (0: none)
   SMG_DEV bool two() const { return (shifts >> 24 & 1u) != 0; }         // two-bit block map (BM2_* in smg_fast.hpp)
+  SMG_DEV bool ow() const { return (shifts >> 25 & 1u) != 0; }          // one-way requests (smg_fast.hpp; odd k, key-only records)
 };
 
 struct P1Cold                             // in device memory: what only a flush touches (kept out of the register file)
@@ -202,9 +203,6 @@ struct P1Cold                             // in device memory: what only a flush
   unsigned  owners;              //   chunk slots are dealt out without a counter: owner w fills w, w + owners, w + 2 owners, ..
   unsigned  max_chunks;
   uint32_t *dbits;               // deferred entries: one bit per table entry (kf_bigfix redoes them exactly and clears the bits)
-  u64      *times;               // start / end of every workgroup on the constant 100 MHz clock when set; the host always passes
-                                 //   NULL.  Kept only because dropping it and its two stores in kf_pass1_d changes the pass-1 code
-                                 //   object that profiles/hbm_traffic.json is tied to: it goes with the next change of kf_pass1_d.
   unsigned *tick;                // tile tickets: D_NCLS counters, 128 bytes apart (zeroed before the launch)
 };
 
@@ -479,6 +477,10 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
   //@mark D_BMAP
   // word 0 of the tile's LDS bit map = the map word of the tile's first owned entry (a uniform, scalar load)
   // (inner tiles: loaded one tile ahead with the entries -- as a load of its own it was waited for on the spot)
+  // one-way requests: which entries are the lower members of their classes (the high bit of the middle base is clear)
+  const bool ow = ODD && RW == W && A.ow();
+  const unsigned lowbit = 1u << (((W == 1 ? 32 : 64) - G.k) & 31);
+  u64 lowM[4] = { 0, 0, 0, 0 };
   const uint32_t bmbase = D_BM ? (((INNER ? pf_anchor : (uint32_t) (A.keys[(g0 + D_LEAD) * W] >> 32)) >> bmsh) & ~31u) : 0u;
   if (D_BM && A.bmap)
     { // leading word of the thread's own entries, back from the staged copy (cheaper than four registers kept alive
@@ -494,17 +496,25 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 #pragma unroll
           for (int e = 0; e < 4; e++) kw[e] = S.ent[(slot0 + e) * W];
         }
+      if (ow)
+        {
+#pragma unroll
+          for (int e = 0; e < 4; e++) lowM[e] = __ballot(((W == 1 ? (unsigned) (kw[e] >> 32) : (unsigned) kw[e]) & lowbit) == 0u);
+        }
       if ((VAR & 2) || A.two())
         { u64 *bm64 = reinterpret_cast<u64 *>(S.bm);
           u64 *gm64 = reinterpret_cast<u64 *>(A.bmap);
 #pragma unroll
           for (int e = 0; e < 4; e++)
-            { u64 cm = uniqM[e] & ownM;
+            { // (one-way: the upper entries with A = 1 or H > 0 mark, each its planes)
+              u64 cm = (ow ? (uniqM[e] | hiM[e]) & ~lowM[e] : uniqM[e]) & ownM;
               if (!INNER) cm &= V[e];
               if (cm)
                 { const uint32_t id = (uint32_t) (kw[e] >> 32) >> bmsh;
                   const uint32_t rel = id - bmbase;
-                  const u64 v = bm2_bits(id, (uint32_t) kw[e]);
+                  u64 v;
+                  if (ow) v = bm2_planes(id, (uint32_t) kw[e], d_lane(uniqM[e]), d_lane(hiM[e]));
+                  else    v = bm2_bits(id, (uint32_t) kw[e]);
                   const u64 nearM = __ballot(rel < D_BMF) & cm;
                   if (d_lane(nearM)) atomicOr(&bm64[rel >> 5], v);
                   const u64 farM = cm & ~nearM;
@@ -516,7 +526,7 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
         {
 #pragma unroll
           for (int e = 0; e < 4; e++)
-            { u64 cm = uniqM[e] & ownM;
+            { u64 cm = (ow ? (uniqM[e] | hiM[e]) & ~lowM[e] : uniqM[e]) & ownM;       // (one-way, one-bit map: the upper entries with a pair)
               if (!INNER) cm &= V[e];
               if (cm)
                 { const uint32_t id = (uint32_t) (kw[e] >> 32) >> bmsh;
@@ -539,7 +549,18 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
   // that flag.  (A deferred entry that turns out to own more pairs than the register scan saw sends again from
   // kf_bigfix: the flag of a request is only ever ORed into its target.)
   const u64 all = (!(VAR & 2) && A.emit_all()) ? ~0ull : 0ull;       // (VAR & 2: the hash proof -- owners of a hi-side pair only)
-  u64 E0 = (hiM[0] | all) & ownM, E1 = (hiM[1] | all) & ownM, E2 = (hiM[2] | all) & ownM, E3 = (hiM[3] | all) & ownM;
+  // one-way: the LOWER entries with a pair send, each with the flag "owns a pair at p > k-1-p" in bit 0 of the record's last word
+  if (ow && !(D_BM && A.bmap))               // (no map in this launch: the masks have not been made above)
+    {
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+        { const u64 w0 = S.ent[(slot0 + e) * W];
+          lowM[e] = __ballot(((W == 1 ? (unsigned) (w0 >> 32) : (unsigned) w0) & lowbit) == 0u);
+        }
+    }
+  const u64 owS = ow ? ~0ull : 0ull;
+  u64 E0 = ((hiM[0] | all | (uniqM[0] & owS)) & (lowM[0] | ~owS)) & ownM, E1 = ((hiM[1] | all | (uniqM[1] & owS)) & (lowM[1] | ~owS)) & ownM,
+      E2 = ((hiM[2] | all | (uniqM[2] & owS)) & (lowM[2] | ~owS)) & ownM, E3 = ((hiM[3] | all | (uniqM[3] & owS)) & (lowM[3] | ~owS)) & ownM;
   if (!INNER) { E0 &= V[0]; E1 &= V[1]; E2 &= V[2]; E3 &= V[3]; }
   const unsigned cnt_w = (unsigned) (__popcll(E0) + __popcll(E1) + __popcll(E2) + __popcll(E3));
   unsigned base = 0;
@@ -590,7 +611,10 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
         { if (d_lane(E0))
             { const unsigned q = __builtin_amdgcn_mbcnt_hi((unsigned) (E0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) E0, base));
 #pragma unroll
-              for (int w = 0; w < W; w++) S.sq[q * RW + w] = rc.w[w];
+              for (int w = 0; w < W - 1; w++) S.sq[q * RW + w] = rc.w[w];
+              // (bit 0 of the last word is a pad bit of the k-mer: the flag of a one-way record is added in, no carry)
+              const unsigned lo32 = (unsigned) rc.w[W - 1] + (d_lane(hiM[e] & owS) ? 1u : 0u);
+              S.sq[q * RW + W - 1] = (rc.w[W - 1] & 0xFFFFFFFF00000000ull) | (u64) lo32;
               if (RW > W) S.sq[q * RW + W] = (u64) c | (d_lane(hiM[e]) ? 1ull << 16 : 0ull);
             }
           base += (unsigned) __popcll(E0);
@@ -719,10 +743,6 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
     }
   lds_barrier();
   (void) lane; (void) slot0; (void) n;
-  if (cold->times && t == 0)
-    { unsigned hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-      cold->times[3 * (size_t) blockIdx.x] = wall_clock64(); cold->times[3 * (size_t) blockIdx.x + 2] = hw;
-    }
 
   DPrefetch<W> pf;
   pf.valid = false;
@@ -841,7 +861,6 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
       tnext2 = (int64_t) gridDim.x + (int64_t) (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk[par]) * D_NCLS + cls;
     }
 
-  if (cold->times && t == 0) cold->times[3 * (size_t) blockIdx.x + 1] = wall_clock64();
   if (D_BM && RW == W && ((VAR & 2) || A.hbits()))                   // this workgroup's row of the request histogram (kl_tot / kl_woff)
     for (int w = t; w < D_HB; w += D_TPB) cold->whist[(size_t) blockIdx.x * D_HB + w] = hist[w];
   if (t == 0)
