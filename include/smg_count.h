@@ -9,7 +9,7 @@
  *   - hist[c] = number of distinct canonical k-mers with count c BEFORE trimming, c = 1..32767
  *     (the last bin holds the saturated ones, hist[0] is 0).
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
- * key ranges the run is partitioned into.
+ * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
  * return SMG_ENODEV; smg_count_parse and smg_count_version need no device.
  */
@@ -41,6 +41,8 @@ extern "C" {
 #define SMG_COUNT_SEPARATOR  '\n'      /* the byte between two records of a stripped stream */
 #define SMG_COUNT_BIN_BITS   12        /* key ranges are cut between bins of the leading 12 bits  */
 #define SMG_COUNT_BINS       4096      /* of the canonical k-mer                                  */
+#define SMG_COUNT_FINE_BITS  24        /* a bin with more windows than one merge holds is split on its next 12 bits: */
+#define SMG_COUNT_FINE_BINS  (1 << SMG_COUNT_FINE_BITS)   /* the ends of a range are values of the leading 24 bits  */
 
 typedef struct smg_count_opts
 { int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
@@ -66,7 +68,11 @@ typedef struct smg_count_stats
 
 /* Counting by key range.  Where one merge is not guaranteed to hold the distinct k-mers of the input, the input is
    read once, kept on the device at 3 bits per base, and counted one contiguous range of canonical k-mers at a time;
-   the result is that of one pass.  partitions = 1 is today's single pass and refuses (SMG_ENOMEM) what does not fit. */
+   the result is that of one pass.  partitions = 1 is today's single pass and refuses (SMG_ENOMEM) what does not fit.
+   Ranges are cut between the bins of the leading 12 bits of the canonical k-mer.  In automatic mode a bin that alone holds
+   more windows than one merge holds entries is split into the 4096 sub-bins of its next 12 bits, and a range may begin or
+   end inside it; refused (SMG_ENOMEM, bin and sub-bin named) is only a single sub-bin above one merge: windows that share
+   their twelve leading bases, a homopolymer run.  partitions = 2 .. SMG_COUNT_BINS cuts between whole bins only.        */
 typedef struct smg_count_parts
 { int32_t partitions;    /* in: 0 automatic (one pass where the size of the input guarantees that it fits, else ranges
                                 cut so that none can overflow a merge), 1 one pass, 2 .. SMG_COUNT_BINS that many ranges
@@ -76,7 +82,9 @@ typedef struct smg_count_parts
   int32_t used;          /* out: ranges the run was cut into (1: one pass, nothing was packed)                      */
   int64_t store_bytes;   /* out: device memory of the packed input                                                  */
   double  ms_pack;       /* out: device events, packing the batches into the store                                  */
-  double  ms_plan;       /* out: host clock, window histogram over the store and the choice of the cuts            */
+  double  ms_plan;       /* out: host clock, window histograms over the store and the choice of the cuts           */
+  int32_t split;         /* out: bins of the leading 12 bits that were split on their next 12 bits (0: every range is
+                                whole bins); `used` counts all ranges                                                */
 } smg_count_parts;
 
 /* *keys: malloc'ed *nels * *key_words uint64, left aligned, sorted; *counts: malloc'ed uint16[*nels];
@@ -121,6 +129,19 @@ void smg_count_device_free(void *d);
    cuts[0] = 0 and cuts[*nranges] = SMG_COUNT_BINS.                                                                  */
 int smg_count_plan(const uint64_t *windows, int64_t budget, int32_t partitions, int32_t *cuts, int32_t *nranges,
                    char *errbuf, size_t errlen);
+
+/* host only: the cuts where smg_count_plan refuses a single bin.  split[nsplit] = the bins that are split, ascending;
+   sub[s * SMG_COUNT_BINS + j] = windows of bin split[s] whose next 12 bits are j (they add up to windows[split[s]]).
+   The bins that are not split and the sub-bins of those that are form one ascending sequence of units; as in
+   smg_count_plan a range takes units while its windows stay within `budget`, which gives the fewest contiguous ranges.
+   Range r holds the canonical k-mers whose leading SMG_COUNT_FINE_BITS bits lie in cuts[r] .. cuts[r + 1] - 1;
+   cuts[0] = 0, cuts[*nranges] = SMG_COUNT_FINE_BINS, and a cut that is no multiple of SMG_COUNT_BINS lies inside a split
+   bin.  cuts has room for cuts_cap values: 2 * (sum of windows) / budget + 3 are enough, and SMG_COUNT_FINE_BINS + 1
+   always are.  A sub-bin above the budget is refused with SMG_ENOMEM: the message is that of smg_count_plan for its bin,
+   then the sub-bin, its twelve leading bases and its windows.  A bin above the budget that is not in `split` is
+   SMG_EINVAL.                                                                                                        */
+int smg_count_plan_fine(const uint64_t *windows, const int32_t *split, int32_t nsplit, const uint64_t *sub, int64_t budget,
+                        int32_t *cuts, int64_t cuts_cap, int32_t *nranges, char *errbuf, size_t errlen);
 
 /* host only: the stripped byte stream of one file, the sequence of every record with line ends removed
    and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).            */

@@ -14,13 +14,14 @@ import numpy as np
 from . import ktab
 
 MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
+FINE_BINS = 1 << 24                       # the ends of a range are values of the leading 24 bits where a bin was split
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
 BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
-           "smg_count_parse", "smg_count_free", "smg_count_version",
+           "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
            "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free"]
 
 
@@ -46,7 +47,7 @@ class Stats(C.Structure):
 
 class Parts(C.Structure):
     _fields_ = [("partitions", C.c_int32), ("max_entries", C.c_int64), ("used", C.c_int32), ("store_bytes", C.c_int64),
-                ("ms_pack", C.c_double), ("ms_plan", C.c_double)]
+                ("ms_pack", C.c_double), ("ms_plan", C.c_double), ("split", C.c_int32)]
 
 
 _lib = None
@@ -81,6 +82,8 @@ def load_library():
     lib.smg_count_device_free.restype = None
     lib.smg_count_plan.argtypes = [vp, C.c_int64, C.c_int32, vp, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
     lib.smg_count_plan.restype = C.c_int
+    lib.smg_count_plan_fine.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
+    lib.smg_count_plan_fine.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_parse.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
@@ -131,7 +134,7 @@ def _run(call, k, t, device, threads, partitions, max_entries):
         lib.smg_count_free(keys)
         lib.smg_count_free(cnt)
     stats = st.asdict()
-    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan)
+    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan, split=parts.split)
     return _table(int(k), int(t), k64, c16), hist, stats
 
 
@@ -140,7 +143,8 @@ def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0)
 
     partitions: 0 lets the library count by key range where one pass is not guaranteed to fit, 1 is one pass,
     2 .. 4096 that many ranges; max_entries (test hook) plans as if one merge held only that many entries.
-    The stats carry `used` (ranges), `store_bytes`, `ms_pack` and `ms_plan` of a partitioned run."""
+    The stats carry `used` (ranges), `store_bytes`, `ms_pack` and `ms_plan` of a partitioned run, and `split`: the bins of
+    the leading 12 bits that held more windows than one merge and were split on their next 12 bits (automatic mode only)."""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
     return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries)
@@ -202,7 +206,7 @@ def _run_device(call, k, t, device, threads, partitions, max_entries):
     if rc != 0:
         raise CountError(rc, err.value.decode(errors="replace"))
     stats = st.asdict()
-    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan)
+    stats.update(used=parts.used, store_bytes=parts.store_bytes, ms_pack=parts.ms_pack, ms_plan=parts.ms_plan, split=parts.split)
     return DeviceTable(k, t, nels.value, words.value, keys.value, cnt.value, device), hist, stats
 
 
@@ -258,6 +262,30 @@ def plan(windows, budget, partitions=0):
     err = C.create_string_buffer(1024)
     rc = lib.smg_count_plan(w.ctypes.data_as(C.c_void_p), int(budget), int(partitions), cuts.ctypes.data_as(C.c_void_p), C.byref(n),
                             err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    return cuts[: n.value + 1].copy()
+
+
+def plan_fine(windows, split, sub, budget):
+    """Host only: the cuts where `plan` refuses a single bin.  split: the bins that are split, ascending; sub[s] = the 4096
+    windows of bin split[s] by its next 12 bits.  -> int32 array of values of the leading 24 bits, range r is
+    cuts[r] .. cuts[r + 1] - 1, cuts[-1] = 2^24; a cut that is no multiple of 4096 lies inside a split bin.  Raises
+    CountError (-3) with bin and sub-bin named when one sub-bin alone is above the budget."""
+    lib = load_library()
+    w = np.ascontiguousarray(windows, dtype=np.uint64)
+    if w.shape != (BINS,):
+        raise ValueError(f"windows must have {BINS} entries")
+    b = np.ascontiguousarray(split, dtype=np.int32).reshape(-1)
+    s = np.ascontiguousarray(sub, dtype=np.uint64)
+    if s.shape != (len(b), BINS):
+        raise ValueError(f"sub must have {BINS} entries for each of the {len(b)} split bins")
+    room = min(2 * (int(w.astype(object).sum()) // max(int(budget), 1)) + 5, FINE_BINS + 1)
+    cuts = np.zeros(room, dtype=np.int32)
+    n = C.c_int32(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_plan_fine(w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), len(b), s.ctypes.data_as(C.c_void_p),
+                                 int(budget), cuts.ctypes.data_as(C.c_void_p), room, C.byref(n), err, len(err))
     if rc != 0:
         raise CountError(rc, err.value.decode(errors="replace"))
     return cuts[: n.value + 1].copy()

@@ -17,7 +17,8 @@
  *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device, in core
  *           -n: write no table (with -e or -H only)
  *
- *  SMUDGEPLOT_GPU picks the device.  No CPU fallback.  A failed run leaves no table, histogram or .smu file behind.
+ *  SMUDGEPLOT_GPU picks the device; SMG_COUNT_MAX_ENTRIES (test hook) is max_entries of smg_count_parts.  No CPU fallback.
+ *  A failed run leaves no table, histogram or .smu file behind.
  *
  ********************************************************************************************/
 
@@ -132,6 +133,7 @@ int main(int argc, char *argv[])
   opts.kmer = kmer; opts.minval = minval; opts.host_threads = nthreads; opts.verbose = verbose;
   memset(&parts, 0, sizeof(parts));
   parts.partitions = nparts;
+  { const char *m = getenv("SMG_COUNT_MAX_ENTRIES"); if (m != NULL && atoll(m) > 0) parts.max_entries = atoll(m); }   /* (test hook) */
   errbuf[0] = 0;
   memset(&hst, 0, sizeof(hst));
   if (ethresh == 0)
@@ -202,8 +204,11 @@ int main(int argc, char *argv[])
     { fprintf(stderr, "  %lld bases, %lld %d-mers, %lld distinct, %lld with count >= %d, %lld batch%s\n", (long long) st.bases,
               (long long) st.windows, kmer, (long long) st.distinct, (long long) st.kept, minval, (long long) st.batches,
               st.batches == 1 ? "" : "es");
-      fprintf(stderr, "  %d key range%s, packed input %.3f GB on the device; ms: pack %.3f  plan %.3f\n", (int) parts.used,
+      fprintf(stderr, "  %d key range%s, packed input %.3f GB on the device; ms: pack %.3f  plan %.3f", (int) parts.used,
               parts.used == 1 ? "" : "s", (double) parts.store_bytes * 1e-9, parts.ms_pack, parts.ms_plan);
+      if (parts.split > 0)
+        fprintf(stderr, "; %d bin%s of six leading bases split on the next six", (int) parts.split, parts.split == 1 ? "" : "s");
+      fprintf(stderr, "\n");
       fprintf(stderr, "  ms: read %.1f  extract %.3f  sort %.3f  reduce+merge %.3f  finish %.3f  wall %.1f\n", st.ms_read, st.ms_extract,
               st.ms_sort, st.ms_reduce, st.ms_finish, st.ms_wall);
       if (ethresh > 0)

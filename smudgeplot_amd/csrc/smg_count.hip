@@ -16,9 +16,12 @@
 //   pack    kc_pack  every batch of bytes -> 3 bits per position (2-bit codes, validity) appended to a resident store
 //   plan    kc_bins  windows per bin of the leading 12 bits of the canonical k-mer; smg_count_plan cuts the 4096 bins
 //           into contiguous ranges whose windows (an upper bound of their distinct k-mers) stay within one sorted
-//           batch or, where a single bin is larger than that, within one merge
+//           batch or, where a single bin is larger than that, within one merge.  Only where a single bin is larger than
+//           one merge: kc_subbins  the windows of that bin by their next 12 bits, and smg_count_plan_fine cuts the
+//           whole bins and the 4096 sub-bins of every such bin, so that a range is an interval of the leading 24 bits
 //   range   kc_extract_packed<W>  the store -> canonical k-mers of ONE range, the key buffer filled across the store
 //           and sorted when full; then batch / merge / finish as above, the kept entries appended to the host table
+//           (kc_extract_fine<W>: the same for a range with an end inside a split bin, its filter on 24 bits)
 // Every instance of a k-mer lies in one range, so ranges in ascending order give the sorted table.
 //
 // The _device entries leave the table where it was made: the kept entries of a range are appended to a table in device
@@ -98,6 +101,16 @@ SMG_DEV unsigned kc_bin(const u64 *s_code, int p, int k)
   return f < r ? f : r;
 }
 
+// The same for the leading SMG_COUNT_FINE_BITS bits, twelve bases: kc_bin24 >> 12 is kc_bin.  k >= 13, so both reads stay
+// inside the window; at k = 13 the first and the last twelve bases overlap in all but one base.
+#define KC_FINE_BASES (SMG_COUNT_FINE_BITS / 2)
+SMG_DEV unsigned kc_bin24(const u64 *s_code, int p, int k)
+{ const unsigned f = (unsigned) (kc_take64(s_code, 2 * p) >> (64 - SMG_COUNT_FINE_BITS));
+  const u64 l = kc_take64(s_code, 2 * (p + k - KC_FINE_BASES)) & (~0ull << (64 - SMG_COUNT_FINE_BITS));
+  const unsigned r = (unsigned) rev2_comp_word(l) & (SMG_COUNT_FINE_BINS - 1u);
+  return f < r ? f : r;
+}
+
 // does a window of k valid bases start at position p of the LDS validity stream?
 SMG_DEV bool kc_window(const u64 *s_val, int p, int k)
 { const u64 x0 = kc_take64(s_val, p);
@@ -108,11 +121,11 @@ SMG_DEV bool kc_window(const u64 *s_val, int p, int k)
 
 // The back half of both extract kernels.  The two LDS bit streams of a tile (2-bit codes, validity; both big endian so
 // that one funnel shift serves both) are in place.  Position p of the tile starts a window when the k validity bits
-// from p on are all set, its global position lies in [p0, p1) and, with FILTER, the bin of its canonical k-mer lies in
-// [lo, hi): the predicate is complete BEFORE the ballot, so a rejected window never builds, reverse-complements or
-// compares its k-mer.  The canonical k-mers go out in position order behind ONE atomic per workgroup (64 ballot
+// from p on are all set, its global position lies in [p0, p1) and, with BITS = 12 or 24 (0: no filter), the leading BITS
+// bits of its canonical k-mer (kc_bin, kc_bin24) lie in [lo, hi): the predicate is complete BEFORE the ballot, so a rejected window never
+// builds, reverse-complements or compares its k-mer.  The canonical k-mers go out in position order behind ONE atomic per workgroup (64 ballot
 // counts, scanned by the first wavefront): 8 W bytes out per accepted window.
-template <int W, bool FILTER> SMG_DEV void
+template <int W, int BITS> SMG_DEV void
 kc_emit(const u64 *s_code, const u64 *s_val, unsigned *s_cnt, unsigned long long *s_base, int64_t tile0, int64_t p0, int64_t p1, int k,
         unsigned lo, unsigned hi, u64 *__restrict__ out, unsigned long long limit, unsigned long long *__restrict__ nout)
 { const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -123,8 +136,8 @@ kc_emit(const u64 *s_code, const u64 *s_val, unsigned *s_cnt, unsigned long long
     { const int p = j * KC_TPB + t;
       bool ok = (tile0 + p >= p0) & (tile0 + p < p1);
       ok &= kc_window(s_val, p, k);
-      if (FILTER)
-        { const unsigned b = kc_bin(s_code, p, k);               // (garbage where ok is false already: ANDed away)
+      if constexpr (BITS != 0)
+        { const unsigned b = BITS == SMG_COUNT_BIN_BITS ? kc_bin(s_code, p, k) : kc_bin24(s_code, p, k);   // (garbage where ok is false: ANDed away)
           ok &= (b >= lo) & (b < hi);
         }
       const unsigned long long bal = __ballot(ok);
@@ -200,7 +213,7 @@ kc_extract(const uint8_t *__restrict__ seq, int64_t n, int k, u64 *__restrict__ 
       v16[c ^ 3] = (uint16_t) valid;
     }
   __syncthreads();
-  kc_emit<W, false>(s_code, s_val, s_cnt, &s_base, tile0, 0, n - k + 1, k, 0u, 0u, out, (unsigned long long) n, nout);
+  kc_emit<W, 0>(s_code, s_val, s_cnt, &s_base, tile0, 0, n - k + 1, k, 0u, 0u, out, (unsigned long long) n, nout);
 }
 
 // ---- the resident store of a partitioned run: the two bit streams of kc_extract's LDS, kept in device memory -----------
@@ -276,6 +289,34 @@ kc_bins(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos,
     if (h[b]) atomicAdd(&bins[b], (unsigned long long) h[b]);
 }
 
+// kc_bins restricted to ONE bin: the windows whose leading 12 bits are `bin`, counted by their next 12 bits.  Launched once
+// per bin that is above one merge, which is rare: the 4096 LDS bins, the grid-stride and the single flush are kc_bins'.
+__global__ void __launch_bounds__(KC_TPB)
+kc_subbins(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos, int k, unsigned bin, unsigned long long *__restrict__ sub)
+{ __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
+  __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
+  __shared__ unsigned h[SMG_COUNT_BINS];
+  const int t = threadIdx.x;
+  for (int b = t; b < SMG_COUNT_BINS; b += KC_TPB) h[b] = 0;
+  const int64_t ntiles = (npos + KC_TILE - 1) / KC_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
+    { __syncthreads();
+      kc_load_tile(code, val, npos, tile * KC_TILE, s_code, s_val);
+      __syncthreads();
+#pragma unroll 4
+      for (int j = 0; j < KC_TILE / KC_TPB; j++)
+        { const int p = j * KC_TPB + t;
+          if (kc_window(s_val, p, k))
+            { const unsigned f = kc_bin24(s_code, p, k);
+              if ((f >> SMG_COUNT_BIN_BITS) == bin) atomicAdd(&h[f & (SMG_COUNT_BINS - 1u)], 1u);
+            }
+        }
+    }
+  __syncthreads();
+  for (int b = t; b < SMG_COUNT_BINS; b += KC_TPB)
+    if (h[b]) atomicAdd(&sub[b], (unsigned long long) h[b]);
+}
+
 // kc_extract with its front half replaced by loads of the two streams from the store: the windows that start in
 // [p0, p1) and whose bin lies in [lo, hi).  The grid starts at the tile that holds p0; 0.375 bytes in per position.
 template <int W> __global__ void __launch_bounds__(KC_TPB)
@@ -288,7 +329,23 @@ kc_extract_packed(const u64 *__restrict__ code, const u64 *__restrict__ val, int
   const int64_t tile0 = (p0 / KC_TILE + blockIdx.x) * KC_TILE;
   kc_load_tile(code, val, npos, tile0, s_code, s_val);
   __syncthreads();
-  kc_emit<W, true>(s_code, s_val, s_cnt, &s_base, tile0, p0, p1, k, lo, hi, out, limit, nout);
+  kc_emit<W, SMG_COUNT_BIN_BITS>(s_code, s_val, s_cnt, &s_base, tile0, p0, p1, k, lo, hi, out, limit, nout);
+}
+
+// The same with lo and hi on the leading 24 bits, for a range with an end inside a split bin.  A kernel of its own and
+// not a run-time switch in kc_extract_packed: a range of whole 12-bit bins keeps the pass it had, which is bound by what
+// it does per position (profiles/count_partitioned.md).
+template <int W> __global__ void __launch_bounds__(KC_TPB)
+kc_extract_fine(const u64 *__restrict__ code, const u64 *__restrict__ val, int64_t npos, int64_t p0, int64_t p1, int k,
+                unsigned lo, unsigned hi, u64 *__restrict__ out, unsigned long long limit, unsigned long long *__restrict__ nout)
+{ __shared__ u64 s_code[KC_CHUNKS / 2 + 2];
+  __shared__ u64 s_val[KC_CHUNKS / 4 + 2];
+  __shared__ unsigned s_cnt[64];
+  __shared__ unsigned long long s_base;
+  const int64_t tile0 = (p0 / KC_TILE + blockIdx.x) * KC_TILE;
+  kc_load_tile(code, val, npos, tile0, s_code, s_val);
+  __syncthreads();
+  kc_emit<W, SMG_COUNT_FINE_BITS>(s_code, s_val, s_cnt, &s_base, tile0, p0, p1, k, lo, hi, out, limit, nout);
 }
 
 template <int W> __global__ void __launch_bounds__(KC_TPB)
@@ -925,6 +982,35 @@ struct Counter
     return 0;
   }
 
+  // Where smg_count_plan refuses a single bin: the windows of every bin above the budget by their next 12 bits (one
+  // kc_subbins pass over the store each), and the flat plan over whole bins and sub-bins.  split: those bins; sub: their
+  // 4096 sub-bin windows each; cuts: values of the leading 24 bits.
+  int plan_split(const std::vector<uint64_t> &bins, int64_t budget, std::vector<int32_t> &split, std::vector<uint64_t> &sub,
+                 std::vector<int32_t> &cuts, int32_t *nranges)
+  { uint64_t total = 0;
+    for (int b = 0; b < SMG_COUNT_BINS; b++)
+      { total += bins[(size_t) b];
+        if (bins[(size_t) b] > (uint64_t) budget) split.push_back(b);
+      }
+    sub.assign(split.size() * SMG_COUNT_BINS, 0);
+    Dev ds;
+    RCHK(alloc(ds, sizeof(uint64_t) * SMG_COUNT_BINS));
+    const int64_t ntiles = (store_n + KC_TILE - 1) / KC_TILE;
+    for (size_t s = 0; s < split.size(); s++)
+      { DCHK(hipMemsetAsync(ds.p, 0, sizeof(uint64_t) * SMG_COUNT_BINS, stream));
+        hipLaunchKernelGGL(kc_subbins, dim3((unsigned) (ntiles < 2048 ? ntiles : 2048)), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(),
+                           store_n, k, (unsigned) split[s], ds.as<unsigned long long>());
+        DCHK(hipGetLastError());
+        DCHK(hipMemcpyAsync(sub.data() + s * SMG_COUNT_BINS, ds.p, sizeof(uint64_t) * SMG_COUNT_BINS, hipMemcpyDeviceToHost, stream));
+        DCHK(hipStreamSynchronize(stream));
+      }
+    uint64_t room = 2 * (total / (uint64_t) budget) + 5;       // (two neighbouring ranges of a greedy plan hold more than the budget)
+    if (room > (uint64_t) SMG_COUNT_FINE_BINS + 1) room = (uint64_t) SMG_COUNT_FINE_BINS + 1;
+    cuts.assign((size_t) room, 0);
+    return smg_count_plan_fine(bins.data(), split.data(), (int32_t) split.size(), sub.data(), budget, cuts.data(), (int64_t) room, nranges,
+                               errbuf, errlen);
+  }
+
   // the ranges of a partitioned run, in ascending order
   int run_ranges()
   { const double t0 = now_ms();
@@ -945,18 +1031,39 @@ struct Counter
     int64_t budget = 0;
     RCHK(merge_budget(&budget));
     // Automatic mode: ranges of one sorted batch each, which never merge (an extra pass over the store costs less than the
-    // merge it saves, profiles/count_partitioned.md); where a single bin is above a batch, the merge limit is the budget.
+    // merge it saves, profiles/count_partitioned.md); where a single bin is above a batch, the merge limit is the budget;
+    // where a single bin is above that as well, it is split on its next 12 bits and the cuts are values of 24 bits.
     int rc = SMG_ENOMEM;
     if (req_parts == 0 && cap < budget) rc = smg_count_plan(bins.data(), cap, 0, cuts.data(), &nranges, errbuf, errlen);
     if (rc == SMG_ENOMEM) rc = smg_count_plan(bins.data(), budget, req_parts, cuts.data(), &nranges, errbuf, errlen);
+    std::vector<int32_t> split;
+    std::vector<uint64_t> sub;
+    if (rc == SMG_ENOMEM) rc = plan_split(bins, budget, split, sub, cuts, &nranges);
+    else
+      for (int r = 0; r <= nranges && rc == 0; r++) cuts[(size_t) r] <<= SMG_COUNT_BIN_BITS;
     RCHK(rc);
     pt.used = nranges;
+    pt.split = (int32_t) split.size();
     pt.ms_plan = now_ms() - t0;
+
+    // windows below a cut: whole bins in front of it, and inside a split bin the sub-bins in front of it
+    std::vector<int64_t> cum(SMG_COUNT_BINS + 1, 0);
+    for (int b = 0; b < SMG_COUNT_BINS; b++) cum[(size_t) b + 1] = cum[(size_t) b] + (int64_t) bins[(size_t) b];
+    auto below = [&](unsigned x) -> int64_t
+      { const unsigned b = x >> SMG_COUNT_BIN_BITS, j = x & (SMG_COUNT_BINS - 1u);
+        int64_t n = cum[b];
+        if (j)
+          { size_t s = 0;
+            while (s + 1 < split.size() && (unsigned) split[s] != b) s++;
+            for (unsigned i = 0; i < j; i++) n += (int64_t) sub[s * SMG_COUNT_BINS + i];
+          }
+        return n;
+      };
 
     for (int r = 0; r < nranges; r++)
       { const unsigned lo = (unsigned) cuts[(size_t) r], hi = (unsigned) cuts[(size_t) r + 1];
-        int64_t left = 0;                                      // windows of the range not yet in the key buffer
-        for (unsigned b = lo; b < hi; b++) left += (int64_t) bins[b];
+        const bool fine = ((lo | hi) & (SMG_COUNT_BINS - 1u)) != 0;      // an end inside a split bin: the 24-bit filter
+        int64_t left = below(hi) - below(lo);                  // windows of the range not yet in the key buffer
         if (left == 0) continue;
         int64_t p = 0, have = 0;                               // next store position, keys in the buffer
         DCHK(hipMemsetAsync(ctr.p, 0, 16, stream));
@@ -967,8 +1074,13 @@ struct Counter
             const unsigned ntiles = (unsigned) ((p1 - 1) / KC_TILE - p / KC_TILE + 1);
             tic();
 #define CALL(WW) hipLaunchKernelGGL(kc_extract_packed<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n, \
-                                    p, p1, k, lo, hi, ka.as<u64>(), (unsigned long long) cap, ctr.as<unsigned long long>())
-            DISPATCH_W(CALL)
+                                    p, p1, k, lo >> SMG_COUNT_BIN_BITS, hi >> SMG_COUNT_BIN_BITS, ka.as<u64>(), (unsigned long long) cap, \
+                                    ctr.as<unsigned long long>())
+#define CALL_FINE(WW) hipLaunchKernelGGL(kc_extract_fine<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n, \
+                                         p, p1, k, lo, hi, ka.as<u64>(), (unsigned long long) cap, ctr.as<unsigned long long>())
+            if (fine) { DISPATCH_W(CALL_FINE) }
+            else { DISPATCH_W(CALL) }
+#undef CALL_FINE
 #undef CALL
             DCHK(hipGetLastError());
             unsigned long long now = 0;
@@ -1012,7 +1124,10 @@ struct Counter
       { *keys = hk; *counts = hc; *nels = hn; *key_words = W;
         hk = nullptr; hc = nullptr;
       }
-    if (parts) { parts->used = pt.used; parts->store_bytes = pt.store_bytes; parts->ms_pack = pt.ms_pack; parts->ms_plan = pt.ms_plan; }
+    if (parts)
+      { parts->used = pt.used; parts->store_bytes = pt.store_bytes; parts->ms_pack = pt.ms_pack; parts->ms_plan = pt.ms_plan;
+        parts->split = pt.split;
+      }
     return 0;
   }
 };
@@ -1286,6 +1401,66 @@ static int plan(const uint64_t *windows, int64_t budget, int32_t partitions, int
 extern "C" int smg_count_plan(const uint64_t *windows, int64_t budget, int32_t partitions, int32_t *cuts, int32_t *nranges, char *errbuf,
                               size_t errlen)
 { GUARD(plan(windows, budget, partitions, cuts, nranges, errbuf, errlen)) }
+
+// The cuts where `plan` refuses a bin (host only): the same greedy rule over one ascending sequence of units, a bin that is
+// not split or one of the 4096 sub-bins of a bin that is.  What is left to refuse is a single sub-bin above the budget.
+static void lead_bases(char *out, unsigned v, int bases)
+{ for (int j = 0; j < bases; j++) out[j] = "acgt"[(v >> (2 * (bases - 1 - j))) & 3];
+  out[bases] = 0;
+}
+
+static int plan_fine(const uint64_t *windows, const int32_t *split, int32_t nsplit, const uint64_t *sub, int64_t budget, int32_t *cuts,
+                     int64_t cuts_cap, int32_t *nranges, char *errbuf, size_t errlen)
+{ if (!windows || !cuts || !nranges || cuts_cap < 2 || nsplit < 0 || nsplit > SMG_COUNT_BINS || (nsplit > 0 && (!split || !sub)))
+    return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  if (budget < 1) return fail(errbuf, errlen, SMG_EINVAL, "budget = %lld is not positive", (long long) budget);
+  for (int s = 0; s < nsplit; s++)
+    { const int b = split[s];
+      if (b < 0 || b >= SMG_COUNT_BINS || (s > 0 && b <= split[s - 1]))
+        return fail(errbuf, errlen, SMG_EINVAL, "split bins must be ascending values 0 .. %d (entry %d is %d)", SMG_COUNT_BINS - 1, s, b);
+      uint64_t sum = 0;
+      for (int j = 0; j < SMG_COUNT_BINS; j++) sum += sub[(size_t) s * SMG_COUNT_BINS + j];
+      if (sum != windows[b])
+        return fail(errbuf, errlen, SMG_EINVAL, "bin %d holds %llu windows, its sub-bins %llu", b, (unsigned long long) windows[b],
+                    (unsigned long long) sum);
+    }
+  int64_t n = 0;
+  uint64_t sum = 0;
+  int s = 0;
+  cuts[0] = 0;
+  for (int b = 0; b < SMG_COUNT_BINS; b++)
+    { const bool is_split = s < nsplit && split[s] == b;
+      if (!is_split && windows[b] > (uint64_t) budget)
+        return fail(errbuf, errlen, SMG_EINVAL, "bin %d holds %llu windows, one merge holds %lld entries, and it is not among the bins to split",
+                    b, (unsigned long long) windows[b], (long long) budget);
+      for (int j = 0; j < (is_split ? SMG_COUNT_BINS : 1); j++)
+        { const uint64_t w = is_split ? sub[(size_t) s * SMG_COUNT_BINS + j] : windows[b];
+          if (w > (uint64_t) budget)
+            { char lead[KC_BIN_BASES + 1], lead2[2 * KC_BIN_BASES + 1];
+              lead_bases(lead, (unsigned) b, KC_BIN_BASES);
+              lead_bases(lead2, ((unsigned) b << SMG_COUNT_BIN_BITS) | (unsigned) j, 2 * KC_BIN_BASES);
+              return fail(errbuf, errlen, SMG_ENOMEM, "bin %d (canonical k-mers that begin with %s) holds %llu windows, one merge holds %lld "
+                          "entries: its sub-bin %d (canonical k-mers that begin with %s) holds %llu windows, and a bin of the leading %d bits "
+                          "cannot be split", b, lead, (unsigned long long) windows[b], (long long) budget, j, lead2, (unsigned long long) w,
+                          SMG_COUNT_FINE_BITS);
+            }
+          if (sum + w > (uint64_t) budget)
+            { if (n + 3 > cuts_cap) return fail(errbuf, errlen, SMG_EINVAL, "more ranges than the %lld cuts there is room for", (long long) cuts_cap);
+              cuts[++n] = (int32_t) (((unsigned) b << SMG_COUNT_BIN_BITS) | (unsigned) j);
+              sum = 0;
+            }
+          sum += w;
+        }
+      if (is_split) s++;
+    }
+  cuts[++n] = SMG_COUNT_FINE_BINS;
+  *nranges = (int32_t) n;
+  return 0;
+}
+
+extern "C" int smg_count_plan_fine(const uint64_t *windows, const int32_t *split, int32_t nsplit, const uint64_t *sub, int64_t budget,
+                                   int32_t *cuts, int64_t cuts_cap, int32_t *nranges, char *errbuf, size_t errlen)
+{ GUARD(plan_fine(windows, split, nsplit, sub, budget, cuts, cuts_cap, nranges, errbuf, errlen)) }
 
 static int parse_path(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { if (!path || !seq || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");

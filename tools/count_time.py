@@ -12,7 +12,8 @@ fails:  gen    reads of 150 bases from both strands of a seeded random genome (0
         files  smg_count_files on reads.fq (page cache warm after the first run), the same way
 Stage times are the library's own (HIP events around extract, sort, reduce+merge, finish; host clock for read and wall).
 Printed: one JSON line per step and a markdown table of medians with the min-max spread.
---partitions runs every timed step once per listed number of key ranges (0 = automatic); --random replaces the reads of a genome
+--partitions runs every timed step once per listed number of key ranges (0 = automatic); --max-entries is the library's test
+hook of that name: with --partitions 0 a value below the windows of the fullest 12-bit bin forces bins to be split; --random replaces the reads of a genome
 by independent random reads (nearly every window distinct); --steps picks the steps (the FASTQ is written only for `files`).
 A binding without the `partitions` argument (an older build, for comparison) is run as it is.
 """
@@ -140,7 +141,8 @@ def summarise(res):
             runs = got["runs"]
             r0 = runs[0]
             med = lambda s: sorted(r.get(s, 0.0) for r in runs)[len(runs) // 2]
-            lines.append(f"\n### {what}, partitions = {parts} ({r0.get('used', 1)} used, store {r0.get('store_bytes', 0) * 1e-9:.3f} GB): "
+            lines.append(f"\n### {what}, partitions = {parts} ({r0.get('used', 1)} used, {r0.get('split', 0)} bins split, "
+                         f"store {r0.get('store_bytes', 0) * 1e-9:.3f} GB): "
                          f"{r0['bases']:.3e} bases, {r0['windows']:.3e} windows, {r0['distinct']:.3e} distinct, "
                          f"{got['entries']:.3e} kept, {r0['batches']} batches, {len(runs)} runs after {res[what]['warmup']} warm-up\n")
             lines.append("| stage | median ms | min | max |")
