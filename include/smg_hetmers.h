@@ -361,6 +361,12 @@ int     smg_engine_stats(smg_engine *e, smg_stats *stats);
 int     smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity,
                            int64_t *nrec, char *errbuf, size_t errlen);
 
+/* where pass 2 and the extract leg of the symmetric path change regime (read-only, needs no device; for tests):
+   out[0] entries per kf_pass2 tile, [1] candidates its queue holds per tile, [2] slots of its cache for cells beyond
+   the LDS plot tile, [3] the sum at which those cells begin, [4] its workgroups at most, [5] records kf_extract
+   stages per workgroup, [6] entries a kf_extract workgroup takes per round, [7] its workgroups at most.             */
+void    smg_engine_pass2_limits(int32_t out[8]);
+
 /* library / build identification, e.g. "smudgeplot_amd 0.1 gfx950" */
 const char *smg_version(void);
 

@@ -45,7 +45,10 @@
 //   test hooks          test_hook(): force, on a table of any size, a code path that the engine otherwise picks from the table's
 //                       size, k or counts (the 30-bit exchanged map, the one-bit map of k < 24, kl_probe_x, the unfiltered chain,
 //                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle;
-//                       SMG_TWO_WAY=1 keeps the two-way request protocol where one-way would be chosen (tests/test_one_way_gpu.py).
+//                       SMG_TWO_WAY=1 keeps the two-way request protocol where one-way would be chosen (tests/test_one_way_gpu.py);
+//                       SMG_P2_GRID=<g> (1 .. P2_GRID) and SMG_EXTRACT_GRID=<g> (1 .. EX_GRID) launch kf_pass2 / kf_extract with at
+//                       most g workgroups, so that a table of 1e5 entries takes a workgroup through several tiles or rounds
+//                       (tests/test_pass2_regimes_gpu.py); the tile sizes they are cut at are read from smg_engine_pass2_limits.
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
 #define WIN_LIM   32          // window blocks up to this many entries are walked linearly
@@ -673,6 +676,7 @@ k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ 
 #define P1_MAXGRID   4096      // upper bound of any pass-1 grid (partial fingerprint sums)
 #define BF_MAXGRID   512       // workgroups of kf_bigfix (1024 threads each: two per CU)
 #define P2_GRID      512       // persistent workgroups of kf_pass2 (2 per CU: 43.7 KB plot tile + 32 KB queue each)
+#define EX_GRID      2048      // workgroups of kf_extract at most
 
 struct smg_engine
 { int          device;
@@ -1868,6 +1872,7 @@ static int fast_pass2(smg_engine *e, int64_t *d_plot, bool with_sum, char *errbu
   if (e->n > 0)
     { int64_t nb = (e->n + P2_TPB - 1) / P2_TPB;
       if (nb > P2_GRID) nb = P2_GRID;
+      { const char *v = test_hook("SMG_P2_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= P2_GRID && atoi(v) < nb) nb = atoi(v); }
 #define CALL(WW) hipLaunchKernelGGL(kf_pass2<WW>, dim3((unsigned) nb), dim3(P2_TPB), 0, e->stream, a, (u64 *) d_plot)
       DISPATCH_W3(e, CALL)
 #undef CALL
@@ -2811,7 +2816,8 @@ static int engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_o
   else if (e->n > 0)
     { FastArgs a = make_fast(e);
       int64_t nb = (e->n + F_TPB - 1) / F_TPB;
-      if (nb > 2048) nb = 2048;
+      if (nb > EX_GRID) nb = EX_GRID;
+      { const char *v = test_hook("SMG_EXTRACT_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= EX_GRID && atoi(v) < nb) nb = atoi(v); }
 #define CALL(WW) hipLaunchKernelGGL(kf_extract<WW>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, d_labels, \
                    (u64 *) d_out, (u64) (d_out ? capacity : 0), d_total)
       DISPATCH_W3(e, CALL)
@@ -2829,6 +2835,11 @@ static int engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_o
 extern "C" int smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity,
                                   int64_t *nrec, char *errbuf, size_t errlen)
 { return engine_extract(e, d_labels, d_out, capacity, nrec, NULL, errbuf, errlen); }
+
+extern "C" void smg_engine_pass2_limits(int32_t out[8])
+{ const int32_t v[8] = { P2_TILE, P2_QCAP, P2_FAR, P2_SMAX, P2_GRID, EX_STAGE, F_TPB, EX_GRID };
+  memcpy(out, v, sizeof(v));
+}
 
 #include "smg_ingest.hpp"
 #include "smg_multi.hpp"

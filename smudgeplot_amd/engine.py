@@ -68,7 +68,7 @@ EXPORTS = [
     "smg_engine_symm_hist", "smg_engine_symm_route", "smg_engine_symm_finish", "smg_engine_table",
     "smg_engine_table_host",
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
-    "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device",
+    "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
 ]
 
 _lib = None
@@ -123,6 +123,8 @@ def load_library():
     lib.smg_engine_condition.argtypes = [vp, i32, i32, i32, C.POINTER(i64), *err]
     lib.smg_engine_close_canonical.argtypes = [vp, C.POINTER(i64), *err]
     lib.smg_engine_merge_tile.argtypes = [i32]
+    lib.smg_engine_pass2_limits.argtypes = [C.POINTER(C.c_int32)]
+    lib.smg_engine_pass2_limits.restype = None
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
@@ -213,6 +215,18 @@ def merge_tile(words: int) -> int:
     return int(load_library().smg_engine_merge_tile(words))
 
 
+PASS2_LIMITS = ("P2_TILE", "P2_QCAP", "P2_FAR", "P2_SMAX", "P2_GRID", "EX_STAGE", "F_TPB", "EX_GRID")
+
+
+def pass2_limits() -> dict:
+    """where kf_pass2 and kf_extract change regime (smg_engine_pass2_limits; no device needed): entries per pass-2 tile, the
+    candidates its queue holds, the slots of its far-cell cache, the sum at which far cells begin, its grid at most; the
+    records a workgroup of the extract kernel stages, the entries it takes per round, its grid at most"""
+    out = (C.c_int32 * 8)()
+    load_library().smg_engine_pass2_limits(out)
+    return dict(zip(PASS2_LIMITS, (int(v) for v in out)))
+
+
 def _table_view(table):
     """`ktab.KTable` -> (TableView, objects that must stay alive while it is used)"""
     kb = (table.k + 3) >> 2
@@ -257,17 +271,23 @@ def hetmers_extract(table, labels: dict, device: int = 0, symcheck: str = "hash"
     n, w = int(nrec.value), int(rw.value)
     arr = np.ctypeslib.as_array(C.cast(recs, C.POINTER(C.c_uint64)), shape=(max(n, 1) * w,))[: n * w].copy().reshape(n, w)
     lib.smg_free(recs)
+    return plot.reshape(PLOT_ROWS, PLOT_COLS), record_lines(arr, table.k, names)
+
+
+def record_lines(arr: np.ndarray, k: int, names: list) -> dict:
+    """extract records (uint64[n, words + 1]: the k-mer to print, then position | alt base << 8 | label << 16) ->
+    {smudge name: list of text lines as the reference prints them}; label l stands for names[l - 1]"""
+    w = arr.shape[1]
     out = {name: [] for name in names}
     dna = "acgt"
-    for row in arr:
-        meta = int(row[w - 1])
+    q = np.arange(k)
+    bases = (arr[:, q >> 5] >> (62 - 2 * (q & 31)).astype(np.uint64)) & np.uint64(3) if len(arr) else np.zeros((0, k), np.uint64)
+    text = np.frombuffer(dna.encode(), dtype=np.uint8)[bases.astype(np.intp)]
+    for row, meta in zip(text, arr[:, w - 1].tolist()):
         pos, alt, label = meta & 0xFF, (meta >> 8) & 3, meta >> 16
-        bases = []
-        for q in range(table.k):
-            bases.append((int(row[q >> 5]) >> (62 - 2 * (q & 31))) & 3)
-        out[names[label - 1]].append("".join(dna[b] for b in bases[:pos]) + f"({dna[bases[pos]]}/{dna[alt]})"
-                                     + "".join(dna[b] for b in bases[pos + 1:]) + "\n")
-    return plot.reshape(PLOT_ROWS, PLOT_COLS), out
+        seq = row.tobytes().decode()
+        out[names[label - 1]].append(f"{seq[:pos]}({seq[pos]}/{dna[alt]}){seq[pos + 1:]}\n")
+    return out
 
 
 def smu_text(plot: np.ndarray) -> str:
@@ -465,6 +485,15 @@ class Engine:
 
     def pass2(self, plot_ptr: int):
         _check(self.lib.smg_engine_pass2(self.h, plot_ptr, self._buf, 512), self._buf)
+
+    def extract(self, labels_ptr: int, out_ptr: int, capacity: int) -> int:
+        """the extract leg after a completed run: labels_ptr = device uint16[PLOT_CELLS], out_ptr = device buffer of
+        `capacity` records of record width (words per k-mer + 1) uint64 each, or 0 with capacity 0 to count only.
+        -> the number of records there are, whatever the capacity; at most `capacity` of them are written"""
+        n = C.c_int64(0)
+        _check(self.lib.smg_engine_extract(self.h, labels_ptr, out_ptr or None, capacity, C.byref(n), self._buf, 512),
+               self._buf)
+        return int(n.value)
 
     def stats(self) -> dict:
         st = Stats()
