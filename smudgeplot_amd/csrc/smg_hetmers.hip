@@ -48,7 +48,10 @@
 //                       SMG_TWO_WAY=1 keeps the two-way request protocol where one-way would be chosen (tests/test_one_way_gpu.py);
 //                       SMG_P2_GRID=<g> (1 .. P2_GRID) and SMG_EXTRACT_GRID=<g> (1 .. EX_GRID) launch kf_pass2 / kf_extract with at
 //                       most g workgroups, so that a table of 1e5 entries takes a workgroup through several tiles or rounds
-//                       (tests/test_pass2_regimes_gpu.py); the tile sizes they are cut at are read from smg_engine_pass2_limits.
+//                       (tests/test_pass2_regimes_gpu.py); the tile sizes they are cut at are read from smg_engine_pass2_limits;
+//                       SMG_P1_GRID=<g> (>= 1) launches pass 1 with at most g workgroups, so that one owner of the request list
+//                       holds several batches of kl_part on a table of 4e5 entries (tests/test_lookup_regimes_gpu.py, with
+//                       smg_engine_lookup_limits and smg_engine_lookup_state).
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
 #define WIN_LIM   32          // window blocks up to this many entries are walked linearly
@@ -736,6 +739,8 @@ struct smg_engine
                            //   owner w fills the chunk slots w, w + nown, w + 2 nown, ..
   u64         *boff;       //   bucket offsets [L_BK + 1] and scatter cursors [L_BK] behind them
   LookupGeo    lg;         //   geometry of the current run (lg.nb = 0: the round-1 chain is used)
+  int          probe_form; //   the probe kernel of the last filter / look-up: 0 none, 1 kl_probe fused, 2 kl_probe_x, 3 kl_probe list
+  unsigned     probe_part; //   ... and the requests per ticket it passed to kl_probe_x (0 otherwise): smg_engine_lookup_state
   bool         far_listed;   // pass 1 left the list of its deferred entries in biglist[0 .. st.nbig): pass 2 finishes the far partners from it
   bool         counted_done; // the counted path (k > 85) has run on a closed table: deg[] holds the wrapped degrees
   bool         lookup_pending; // look-ups of received requests were queued without a host wait (their time is read later)
@@ -1292,7 +1297,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   // sharded run reports the same geometry and takes part in the exchange of the maps)
   e->bm_bits = 0; e->bm2 = 0;
   e->filtered = false; e->presorted = 0;
-  e->lg.nb = 0;
+  e->lg.nb = 0; e->probe_form = 0; e->probe_part = 0;
   if (filter_ok(e) && !emit_all && !e->no_filter && !test_hook("SMG_NO_FILTER"))
     { const int nbits = bm_id_bits(e->kmer, e->bm_cap);
       // the look-up chain of smg_lookup.hpp: one-word k-mers, key-only records, a map of >= 12 id bits
@@ -1359,6 +1364,11 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
     }
   if (grid > P1_MAXGRID) grid = P1_MAXGRID;
   if ((int64_t) grid > ntiles) grid = (unsigned) ntiles;
+  // (tests: fewer workgroups, never more -- and the cached occupancy above stays what the device said.  The chunk slots of an
+  //  owner are strided by the number of owners, grid + BF_MAXGRID, so with ONE workgroup the list below holds 513 times the chunks
+  //  of that owner plus the usual slack: by this arithmetic ~5 GB for a table of 4e5 one-word entries, ~11 GB for 1e6 two-word ones,
+  //  and the filtered list takes the same again.  Sized, not measured; a hook for small tables on a device with room to spare.)
+  { const char *v = test_hook("SMG_P1_GRID"); if (v && atoi(v) >= 1 && (unsigned) atoi(v) < grid) grid = (unsigned) atoi(v); }
   // a chunk is closed as soon as the next tile's batch (<= one tile of records) does not fit, so
   // chunks fill to >= 75 %: size the list for that, and never below what is already allocated
   // (an engine that is reused on the same table must not redo pass 1 every time)
@@ -1685,6 +1695,7 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
         else     { if (e->rw == 1) PROBEX(false, 1); else PROBEX(false, 2); }
 #undef PROBEX
         HIPCHK(hipGetLastError());
+        e->probe_form = 2; e->probe_part = part & 0x7FFFFFFFu;
         return SMG_OK;
       }
   }
@@ -1697,6 +1708,7 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
 #undef PROBE_RW
 #undef PROBE
   HIPCHK(hipGetLastError());
+  e->probe_form = list ? 3 : 1; e->probe_part = 0;
   return SMG_OK;
 }
 
@@ -2839,6 +2851,22 @@ extern "C" int smg_engine_extract(smg_engine *e, const uint16_t *d_labels, uint6
 extern "C" void smg_engine_pass2_limits(int32_t out[8])
 { const int32_t v[8] = { P2_TILE, P2_QCAP, P2_FAR, P2_SMAX, P2_GRID, EX_STAGE, F_TPB, EX_GRID };
   memcpy(out, v, sizeof(v));
+}
+
+extern "C" void smg_engine_lookup_limits(int32_t out[12])
+{ const int32_t v[12] = { F_CH, PT_LDSREC, PT_LDSREC / 2, PB_WAVES * 64 * PB_PER, PB_WQ, PX_PART, PX_TPB / 64 * 64 * PX_PER,
+                          L_NB_MAX, L_SLICE_LG, BF_MAXGRID, LW_SL, LW_UNR };
+  memcpy(out, v, sizeof(v));
+}
+
+extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])
+{ if (!e || !out) return SMG_EINVAL;
+  const bool chain = e->prepared && e->fast && e->lg.nb > 0;
+  out[0] = e->prepared ? e->bm_bits : 0; out[1] = chain ? e->lg.nb : 0; out[2] = e->bm2; out[3] = e->one_way; out[4] = e->rw;
+  out[5] = chain ? e->p1grid : 0; out[6] = chain ? e->nown : 0;
+  out[7] = chain ? (int64_t) e->h_ctrl->fast.n_chunks : 0;       // (pass 1's counter: the filter counts in nf_chunks)
+  out[8] = e->probe_form; out[9] = e->probe_part;
+  return SMG_OK;
 }
 
 #include "smg_ingest.hpp"

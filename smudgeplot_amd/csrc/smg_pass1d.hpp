@@ -748,8 +748,11 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
   pf.valid = false;
   int par = 0;
   const unsigned cls = blockIdx.x % D_NCLS;
-  unsigned ticket = (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk0);      // ticket r stands for tile grid + D_NCLS r + cls
-  int64_t tnext = (int64_t) gridDim.x + (int64_t) ticket * D_NCLS + cls, tnext2 = tnext + D_NCLS;
+  // (a launch of fewer workgroups than classes has that many classes: with D_NCLS of them the tiles of the classes nobody is
+  //  in were never drawn.  The engine's own grids are >= D_NCLS or = ntiles; the test hook SMG_P1_GRID goes down to 1.)
+  const unsigned ncls = gridDim.x < D_NCLS ? gridDim.x : D_NCLS;
+  unsigned ticket = (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk0);      // ticket r stands for tile grid + ncls r + cls
+  int64_t tnext = (int64_t) gridDim.x + (int64_t) ticket * ncls + cls, tnext2 = tnext + ncls;
   ticket += 2u;                                 // thread 0: the ticket on its way (the first one is known)
   for (int64_t tile = blockIdx.x; tile < A.ntiles; par ^= 1)
     { const int64_t g0 = tile * D_OWN - D_LEAD;
@@ -858,7 +861,7 @@ kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)
       lds_barrier();
       if (t == 0) s_tn[par] = 0;
       tile = tnext; tnext = tnext2;
-      tnext2 = (int64_t) gridDim.x + (int64_t) (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk[par]) * D_NCLS + cls;
+      tnext2 = (int64_t) gridDim.x + (int64_t) (unsigned) __builtin_amdgcn_readfirstlane((int) s_tk[par]) * ncls + cls;
     }
 
   if (D_BM && RW == W && ((VAR & 2) || A.hbits()))                   // this workgroup's row of the request histogram (kl_tot / kl_woff)

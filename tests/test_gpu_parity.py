@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import brute
+import lookup_oracle
 from conftest import HETMERS_BIN, ORACLE_BIN, golden_names, load_golden, make_table
 from smudgeplot_amd import engine, ktab, synth
 
@@ -72,42 +73,8 @@ def test_big_window_blocks():
         assert np.array_equal(plot, want), mode
 
 
-def _long_block_families(k, seed):
-    """families of 120 .. 2600 k-mers that share their first k/2 + 1 bases (one window block each, in buckets of their
-    own): dense ones (a k-mer, all its single mutants behind the shared part, double mutants) and sparse ones (random
-    tails, a few hundred of them with exactly one partner -- often far away in the block), some counts beyond the
-    sum limit, a random background"""
-    rng = np.random.default_rng(seed)
-    share = k // 2 + 1
-    rows = []
-    for f, size in enumerate([120, 400, 1000, 1800, 2600, 150, 700, 1500, 2000, 2300]):
-        base = rng.integers(0, 4, k, dtype=np.uint8)
-        base[0], base[1] = f & 3, f >> 2                       # (a leading 2-mer of its own: never two families in a bucket)
-        fam = np.tile(base, (size, 1))
-        if f < 5:                                              # dense
-            j = 1
-            for p in range(share, k):
-                for d in (1, 2, 3):
-                    if j < size:
-                        fam[j, p] = (base[p] + d) & 3; j += 1
-            while j < size:
-                p, q = rng.integers(share, k, 2)
-                fam[j, p] = (base[p] + rng.integers(1, 4)) & 3
-                fam[j, q] = (base[q] + rng.integers(1, 4)) & 3
-                j += 1
-        else:                                                  # sparse
-            fam[:, share:] = rng.integers(0, 4, (size, k - share), dtype=np.uint8)
-            for j in range(0, min(size - 1, 600), 2):
-                fam[j + 1] = fam[j]
-                p = rng.integers(share, k)
-                fam[j + 1, p] = (fam[j, p] + rng.integers(1, 4)) & 3
-        rows.append(fam)
-    rows.append(rng.integers(0, 4, (3000, k), dtype=np.uint8))
-    packed = ktab.pack_bases(np.concatenate(rows))
-    cnt = rng.integers(5, 60, size=len(packed)).astype(np.uint16)
-    cnt[rng.random(len(cnt)) < 0.04] = 700                     # (pairs of two such counts exceed the sum limit)
-    packed, cnt = ktab.sort_unique_packed(packed, cnt)
-    return ktab.symmetrize(packed, cnt, k)
+# (the generator lives in tests/lookup_oracle.py: tests/test_lookup_regimes_gpu.py sends the same families through the look-up chain)
+_long_block_families = lookup_oracle.long_block_families
 
 
 @pytest.mark.parametrize("k", [22, 24, 31, 32, 40, 51, 64])
