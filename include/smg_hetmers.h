@@ -382,6 +382,12 @@ void    smg_engine_lookup_limits(int32_t out[12]);
    2 kl_probe_x, 3 kl_probe writing the survivor list, [9] requests per ticket passed to kl_probe_x (else 0).       */
 int     smg_engine_lookup_state(smg_engine *e, int64_t out[10]);
 
+/* which pass-1 kernel the last pass 1 of this engine launched (plain host fields; for tests): out[0] the form of kf_pass1_d
+   (its template argument VAR: 1 general, 2 hot -- one-way where k is odd --, 6 hot and two-way although k is odd; 0: the
+   kernels of k > 64, or no pass 1 yet), [1] words per k-mer, [2] words per request record, [3] always 0 (reserved: a launch
+   of inner tiles only).                                                                                                  */
+int     smg_engine_pass1_form(smg_engine *e, int32_t out[4]);
+
 /* library / build identification, e.g. "smudgeplot_amd 0.1 gfx950" */
 const char *smg_version(void);
 

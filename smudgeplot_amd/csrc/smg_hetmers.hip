@@ -681,6 +681,8 @@ k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ 
 #define P2_GRID      512       // persistent workgroups of kf_pass2 (2 per CU: 43.7 KB plot tile + 32 KB queue each)
 #define EX_GRID      2048      // workgroups of kf_extract at most
 
+typedef void (*P1Kernel)(P1Hot, const P1Cold *);          // an instantiation of kf_pass1_d (p1_kernel)
+
 struct smg_engine
 { int          device;
   hipStream_t  stream;
@@ -759,7 +761,9 @@ struct smg_engine
   Dir          dir;
   bool         prepared;      // pass 1 of the current table has run
   bool         fast;          // fast path in use
-  unsigned     p1_grid[2][3]; // resident workgroups of kf_pass1_d<W, RW, ..> by [W-1][RW-1] (0 = not asked yet)
+  P1Kernel     p1_asked;      // the instantiation of kf_pass1_d whose resident workgroups were asked for last (NULL: none yet) ..
+  unsigned     p1_resident;   //   .. and the answer
+  int          p1_var, p1_w, p1_rw;   // the last pass 1: VAR of kf_pass1_d (0: the wide or the counted kernels), W, RW (smg_engine_pass1_form)
   unsigned     n_chunks;
   u64          fp[4];
   smg_stats    st;
@@ -1264,6 +1268,28 @@ static FastArgs make_fast(smg_engine *e)
   return a;
 }
 
+// The instantiation of kf_pass1_d for a table (var: VAR of smg_pass1d.hpp; kf: 17 <= k <= 32).  The one place that names them: the
+// occupancy query and the launch of fast_pass1 both go through it, so what is asked about is what is launched.  20 instantiations,
+// none that no caller can select: the hot forms exist for key-only records, the two-way hot form of odd k (VAR = 6) where the
+// two-bit map it needs does (k >= 24: one-word k-mers with KF, two-word k-mers).  NULL: no such instantiation.
+static P1Kernel p1_kernel(int W, int rw, bool odd, bool kf, int var)
+{
+#define P1_K(W_, RW_, ODD_, KF_) do { \
+    if constexpr ((RW_) == (W_)) \
+      { if constexpr ((ODD_) && ((W_) == 2 || (KF_))) if (var == 6) return kf_pass1_d<W_, W_, ODD_, KF_, 6>; \
+        if (var == 2) return kf_pass1_d<W_, W_, ODD_, KF_, 2>; \
+      } \
+    if (var == 1) return kf_pass1_d<W_, RW_, ODD_, KF_, 1>; \
+    return NULL; } while (0)
+#define P1_K2(RW_, ODD_) { if (kf) P1_K(1, RW_, ODD_, true); else P1_K(1, RW_, ODD_, false); }
+  if (W == 2 && rw == 2) { if (odd) P1_K(2, 2, true, false); else P1_K(2, 2, false, false); }
+  else if (W == 2)  { if (odd) P1_K(2, 3, true, false); else P1_K(2, 3, false, false); }
+  else if (rw == 1) { if (odd) P1_K2(1, true) else P1_K2(1, false) }
+  else              { if (odd) P1_K2(2, true) else P1_K2(2, false) }
+#undef P1_K2
+#undef P1_K
+}
+
 static int bm_id_bits(int kmer, int cap);
 // (k = 1 has no prefix bases to name a block by)
 static bool filter_ok(const smg_engine *e)
@@ -1288,6 +1314,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
   e->fast = true; e->counted_done = false; e->general_done = false;
+  e->p1_var = 0; e->p1_w = e->W; e->p1_rw = e->rw;
   if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
   const int64_t pbytes = ((e->n + 15) & ~15ll) + 32;
   e->use_sig = e->W <= 2;
@@ -1344,23 +1371,27 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   }
   const bool odd = (e->kmer & 1) != 0;
   unsigned grid = P1_GRID;
+  P1Kernel p1k = NULL;
   if (narrow)
-    { // persistent workgroups: exactly what is resident (a static tile stride must not have stragglers)
-      unsigned &cached = e->p1_grid[e->W - 1][e->rw - 1];
-      if (!cached)
+    { // The form of kf_pass1_d (VAR of smg_pass1d.hpp).  The hot form: key-only records through the look-up chain with the
+      // two-bit map and the fingerprint, on a table that came with its index (no directory, no signatures); where k is odd it has
+      // the protocol compiled in, one-way (2) or two-way (6: the phase API, the hook SMG_TWO_WAY).  Everything else: the general form.
+      const bool hot_form = e->rw == e->W && e->dir_preset && !(e->W <= 2 && e->use_sig) && e->bm2 && e->bm_bits && want_fp && !emit_all && e->lg.nb;
+      const int var = !hot_form ? 1 : (odd && !e->one_way) ? 6 : 2;
+      p1k = p1_kernel(e->W, e->rw, odd, gr.pshift < 32 && gr.kshift < 32, var);
+      if (!p1k) return fail(errbuf, errlen, SMG_EINVAL, "pass 1: no kernel for this table%s");
+      e->p1_var = var;
+      // persistent workgroups: exactly what is resident (a static tile stride must not have stragglers)
+      if (e->p1_asked != p1k)
         { int nb = 0, cus = 0;
-          hipError_t he;
-          // (the ODD / KF variants of one (W, RW) class use the same registers and LDS: ask for one of them)
-          if (e->W == 1 && e->rw == 1) he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf_pass1_d<1, 1, true, true>, D_TPB, 0);
-          else if (e->W == 1)          he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf_pass1_d<1, 2, true, true>, D_TPB, 0);
-          else if (e->rw == 2)         he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf_pass1_d<2, 2, true, false>, D_TPB, 0);
-          else                         he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kf_pass1_d<2, 3, true, false>, D_TPB, 0);
+          const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, p1k, D_TPB, 0);
           if (he != hipSuccess || nb < 1) nb = 3;
           if (nb > 8) nb = 8;
           if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus < 1) cus = 256;
-          cached = (unsigned) (nb * cus);
+          e->p1_resident = (unsigned) (nb * cus);
+          e->p1_asked = p1k;
         }
-      grid = cached;
+      grid = e->p1_resident;
     }
   if (grid > P1_MAXGRID) grid = P1_MAXGRID;
   if ((int64_t) grid > ntiles) grid = (unsigned) ntiles;
@@ -1424,20 +1455,10 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
           e->h_p1cold->tick = e->p1tick;
           HIPCHK(hipMemcpyAsync(e->p1cold, e->h_p1cold, sizeof(P1Cold), hipMemcpyHostToDevice, e->stream));
-#define LAUNCH_R(W_, RW_, ODD_, KF_) do { bool hot_form = false; \
-          if constexpr ((RW_) == (W_))            /* (the hot form exists for key-only records: no dead instantiations) */ \
-            if (hot.bstart == NULL && hot.sig == NULL && e->bm2 && hot.bmap != NULL && want_fp && !emit_all && e->lg.nb) \
-              { hot_form = true; \
-                hipLaunchKernelGGL((kf_pass1_d<W_, W_, ODD_, KF_, 2>), dim3(grid), dim3(D_TPB), 0, e->stream, hot, (const P1Cold *) e->p1cold); } \
-          if (!hot_form) hipLaunchKernelGGL((kf_pass1_d<W_, RW_, ODD_, KF_, 1>), dim3(grid), dim3(D_TPB), 0, e->stream, hot, (const P1Cold *) e->p1cold); } while (0)
-#define LAUNCH_R2(RW_, ODD_) { if (kf) LAUNCH_R(1, RW_, ODD_, true); else LAUNCH_R(1, RW_, ODD_, false); }
-          const bool kf = gr.pshift < 32 && gr.kshift < 32;          // 17 <= k <= 32
-          if (e->W == 2 && e->rw == 2) { if (odd) LAUNCH_R(2, 2, true, false); else LAUNCH_R(2, 2, false, false); }
-          else if (e->W == 2)  { if (odd) LAUNCH_R(2, 3, true, false); else LAUNCH_R(2, 3, false, false); }
-          else if (e->rw == 1) { if (odd) LAUNCH_R2(1, true) else LAUNCH_R2(1, false) }
-          else                 { if (odd) LAUNCH_R2(2, true) else LAUNCH_R2(2, false) }
-#undef LAUNCH_R2
-#undef LAUNCH_R
+          // (the hot forms take these for granted: what chose them above is what the kernel argument says)
+          if (e->p1_var != 1 && (hot.bstart != NULL || hot.sig != NULL || hot.bmap == NULL))
+            return fail(errbuf, errlen, SMG_EINVAL, "pass 1: the hot form without its preconditions%s");
+          hipLaunchKernelGGL(p1k, dim3(grid), dim3(D_TPB), 0, e->stream, hot, (const P1Cold *) e->p1cold);
         }
       else
         {
@@ -2866,6 +2887,14 @@ extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])
   out[5] = chain ? e->p1grid : 0; out[6] = chain ? e->nown : 0;
   out[7] = chain ? (int64_t) e->h_ctrl->fast.n_chunks : 0;       // (pass 1's counter: the filter counts in nf_chunks)
   out[8] = e->probe_form; out[9] = e->probe_part;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_pass1_form(smg_engine *e, int32_t out[4])
+{ if (!e || !out) return SMG_EINVAL;
+  const bool ran = e->prepared && e->fast;
+  out[0] = ran ? e->p1_var : 0; out[1] = ran ? e->p1_w : 0; out[2] = ran ? e->p1_rw : 0;
+  out[3] = 0;                                // (no launch is an INNER-only grid)
   return SMG_OK;
 }
 

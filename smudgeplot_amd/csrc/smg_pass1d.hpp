@@ -190,7 +190,8 @@ struct P1Hot                              // kernel argument: what every tile to
   SMG_DEV bool want_fp() const { return (shifts >> 19 & 1u) != 0; }
   SMG_DEV int hbits() const { return (int) ((shifts >> 20) & 15u); }    // request histogram on the leading hbits bits (0: none)
   SMG_DEV bool two() const { return (shifts >> 24 & 1u) != 0; }         // two-bit block map (BM2_* in smg_fast.hpp)
-  SMG_DEV bool ow() const { return (shifts >> 25 & 1u) != 0; }          // one-way requests (smg_fast.hpp; odd k, key-only records)
+  SMG_DEV bool ow() const { return (shifts >> 25 & 1u) != 0; }          // one-way requests (smg_fast.hpp; odd k, key-only records):
+                                                                        //   read by the general form only, the hot forms have it compiled in
 };
 
 struct P1Cold                             // in device memory: what only a flush touches (kept out of the register file)
@@ -290,6 +291,9 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 { typedef typename DWord<W>::type WT;
   constexpr bool D_BM = (W == 1 && RW == 1) || (W == 2 && RW != 1);     // variants that feed the request filter
   constexpr bool DIR = (VAR & 1) != 0;       // this launch writes a directory and / or signatures
+  constexpr bool HOT = (VAR & 2) != 0;       // the hot form: nothing below asks the kernel argument which protocol runs
+  constexpr bool OW_HOT = HOT && ODD && RW == W && !(VAR & 4);           // ... one-way, compiled in
+  static_assert(!(VAR & 4) || (HOT && ODD && RW == W), "VAR bit 2: the hot form of odd k that stays two-way");
   const GeoR &G = A.G;
   const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);       // the wave number is uniform: keep it scalar
   const int slot0 = (wv * D_WL + lane) * 4;
@@ -478,9 +482,13 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
   // word 0 of the tile's LDS bit map = the map word of the tile's first owned entry (a uniform, scalar load)
   // (inner tiles: loaded one tile ahead with the entries -- as a load of its own it was waited for on the spot)
   // one-way requests: which entries are the lower members of their classes (the high bit of the middle base is clear)
-  const bool ow = ODD && RW == W && A.ow();
+  bool ow = OW_HOT;                         // (the hot forms: a constant, every `ow ? :` below folds)
+  if constexpr (!HOT) ow = ODD && RW == W && A.ow();
   const unsigned lowbit = 1u << (((W == 1 ? 32 : 64) - G.k) & 31);
-  u64 lowM[4] = { 0, 0, 0, 0 };
+  u64 lowM[4] = { 0, 0, 0, 0 };             // (general form)
+  // (one-way hot form: the `lower` mask of an entry lives for that entry's turn in the map section only, where senders and markers
+  //  are told apart -- four of them kept next to uniqM and hiM until the requests are chosen were 7 of the form's 22 spilled SGPRs)
+  u64 sendM[4] = { 0, 0, 0, 0 };
   const uint32_t bmbase = D_BM ? (((INNER ? pf_anchor : (uint32_t) (A.keys[(g0 + D_LEAD) * W] >> 32)) >> bmsh) & ~31u) : 0u;
   if (D_BM && A.bmap)
     { // leading word of the thread's own entries, back from the staged copy (cheaper than four registers kept alive
@@ -496,18 +504,26 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 #pragma unroll
           for (int e = 0; e < 4; e++) kw[e] = S.ent[(slot0 + e) * W];
         }
-      if (ow)
+      if (!HOT && ow)
         {
 #pragma unroll
           for (int e = 0; e < 4; e++) lowM[e] = __ballot(((W == 1 ? (unsigned) (kw[e] >> 32) : (unsigned) kw[e]) & lowbit) == 0u);
         }
-      if ((VAR & 2) || A.two())
+      if (HOT || A.two())
         { u64 *bm64 = reinterpret_cast<u64 *>(S.bm);
           u64 *gm64 = reinterpret_cast<u64 *>(A.bmap);
 #pragma unroll
           for (int e = 0; e < 4; e++)
             { // (one-way: the upper entries with A = 1 or H > 0 mark, each its planes)
-              u64 cm = (ow ? (uniqM[e] | hiM[e]) & ~lowM[e] : uniqM[e]) & ownM;
+              u64 cm;
+              if constexpr (OW_HOT)
+                { // this entry's lower / upper members with a pair: the former send below, the latter mark here
+                  const u64 low = __ballot(((W == 1 ? (unsigned) (kw[e] >> 32) : (unsigned) kw[e]) & lowbit) == 0u);
+                  const u64 anyM = (uniqM[e] | hiM[e]) & ownM;
+                  sendM[e] = anyM & low;
+                  cm = anyM & ~low;
+                }
+              else cm = (ow ? (uniqM[e] | hiM[e]) & ~lowM[e] : uniqM[e]) & ownM;
               if (!INNER) cm &= V[e];
               if (cm)
                 { const uint32_t id = (uint32_t) (kw[e] >> 32) >> bmsh;
@@ -548,9 +564,11 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
   // hash proof: rc(x) of every owned entry that owns a pair at p > k-1-p; exact proof: of every owned entry, with
   // that flag.  (A deferred entry that turns out to own more pairs than the register scan saw sends again from
   // kf_bigfix: the flag of a request is only ever ORed into its target.)
-  const u64 all = (!(VAR & 2) && A.emit_all()) ? ~0ull : 0ull;       // (VAR & 2: the hash proof -- owners of a hi-side pair only)
+  u64 all = 0ull;                            // (the hot forms: the hash proof -- no entry sends for the proof's sake)
+  if constexpr (!HOT) all = A.emit_all() ? ~0ull : 0ull;
   // one-way: the LOWER entries with a pair send, each with the flag "owns a pair at p > k-1-p" in bit 0 of the record's last word
-  if (ow && !(D_BM && A.bmap))               // (no map in this launch: the masks have not been made above)
+  // (no map in this launch: the masks have not been made above.  The hot forms are launched with a map, always)
+  if (!HOT && ow && !(D_BM && A.bmap))
     {
 #pragma unroll
       for (int e = 0; e < 4; e++)
@@ -559,14 +577,21 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
         }
     }
   const u64 owS = ow ? ~0ull : 0ull;
-  u64 E0 = ((hiM[0] | all | (uniqM[0] & owS)) & (lowM[0] | ~owS)) & ownM, E1 = ((hiM[1] | all | (uniqM[1] & owS)) & (lowM[1] | ~owS)) & ownM,
-      E2 = ((hiM[2] | all | (uniqM[2] & owS)) & (lowM[2] | ~owS)) & ownM, E3 = ((hiM[3] | all | (uniqM[3] & owS)) & (lowM[3] | ~owS)) & ownM;
+  u64 E0, E1, E2, E3;
+  if constexpr (OW_HOT)                      // the lower owners of any pair
+    { E0 = sendM[0]; E1 = sendM[1]; E2 = sendM[2]; E3 = sendM[3]; }
+  else if constexpr (HOT)                    // two-way: the owners of a hi-side pair
+    { E0 = hiM[0] & ownM; E1 = hiM[1] & ownM; E2 = hiM[2] & ownM; E3 = hiM[3] & ownM; }
+  else                                       // the general form: either protocol, or every entry (the exact proof)
+    { E0 = ((hiM[0] | all | (uniqM[0] & owS)) & (lowM[0] | ~owS)) & ownM; E1 = ((hiM[1] | all | (uniqM[1] & owS)) & (lowM[1] | ~owS)) & ownM;
+      E2 = ((hiM[2] | all | (uniqM[2] & owS)) & (lowM[2] | ~owS)) & ownM; E3 = ((hiM[3] | all | (uniqM[3] & owS)) & (lowM[3] | ~owS)) & ownM;
+    }
   if (!INNER) { E0 &= V[0]; E1 &= V[1]; E2 &= V[2]; E3 &= V[3]; }
   const unsigned cnt_w = (unsigned) (__popcll(E0) + __popcll(E1) + __popcll(E2) + __popcll(E3));
   unsigned base = 0;
   if (cnt_w)
     base = d_wave_add(S.s_qn, cnt_w, lane);
-  const bool fp = (VAR & 2) || A.want_fp();
+  const bool fp = HOT || A.want_fp();
   // Unrolled, the four entries kept apart by scheduling fences (D_SCHED_FENCE).  The rolled loop -- the masks rotating
   // through one register pair, a counter, two branches per entry -- cost 0.7 ms more: scalar instructions and branches are
   // not free next to a busy vector unit (tools/issue_mix.hip).
@@ -613,8 +638,14 @@ d_tile(const P1Hot &A, const DShared &S, int64_t g0, int64_t g0_next, int t, u64
 #pragma unroll
               for (int w = 0; w < W - 1; w++) S.sq[q * RW + w] = rc.w[w];
               // (bit 0 of the last word is a pad bit of the k-mer: the flag of a one-way record is added in, no carry)
-              const unsigned lo32 = (unsigned) rc.w[W - 1] + (d_lane(hiM[e] & owS) ? 1u : 0u);
-              S.sq[q * RW + W - 1] = (rc.w[W - 1] & 0xFFFFFFFF00000000ull) | (u64) lo32;
+              if constexpr (HOT && !OW_HOT) S.sq[q * RW + W - 1] = rc.w[W - 1];       // (two-way: no flag)
+              else
+                { // (the flag from the entry's code byte instead -- the packed codes are live anyway, the four hiM masks then end
+                  //  with the map section: 10 spilled SGPRs instead of 15 -- costs three vector instructions per sending entry
+                  //  and was 0.10 ms slower, profiles/one_way_hot_form.md)
+                  const unsigned lo32 = (unsigned) rc.w[W - 1] + (d_lane(OW_HOT ? hiM[e] : hiM[e] & owS) ? 1u : 0u);
+                  S.sq[q * RW + W - 1] = (rc.w[W - 1] & 0xFFFFFFFF00000000ull) | (u64) lo32;
+                }
               if (RW > W) S.sq[q * RW + W] = (u64) c | (d_lane(hiM[e]) ? 1ull << 16 : 0ull);
             }
           base += (unsigned) __popcll(E0);
@@ -702,6 +733,11 @@ d_detect(const P1Hot &A, const u64 *ent, const uint16_t *lcn, int64_t g0, int sa
 // the fingerprint, requests from the owners of a hi-side pair only, the per-bucket request histogram: all of it known at compile
 // time, none of those tests in the tile and none of their arguments in registers (33 -> 15 spilled SGPRs, 52 -> ~20 spill moves
 // per thread and tile: -0.27 ms on the diploid table for the directory / signature half alone).  VAR = 1 is the general form.
+// The request protocol of odd k (smg_fast.hpp) is compiled into the hot form as well: VAR = 2 sends ONE-WAY where k is odd and
+// the record is the key alone (what smg_engine_run launches), bit 2 -- VAR = 6 -- is "the hot form, two-way although k is odd"
+// (the phase API with a 32-bit two-bit map, the test hook SMG_TWO_WAY=1).  Even k has no one-way rule: VAR = 2 is its only hot form.
+// As a run-time switch in the hot form the choice cost 14 spilled SGPRs and 0.7 ms (profiles/one_way_hot_form.md); the general
+// form keeps the switch (P1Hot::ow).
 template <int W, int RW, bool ODD, bool KF, int VAR = 1> __global__ void __launch_bounds__(D_TPB)
 __attribute__((amdgpu_waves_per_eu(D_WAVES(W, RW), D_WAVES(W, RW))))
 kf_pass1_d(P1Hot A, const P1Cold *__restrict__ cold)

@@ -69,7 +69,7 @@ EXPORTS = [
     "smg_engine_table_host",
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
-    "smg_engine_lookup_limits", "smg_engine_lookup_state",
+    "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form",
 ]
 
 _lib = None
@@ -129,6 +129,8 @@ def load_library():
     lib.smg_engine_lookup_limits.argtypes = [C.POINTER(C.c_int32)]
     lib.smg_engine_lookup_limits.restype = None
     lib.smg_engine_lookup_state.argtypes = [vp, C.POINTER(i64)]
+    if hasattr(lib, "smg_engine_pass1_form"):          # (SMG_LIB / tools/ab_libs.py load the libraries of earlier commits too)
+        lib.smg_engine_pass1_form.argtypes = [vp, C.POINTER(C.c_int32)]
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
@@ -525,6 +527,18 @@ class Engine:
         if rc != 0:
             raise EngineError(rc, "lookup_state")
         return dict(zip(self.LOOKUP_STATE, (int(v) for v in out)))
+
+    PASS1_FORM = ("var", "w", "rw", "inner_only")
+
+    def pass1_form(self) -> dict:
+        """the kernel of this engine's last pass 1 (smg_engine_pass1_form): the form of kf_pass1_d (1 general, 2 hot -- one-way
+        where k is odd --, 6 hot and two-way although k is odd; 0: none, or the kernels of k > 64), words per k-mer, words per
+        request record, 0 (reserved)"""
+        out = (C.c_int32 * 4)()
+        rc = self.lib.smg_engine_pass1_form(self.h, out)
+        if rc != 0:
+            raise EngineError(rc, "pass1_form")
+        return dict(zip(self.PASS1_FORM, (int(v) for v in out)))
 
     def stats(self) -> dict:
         st = Stats()
