@@ -1,0 +1,427 @@
+// smg_condition.hpp -- table conditioning of the hetmers engine on the device: trim and symmetrise a bound table, close a
+// canonical one by merge, symmetrise a table that is cut into shards, and hand the table out.  Included by
+// smg_hetmers.hip behind route_records; no state of its own.
+
+#pragma once
+
+// ---- table conditioning on device ----------------------------------------
+// The reference shells out to FastK's Logex / Symmex (PloidyPlot.c:1381-1414), which are neither vendored
+// nor pinned.  Restated semantics:
+//   trim        : keep the entries with count >= ethresh                    (Logex 'A[e-]')
+//   symmetrise  : add rc(x) with the count of x for every entry x, sort, keep one copy of a k-mer that
+//                 occurs twice (a self-complementary k-mer, or -- only on input that is neither canonical
+//                 nor symmetric -- a k-mer whose complement was already present: the original entry wins)
+// The sort, the scans and the buffers are those of the k-mer counter (smg_keysort.hpp).
+
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_append_rc(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k,
+             u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  const Key<W> r = revcomp<W>(x, k);
+#pragma unroll
+  for (int w = 0; w < W; w++) { okeys[i * W + w] = x.w[w]; okeys[(n + i) * W + w] = r.w[w]; }
+  ocnt[i] = cnt[i]; ocnt[n + i] = cnt[i];
+}
+
+// flag[i] = 1 when the i-th entry in sorted order survives (first of its k-mer)
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_flag_first(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, int64_t n,
+              uint32_t *__restrict__ flag)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  bool first = i == 0;
+  if (i > 0) first = !key_eq<W>(load_key<W>(keys, perm[i]), load_key<W>(keys, perm[i - 1]));
+  flag[i] = first;
+}
+
+__global__ void __launch_bounds__(TPB)
+kc_flag_trim(const uint16_t *__restrict__ cnt, int64_t n, unsigned ethresh, uint32_t *__restrict__ flag)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i < n) flag[i] = cnt[i] >= ethresh;
+}
+
+// out[pos[i]] = in[perm ? perm[i] : i] for the flagged i
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_compact(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint32_t *__restrict__ perm,
+           const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
+           u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t src = perm ? (int64_t) perm[i] : i;
+  const int64_t dst = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
+  ocnt[dst] = cnt[src];
+}
+
+// like kc_compact, for a sorted permutation in which a k-mer occurs at most twice (once as an entry, once as a
+// complement): the survivor is the first of the two, its count the ENTRY's
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_compact_pref(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint8_t *__restrict__ copy,
+                const uint32_t *__restrict__ perm, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
+                int64_t n, u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t src = perm[i];
+  int64_t csrc = src;
+  if (copy[src] && i + 1 < n && !flag[i + 1]) csrc = perm[i + 1];        // (the next one is the same k-mer: the entry)
+  const int64_t dst = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
+  ocnt[dst] = cnt[csrc];
+}
+
+// the engine's table has n entries now and is another table: what a run, the prefix index and the ends said is gone
+static void table_changed(smg_engine *e, int64_t n)
+{ e->n = n;
+  e->prepared = false; e->counted_done = false; e->general_done = false;
+  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
+  e->st.nels = n;
+}
+
+// (k, c), n finished entries, leave their buffers and become the engine's own table.  The stream is idle: the old one is freed.
+static void adopt_table(smg_engine *e, Dev &k, Dev &c, int64_t n)
+{ e->own_keys.take(k); e->own_cnt.take(c);
+  e->keys = e->own_keys; e->cnt = e->own_cnt;
+  table_changed(e, n);
+}
+
+// sorted, duplicate-free table from 2-copies-at-most material: keys[n2 * W], counts, copy flags (NULL: the first of two
+// equal k-mers in INPUT order wins, as the stable sort leaves it) -> the engine's own table.  Frees nothing of the caller's.
+static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, const uint8_t *copy, int64_t n2,
+                            int64_t *kept_out, char *errbuf, size_t errlen)
+{ const int W = e->W;
+  if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
+  const unsigned nblk2 = (unsigned) ((n2 + TPB - 1) / TPB);
+  Dev perm, flag, pos, ko, co;
+  int64_t kept = 0;
+  HIPCHK(sort_permutation(k2, W, n2, e->stream, e->sort_tmp, perm));
+  HIPCHK(flag.alloc(sizeof(uint32_t) * (size_t) n2));
+  HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n2));
+  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_flag_first<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm.as<uint32_t>(), n2, flag.as<uint32_t>()); });
+  HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n2, e->stream, e->sort_tmp, &kept));
+  HIPCHK(ko.alloc(sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
+  HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
+  if (copy)
+    {
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact_pref<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm.as<uint32_t>(),
+          flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>()); });
+    }
+  else
+    {
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm.as<uint32_t>(),
+          flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>()); });
+    }
+  HIPCHK(hipStreamSynchronize(e->stream));
+  adopt_table(e, ko, co, kept);
+  *kept_out = kept;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
+                                    int64_t *new_nels, char *errbuf, size_t errlen)
+{ if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
+  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  const int W = e->W;
+  int rc;
+  int64_t n = e->n;
+  hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);                 // (the decode pair: conditioning is booked under ms_decode)
+
+  if (do_trim && n > 0)
+    { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
+      Dev flag, pos, ko, co;
+      HIPCHK(flag.alloc(sizeof(uint32_t) * (size_t) n));
+      HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n));
+      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->cnt, n, (unsigned) ethresh, flag.as<uint32_t>());
+      int64_t kept = 0;
+      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, e->sort_tmp, &kept));
+      HIPCHK(ko.alloc(sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
+      HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt,
+          (const uint32_t *) NULL, flag.as<uint32_t>(), pos.as<uint32_t>(), n, ko.as<u64>(), co.as<uint16_t>()); });
+      HIPCHK(hipStreamSynchronize(e->stream));
+      adopt_table(e, ko, co, kept);
+      n = kept;
+    }
+
+  if (do_symm && n > 0)
+    { const int64_t n2 = 2 * n;
+      if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
+      const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
+      Dev k2, c2;
+      HIPCHK(k2.alloc(sizeof(u64) * (size_t) n2 * W));
+      HIPCHK(c2.alloc(sizeof(uint16_t) * (size_t) n2));
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_append_rc<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, n, e->kmer,
+          k2.as<u64>(), c2.as<uint16_t>()); });
+      // (entries first, complements behind them: the stable sort keeps the entry in front of an equal complement)
+      if ((rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), NULL, n2, &n, errbuf, errlen))) return rc;
+    }
+  hipEventRecord(e->ev[EV_DECODE_END], e->stream);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const float ms = ms_between(e, EV_DECODE_BEG, EV_DECODE_END);
+  table_changed(e, n);                                 // (also where nothing was asked for, or of an empty table)
+  e->rp_have = false; e->rp_active = false;
+  e->st.ms_decode += ms;
+  if (new_nels) *new_nels = n;
+  return SMG_OK;
+}
+
+// ---- closure of a CANONICAL table by merge ------------------------------------------------------------------------------
+// A table as the k-mer counter leaves it holds, of every k-mer and its reverse complement, the smaller one only (x <= rc x),
+// sorted.  The complements R of its entries that are not their own complement are then disjoint from the table C (were
+// rc x = y in C, y <= rc y = x and x <= rc x = y would make them equal), so the closure is C merged with sorted R: one sort
+// of m <= n k-mers where smg_engine_condition sorts 2 n, nothing to de-duplicate, no count to choose.  Entry for entry the
+// table smg_engine_condition(e, 0, 0, 1) leaves.
+
+// rc[i] = the reverse complement of entry i, flag[i] = it is another k-mer; *bad is set where it is the SMALLER one
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_rc_flag(const u64 *__restrict__ keys, int64_t n, int k, u64 *__restrict__ rc, uint32_t *__restrict__ flag, uint32_t *__restrict__ bad)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  const Key<W> r = revcomp<W>(x, k);
+#pragma unroll
+  for (int w = 0; w < W; w++) rc[i * W + w] = r.w[w];
+  flag[i] = !key_eq<W>(x, r);
+  if (key_lt<W>(r, x)) *bad = 1u;
+}
+
+// the flagged complements, compacted, and the entry each came from
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_rc_compact(const u64 *__restrict__ rc, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
+              u64 *__restrict__ okeys, uint32_t *__restrict__ osrc)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const int64_t dst = pos[i];
+#pragma unroll
+  for (int w = 0; w < W; w++) okeys[dst * W + w] = rc[i * W + w];
+  osrc[dst] = (uint32_t) i;
+}
+
+extern "C" int smg_engine_merge_tile(int key_words)
+{ return key_words >= 1 && key_words <= 4 ? ks_merge_tile(key_words) : 0; }
+
+// *not_canonical tells that refusal (SMG_EINVAL like the others, the table untouched) from every other one
+static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical, char *errbuf, size_t errlen)
+{ *not_canonical = false;
+  if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
+  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  const int W = e->W;
+  const int64_t n = e->n;
+  int64_t m = 0;
+  hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);                 // (booked under ms_decode, like smg_engine_condition)
+  if (n > 0)
+    { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
+      Dev rc, flag, pos, bad, rk, rsrc, perm, split, ko, co;
+      uint32_t h_bad = 0;
+      HIPCHK(rc.alloc(sizeof(u64) * (size_t) n * W));
+      HIPCHK(flag.alloc(sizeof(uint32_t) * (size_t) n));
+      HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n));
+      HIPCHK(bad.alloc(16));
+      HIPCHK(hipMemsetAsync(bad.p, 0, 16, e->stream));
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_rc_flag<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, n, e->kmer, rc.as<u64>(),
+          flag.as<uint32_t>(), bad.as<uint32_t>()); });
+      HIPCHK(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, e->sort_tmp, &m));    // (waits)
+      if (h_bad)
+        { *not_canonical = true;
+          return fail(errbuf, errlen, SMG_EINVAL, "table is not canonical: an entry is larger than its reverse complement "
+                      "(smg_engine_condition closes any sorted table)%s");
+        }
+      if (n + m >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
+      HIPCHK(ko.alloc(sizeof(u64) * (size_t) (n + m) * W));
+      HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (n + m) + 16));
+      if (m == 0)                                      // every entry is its own complement: the closure is a copy
+        { HIPCHK(hipMemcpyAsync(ko.p, e->keys, sizeof(u64) * (size_t) n * W, hipMemcpyDeviceToDevice, e->stream));
+          HIPCHK(hipMemcpyAsync(co.p, e->cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToDevice, e->stream));
+        }
+      else
+        { HIPCHK(rk.alloc(sizeof(u64) * (size_t) m * W));
+          HIPCHK(rsrc.alloc(sizeof(uint32_t) * (size_t) m));
+          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_rc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, rc.as<u64>(), flag.as<uint32_t>(),
+              pos.as<uint32_t>(), n, rk.as<u64>(), rsrc.as<uint32_t>()); });
+          HIPCHK(hipStreamSynchronize(e->stream));
+          rc.reset(); flag.reset(); pos.reset();
+          HIPCHK(sort_permutation(rk.as<u64>(), W, m, e->stream, e->sort_tmp, perm));
+          const int64_t ntiles = (n + m + ks_merge_tile(W) - 1) / ks_merge_tile(W);
+          HIPCHK(split.alloc(sizeof(uint32_t) * (size_t) (ntiles + 1)));
+          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(ks_merge_split<w()>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, e->keys, n,
+              rk.as<u64>(), perm.as<uint32_t>(), m, ntiles, split.as<uint32_t>()); });
+          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(ks_merge<w()>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, e->keys, e->cnt, n, rk.as<u64>(),
+              perm.as<uint32_t>(), rsrc.as<uint32_t>(), m, split.as<uint32_t>(), ko.as<u64>(), co.as<uint16_t>()); });
+          HIPCHK(hipGetLastError());
+        }
+      HIPCHK(hipStreamSynchronize(e->stream));
+      adopt_table(e, ko, co, n + m);
+    }
+  hipEventRecord(e->ev[EV_DECODE_END], e->stream);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const float ms = ms_between(e, EV_DECODE_BEG, EV_DECODE_END);
+  table_changed(e, n + m);
+  e->rp_have = false; e->rp_active = false;
+  e->st.ms_decode += ms;
+  if (new_nels) *new_nels = n + m;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char *errbuf, size_t errlen)
+{ bool not_canonical;
+  return close_canonical(e, new_nels, &not_canonical, errbuf, errlen);
+}
+
+extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
+{ if (!e) return SMG_EINVAL;
+  if (nels) *nels = e->n;
+  if (d_keys) *d_keys = (const uint64_t *) e->keys;
+  if (d_counts) *d_counts = e->cnt;
+  return SMG_OK;
+}
+
+// the same table copied to the host (tests and tools that want to look at a conditioned table): two copies and a wait
+extern "C" int smg_engine_table_host(smg_engine *e, uint64_t *keys, uint16_t *counts, int64_t capacity, char *errbuf, size_t errlen)
+{ NEED_ENGINE(e)
+  if (capacity < e->n || (e->n > 0 && (!keys || !counts)))
+    return fail(errbuf, errlen, SMG_EINVAL, "table_host: the buffers must hold every entry of the table%s");
+  if (e->n == 0) return SMG_OK;
+  if (!e->keys || !e->cnt) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  HIPCHK(hipMemcpyAsync(keys, e->keys, sizeof(u64) * (size_t) e->n * e->W, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(counts, e->cnt, sizeof(uint16_t) * (size_t) e->n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  return SMG_OK;
+}
+
+// ---- symmetrising a table that is cut into prefix shards (several GPUs, or one device and more than 2^32 entries) -----
+// The reference's Symmex has no size limit (PloidyPlot.c:1395-1414 hands it any table).  Here every shard
+//   1. counts its own entries and their reverse complements per leading `bits` k-mer bits (smg_engine_symm_hist): the
+//      sum over the shards is the shape of the CLOSED table, from which the caller takes balanced splitters -- a table
+//      of canonical k-mers crowds the low end of the k-mer space (7/8 of the k-mers that start with an a are canonical,
+//      1/8 of those that start with a t), its closure does not;
+//   2. writes one record per entry and one per complement, grouped by the shard whose range holds the k-mer
+//      (smg_engine_symm_route; records of W + 1 words: the k-mer, then count | is-a-complement << 16);
+//   3. after the exchange sorts what it received and keeps one entry per k-mer (smg_engine_symm_finish; a k-mer that
+//      arrives as an entry AND as a complement keeps the entry's count -- self-complementary k-mers, or input that was
+//      neither canonical nor closed: the same rule as the single-shard code above).
+
+#define SY_MAXBITS 12
+
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_symm_hist(const u64 *__restrict__ keys, int64_t n, int k, int bits, u64 *__restrict__ hist /* [2 << bits]: own, complements */)
+{ __shared__ unsigned h[2 << SY_MAXBITS];
+  const int nb = 1 << bits;
+  for (int b = threadIdx.x; b < 2 * nb; b += TPB) h[b] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t) gridDim.x * TPB)
+    { const Key<W> x = load_key<W>(keys, i);
+      const Key<W> r = revcomp<W>(x, k);
+      atomicAdd(&h[(unsigned) (x.w[0] >> (64 - bits))], 1u);
+      atomicAdd(&h[nb + (unsigned) (r.w[0] >> (64 - bits))], 1u);
+    }
+  __syncthreads();
+  for (int b = threadIdx.x; b < 2 * nb; b += TPB)
+    if (h[b]) atomicAdd(&hist[b], (u64) h[b]);
+}
+
+// record i = (entry i, count), record n + i = (its reverse complement, count | 1 << 16)
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_symm_records(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k, u64 *__restrict__ rec)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const Key<W> x = load_key<W>(keys, i);
+  const Key<W> r = revcomp<W>(x, k);
+  u64 *a = rec + (size_t) i * (W + 1), *b = rec + (size_t) (n + i) * (W + 1);
+#pragma unroll
+  for (int w = 0; w < W; w++) { a[w] = x.w[w]; b[w] = r.w[w]; }
+  a[W] = (u64) cnt[i];
+  b[W] = (u64) cnt[i] | (1ull << 16);
+}
+
+// records -> separate k-mer / count / is-a-complement arrays
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, uint16_t *__restrict__ cnt, uint8_t *__restrict__ copy)
+{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const u64 *q = rec + (size_t) i * (W + 1);
+#pragma unroll
+  for (int w = 0; w < W; w++) keys[i * W + w] = q[w];
+  cnt[i] = (uint16_t) q[W];
+  copy[i] = (uint8_t) ((q[W] >> 16) & 1u);
+}
+
+extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
+{ if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
+  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
+  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
+  Dev d;
+  HIPCHK(d.alloc(bytes));
+  hipError_t he = hipMemsetAsync(d.p, 0, bytes, e->stream);
+  if (he == hipSuccess && e->n > 0)
+    { int64_t nb = (e->n + TPB - 1) / TPB;
+      if (nb > 2048) nb = 2048;
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_hist<w()>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->keys, e->n, e->kmer, bits, d.as<u64>()); });
+      he = hipGetLastError();
+    }
+  if (he == hipSuccess) he = hipMemcpyAsync(hist, d.p, bytes, hipMemcpyDeviceToHost, e->stream);
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+  if (he != hipSuccess) return fail(errbuf, errlen, SMG_ENODEV, "symm_hist: %s", hipGetErrorString(he));
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, int nranks, uint64_t *d_send,
+                                     int64_t capacity, int64_t *counts, char *errbuf, size_t errlen)
+{ if (!e || !counts || nranks < 1 || nranks > 16) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_route arguments (1..16 ranks)%s");
+  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  const int64_t n2 = 2 * e->n;
+  if (capacity < n2 || (n2 > 0 && !d_send)) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: the send buffer must hold two records per entry%s");
+  for (int r = 0; r < nranks; r++) counts[r] = 0;
+  if (n2 == 0) return SMG_OK;
+  HIPCHK(hipSetDevice(e->device));
+  const int rw = e->W + 1;
+  const int64_t nc = (n2 + F_CH - 1) / F_CH;
+  if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: shard too large%s");
+  Dev rec, fill;
+  int rc = SMG_OK;
+  if (rec.alloc(sizeof(u64) * (size_t) n2 * rw) != hipSuccess || fill.alloc(sizeof(uint32_t) * (size_t) nc) != hipSuccess)
+    return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
+  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_records<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, e->n, e->kmer, rec.as<u64>()); });
+  hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill.as<uint32_t>(), nc, (uint32_t) F_CH,
+                     (uint32_t) (n2 - (nc - 1) * F_CH));
+  if (hipGetLastError() != hipSuccess) rc = fail(errbuf, errlen, SMG_ENODEV, "symm_route: launch failed%s");
+  if (rc == SMG_OK) rc = route_records(e, rec.as<u64>(), fill.as<uint32_t>(), (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
+  hipStreamSynchronize(e->stream);                     // (the records are freed on return)
+  return rc;
+}
+
+extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int64_t nrecv, int64_t *new_nels,
+                                      char *errbuf, size_t errlen)
+{ if (!e || nrecv < 0 || (nrecv > 0 && !d_recv)) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_finish arguments%s");
+  if (e->kmer < 1) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  int64_t kept = 0;
+  if (nrecv == 0)
+    { Dev ko, co;
+      HIPCHK(ko.alloc(sizeof(u64) * e->W)); HIPCHK(co.alloc(16));
+      adopt_table(e, ko, co, 0);
+    }
+  else
+    { if (nrecv >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
+      Dev k2, c2, cp;
+      if (k2.alloc(sizeof(u64) * (size_t) nrecv * e->W) != hipSuccess || c2.alloc(sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
+          || cp.alloc((size_t) nrecv + 16) != hipSuccess)
+        return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
+      const unsigned nblk = (unsigned) ((nrecv + TPB - 1) / TPB);
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_unpack<w()>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2.as<u64>(),
+          c2.as<uint16_t>(), cp.as<uint8_t>()); });
+      const int rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), cp.as<uint8_t>(), nrecv, &kept, errbuf, errlen);
+      if (rc) return rc;
+    }
+  if (new_nels) *new_nels = kept;
+  return SMG_OK;
+}

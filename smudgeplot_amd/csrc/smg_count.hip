@@ -563,7 +563,6 @@ struct GrowSink : Sink
 #define DCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) \
     return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (" #call ")", hipGetErrorString(_e)); } while (0)
 #define RCHK(call) do { const int _rc = (call); if (_rc) return _rc; } while (0)
-#define DISPATCH_W(CALL) switch (W) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; default: CALL(4); break; }
 
 static unsigned nblk(int64_t n) { return (unsigned) ((n + KC_TPB - 1) / KC_TPB); }
 
@@ -576,8 +575,7 @@ struct Counter
   int64_t fill = 0;                                            // bytes in the batch buffer
   int last_file = -1;                                          // the file whose stream ends at `fill`
   std::vector<std::vector<uint8_t>> tails;                     // per file: the last k-1 bytes handed over
-  Dev seq, ka, kb, flag, pos, start, tmp, ctr, dk, dc;         // dk, dc: the running distinct list (k-mers, uint32 counts)
-  int64_t tmp_cap = 0;                                         // bytes behind tmp, the grow-only rocPRIM scratch
+  Dev seq, ka, kb, flag, pos, start, tmp, ctr, dk, dc;         // tmp: the grow-only rocPRIM scratch; dk, dc: the running distinct list (k-mers, uint32 counts)
   int64_t nd = 0;
   smg_count_stats st;
   // a partitioned run: the packed input (positions; store_n is a multiple of 64), the bins, the host table so far
@@ -602,7 +600,7 @@ struct Counter
   }
 
   int alloc(Dev &d, size_t bytes)
-  { const hipError_t e = dev_alloc(d, bytes);
+  { const hipError_t e = d.alloc(bytes);
     if (e != hipSuccess)
       return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV,
                   "cannot allocate %.3f GB of device memory: %s", (double) bytes * 1e-9, hipGetErrorString(e));
@@ -765,22 +763,17 @@ struct Counter
         // All 64 bits, not 64-2k .. 64: the pad bits are zero, so the order is the same, and a partial bit range is not
         // safe on rocPRIM's merge-sort path (sort_permutation, smg_keysort.hpp).
         const unsigned b0 = 0u;
-        size_t bytes = 0;
-        if (va) { DCHK(rocprim::radix_sort_pairs(nullptr, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
-        else { DCHK(rocprim::radix_sort_keys(nullptr, bytes, dk2, (size_t) n, b0, 64u, stream)); }
-        DCHK(ks_scratch(&tmp.p, &tmp_cap, bytes));
-        if (va) { DCHK(rocprim::radix_sort_pairs(tmp.p, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)); }
-        else { DCHK(rocprim::radix_sort_keys(tmp.p, bytes, dk2, (size_t) n, b0, 64u, stream)); }
+        DCHK(with_scratch(tmp, [&](void *t, size_t &bytes)
+          { return va ? rocprim::radix_sort_pairs(t, bytes, dk2, dv2, (size_t) n, b0, 64u, stream)
+                      : rocprim::radix_sort_keys(t, bytes, dk2, (size_t) n, b0, 64u, stream); }));
         *ko = dk2.current();
         if (vo) *vo = va ? dv2.current() : nullptr;
         return 0;
       }
     // W > 1: the sorted order as a permutation (smg_keysort.hpp), then one gather
     Dev perm;
-    DCHK(sort_permutation(a, W, n, stream, &tmp.p, &tmp_cap, perm));
-#define CALL(WW) hipLaunchKernelGGL(kc_gather_entries<WW>, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, va, perm.as<uint32_t>(), n, b, vb)
-    DISPATCH_W(CALL)
-#undef CALL
+    DCHK(sort_permutation(a, W, n, stream, tmp, perm));
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_gather_entries<w()>, dim3(nblk(n)), dim3(KC_TPB), 0, stream, a, va, perm.as<uint32_t>(), n, b, vb); });
     DCHK(hipStreamSynchronize(stream));                        // (the permutation is freed on return)
     *ko = b;
     if (vo) *vo = va ? vb : nullptr;
@@ -797,10 +790,8 @@ struct Counter
     tic();
     DCHK(hipMemsetAsync(ctr.p, 0, 16, stream));
     const unsigned ntiles = (unsigned) ((n + KC_TILE - 1) / KC_TILE);
-#define CALL(WW) hipLaunchKernelGGL(kc_extract<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, seq.as<uint8_t>(), n, k, ka.as<u64>(), \
-                                    ctr.as<unsigned long long>())
-    DISPATCH_W(CALL)
-#undef CALL
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_extract<w()>, dim3(ntiles), dim3(KC_TPB), 0, stream, seq.as<uint8_t>(), n, k, ka.as<u64>(),
+        ctr.as<unsigned long long>()); });
     DCHK(hipGetLastError());
     unsigned long long nwin = 0;
     DCHK(hipMemcpyAsync(&nwin, ctr.p, 8, hipMemcpyDeviceToHost, stream));
@@ -820,14 +811,10 @@ struct Counter
     u64 *uk = sorted == ka.as<u64>() ? kb.as<u64>() : ka.as<u64>();
     int64_t nruns = 0;
     tic();
-#define CALL(WW) hipLaunchKernelGGL(kc_flag_heads<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, (int64_t) nwin, flag.as<uint32_t>())
-    DISPATCH_W(CALL)
-#undef CALL
-    DCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), (int64_t) nwin, stream, &tmp.p, &tmp_cap, &nruns));
-#define CALL(WW) hipLaunchKernelGGL(kc_runs<WW>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, flag.as<uint32_t>(), pos.as<uint32_t>(), \
-                                    (int64_t) nwin, uk, start.as<uint32_t>())
-    DISPATCH_W(CALL)
-#undef CALL
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_flag_heads<w()>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, (int64_t) nwin, flag.as<uint32_t>()); });
+    DCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), (int64_t) nwin, stream, tmp, &nruns));
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_runs<w()>, dim3(nblk(nwin)), dim3(KC_TPB), 0, stream, sorted, flag.as<uint32_t>(), pos.as<uint32_t>(),
+        (int64_t) nwin, uk, start.as<uint32_t>()); });
     uint32_t *rc = flag.as<uint32_t>();                        // (the flags are spent: the run counts take their place)
     hipLaunchKernelGGL(kc_run_counts, dim3(nblk(nruns)), dim3(KC_TPB), 0, stream, start.as<uint32_t>(), nruns, rc);
     DCHK(hipGetLastError());
@@ -871,16 +858,12 @@ struct Counter
     u64 *sk = nullptr; uint32_t *sc = nullptr;
     RCHK(sort_entries(ck.as<u64>(), ak.as<u64>(), cc.as<uint32_t>(), ac.as<uint32_t>(), m, &sk, &sc));
     RCHK(alloc(mf, sizeof(uint32_t) * (size_t) m)); RCHK(alloc(mp, sizeof(uint32_t) * (size_t) m));
-#define CALL(WW) hipLaunchKernelGGL(kc_flag_heads<WW>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, m, mf.as<uint32_t>())
-    DISPATCH_W(CALL)
-#undef CALL
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_flag_heads<w()>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, m, mf.as<uint32_t>()); });
     int64_t nn = 0;
-    DCHK(scan_flags(mf.as<uint32_t>(), mp.as<uint32_t>(), m, stream, &tmp.p, &tmp_cap, &nn));
+    DCHK(scan_flags(mf.as<uint32_t>(), mp.as<uint32_t>(), m, stream, tmp, &nn));
     RCHK(alloc(nk, sizeof(u64) * (size_t) nn * W)); RCHK(alloc(nc, sizeof(uint32_t) * (size_t) nn));
-#define CALL(WW) hipLaunchKernelGGL(kc_merge_write<WW>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, sc, mf.as<uint32_t>(), mp.as<uint32_t>(), m, \
-                                    nk.as<u64>(), nc.as<uint32_t>())
-    DISPATCH_W(CALL)
-#undef CALL
+    with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_merge_write<w()>, dim3(nblk(m)), dim3(KC_TPB), 0, stream, sk, sc, mf.as<uint32_t>(), mp.as<uint32_t>(), m,
+        nk.as<u64>(), nc.as<uint32_t>()); });
     DCHK(hipGetLastError());
     DCHK(hipStreamSynchronize(stream));
     dk.take(nk); dc.take(nc); nd = nn;
@@ -897,12 +880,10 @@ struct Counter
         const unsigned g = nblk(nd) < 2048u ? nblk(nd) : 2048u;
         hipLaunchKernelGGL(kc_finish_flag, dim3(g), dim3(KC_TPB), 0, stream, dc.as<uint32_t>(), nd, (unsigned) t,
                            dh.as<unsigned long long>(), ff.as<uint32_t>());
-        DCHK(scan_flags(ff.as<uint32_t>(), fp.as<uint32_t>(), nd, stream, &tmp.p, &tmp_cap, &kept));
+        DCHK(scan_flags(ff.as<uint32_t>(), fp.as<uint32_t>(), nd, stream, tmp, &kept));
         RCHK(alloc(ok, sizeof(u64) * (size_t) kept * W)); RCHK(alloc(oc, sizeof(uint16_t) * (size_t) kept));
-#define CALL(WW) hipLaunchKernelGGL(kc_finish_compact<WW>, dim3(nblk(nd)), dim3(KC_TPB), 0, stream, dk.as<u64>(), dc.as<uint32_t>(), \
-                                    ff.as<uint32_t>(), fp.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>())
-        DISPATCH_W(CALL)
-#undef CALL
+        with_words<4>(W, [&](auto w) { hipLaunchKernelGGL(kc_finish_compact<w()>, dim3(nblk(nd)), dim3(KC_TPB), 0, stream, dk.as<u64>(), dc.as<uint32_t>(),
+            ff.as<uint32_t>(), fp.as<uint32_t>(), nd, ok.as<u64>(), oc.as<uint16_t>()); });
         DCHK(hipGetLastError());
       }
     RCHK(toc(&st.ms_finish));
@@ -1073,15 +1054,13 @@ struct Counter
             const int64_t p1 = left <= room ? store_n : (p + room < store_n ? p + room : store_n);
             const unsigned ntiles = (unsigned) ((p1 - 1) / KC_TILE - p / KC_TILE + 1);
             tic();
-#define CALL(WW) hipLaunchKernelGGL(kc_extract_packed<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n, \
-                                    p, p1, k, lo >> SMG_COUNT_BIN_BITS, hi >> SMG_COUNT_BIN_BITS, ka.as<u64>(), (unsigned long long) cap, \
-                                    ctr.as<unsigned long long>())
-#define CALL_FINE(WW) hipLaunchKernelGGL(kc_extract_fine<WW>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n, \
-                                         p, p1, k, lo, hi, ka.as<u64>(), (unsigned long long) cap, ctr.as<unsigned long long>())
-            if (fine) { DISPATCH_W(CALL_FINE) }
-            else { DISPATCH_W(CALL) }
-#undef CALL_FINE
-#undef CALL
+            with_words<4>(W, [&](auto w)
+              { if (fine) hipLaunchKernelGGL(kc_extract_fine<w()>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n,
+                                             p, p1, k, lo, hi, ka.as<u64>(), (unsigned long long) cap, ctr.as<unsigned long long>());
+                else hipLaunchKernelGGL(kc_extract_packed<w()>, dim3(ntiles), dim3(KC_TPB), 0, stream, scode.as<u64>(), sval.as<u64>(), store_n,
+                                        p, p1, k, lo >> SMG_COUNT_BIN_BITS, hi >> SMG_COUNT_BIN_BITS, ka.as<u64>(), (unsigned long long) cap,
+                                        ctr.as<unsigned long long>());
+              });
             DCHK(hipGetLastError());
             unsigned long long now = 0;
             DCHK(hipMemcpyAsync(&now, ctr.p, 8, hipMemcpyDeviceToHost, stream));

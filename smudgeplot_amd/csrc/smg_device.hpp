@@ -8,10 +8,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define SMG_DEV __device__ __forceinline__
 
 typedef unsigned long long u64;
+
+// host: f(std::integral_constant<int, N>) with N = W for W = 1 .. MAXW - 1 and N = MAXW for every other W -- the one
+// dispatch from a run-time word count to the kernels that have it as a template argument: [&](auto w) { .. k<w()> .. }
+template <int MAXW, int N = 1, class F> static inline void with_words(int W, F &&f)
+{ if constexpr (N < MAXW) { if (W == N) f(std::integral_constant<int, N>{}); else with_words<MAXW, N + 1>(W, f); }
+  else f(std::integral_constant<int, MAXW>{});
+}
 
 template <int W> struct Key { u64 w[W]; };
 

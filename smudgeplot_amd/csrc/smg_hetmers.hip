@@ -23,6 +23,10 @@
 //     nothing is assumed about the table.  Slow, exact, used only for asymmetric input.
 //
 // All arithmetic is integer; results are bit-exact against the reference.
+//
+// This file: the engine struct, the fast path (k <= 85), the phase API of sharded runs, the run entry points and the C ABI.
+// The other paths are headers of this one translation unit, included where they are needed: smg_decode.hpp (FastK records ->
+// table), smg_counted.hpp (k > 85 and the general path), smg_condition.hpp (trim, symmetrise, close), smg_ingest.hpp, smg_multi.hpp.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -80,597 +84,6 @@ struct Tab                     // kernel argument block (passed by value)
 };
 
 // ------------------------------------------------------------------------------------------
-//  Kernels
-// ------------------------------------------------------------------------------------------
-
-// format F records -> interleaved left-aligned words + counts
-// (restates Current_Entry, libfastk.c:1230-1269: prefix from the index, suffix from the record)
-//
-// One workgroup decodes DEC_TILE consecutive entries, four per thread:
-//   * their record bytes (DEC_TILE * pbyte, contiguous) are staged in LDS with coalesced dword loads
-//     (records are 3..34 bytes wide and unaligned: per-thread byte loads ran at ~4 G entries/s);
-//   * a k-mer is put together 32 bits at a time: an unaligned little-endian dword of the staged bytes is one
-//     v_alignbyte over two LDS dwords, its big-endian value one v_perm; the first dword takes the prefix bytes from
-//     the index, the last one is masked behind the k-mer's last byte (the count bytes follow it in the record).
-//     (Round 2 walked the 8 W bytes of an entry one at a time, runtime shifts and all: 36-77 ms per 1e9 entries,
-//      6 % of the HBM roofline, the slowest kernel of the product path.)
-//   * the prefix of an entry is the smallest p with index[p] > i.  Thread 0 bisects the index for the first and the
-//     last entry of the tile, the (few) index values in between are staged in LDS; a thread bisects there for its
-//     first entry and steps on for the other three; a tile that spans more than DEC_IX buckets (sparse table)
-//     bisects the global index per entry.
-#define DEC_TILE  1024
-#define DEC_EPT   4
-#define DEC_IX    512
-#define DEC_MAXPB 34                      // pbyte <= ceil(128/4) + 2 - 1
-
-SMG_DEV int dec_bisect(const int64_t *__restrict__ index, int lo, int hi, int64_t i)
-{ while (lo < hi)                         // smallest p in [lo, hi] with index[p] > i  (index[hi] > i)
-    { const int m = (lo + hi) >> 1;
-      if (index[m] <= i) lo = m + 1; else hi = m;
-    }
-  return lo;
-}
-
-// the little-endian dword at byte offset o of the staged bytes
-SMG_DEV unsigned dec_u32(const unsigned *sraw, int o)
-{ return __builtin_amdgcn_alignbyte(sraw[(o >> 2) + 1], sraw[o >> 2], (unsigned) (o & 3)); }
-
-static inline size_t dec_lds_bytes(int pbyte) { return sizeof(unsigned) * (size_t) ((DEC_TILE * pbyte + 3) / 4 + 4); }
-
-template <int W> __global__ void __launch_bounds__(TPB)
-k_decode(const uint8_t *__restrict__ rec, const int64_t *__restrict__ index, int ixlen,
-         int ibyte, int kbyte, int64_t n, int64_t ibase, u64 *__restrict__ keys,
-         uint16_t *__restrict__ cnt)
-{ // rec / keys / cnt are indexed by the LOCAL entry number 0..n-1; the prefix index by ibase + local
-  // (a piece of a table that is decoded as it arrives, or a shard of a table that was cut for several GPUs,
-  //  starts at entry ibase of the whole table)
-  extern __shared__ unsigned sraw[];         // dec_lds_bytes(pbyte): the staged record bytes of a tile (+ slack)
-  __shared__ int64_t  six[DEC_IX];
-  __shared__ int      s_lo, s_hi;
-  const int t = threadIdx.x;
-  const int hbyte = kbyte - ibyte, pbyte = hbyte + 2;
-  const int64_t i0 = (int64_t) blockIdx.x * DEC_TILE;
-  const int64_t i1 = i0 + DEC_TILE < n ? i0 + DEC_TILE : n;
-  // record bytes of [i0, i1): aligned dword loads around the (unaligned) byte range
-  const int64_t b0 = i0 * pbyte, b1 = i1 * pbyte;
-  const uintptr_t base = (uintptr_t) rec + (uintptr_t) b0;
-  const uintptr_t abase = base & ~(uintptr_t) 3;
-  const int skew = (int) (base - abase);
-  const int ndw = (int) ((b1 - b0 + skew + 3) >> 2);
-  const uintptr_t rbeg = (uintptr_t) rec, rend = (uintptr_t) rec + (uintptr_t) (n * pbyte);
-  for (int w = t; w < ndw + 2; w += TPB)      // (+2: dec_u32 reads one dword past the last byte it needs)
-    { const uintptr_t a = abase + 4 * (uintptr_t) w;
-      unsigned v = 0;
-      if (a >= rbeg && a + 4 <= rend) v = *reinterpret_cast<const unsigned *>(a);
-      else                                  // first / last dword of the table: never touch bytes outside it
-        for (int q = 0; q < 4; q++)
-          if (a + q >= rbeg && a + q < rend) v |= (unsigned) *reinterpret_cast<const uint8_t *>(a + q) << (8 * q);
-      sraw[w] = v;
-    }
-  if (t == 0)
-    { s_lo = dec_bisect(index, 0, ixlen - 1, ibase + i0);
-      s_hi = dec_bisect(index, 0, ixlen - 1, ibase + i1 - 1);
-    }
-  __syncthreads();
-  const int lo = s_lo, hi = s_hi;
-  const bool staged = hi - lo < DEC_IX;
-  if (staged)
-    for (int p = lo + t; p <= hi; p += TPB) six[p - lo] = index[p];
-  __syncthreads();
-
-  const int64_t e0 = i0 + (int64_t) DEC_EPT * t;
-  if (e0 >= i1) return;
-  int pa = 0;                                // position of the first entry's prefix in the staged slice
-  if (staged)
-    { int a = 0, b = hi - lo;
-      while (a < b)
-        { const int m = (a + b) >> 1;
-          if (six[m] <= ibase + e0) a = m + 1; else b = m;
-        }
-      pa = a;
-    }
-  const int psh = 32 - 8 * ibyte;            // the prefix sits on top of the first dword
-  u64 kw[DEC_EPT][W]; unsigned cw[DEC_EPT];
-#pragma unroll
-  for (int r = 0; r < DEC_EPT; r++)
-    { const int64_t i = e0 + r;
-      if (i >= i1) { for (int w = 0; w < W; w++) kw[r][w] = 0; cw[r] = 0; continue; }
-      int p;
-      if (staged) { while (six[pa] <= ibase + i) pa++; p = lo + pa; }      // (index[hi] > i1 - 1: the walk ends)
-      else p = dec_bisect(index, lo, hi, ibase + i);
-      const int o = (int) (i - i0) * pbyte + skew;
-      unsigned D[2 * W];
-#pragma unroll
-      for (int j = 0; j < 2 * W; j++)
-        { unsigned v = 0;
-          if (4 * j < kbyte)
-            { if (j == 0)
-                { const unsigned sv = __builtin_bswap32(dec_u32(sraw, o));
-                  v = ((unsigned) p << psh) | (sv >> (8 * ibyte));
-                }
-              else v = __builtin_bswap32(dec_u32(sraw, o + 4 * j - ibyte));
-              const int over = 4 * j + 4 - kbyte;                         // bytes of this dword behind the k-mer
-              if (over > 0) v &= ~0u << (8 * over);
-            }
-          D[j] = v;
-        }
-#pragma unroll
-      for (int w = 0; w < W; w++) kw[r][w] = ((u64) D[2 * w] << 32) | D[2 * w + 1];
-      cw[r] = dec_u32(sraw, o + hbyte) & 0xFFFFu;
-    }
-  const bool full = e0 + DEC_EPT <= i1 && (((uintptr_t) (keys + e0 * W)) & 15) == 0 && (((uintptr_t) (cnt + e0)) & 7) == 0;
-  if (full)
-    { if constexpr (W == 1)
-        { ulonglong2 a, b; a.x = kw[0][0]; a.y = kw[1][0]; b.x = kw[2][0]; b.y = kw[3][0];
-          *reinterpret_cast<ulonglong2 *>(keys + e0) = a;
-          *reinterpret_cast<ulonglong2 *>(keys + e0 + 2) = b;
-        }
-      else
-        {
-#pragma unroll
-          for (int r = 0; r < DEC_EPT; r++)
-#pragma unroll
-            for (int w = 0; w < W; w += 2)
-              { if (w + 1 < W)
-                  { ulonglong2 a; a.x = kw[r][w]; a.y = kw[r][w + 1];
-                    *reinterpret_cast<ulonglong2 *>(keys + (e0 + r) * W + w) = a;
-                  }
-                else keys[(e0 + r) * W + w] = kw[r][w];
-              }
-        }
-      *reinterpret_cast<ushort4 *>(cnt + e0) = make_ushort4((unsigned short) cw[0], (unsigned short) cw[1],
-                                                            (unsigned short) cw[2], (unsigned short) cw[3]);
-    }
-  else
-    for (int r = 0; r < DEC_EPT; r++)
-      if (e0 + r < i1)
-        { for (int w = 0; w < W; w++) keys[(e0 + r) * W + w] = kw[r][w];
-          cnt[e0 + r] = (uint16_t) cw[r];
-        }
-}
-
-// bucket directory + strict-order validation
-template <int W> __global__ void __launch_bounds__(TPB)
-k_directory(Tab t, uint32_t *__restrict__ bstart, Ctrl *__restrict__ ctrl)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i > t.n) return;
-  if (i < t.n)
-    { const uint32_t bcur = dir_bucket(t.dir, t.keys[i * W]);
-      bool first = i == 0;
-      if (i > 0)
-        { first = dir_bucket(t.dir, t.keys[(i - 1) * W]) != bcur;
-          if (!key_lt<W>(load_key<W>(t.keys, i - 1), load_key<W>(t.keys, i))) ctrl->unsorted = 1;
-        }
-      if (first) bstart[bcur] = (uint32_t) i;
-    }
-  else bstart[t.dir.nb] = (uint32_t) t.n;
-}
-
-// ---- the general path over a table that is cut into prefix shards ON ONE DEVICE (more than 2^32 entries) -----------
-// The prefix-side partner of an entry (the k-mer with one of its first p0 bases replaced) may live in another shard:
-// the look-up first picks the shard whose k-mer range holds it (<= 16 comparisons with the shards' first k-mers), then
-// searches that shard's directory.  Window blocks never straddle a cut, so everything else stays shard local.
-#define SET_MAX 16
-struct TabSet
-{ int ns;
-  Tab shard[SET_MAX];
-  u64 first[SET_MAX][4];       // first k-mer of shard s (all ones for an empty shard behind the last one)
-};
-
-template <int W> SMG_DEV int set_find(const TabSet *set, const Key<W> &y, int64_t &j)
-{ int s = 0;
-  for (int q = 1; q < set->ns; q++)
-    { Key<W> f;
-#pragma unroll
-      for (int w = 0; w < W; w++) f.w[w] = set->first[q][w];
-      if (!key_lt<W>(y, f)) s = q;
-    }
-  const Tab &t = set->shard[s];
-  j = t.n > 0 ? find_key<W>(t.keys, t.dir, y) : -1;
-  return s;
-}
-
-// ---- pass 1 -------------------------------------------------------------------------------
-// One thread per entry.  SYM: scan positions >= p0 inside the window block, write
-// deg = S_all, emit a request (rc(x), cnt, S_hi) when S_hi > 0 (or for every entry when
-// emit_all), accumulate the fingerprints when want_fp.
-// !SYM (general path): additionally resolve positions < p0 by directory look-ups; deg = all.
-
-template <int W, bool SYM> __global__ void __launch_bounds__(TPB)
-k_pass1(Tab t, int64_t lo, int64_t hi, int emit_all, int want_fp, u64 *__restrict__ req,
-        int64_t req_cap, Ctrl *__restrict__ ctrl, const TabSet *__restrict__ set = NULL)
-{ const int64_t i = lo + (int64_t) blockIdx.x * TPB + threadIdx.x;
-  const bool live = i < hi;
-  const Geo g = t.g;
-  unsigned s_all = 0, s_hi = 0;
-  Key<W> x;
-  unsigned c = 0;
-#pragma unroll
-  for (int w = 0; w < W; w++) x.w[w] = 0;
-
-  if (live)
-    { x = load_key<W>(t.keys, i);
-      c = t.cnt[i];
-      bool big = false;
-      if (i + WIN_LIM < t.n) big |= same_block<W>(x, load_key<W>(t.keys, i + WIN_LIM), g);
-      if (i - WIN_LIM >= 0)  big |= same_block<W>(x, load_key<W>(t.keys, i - WIN_LIM), g);
-      if (!big)
-        { for (int64_t j = i + 1; j < t.n; j++)
-            { const Key<W> y = load_key<W>(t.keys, j);
-              if (!same_block<W>(x, y, g)) break;
-              const int p = pair_pos<W>(x, y);
-              if (p >= 0 && c + (unsigned) t.cnt[j] <= SMG_SMAX)
-                { s_all++; s_hi += (p != g.k - 1 - p); }
-            }
-          for (int64_t j = i - 1; j >= 0; j--)
-            { const Key<W> y = load_key<W>(t.keys, j);
-              if (!same_block<W>(x, y, g)) break;
-              const int p = pair_pos<W>(x, y);
-              if (p >= 0 && c + (unsigned) t.cnt[j] <= SMG_SMAX)
-                { s_all++; s_hi += (p != g.k - 1 - p); }
-            }
-        }
-      else
-        { // block bounds by bisection on the (monotone) same_block predicate
-          int64_t a = 0, b = i;
-          while (a < b)
-            { const int64_t m = (a + b) >> 1;
-              if (same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
-            }
-          const int64_t blo = a;
-          a = i + 1; b = t.n;
-          while (a < b)
-            { const int64_t m = (a + b) >> 1;
-              if (!same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
-            }
-          const int64_t bhi = a;
-          for (int p = g.p0; p < g.k; p++)
-            for (int d = 1; d <= 3; d++)
-              { const Key<W> y = flip_base<W>(x, p, d);
-                const int64_t j = lower_bound_key<W>(t.keys, blo, bhi, y);
-                if (j < bhi && key_eq<W>(load_key<W>(t.keys, j), y)
-                    && c + (unsigned) t.cnt[j] <= SMG_SMAX)
-                  { s_all++; s_hi += (p != g.k - 1 - p); }
-              }
-        }
-      if (!SYM)
-        { for (int p = 0; p < g.p0; p++)
-            for (int d = 1; d <= 3; d++)
-              { const Key<W> y = flip_base<W>(x, p, d);
-                if (set)                      // (the partner may live in another shard of the same device)
-                  { int64_t j;
-                    const int sh = set_find<W>(set, y, j);
-                    if (j >= 0 && c + (unsigned) set->shard[sh].cnt[j] <= SMG_SMAX) s_all++;
-                  }
-                else
-                  { const int64_t j = find_key<W>(t.keys, t.dir, y);
-                    if (j >= 0 && c + (unsigned) t.cnt[j] <= SMG_SMAX) s_all++;
-                  }
-              }
-        }
-      t.deg[i] = (uint8_t) s_all;
-    }
-
-  if (SYM)
-    { const bool emit = live && (emit_all || s_hi > 0);
-      const u64 mask = __ballot(emit);
-      if (mask)
-        { const int lane = threadIdx.x & 63;
-          u64 base = 0;
-          if (lane == __ffsll((long long) mask) - 1)
-            base = atomicAdd(&ctrl->nreq, (u64) __popcll(mask));
-          base = __shfl(base, __ffsll((long long) mask) - 1, 64);
-          if (emit)
-            { const u64 slot = base + __popcll(mask & ((1ull << lane) - 1));
-              if ((int64_t) slot < req_cap)
-                { const Key<W> r = revcomp<W>(x, g.k);
-                  u64 *o = req + slot * (W + 1);
-#pragma unroll
-                  for (int w = 0; w < W; w++) o[w] = r.w[w];
-                  o[W] = (u64) c | ((u64) (s_hi & 0xFF) << 16);
-                }
-            }
-        }
-      if (want_fp)
-        { u64 f0 = 0, f1 = 0, f2 = 0, f3 = 0;
-          if (live)
-            { const Key<W> r = revcomp<W>(x, g.k);
-              f0 = hash_entry<W>(x, c, 0x243f6a8885a308d3ull);
-              f1 = hash_entry<W>(x, c, 0x13198a2e03707344ull);
-              f2 = hash_entry<W>(r, c, 0x243f6a8885a308d3ull);
-              f3 = hash_entry<W>(r, c, 0x13198a2e03707344ull);
-            }
-          // (XOR, as on the fast path: the entries are strictly increasing, nothing can cancel; shards XOR their residues)
-          f0 = wave_xor_u64(f0); f1 = wave_xor_u64(f1);
-          f2 = wave_xor_u64(f2); f3 = wave_xor_u64(f3);
-          if ((threadIdx.x & 63) == 0)
-            { atomicXor((unsigned long long *) &ctrl->fp[0], (unsigned long long) f0); atomicXor((unsigned long long *) &ctrl->fp[1], (unsigned long long) f1);
-              atomicXor((unsigned long long *) &ctrl->fp[2], (unsigned long long) f2); atomicXor((unsigned long long *) &ctrl->fp[3], (unsigned long long) f3);
-            }
-        }
-    }
-}
-
-// requests -> degrees (the S_hi(rc(x)) term), and the per-request symmetry proof
-template <int W> __global__ void __launch_bounds__(TPB)
-k_apply(Tab t, const u64 *__restrict__ req, int64_t nreq, Ctrl *__restrict__ ctrl)
-{ const int64_t r = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (r >= nreq) return;
-  Key<W> y;
-  const u64 *q = req + r * (W + 1);
-#pragma unroll
-  for (int w = 0; w < W; w++) y.w[w] = q[w];
-  const unsigned c = (unsigned) (q[W] & 0xFFFF), v = (unsigned) ((q[W] >> 16) & 0xFF);
-  const int64_t j = find_key<W>(t.keys, t.dir, y);
-  if (j < 0 || t.cnt[j] != c) { if (ctrl->missing == 0) ctrl->missing = 1; return; }
-  if (v) deg_add(t.deg, j, v, t.g.wrap);
-}
-
-// exact symmetry proof for every entry of [lo,hi) against the local table (single GPU)
-template <int W> __global__ void __launch_bounds__(TPB)
-k_verify(Tab t, int64_t lo, int64_t hi, Ctrl *__restrict__ ctrl)
-{ const int64_t i = lo + (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= hi) return;
-  const Key<W> r = revcomp<W>(load_key<W>(t.keys, i), t.g.k);
-  const int64_t j = find_key<W>(t.keys, t.dir, r);
-  if (j < 0 || t.cnt[j] != t.cnt[i]) { if (ctrl->missing == 0) ctrl->missing = 1; }
-}
-
-// ---- pass 2 -------------------------------------------------------------------------------
-// Entry i with (wrapped) degree <= 1 looks for its partners j > i; the pair enters the plot
-// when deg(j) <= 1 too.  SYM: pairs at p != k-1-p stand for themselves and their complement
-// image (weight 2).  General: every position is visited, weight 1.
-
-SMG_DEV void plot_add(u64 *__restrict__ plot, unsigned ci, unsigned cj, unsigned wgt)
-{ const unsigned s = ci + cj, m = ci < cj ? ci : cj;
-  atomicAdd(plot + (size_t) s * SMG_PLOT_COLS + m, (u64) wgt);
-}
-
-template <int W, bool SYM> __global__ void __launch_bounds__(TPB)
-k_pass2(Tab t, int64_t lo, int64_t hi, u64 *__restrict__ plot, const TabSet *__restrict__ set = NULL)
-{ const int64_t i = lo + (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= hi) return;
-  const Geo g = t.g;
-  const unsigned di = t.deg[i];
-  if (di > 1) return;
-  if (di == 0 && !g.wrap) return;            // no wrap possible: degree 0 means no pair at all
-  const Key<W> x = load_key<W>(t.keys, i);
-  const unsigned c = t.cnt[i];
-
-  bool big = false;
-  if (i + WIN_LIM < t.n) big = same_block<W>(x, load_key<W>(t.keys, i + WIN_LIM), g);
-  if (!big)
-    { for (int64_t j = i + 1; j < t.n; j++)
-        { const Key<W> y = load_key<W>(t.keys, j);
-          if (!same_block<W>(x, y, g)) break;
-          const int p = pair_pos<W>(x, y);
-          if (p >= 0)
-            { const unsigned cj = t.cnt[j];
-              if (c + cj <= SMG_SMAX && t.deg[j] <= 1)
-                { const unsigned wgt = (SYM && p != g.k - 1 - p) ? 2 : 1;
-                  plot_add(plot, c, cj, wgt);
-                }
-            }
-        }
-    }
-  else
-    { int64_t a = i + 1, b = t.n;
-      while (a < b)
-        { const int64_t m = (a + b) >> 1;
-          if (!same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
-        }
-      const int64_t bhi = a;
-      for (int p = g.p0; p < g.k; p++)
-        for (int d = 1; d <= 3; d++)
-          { const Key<W> y = flip_base<W>(x, p, d);
-            if (!key_lt<W>(x, y)) continue;
-            const int64_t j = lower_bound_key<W>(t.keys, i + 1, bhi, y);
-            if (j < bhi && key_eq<W>(load_key<W>(t.keys, j), y))
-              { const unsigned cj = t.cnt[j];
-                if (c + cj <= SMG_SMAX && t.deg[j] <= 1)
-                  { const unsigned wgt = (SYM && p != g.k - 1 - p) ? 2 : 1;
-                    plot_add(plot, c, cj, wgt);
-                  }
-              }
-          }
-    }
-  if (!SYM)
-    { for (int p = 0; p < g.p0; p++)
-        for (int d = 1; d <= 3; d++)
-          { const Key<W> y = flip_base<W>(x, p, d);
-            if (!key_lt<W>(x, y)) continue;
-            if (set)
-              { int64_t j;
-                const int sh = set_find<W>(set, y, j);
-                if (j >= 0)
-                  { const unsigned cj = set->shard[sh].cnt[j];
-                    if (c + cj <= SMG_SMAX && set->shard[sh].deg[j] <= 1) plot_add(plot, c, cj, 1);
-                  }
-              }
-            else
-              { const int64_t j = find_key<W>(t.keys, t.dir, y);
-                if (j >= 0)
-                  { const unsigned cj = t.cnt[j];
-                    if (c + cj <= SMG_SMAX && t.deg[j] <= 1) plot_add(plot, c, cj, 1);
-                  }
-              }
-          }
-    }
-}
-
-// ---- extract on the counted path (k > 85): the pairs pass 2 counts, as records ---------------------
-// The same walk as k_pass2<W, true>; a pair at a labelled pixel is written out like kf_extract writes it (the pair,
-// and for p != k-1-p its mirror image at k-1-p).  One global atomic per pair: this path is exact, not fast.
-template <int W> __global__ void __launch_bounds__(TPB)
-k_extract(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ out, u64 capacity, u64 *__restrict__ total)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= t.n) return;
-  const Geo g = t.g;
-  const unsigned di = t.deg[i];
-  if (di > 1) return;
-  if (di == 0 && !g.wrap) return;
-  const Key<W> x = load_key<W>(t.keys, i);
-  const unsigned c = t.cnt[i];
-  const int k = g.k;
-
-  auto emit = [&](int64_t j, const Key<W> &y, int p)
-  { const unsigned cj = t.cnt[j];
-    if (c + cj > SMG_SMAX || t.deg[j] > 1) return;
-    const unsigned sum = c + cj, mn = c < cj ? c : cj;
-    const unsigned lab = labels[(size_t) sum * SMG_PLOT_COLS + mn];
-    if (!lab) return;
-    const bool w2 = p != k - 1 - p;
-    const unsigned bi = base_at<W>(x, p), bj = base_at<W>(y, p);              // bi < bj (i < j)
-    const u64 q = atomicAdd(total, (u64) (w2 ? 2 : 1));
-    if (q < capacity)
-      { const bool pj = c < cj;                                                 // cnt[a] < cnt[b]: print b, alt base of a
-        const Key<W> &who = pj ? y : x;
-        u64 *o = out + q * (W + 1);
-#pragma unroll
-        for (int w = 0; w < W; w++) o[w] = who.w[w];
-        o[W] = (u64) p | ((u64) (pj ? bi : bj) << 8) | ((u64) lab << 16);
-      }
-    if (w2 && q + 1 < capacity)
-      { const bool pb = cj < c;                                                 // mirror image: a = rc(y), b = rc(x)
-        const Key<W> who = revcomp<W>(pb ? x : y, k);
-        u64 *o = out + (q + 1) * (W + 1);
-#pragma unroll
-        for (int w = 0; w < W; w++) o[w] = who.w[w];
-        o[W] = (u64) (k - 1 - p) | ((u64) (pb ? 3u - bj : 3u - bi) << 8) | ((u64) lab << 16);
-      }
-  };
-
-  bool big = false;
-  if (i + WIN_LIM < t.n) big = same_block<W>(x, load_key<W>(t.keys, i + WIN_LIM), g);
-  if (!big)
-    { for (int64_t j = i + 1; j < t.n; j++)
-        { const Key<W> y = load_key<W>(t.keys, j);
-          if (!same_block<W>(x, y, g)) break;
-          const int p = pair_pos<W>(x, y);
-          if (p >= 0) emit(j, y, p);
-        }
-    }
-  else
-    { int64_t a = i + 1, b = t.n;
-      while (a < b)
-        { const int64_t m = (a + b) >> 1;
-          if (!same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
-        }
-      const int64_t bhi = a;
-      for (int p = g.p0; p < g.k; p++)
-        for (int d = 1; d <= 3; d++)
-          { const Key<W> y = flip_base<W>(x, p, d);
-            if (!key_lt<W>(x, y)) continue;
-            const int64_t j = lower_bound_key<W>(t.keys, i + 1, bhi, y);
-            if (j < bhi && key_eq<W>(load_key<W>(t.keys, j), y)) emit(j, y, p);
-          }
-    }
-}
-
-// ---- extract on the general path (a table that is not closed under reverse complement): the pairs k_pass2<W, false> counts
-// The walk of k_pass2<W, false>: suffix-side partners from the window block, prefix-side partners (p < p0) looked up in the
-// table, or over virtual shards in whichever shard holds them (TabSet).  A pair is written ONCE, by its lower member, with the
-// printed member and the alt base chosen as k_extract chooses them; no mirror image (if the table holds the complement pair,
-// the walk finds it as a pair of its own).  Weight 1 per pair, as in the plot of the general path.
-// Without wrap a degree <= 1 means at most one partner: the walk stops at it, and a wave reserves the slots of its records
-// with one atomic.  A wrapped degree (k > 85: 0 or 1 mod 256) can stand for hundreds of partners: one atomic per record.
-template <int W> __global__ void __launch_bounds__(TPB)
-k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ out, u64 capacity, u64 *__restrict__ total,
-                  const TabSet *__restrict__ set)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  const Geo g = t.g;
-  bool has = false;                          // (no wrap) the one record of this lane
-  Key<W> rk; u64 rmeta = 0;
-#pragma unroll
-  for (int w = 0; w < W; w++) rk.w[w] = 0;
-  unsigned di = 2;
-  if (i < t.n) di = t.deg[i];
-  if (di <= 1 && (di == 1 || g.wrap))        // (lanes without work stay for the wave's ballot below)
-    { const Key<W> x = load_key<W>(t.keys, i);
-      const unsigned c = t.cnt[i];
-      bool done = false;
-      // a partner y > x with count cj and degree dj: -> true when the walk can stop (no wrap: the one partner was found)
-      auto visit = [&](const Key<W> &y, int p, unsigned cj, unsigned dj) -> bool
-      { if (c + cj > SMG_SMAX) return false;                                   // not a pair (nor counted in a degree)
-        const unsigned sum = c + cj, mn = c < cj ? c : cj;
-        const unsigned lab = dj <= 1 ? labels[(size_t) sum * SMG_PLOT_COLS + mn] : 0u;
-        if (lab)
-          { const bool pj = c < cj;                                               // print the larger count; tie: x (smaller base)
-            const Key<W> &who = pj ? y : x;
-            const u64 meta = (u64) p | ((u64) (pj ? base_at<W>(x, p) : base_at<W>(y, p)) << 8) | ((u64) lab << 16);
-            if (!g.wrap) { rk = who; rmeta = meta; has = true; }
-            else
-              { const u64 q = atomicAdd(total, (u64) 1);
-                if (q < capacity)
-                  { u64 *o = out + q * (W + 1);
-#pragma unroll
-                    for (int w = 0; w < W; w++) o[w] = who.w[w];
-                    o[W] = meta;
-                  }
-              }
-          }
-        return !g.wrap;
-      };
-
-      bool big = false;
-      if (i + WIN_LIM < t.n) big = same_block<W>(x, load_key<W>(t.keys, i + WIN_LIM), g);
-      if (!big)
-        { for (int64_t j = i + 1; j < t.n && !done; j++)
-            { const Key<W> y = load_key<W>(t.keys, j);
-              if (!same_block<W>(x, y, g)) break;
-              const int p = pair_pos<W>(x, y);
-              if (p >= 0) done = visit(y, p, t.cnt[j], t.deg[j]);
-            }
-        }
-      else
-        { int64_t a = i + 1, b = t.n;
-          while (a < b)
-            { const int64_t m = (a + b) >> 1;
-              if (!same_block<W>(x, load_key<W>(t.keys, m), g)) b = m; else a = m + 1;
-            }
-          const int64_t bhi = a;
-          for (int p = g.p0; p < g.k && !done; p++)
-            for (int d = 1; d <= 3 && !done; d++)
-              { const Key<W> y = flip_base<W>(x, p, d);
-                if (!key_lt<W>(x, y)) continue;
-                const int64_t j = lower_bound_key<W>(t.keys, i + 1, bhi, y);
-                if (j < bhi && key_eq<W>(load_key<W>(t.keys, j), y)) done = visit(y, p, t.cnt[j], t.deg[j]);
-              }
-        }
-      for (int p = 0; p < g.p0 && !done; p++)
-        for (int d = 1; d <= 3 && !done; d++)
-          { const Key<W> y = flip_base<W>(x, p, d);
-            if (!key_lt<W>(x, y)) continue;
-            if (set)
-              { int64_t j;
-                const int sh = set_find<W>(set, y, j);
-                if (j >= 0) done = visit(y, p, set->shard[sh].cnt[j], set->shard[sh].deg[j]);
-              }
-            else
-              { const int64_t j = find_key<W>(t.keys, t.dir, y);
-                if (j >= 0) done = visit(y, p, t.cnt[j], t.deg[j]);
-              }
-          }
-    }
-  if (g.wrap) return;                        // (uniform over the grid)
-  const u64 mask = __ballot(has);
-  if (!mask) return;
-  const int lead = __ffsll((long long) mask) - 1;
-  u64 base = 0;
-  if ((int) (threadIdx.x & 63) == lead) base = atomicAdd(total, (u64) __popcll(mask));
-  base = __shfl(base, lead, 64);
-  if (has)
-    { const u64 q = base + __builtin_amdgcn_mbcnt_hi((unsigned) (mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) mask, 0u));
-      if (q < capacity)
-        { u64 *o = out + q * (W + 1);
-#pragma unroll
-          for (int w = 0; w < W; w++) o[w] = rk.w[w];
-          o[W] = rmeta;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 //  Host side
 // ------------------------------------------------------------------------------------------
 
@@ -683,6 +96,12 @@ k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ 
 
 typedef void (*P1Kernel)(P1Hot, const P1Cold *);          // an instantiation of kf_pass1_d (p1_kernel)
 
+// the timing events, in pairs around: decode or conditioning (the first also starts kf_collect + kf_bigfix, whose time ends with
+// pass 1's), pass 1, the look-ups (filter included), pass 2, the whole run, the filter of a replayed step, extract;
+// EV_PROBE_BEG sits between the partition and the probe of the look-up chain
+enum Ev { EV_DECODE_BEG, EV_DECODE_END, EV_PASS1_BEG, EV_PASS1_END, EV_LOOKUP_BEG, EV_LOOKUP_END, EV_PASS2_BEG, EV_PASS2_END,
+          EV_RUN_BEG, EV_RUN_END, EV_PROBE_BEG, EV_REPLAY_FILTER_BEG, EV_REPLAY_FILTER_END, EV_EXTRACT_BEG, EV_EXTRACT_END, EV_COUNT };
+
 struct smg_engine
 { int          device;
   hipStream_t  stream;
@@ -690,12 +109,13 @@ struct smg_engine
   int64_t      n;
   const u64   *keys;          // bound or owned
   const uint16_t *cnt;
-  u64         *own_keys;      // owned copies (decode path)
-  uint16_t    *own_cnt;
-  uint8_t     *deg;    int64_t deg_cap;      // degree bytes (counted path) / code bytes (fast path)
-  uint16_t    *sig;    int64_t sig_cap;       // k <= 32: look-up signatures (2 bytes per entry)
-  uint32_t    *bstart; int64_t bstart_cap;
-  uint32_t    *ixdir;  int64_t ixdir_cap;    // the table's own FastK prefix index (2^24 + 1 bucket starts, relative to this shard) as directory
+  // (every device allocation is a DevBuf: grown where it is used by reserve(), freed with the engine)
+  DevBuf<u64>  own_keys;      // owned copies (decode path)
+  DevBuf<uint16_t> own_cnt;
+  DevBuf<uint8_t>  deg;       // degree bytes (counted path) / code bytes (fast path)
+  DevBuf<uint16_t> sig;       // k <= 32: look-up signatures (2 bytes per entry)
+  DevBuf<uint32_t> bstart;
+  DevBuf<uint32_t> ixdir;     // the table's own FastK prefix index (2^24 + 1 bucket starts, relative to this shard) as directory
   bool         have_ixdir;                   //   ... handed over with the current table (smg_engine_set_prefix_index); gone when the table changes
   bool         dir_preset;                   //   the current run looks up through ixdir: pass 1 writes no directory
   bool         have_ends;  u64 end_first, end_last;     // leading words of the first and the last entry of the bound table (read once)
@@ -707,39 +127,39 @@ struct smg_engine
   int64_t      rp_nreq, rp_nbig, rp_nf_req;    //   pass 1: requests, deferred entries; filter: requests kept
   unsigned     rp_nf_chunks, rp_grid;          //   filter: chunks of the kept list (the list the routing kernels walk); pass-1 grid (rows of `partials`)
   unsigned     rp_seen_chunks;                 //   chunks the plain step's filter filled (a replayed step walks that many + slack)
-  u64         *rp_totals;  int rp_nranks;      //   router: per-destination totals of the recorded step (device, 16 words) and of this step (16 more)
+  DevBuf<u64>  rp_totals; int rp_nranks;      //   router: per-destination totals of the recorded step (device, 16 words) and of this step (16 more)
   bool         rp_routed;                      //   ... this step's totals are there to be compared
   int          rp_bm_bits, rp_sym;             //   map geometry and proof the record belongs to
-  u64         *req;    int64_t req_cap;      // bytes
-  u64         *req2;   int64_t req2_cap;     // radix sort output
-  void        *sort_tmp; int64_t sort_tmp_cap;
-  u64         *dense;  int64_t dense_cap;    // compacted requests
-  uint32_t    *chunk_off; int64_t chunk_off_cap;
-  uint32_t    *skey[2]; int64_t skey_cap[2];   // index sort of wide records: leading k-mer bits (in, out)
-  uint32_t    *sidx[2]; int64_t sidx_cap[2];   //                                  record numbers (in, out)
-  uint32_t    *dbits;  int64_t dbits_cap;      // deferred entries of kf_pass1_d: one bit per table entry (bytes); all zero between runs
-  bool         dbits_dirty;                     //   ... unless a run was abandoned between pass 1 and kf_bigfix
-  uint32_t    *biglist; int64_t biglist_cap;    // the marked entries, compacted (kf_collect), bytes
-  unsigned    *p1tick;  int64_t p1tick_cap;     // tile tickets of kf_pass1_d
-  unsigned    *xtick;   int64_t xtick_cap;      // (bucket, part) tickets of kl_probe_x, one counter per XCD
-  uint32_t    *farp;    int64_t farp_cap;       // beside it: the partner of a listed entry whose code is CODE_FAR (kf_bigfix -> kf_pass2_far)
+  DevBuf<u64>  req;
+  DevBuf<u64>  req2;          // radix sort output
+  Dev          sort_tmp;      // rocPRIM's scratch (with_scratch)
+  DevBuf<u64>  dense;         // compacted requests
+  DevBuf<uint32_t> chunk_off;
+  DevBuf<uint32_t> skey[2];   // index sort of wide records: leading k-mer bits (in, out)
+  DevBuf<uint32_t> sidx[2];   //                                  record numbers (in, out)
+  DevBuf<uint32_t> dbits;     // deferred entries of kf_pass1_d: one bit per table entry; all zero between runs
+  bool         dbits_dirty;   //   ... unless a run was abandoned between pass 1 and kf_bigfix
+  DevBuf<uint32_t> biglist;   // the marked entries, compacted (kf_collect)
+  DevBuf<unsigned> p1tick;    // tile tickets of kf_pass1_d
+  DevBuf<unsigned> xtick;     // (bucket, part) tickets of kl_probe_x, one counter per XCD
+  DevBuf<uint32_t> farp;      // beside it: the partner of a listed entry whose code is CODE_FAR (kf_bigfix -> kf_pass2_far)
   int          rw;                           // 64-bit words per request record
-  uint32_t    *chunk_fill; int64_t chunk_cap; // bytes
+  DevBuf<uint32_t> chunk_fill;
   unsigned     max_chunks;
-  uint32_t    *bmap;   int64_t bmap_cap;     // candidate block map (request filter)
+  DevBuf<uint32_t> bmap;      // candidate block map (request filter)
   int          bm_bits;                      //   leading k-mer bits per block id (0 = not built by the last pass 1)
   bool         filtered;                     //   the request list of the last pass 1 has been filtered
   int          presorted;                    //   0 not decided, 1 req2 holds the list bucketed on its leading 8 bits, 2 left as it is
-  u64         *reqf;   int64_t reqf_cap;     // filtered request chunks (swapped with req)
-  uint32_t    *chunk_fillf; int64_t chunk_capf;
-  uint32_t    *route_cnt;  int64_t route_cnt_cap;
-  u64         *route_off;  int64_t route_off_cap;
-  u64         *partials;   // [P1_MAXGRID][4]
-  unsigned    *ghist;      // look-up chain: requests per bucket [L_BK], bucket cursor `bnext` behind it
-  unsigned    *whist;  int64_t whist_cap;     //   requests per owner and bucket [owners][L_BK] (owner = a workgroup of pass 1 / kf_bigfix)
+  DevBuf<u64>  reqf;          // filtered request chunks (swapped with req)
+  DevBuf<uint32_t> chunk_fillf;
+  DevBuf<uint32_t> route_cnt;
+  DevBuf<u64>  route_off;
+  DevBuf<u64>  partials;   // [P1_MAXGRID][4]
+  DevBuf<unsigned> ghist;  // look-up chain: requests per bucket [L_BK], bucket cursor `bnext` behind it
+  DevBuf<unsigned> whist;  //   requests per owner and bucket [owners][L_BK] (owner = a workgroup of pass 1 / kf_bigfix)
   unsigned     p1grid, nown; //  workgroups of the last pass 1; owners of the request list (+ BF_MAXGRID for kf_bigfix):
                            //   owner w fills the chunk slots w, w + nown, w + 2 nown, ..
-  u64         *boff;       //   bucket offsets [L_BK + 1] and scatter cursors [L_BK] behind them
+  DevBuf<u64>  boff;       //   bucket offsets [L_BK + 1] and scatter cursors [L_BK] behind them
   LookupGeo    lg;         //   geometry of the current run (lg.nb = 0: the round-1 chain is used)
   int          probe_form; //   the probe kernel of the last filter / look-up: 0 none, 1 kl_probe fused, 2 kl_probe_x, 3 kl_probe list
   unsigned     probe_part; //   ... and the requests per ticket it passed to kl_probe_x (0 otherwise): smg_engine_lookup_state
@@ -751,10 +171,10 @@ struct smg_engine
   int          one_way;    //   this run's requests are one-way (smg_fast.hpp): set by fast_pass1 for smg_engine_run, never by the phase API
   int          bm_cap;     //   id bits of the block map: 32 on one GPU, 30 when the maps of several shards are exchanged
   int          bm_want;    //   ... as asked for by smg_engine_set_blockmap_bits (0: default)
-  P1Cold      *p1cold;     // rarely used arguments of kf_pass1_d (device copy)
+  DevBuf<P1Cold> p1cold;   // rarely used arguments of kf_pass1_d (device copy)
   P1Cold      *h_p1cold;   // pinned staging
-  u64         *d_split;
-  Ctrl        *ctrl;
+  DevBuf<u64>  d_split;
+  DevBuf<Ctrl> ctrl;
   Ctrl        *h_ctrl;        // pinned mirror
   u64         *h_partials;    // pinned
   Geo          geo;
@@ -767,8 +187,8 @@ struct smg_engine
   unsigned     n_chunks;
   u64          fp[4];
   smg_stats    st;
-  hipEvent_t   ev[15];        // 0,1 decode  2,3 pass 1  4,5 look-ups  6,7 pass 2  8,9 whole run  10 between partition and probe  11,12 filter of a replayed step
-                              // 13,14 extract
+  int          cus;           // compute units of the device (256 where it does not say)
+  hipEvent_t   ev[EV_COUNT];
   bool         general_done;  // the general path has run (st.path == 2): deg[] holds the degrees over all positions
   float        ms_extract;    // device time of the last extract launch
 };
@@ -784,11 +204,11 @@ static int fail(char *errbuf, size_t errlen, int code, const char *fmt, const ch
          return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV,     \
                      "HIP error: %s (" #call ")", hipGetErrorString(_e)); } while (0)
 
-#define DISPATCH_W(e, CALL)                                                                   \
-  switch ((e)->W) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;  \
-                    default: CALL(4); break; }
-#define DISPATCH_W3(e, CALL)                                                                  \
-  switch ((e)->W) { case 1: CALL(1); break; case 2: CALL(2); break; default: CALL(3); break; }
+static float ms_between(smg_engine *e, Ev a, Ev b)
+{ float ms = 0;
+  hipEventElapsedTime(&ms, e->ev[a], e->ev[b]);
+  return ms;
+}
 
 extern "C" const char *smg_version(void) { return "smudgeplot_amd 0.4 (hetmers engine, gfx950)"; }
 
@@ -810,24 +230,23 @@ extern "C" smg_engine *smg_engine_create(int device, void *stream, char *errbuf,
     { fail(errbuf, errlen, SMG_ENODEV, "cannot select HIP device%s"); return NULL; }
   smg_engine *e = new (std::nothrow) smg_engine();
   if (!e) { fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s"); return NULL; }
-  memset(e, 0, sizeof(*e));
   e->device = device;
   e->stream = (hipStream_t) stream;
   e->bm_cap = 30;
-  if (hipMalloc(&e->ctrl, sizeof(Ctrl)) != hipSuccess
+  if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || e->cus < 1) e->cus = 256;
+  for (int i = 0; i < EV_COUNT; i++) hipEventCreate(&e->ev[i]);
+  if (e->ctrl.alloc(sizeof(Ctrl)) != hipSuccess
       || hipHostMalloc(&e->h_ctrl, sizeof(Ctrl)) != hipSuccess
-      || hipMalloc(&e->partials, sizeof(u64) * 4 * (P1_MAXGRID + 1)) != hipSuccess      // (+ a row for the proof words)
+      || e->partials.alloc(sizeof(u64) * 4 * (P1_MAXGRID + 1)) != hipSuccess      // (+ a row for the proof words)
       || hipHostMalloc(&e->h_partials, sizeof(u64) * 4 * P1_MAXGRID) != hipSuccess
-      || hipMalloc(&e->d_split, sizeof(u64) * 16 * 4) != hipSuccess
-      || hipMalloc(&e->p1cold, sizeof(P1Cold)) != hipSuccess
-      || hipMalloc(&e->ghist, sizeof(unsigned) * (L_BK + 4)) != hipSuccess
-
-      || hipMalloc(&e->boff, sizeof(u64) * (2 * L_BK + 4)) != hipSuccess
+      || e->d_split.alloc(sizeof(u64) * 16 * 4) != hipSuccess
+      || e->p1cold.alloc(sizeof(P1Cold)) != hipSuccess
+      || e->ghist.alloc(sizeof(unsigned) * (L_BK + 4)) != hipSuccess
+      || e->boff.alloc(sizeof(u64) * (2 * L_BK + 4)) != hipSuccess
       || hipHostMalloc(&e->h_p1cold, sizeof(P1Cold)) != hipSuccess)
     { fail(errbuf, errlen, SMG_ENOMEM, "cannot allocate the control block%s");
-      delete e; return NULL;
+      smg_engine_destroy(e); return NULL;
     }
-  for (int i = 0; i < 15; i++) hipEventCreate(&e->ev[i]);
   return e;
 }
 
@@ -835,13 +254,9 @@ extern "C" void smg_engine_destroy(smg_engine *e)
 { if (!e) return;
   hipSetDevice(e->device);
   hipStreamSynchronize(e->stream);
-  hipFree(e->own_keys); hipFree(e->own_cnt); hipFree(e->deg); hipFree(e->sig); hipFree(e->bstart); hipFree(e->ixdir);
-  hipFree(e->req); hipFree(e->req2); hipFree(e->sort_tmp); hipFree(e->dense); hipFree(e->chunk_off); hipFree(e->skey[0]); hipFree(e->skey[1]); hipFree(e->sidx[0]); hipFree(e->sidx[1]); hipFree(e->dbits); hipFree(e->biglist); hipFree(e->farp); hipFree(e->p1tick); hipFree(e->xtick); hipFree(e->chunk_fill); hipFree(e->bmap); hipFree(e->reqf); hipFree(e->chunk_fillf); hipFree(e->route_cnt); hipFree(e->route_off);
-  hipFree(e->partials); hipFree(e->ctrl); hipFree(e->d_split); hipFree(e->p1cold); hipFree(e->ghist); hipFree(e->boff);
-  hipFree(e->whist); hipFree(e->rp_totals);
   hipHostFree(e->h_ctrl); hipHostFree(e->h_partials); hipHostFree(e->h_p1cold);
-  for (int i = 0; i < 15; i++) hipEventDestroy(e->ev[i]);
-  delete e;
+  for (int i = 0; i < EV_COUNT; i++) hipEventDestroy(e->ev[i]);
+  delete e;                                  // (frees every device buffer)
 }
 
 static int set_table(smg_engine *e, int kmer, int64_t nels, char *errbuf, size_t errlen)
@@ -875,15 +290,6 @@ static void set_geo(smg_engine *e)
   g.wrap = e->kmer > FAST_MAX_K;
 }
 
-template <typename T> static int grow(T **p, int64_t *cap, int64_t need_bytes, char *errbuf, size_t errlen)
-{ if (*cap >= need_bytes && *p) return SMG_OK;
-  if (*p) hipFree(*p);
-  *p = NULL; *cap = 0;
-  HIPCHK(hipMalloc((void **) p, (size_t) need_bytes));
-  *cap = need_bytes;
-  return SMG_OK;
-}
-
 extern "C" int smg_engine_bind(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys,
                                const uint16_t *d_counts, char *errbuf, size_t errlen)
 { if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
@@ -898,94 +304,7 @@ extern "C" int smg_engine_bind(smg_engine *e, int kmer, int64_t nels, const uint
   return SMG_OK;
 }
 
-// the engine's own table for `nels` entries of a format-F table (allocated, not filled yet)
-static int decode_begin(smg_engine *e, int kmer, int ibyte, int64_t nels, char *errbuf, size_t errlen)
-{ if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (ibyte < 1 || ibyte > 3) return fail(errbuf, errlen, SMG_EINVAL, "ibyte must be 1, 2 or 3%s");
-  HIPCHK(hipSetDevice(e->device));
-  int rc = set_table(e, kmer, nels, errbuf, errlen);
-  if (rc) return rc;
-  const int kbyte = (kmer + 3) >> 2;
-  if (kbyte <= ibyte) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
-  hipFree(e->own_keys); hipFree(e->own_cnt);
-  e->own_keys = NULL; e->own_cnt = NULL;
-  HIPCHK(hipMalloc(&e->own_keys, sizeof(u64) * (size_t) (nels > 0 ? nels : 1) * e->W));
-  HIPCHK(hipMalloc(&e->own_cnt, sizeof(uint16_t) * (size_t) (nels > 0 ? nels : 1) + 16));
-  e->keys = e->own_keys; e->cnt = e->own_cnt;
-  return SMG_OK;
-}
-
-// decode `nent` records at d_records into the entries [first, first + nent) of the engine's table; the first of them is
-// entry ibase + first of the whole table (whose prefix index is d_prefix_index).  Queued on `stream`.
-static int decode_piece(smg_engine *e, hipStream_t stream, int ibyte, const uint8_t *d_records, const int64_t *d_prefix_index,
-                        int64_t ibase, int64_t first, int64_t nent)
-{ if (nent <= 0) return 0;
-  const int kbyte = (e->kmer + 3) >> 2;
-  const unsigned nblk = (unsigned) ((nent + DEC_TILE - 1) / DEC_TILE);
-#define CALL(WW) hipLaunchKernelGGL(k_decode<WW>, dim3(nblk), dim3(TPB), dec_lds_bytes(kbyte + 2 - ibyte), stream, d_records, \
-                         d_prefix_index, 1 << (8 * ibyte), ibyte, kbyte, nent, ibase + first, e->own_keys + first * e->W, e->own_cnt + first)
-  DISPATCH_W(e, CALL)
-#undef CALL
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-static int decode_at(smg_engine *e, int kmer, int ibyte, int64_t nels, int64_t ibase, const uint8_t *d_records,
-                     const int64_t *d_prefix_index, char *errbuf, size_t errlen)
-{ int rc = decode_begin(e, kmer, ibyte, nels, errbuf, errlen);
-  if (rc) return rc;
-  hipEventRecord(e->ev[0], e->stream);
-  if (decode_piece(e, e->stream, ibyte, d_records, d_prefix_index, ibase, 0, nels))
-    return fail(errbuf, errlen, SMG_ENODEV, "decode launch failed%s");
-  hipEventRecord(e->ev[1], e->stream);
-  HIPCHK(hipStreamSynchronize(e->stream));
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
-  e->st.ms_decode = ms;
-  return SMG_OK;
-}
-
-// ingest hook: decode a piece behind its copy (smg_ingest.hpp)
-struct DecodeHook { smg_engine *e; const int64_t *d_index; int ibyte; int64_t ibase; };
-static int decode_hook(void *ctx, hipStream_t stream, const uint8_t *d_piece, int64_t first, int64_t nent)
-{ DecodeHook *h = (DecodeHook *) ctx;
-  return decode_piece(h->e, stream, h->ibyte, d_piece, h->d_index, h->ibase, first, nent);
-}
-
-extern "C" int smg_engine_decode(smg_engine *e, int kmer, int ibyte, int64_t nels,
-                                 const uint8_t *d_records, const int64_t *d_prefix_index,
-                                 char *errbuf, size_t errlen)
-{ return decode_at(e, kmer, ibyte, nels, 0, d_records, d_prefix_index, errbuf, errlen); }
-
-// ---- the table's own prefix index as look-up directory -------------------------------------------------------------
-// A FastK table carries the number of entries up to every 3-byte prefix (libfastk.c:841, `index[p]` = entries whose first
-// ibyte bytes are <= p).  With ibyte = 3 that IS a bucket directory over the leading 24 k-mer bits (bucket = hi32 >> 8;
-// ~150 entries per bucket at 2.5e9 entries): ixdir[b] = first entry of bucket b relative to this shard, ixdir[2^24] = n.
-// Pass 1 then writes no directory at all (round 3: a shift, a compare and a rare store per entry, and 130 MB cleared per
-// run); the few million look-ups that survive the request filter bisect one or two steps longer.
-#define IXDIR_BITS 24
-__global__ void __launch_bounds__(TPB)
-k_index_dir(const int64_t *__restrict__ index, int64_t ibase, int64_t n, uint32_t *__restrict__ out)
-{ const int64_t b = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (b > (1ll << IXDIR_BITS)) return;
-  int64_t v = (b ? index[b - 1] : 0) - ibase;
-  if (b == (1ll << IXDIR_BITS)) v = n;
-  out[b] = (uint32_t) (v < 0 ? 0 : v > n ? n : v);
-}
-
-extern "C" int smg_engine_set_prefix_index(smg_engine *e, const int64_t *d_prefix_index, int ibyte, int64_t first_entry,
-                                           char *errbuf, size_t errlen)
-{ if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (ibyte < 1 || ibyte > 3 || !d_prefix_index) return fail(errbuf, errlen, SMG_EINVAL, "prefix index: ibyte must be 1, 2 or 3%s");
-  e->have_ixdir = false;
-  if (ibyte != 3 || e->kmer < 12 || test_hook("SMG_NO_INDEX_DIR")) return SMG_OK;     // (a coarser index is of no use as a directory)
-  HIPCHK(hipSetDevice(e->device));
-  int rc = grow(&e->ixdir, &e->ixdir_cap, (int64_t) sizeof(uint32_t) * ((1ll << IXDIR_BITS) + 2), errbuf, errlen);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_index_dir, dim3((unsigned) (((1ll << IXDIR_BITS) + 1 + TPB - 1) / TPB)), dim3(TPB), 0, e->stream,
-                     d_prefix_index, first_entry, e->n, e->ixdir);
-  HIPCHK(hipGetLastError());
-  e->have_ixdir = true;
-  return SMG_OK;
-}
+#include "smg_decode.hpp"
 
 static int read_ctrl(smg_engine *e, char *errbuf, size_t errlen)
 { HIPCHK(hipMemcpyAsync(e->h_ctrl, e->ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, e->stream));
@@ -1022,36 +341,8 @@ static int dir_geometry(smg_engine *e, int per, char *errbuf, size_t errlen, boo
   e->dir.b0 = hf >> dsh;
   e->dir.dsh = dsh;
   e->dir.nb = (hl >> dsh) - (hf >> dsh) + 1;
-  int rc = grow(&e->bstart, &e->bstart_cap, (int64_t) sizeof(uint32_t) * ((int64_t) e->dir.nb + 2), errbuf, errlen);
-  if (rc) return rc;
+  HIPCHK(e->bstart.reserve((int64_t) sizeof(uint32_t) * ((int64_t) e->dir.nb + 2)));
   e->dir.bstart = e->bstart;
-  return SMG_OK;
-}
-
-// ---- counted path (k > 85, and the general all-positions fallback at any k) ---------------------
-
-static Tab make_tab(smg_engine *e)
-{ Tab t;
-  t.keys = e->keys; t.cnt = e->cnt; t.deg = e->deg; t.n = e->n; t.g = e->geo; t.dir = e->dir;
-  return t;
-}
-
-static int counted_prepare(smg_engine *e, char *errbuf, size_t errlen)
-{ HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
-  set_geo(e);
-  e->fast = false; e->counted_done = false; e->general_done = false;
-  const int64_t dbytes = ((e->n + 3) & ~3ll) + 4;
-  int rc = grow(&e->deg, &e->deg_cap, dbytes, errbuf, errlen);
-  if (rc) return rc;
-  HIPCHK(hipMemsetAsync(e->deg, 0, (size_t) dbytes, e->stream));
-  if ((rc = dir_geometry(e, 8, errbuf, errlen))) return rc;
-  HIPCHK(hipMemsetAsync(e->bstart, 0xFF, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
-  Tab t = make_tab(e);
-  const unsigned nblk = (unsigned) ((e->n + 1 + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_directory<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl)
-  DISPATCH_W(e, CALL)
-#undef CALL
-  HIPCHK(hipGetLastError());
   return SMG_OK;
 }
 
@@ -1064,194 +355,7 @@ static int plot_sum(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
   return SMG_OK;
 }
 
-__global__ void __launch_bounds__(TPB) kc_fill_u32(uint32_t *__restrict__ p, int64_t n, uint32_t v, uint32_t last)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i < n) p[i] = i == n - 1 ? last : v;
-}
-
-// The launches of both paths, each over the whole table, between its pair of events and dispatched on W.  What the
-// one-shot run and the phase API do differently (emit_all, the first size of the record list, k_verify) is their callers'.
-
-// k_pass1<W, SYM>: events 2, 3
-template <bool SYM> static void launch_pass1(smg_engine *e, int emit_all, int want_fp, u64 *req, int64_t cap, const TabSet *d_set)
-{ const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  Tab t = make_tab(e);
-  hipEventRecord(e->ev[2], e->stream);
-  if (e->n > 0)
-    {
-#define CALL(WW) hipLaunchKernelGGL((k_pass1<WW, SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, emit_all, want_fp, req, cap, e->ctrl, d_set)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[3], e->stream);
-}
-
-// k_apply<W> over nrec records, then (verify) k_verify<W> over the table: events 4, 5
-static void launch_apply(smg_engine *e, const u64 *rec, int64_t nrec, bool verify)
-{ Tab t = make_tab(e);
-  hipEventRecord(e->ev[4], e->stream);
-  if (nrec > 0)
-    { const unsigned rb = (unsigned) ((nrec + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_apply<WW>, dim3(rb), dim3(TPB), 0, e->stream, t, rec, nrec, e->ctrl)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  if (verify && e->n > 0)
-    { const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_verify<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, (int64_t) 0, e->n, e->ctrl)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[5], e->stream);
-}
-
-// the plot cleared, then k_pass2<W, SYM>: events 6, 7
-template <bool SYM> static int launch_pass2(smg_engine *e, int64_t *d_plot, const TabSet *d_set, char *errbuf, size_t errlen)
-{ HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
-  hipEventRecord(e->ev[6], e->stream);
-  if (e->n > 0)
-    { Tab t = make_tab(e);
-      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL((k_pass2<WW, SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t, \
-                   (int64_t) 0, e->n, (u64 *) d_plot, d_set)
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  hipEventRecord(e->ev[7], e->stream);
-  HIPCHK(hipGetLastError());
-  return SMG_OK;
-}
-
-// Pass 1 of the symmetric half-scan = k_pass1<W, true>: S_all into deg[], records (rc(x), count | S_hi << 16) from the
-// owners of a hi-side pair (emit_all: from every entry) into the flat list e->req, which holds `cap` records at first and,
-// where pass 1 counted more, that many on the second attempt.
-static int counted_pass1(smg_engine *e, int emit_all, int symcheck, int64_t cap, char *errbuf, size_t errlen)
-{ int rc;
-  if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
-  for (int attempt = 0; attempt < 2; attempt++)
-    { if ((rc = grow(&e->req, &e->req_cap, cap * (int64_t) sizeof(u64) * (e->W + 1), errbuf, errlen))) return rc;
-      launch_pass1<true>(e, emit_all, symcheck == SMG_SYM_HASH, e->req, cap, NULL);
-      if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-      if (e->h_ctrl->unsorted)
-        return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
-      if ((int64_t) e->h_ctrl->nreq <= cap) break;
-      cap = (int64_t) e->h_ctrl->nreq;
-      HIPCHK(hipMemsetAsync(&e->ctrl->nreq, 0, sizeof(u64), e->stream));
-      HIPCHK(hipMemsetAsync(e->ctrl->fp, 0, sizeof(u64) * 4, e->stream));
-    }
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
-  e->st.ms_pass1 = ms;
-  e->st.nrequests = (int64_t) e->h_ctrl->nreq;
-  return SMG_OK;
-}
-
-// symmetric half-scan with counted degrees (exact uint8 wrap emulation), k > 85
-static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool *symmetric,
-                             char *errbuf, size_t errlen)
-{ int rc;
-  if ((rc = counted_pass1(e, 0, symcheck, e->n / 4 + 1024, errbuf, errlen))) return rc;
-  launch_apply(e, e->req, e->st.nrequests, symcheck == SMG_SYM_EXACT);
-  if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
-  e->st.ms_rclookup = ms;
-  *symmetric = e->h_ctrl->missing == 0;
-  if (*symmetric && symcheck == SMG_SYM_HASH)
-    *symmetric = e->h_ctrl->fp[0] == e->h_ctrl->fp[2] && e->h_ctrl->fp[1] == e->h_ctrl->fp[3];
-  if (!*symmetric) return SMG_OK;
-  if ((rc = launch_pass2<true>(e, d_plot, NULL, errbuf, errlen))) return rc;
-  if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
-  hipEventElapsedTime(&ms, e->ev[6], e->ev[7]);
-  e->st.ms_pass2 = ms;
-  e->st.path = 1;
-  e->counted_done = true;
-  return SMG_OK;
-}
-
-// The same in the steps of the phase API (sharded runs): the flat list is presented to the router as full chunks of F_CH
-// records; a received record adds S_hi to the degree of its k-mer (the uint8 wrap of PloidyPlot.c:163 emulated by deg_add)
-// and proves that the k-mer is there with the same count.  The exact proof emits from every entry instead of k_verify.
-static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
-{ const int emit_all = symcheck == SMG_SYM_EXACT;
-  e->rw = e->W + 1;
-  int rc = counted_pass1(e, emit_all, symcheck, (emit_all ? e->n : e->n / 4) + 1024, errbuf, errlen);
-  if (rc) return rc;
-  const int64_t nreq = e->st.nrequests;
-  for (int i = 0; i < 4; i++) e->fp[i] = e->h_ctrl->fp[i];
-  const int64_t nc = (nreq + F_CH - 1) / F_CH;
-  if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large%s");
-  if ((rc = grow(&e->chunk_fill, &e->chunk_cap, nc * 4 + 4, errbuf, errlen))) return rc;
-  if (nc > 0)
-    hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->chunk_fill, nc, (uint32_t) F_CH,
-                       (uint32_t) (nreq - (nc - 1) * F_CH));
-  HIPCHK(hipGetLastError());
-  e->n_chunks = (unsigned) nc; e->bm_bits = 0; e->filtered = false; e->presorted = false;
-  e->st.path = 1; e->st.ms_filter = 0;
-  e->prepared = true;                     // (with e->fast == false: the counted steps)
-  return SMG_OK;
-}
-
-static int counted_phase_apply(smg_engine *e, const u64 *rec, int64_t nrec, int64_t *missing, char *errbuf, size_t errlen)
-{ launch_apply(e, rec, nrec, false);
-  HIPCHK(hipGetLastError());
-  if (!missing) { e->lookup_pending = true; return SMG_OK; }
-  const int rc = read_ctrl(e, errbuf, errlen);
-  if (rc) return rc;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
-  e->st.ms_rclookup += ms;
-  *missing = (int64_t) e->h_ctrl->missing;
-  return SMG_OK;
-}
-
-static int counted_phase_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
-{ const int rc = launch_pass2<true>(e, d_plot, NULL, errbuf, errlen);
-  if (rc) return rc;
-  e->st.path = 1; e->st.npairs = 0; e->st.ms_pass2 = -1.0;      // (no host wait: smg_engine_stats resolves the events)
-  e->counted_done = true;
-  return SMG_OK;
-}
-
-// general (assumption-free) path: both passes over every position
-static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
-{ int rc;
-  if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
-  launch_pass1<false>(e, 0, 0, NULL, 0, NULL);
-  if ((rc = launch_pass2<false>(e, d_plot, NULL, errbuf, errlen))) return rc;
-  if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
-  if (e->h_ctrl->unsorted)
-    return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
-  float ms = 0;
-  hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 += ms;
-  hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->st.ms_pass2 = ms;
-  e->st.path = 2;
-  e->general_done = true;
-  return SMG_OK;
-}
-
-// the general path of ONE shard of a table whose shards all live on this device (smg_multi.hpp: virtual shards): step 1
-// builds the directory and the degree array (then the caller collects the Tabs of all shards into a TabSet on the
-// device), step 2 = pass 1 (degrees, over all positions), step 3 = pass 2 -- a barrier between the steps is the caller's.
-static int general_shard_prepare(smg_engine *e, Tab *out, char *errbuf, size_t errlen)
-{ int rc = counted_prepare(e, errbuf, errlen);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(e->stream));
-  *out = make_tab(e);
-  return SMG_OK;
-}
-
-static int general_shard_pass(smg_engine *e, const TabSet *d_set, int pass, int64_t *d_plot, char *errbuf, size_t errlen)
-{ int rc = SMG_OK;
-  if (pass == 1) launch_pass1<false>(e, 0, 0, NULL, 0, d_set);
-  else rc = launch_pass2<false>(e, d_plot, d_set, errbuf, errlen);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-  if (e->h_ctrl->unsorted) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
-  float ms = 0;
-  if (pass == 1) { hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 += ms; }
-  else { hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); e->st.ms_pass2 = ms; e->st.path = 2; e->general_done = true; }
-  return SMG_OK;
-}
+#include "smg_counted.hpp"
 
 // ---- fast path (k <= 85) --------------------------------------------------------------------------
 
@@ -1291,6 +395,8 @@ static P1Kernel p1_kernel(int W, int rw, bool odd, bool kf, int var)
 }
 
 static int bm_id_bits(int kmer, int cap);
+// 32-bit words of a block map of 2^bits ids (two-bit map, smg_fast.hpp: 64 bits per 32 ids)
+static inline int64_t bm_words(int bits, int two_bit) { return (((1ll << bits) + 31) >> 5) << two_bit; }
 // (k = 1 has no prefix bases to name a block by)
 static bool filter_ok(const smg_engine *e)
 { return e->kmer >= 2 && ((e->W == 1 && e->rw == 1) || (e->W == 2 && e->rw != 1) || (e->W == 3 && e->rw == 4)); }
@@ -1315,7 +421,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   set_geo(e);
   e->fast = true; e->counted_done = false; e->general_done = false;
   e->p1_var = 0; e->p1_w = e->W; e->p1_rw = e->rw;
-  if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
+  HIPCHK(e->deg.reserve(((e->n + 15) & ~15ll) + 32));
   const int64_t pbytes = ((e->n + 15) & ~15ll) + 32;
   e->use_sig = e->W <= 2;
   // (hash proof of one- and two-word k-mers: the table's own prefix index, when it came with one, is the directory)
@@ -1332,8 +438,8 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
       // ... with the two-bit map (smg_fast.hpp) when the k-mer has bits below the id to hash (a function of k and the
       // environment alone: every shard of a table decides the same)
       e->bm2 = (chain && e->kmer >= 24 && !test_hook("SMG_ONE_BIT_MAP")) ? 1 : 0;
-      const int64_t bytes = (4 * (((1ll << nbits) + 31) >> 5) + 4 * D_BMW + 64) << e->bm2;
-      if ((rc = grow(&e->bmap, &e->bmap_cap, bytes, errbuf, errlen))) return rc;
+      const int64_t bytes = 4 * bm_words(nbits, e->bm2) + ((4 * D_BMW + 64) << e->bm2);
+      HIPCHK(e->bmap.reserve(bytes));
       HIPCHK(hipMemsetAsync(e->bmap, 0, (size_t) bytes, e->stream));
       e->bm_bits = nbits;
       if (chain) e->lg = lookup_geo(nbits);
@@ -1344,7 +450,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
       if (chain && e->bm2 && nbits >= 32) e->use_sig = false;
     }
   { const char *v = test_hook("SMG_SIG"); if (v && e->W <= 2) e->use_sig = atoi(v) != 0; }
-  if (e->use_sig && (rc = grow(&e->sig, &e->sig_cap, 2 * pbytes, errbuf, errlen))) return rc;
+  if (e->use_sig) HIPCHK(e->sig.reserve(2 * pbytes));
   if (e->n > 0 && !e->dir_preset)
     HIPCHK(hipMemsetAsync(e->bstart, 0xFF, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
   if (e->n == 0)
@@ -1383,12 +489,11 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
       e->p1_var = var;
       // persistent workgroups: exactly what is resident (a static tile stride must not have stragglers)
       if (e->p1_asked != p1k)
-        { int nb = 0, cus = 0;
+        { int nb = 0;
           const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, p1k, D_TPB, 0);
           if (he != hipSuccess || nb < 1) nb = 3;
           if (nb > 8) nb = 8;
-          if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus < 1) cus = 256;
-          e->p1_resident = (unsigned) (nb * cus);
+          e->p1_resident = (unsigned) (nb * e->cus);
           e->p1_asked = p1k;
         }
       grid = e->p1_resident;
@@ -1407,8 +512,8 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   int64_t want_rec = (emit_all ? e->n + e->n / 24 : e->one_way ? e->n / 8 : e->n / 4) + (int64_t) (grid + 16 + 256) * F_CH;
   const int64_t dwords = ((((e->n + 31) >> 5) + 2) + 3) & ~3ll;          // (kf_bigfix reads the map four words at a time)
   if (narrow)
-    { if (e->dbits_cap < dwords * 4) e->dbits_dirty = true;                 // (fresh memory)
-      if ((rc = grow(&e->dbits, &e->dbits_cap, dwords * 4, errbuf, errlen))) return rc;
+    { if ((int64_t) e->dbits.bytes < dwords * 4) e->dbits_dirty = true;                 // (fresh memory)
+      HIPCHK(e->dbits.reserve(dwords * 4));
     }
   int64_t want_big = e->n / 16 + 4096;      // deferred entries: 0.13 % of the diploid table, 0.4 % with 5 % repeats
   bool done = false;
@@ -1422,23 +527,23 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           const int64_t per = ((int64_t) maxc + grid - 1) / grid + 2;
           if (per * G > (int64_t) maxc && per * G < 0x7FFFFFFFll) maxc = (unsigned) (per * G);
         }
-      { const int64_t have = e->req_cap / ((int64_t) F_CH * (int64_t) sizeof(u64) * e->rw);
+      { const int64_t have = (int64_t) e->req.bytes / ((int64_t) F_CH * (int64_t) sizeof(u64) * e->rw);
         if (e->req && have > (int64_t) maxc && have < 0x7FFFFFFFll) maxc = (unsigned) have;
       }
-      if ((rc = grow(&e->req, &e->req_cap, (int64_t) maxc * F_CH * (int64_t) sizeof(u64) * e->rw, errbuf, errlen))) return rc;
-      if ((rc = grow(&e->chunk_fill, &e->chunk_cap, (int64_t) maxc * 4 + 4, errbuf, errlen))) return rc;
+      HIPCHK(e->req.reserve((int64_t) maxc * F_CH * (int64_t) sizeof(u64) * e->rw));
+      HIPCHK(e->chunk_fill.reserve((int64_t) maxc * 4 + 4));
       e->max_chunks = maxc;
       if (narrow && e->dbits_dirty)
-        { HIPCHK(hipMemsetAsync(e->dbits, 0, (size_t) e->dbits_cap, e->stream)); e->dbits_dirty = false; }
+        { HIPCHK(hipMemsetAsync(e->dbits, 0, e->dbits.bytes, e->stream)); e->dbits_dirty = false; }
       FastArgs a = make_fast(e);
       if (e->lg.nb)
         { // owners of the request chunks: the workgroups of this launch, then those of kf_bigfix (rows zero unless it runs)
-          if ((rc = grow((char **) &e->whist, &e->whist_cap, (int64_t) (grid + BF_MAXGRID) * L_BK * 4, errbuf, errlen))) return rc;
+          HIPCHK(e->whist.reserve((int64_t) (grid + BF_MAXGRID) * L_BK * 4));
           HIPCHK(hipMemsetAsync(e->whist + (size_t) grid * L_BK, 0, sizeof(unsigned) * BF_MAXGRID * L_BK, e->stream));
           HIPCHK(hipMemsetAsync(e->chunk_fill, 0, (size_t) maxc * 4, e->stream));      // (a slot that stays empty has fill 0)
           e->p1grid = grid; e->nown = grid + BF_MAXGRID;
         }
-      hipEventRecord(e->ev[2], e->stream);
+      hipEventRecord(e->ev[EV_PASS1_BEG], e->stream);
       if (narrow)
         {
           P1Hot hot;
@@ -1451,7 +556,7 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           e->dbits_dirty = true;                                               // until kf_bigfix has cleared the bits again
           e->h_p1cold->partials = e->partials; e->h_p1cold->ctl = &e->ctrl->fast; e->h_p1cold->max_chunks = maxc;
           e->h_p1cold->whist = e->whist; e->h_p1cold->owners = grid + BF_MAXGRID;
-          if ((rc = grow(&e->p1tick, &e->p1tick_cap, (int64_t) D_NCLS * D_TICKW * 4, errbuf, errlen))) return rc;
+          HIPCHK(e->p1tick.reserve((int64_t) D_NCLS * D_TICKW * 4));
           HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
           e->h_p1cold->tick = e->p1tick;
           HIPCHK(hipMemcpyAsync(e->p1cold, e->h_p1cold, sizeof(P1Cold), hipMemcpyHostToDevice, e->stream));
@@ -1462,12 +567,10 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
         }
       else
         {
-#define CALL(WW) hipLaunchKernelGGL(kf_pass1<WW>, dim3(grid), dim3(F_TPB), 0, e->stream, a, e->bstart, \
-                   e->req, e->chunk_fill, maxc, emit_all, want_fp, e->partials, &e->ctrl->fast, ntiles)
-          DISPATCH_W3(e, CALL)
-#undef CALL
+          with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass1<w()>, dim3(grid), dim3(F_TPB), 0, e->stream, a, e->bstart,
+              e->req, e->chunk_fill, maxc, emit_all, want_fp, e->partials, &e->ctrl->fast, ntiles); });
         }
-      hipEventRecord(e->ev[3], e->stream);
+      hipEventRecord(e->ev[EV_PASS1_END], e->stream);
       HIPCHK(hipGetLastError());
       if (want_fp)
         HIPCHK(hipMemcpyAsync(e->h_partials, e->partials, sizeof(u64) * 4 * grid, hipMemcpyDeviceToHost, e->stream));
@@ -1477,21 +580,21 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
           // kf_collect compacts the bit map pass 1 marked them in into a list (and clears it), kf_bigfix redoes the list.
           // Launched without waiting for pass 1's control words (a request list that overflowed is guarded on the
           // device; the run is redone below either way, and so it is when the list of deferred entries was too short).
-          if (want_big < e->biglist_cap / 4) want_big = e->biglist_cap / 4;
+          if (want_big < (int64_t) e->biglist.bytes / 4) want_big = (int64_t) e->biglist.bytes / 4;
           if (want_big > 0xFFFFFFF0ll) want_big = 0xFFFFFFF0ll;
-          if ((rc = grow(&e->biglist, &e->biglist_cap, want_big * 4, errbuf, errlen))) return rc;
-          if ((rc = grow(&e->farp, &e->farp_cap, e->biglist_cap, errbuf, errlen))) return rc;
-          bigcap = (unsigned) (e->biglist_cap / 4 > 0xFFFFFFF0ll ? 0xFFFFFFF0ll : e->biglist_cap / 4);
+          HIPCHK(e->biglist.reserve(want_big * 4));
+          HIPCHK(e->farp.reserve(e->biglist.bytes));
+          bigcap = (unsigned) (e->biglist.bytes / 4 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : e->biglist.bytes / 4);
           unsigned cb = (unsigned) ((dwords / 4 + BF_TPB - 1) / BF_TPB);
           if (cb > BF_MAXGRID) cb = BF_MAXGRID;
-          hipEventRecord(e->ev[0], e->stream);
+          hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);
           hipLaunchKernelGGL(kf_collect, dim3(cb), dim3(BF_TPB), 0, e->stream, e->dbits, dwords, e->biglist, bigcap, &e->ctrl->fast.nbig);
 #define BIGFIX(W_, RW_) hipLaunchKernelGGL((kf_bigfix<W_, RW_>), dim3(BF_MAXGRID), dim3(BF_TPB), 0, e->stream, a, e->biglist, &e->ctrl->fast.nbig, bigcap, e->req, \
                               e->chunk_fill, maxc, &e->ctrl->fast, e->lg.nb ? e->whist + (size_t) grid * L_BK : (unsigned *) NULL, \
                               grid, grid + BF_MAXGRID, e->lg.nb, e->farp)
           if (e->W == 2 && e->rw == 2) BIGFIX(2, 2); else if (e->W == 2) BIGFIX(2, 3); else if (e->rw == 1) BIGFIX(1, 1); else BIGFIX(1, 2);
 #undef BIGFIX
-          hipEventRecord(e->ev[3], e->stream);
+          hipEventRecord(e->ev[EV_PASS1_END], e->stream);
           HIPCHK(hipGetLastError());
         }
       if (replay) { done = true; break; }
@@ -1533,15 +636,14 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
   if (want_fp)
     for (unsigned b = 0; b < grid; b++)
       for (int q = 0; q < 4; q++) e->fp[q] ^= e->h_partials[b * 4 + q];     // (XOR fingerprint: smg_device.hpp)
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[2], e->ev[3]);
-  e->st.ms_pass1 = ms;
+  e->st.ms_pass1 = ms_between(e, EV_PASS1_BEG, EV_PASS1_END);
   e->st.nrequests = (int64_t) e->h_ctrl->fast.nreq;
   e->st.nemitted = e->st.nrequests;
   e->st.ms_filter = 0;
   e->st.nbig = narrow ? (int64_t) e->h_ctrl->fast.nbig : 0;
   e->far_listed = narrow;
   e->st.ms_bigfix = 0;
-  if (narrow) { float mb = 0; hipEventElapsedTime(&mb, e->ev[0], e->ev[3]); e->st.ms_bigfix = mb; }
+  if (narrow) e->st.ms_bigfix = ms_between(e, EV_DECODE_BEG, EV_PASS1_END);
   e->prepared = true;
   return SMG_OK;
 }
@@ -1556,8 +658,7 @@ typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_con
 
 // sort nsort keys and look them up in that order; holes != 0: the list contains sentinel words (kf_fill_holes)
 static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int holes, char *errbuf, size_t errlen)
-{ int rc;
-  if (nsort <= 0) return SMG_OK;
+{ if (nsort <= 0) return SMG_OK;
   FastArgs a = make_fast(e);
   int64_t nb = (nsort + F_TPB - 1) / F_TPB;
   if (nb > 16384) nb = 16384;
@@ -1566,14 +667,10 @@ static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int ho
   //  a few hundred thousand look-ups in order, which take 70 us either way)
   const int64_t sort_min = 1 << 21;
   if (nsort >= sort_min)
-    { if ((rc = grow(&e->req2, &e->req2_cap, nsort * (int64_t) sizeof(u64), errbuf, errlen))) return rc;
-      size_t tmp = 0;
+    { HIPCHK(e->req2.reserve(nsort * (int64_t) sizeof(u64)));
       const unsigned lobit = 40;             // sort on bits [lobit, 64) of the k-mer
-      HIPCHK(rocprim::radix_sort_keys<smg_sort_config>(nullptr, tmp, (u64 *) keys_in, e->req2, (size_t) nsort,
-                                                       lobit, 64u, e->stream));
-      if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
-      HIPCHK(rocprim::radix_sort_keys<smg_sort_config>(e->sort_tmp, tmp, (u64 *) keys_in, e->req2, (size_t) nsort,
-                                                       lobit, 64u, e->stream));
+      HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
+        { return rocprim::radix_sort_keys<smg_sort_config>(tmp, bytes, (u64 *) keys_in, (u64 *) e->req2, (size_t) nsort, lobit, 64u, e->stream); }));
       src = e->req2;
       if (test_hook("SMG_VERIFY_SORT"))
         { u64 *d_chk = NULL, h[4];
@@ -1594,34 +691,26 @@ static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int ho
 // records with a count/flag word: sort (leading 32 k-mer bits, record number) pairs on the upper 24 bits, look up in
 // that order (small batches are looked up as they come)
 static int apply_indexed(smg_engine *e, const u64 *rec, int64_t n, int check_count, char *errbuf, size_t errlen)
-{ int rc;
-  if (n <= 0) return SMG_OK;
+{ if (n <= 0) return SMG_OK;
   FastArgs a = make_fast(e);
   int64_t nb = (n + F_TPB - 1) / F_TPB;
   if (nb > 16384) nb = 16384;
   if (n < SORT_MIN || n >= 0xFFFFFFF0ll)
     {
-#define CALL(WW) hipLaunchKernelGGL(kf_apply<WW>, dim3((unsigned) (nb > 8192 ? 8192 : nb)), dim3(F_TPB), 0, e->stream, a, rec, \
-                   (const uint32_t *) NULL, n, check_count, &e->ctrl->fast, e->rw)
-      DISPATCH_W3(e, CALL)
-#undef CALL
+      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_apply<w()>, dim3((unsigned) (nb > 8192 ? 8192 : nb)), dim3(F_TPB), 0, e->stream, a, rec,
+          (const uint32_t *) NULL, n, check_count, &e->ctrl->fast, e->rw); });
       return SMG_OK;
     }
   for (int q = 0; q < 2; q++)
-    { if ((rc = grow(&e->skey[q], &e->skey_cap[q], n * 4 + 16, errbuf, errlen))) return rc;
-      if ((rc = grow(&e->sidx[q], &e->sidx_cap[q], n * 4 + 16, errbuf, errlen))) return rc;
+    { HIPCHK(e->skey[q].reserve(n * 4 + 16));
+      HIPCHK(e->sidx[q].reserve(n * 4 + 16));
     }
   hipLaunchKernelGGL(kf_sortkey, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, rec, e->rw, n, e->skey[0], e->sidx[0]);
-  size_t tmp = 0;
-  HIPCHK(rocprim::radix_sort_pairs<smg_sort_config>(nullptr, tmp, e->skey[0], e->skey[1], e->sidx[0], e->sidx[1], (size_t) n,
-                                                    8u, 32u, e->stream));
-  if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
-  HIPCHK(rocprim::radix_sort_pairs<smg_sort_config>(e->sort_tmp, tmp, e->skey[0], e->skey[1], e->sidx[0], e->sidx[1], (size_t) n,
-                                                    8u, 32u, e->stream));
-#define CALL(WW) hipLaunchKernelGGL(kf_apply_indexed<WW>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, rec, e->sidx[1], n, \
-                   check_count, &e->ctrl->fast, e->rw)
-  DISPATCH_W3(e, CALL)
-#undef CALL
+  uint32_t *const ki = e->skey[0], *const ko = e->skey[1], *const vi = e->sidx[0], *const vo = e->sidx[1];
+  HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
+    { return rocprim::radix_sort_pairs<smg_sort_config>(tmp, bytes, ki, ko, vi, vo, (size_t) n, 8u, 32u, e->stream); }));
+  with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_apply_indexed<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, rec, e->sidx[1], n,
+      check_count, &e->ctrl->fast, e->rw); });
   return SMG_OK;
 }
 
@@ -1642,23 +731,19 @@ static int bm_id_bits(int kmer, int cap)
 // 64-byte fetches otherwise (7 ms for the 4.4e8 requests of the 1 Gbp table); one radix pass (holes of the chunk
 // array as sentinels, as for the look-ups) keeps the map words that the resident workgroups probe inside the L2s.
 static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
-{ int rc;
-  hipEventRecord(e->ev[4], e->stream);                      // start of the filter's time
+{ hipEventRecord(e->ev[EV_LOOKUP_BEG], e->stream);                      // start of the filter's time
   if (e->lg.nb)
     { // smg_lookup.hpp: bucket offsets from pass 1's histogram, one-pass partition into the dense array req2
       const int64_t nreq = e->st.nrequests;
-      if ((rc = grow(&e->req2, &e->req2_cap, (nreq > 0 ? nreq : 1) * (int64_t) sizeof(u64) * e->rw, errbuf, errlen))) return rc;
+      HIPCHK(e->req2.reserve((nreq > 0 ? nreq : 1) * (int64_t) sizeof(u64) * e->rw));
       const int nbk = 1 << e->lg.nb;
       // bucket sizes = column sums of the owners' histogram rows -> bucket offsets -> first slot of every owner in every bucket
       hipLaunchKernelGGL(kl_tot, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, (const unsigned *) e->whist, e->nown, e->ghist);
       hipLaunchKernelGGL(kl_scan, dim3(1), dim3(L_BK), 0, e->stream, e->ghist, nbk, e->boff, e->boff + L_BK + 2, e->ghist + L_BK);
       hipLaunchKernelGGL(kl_woff, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, e->whist, e->nown, (const u64 *) e->boff);
-      if (e->n_chunks && e->rw == 1)
-        hipLaunchKernelGGL(kl_part<1>, dim3(e->nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->nown,
-                           (const unsigned *) e->whist, e->max_chunks, e->lg.nb, e->req2);
-      else if (e->n_chunks)
-        hipLaunchKernelGGL(kl_part<2>, dim3(e->nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->nown,
-                           (const unsigned *) e->whist, e->max_chunks, e->lg.nb, e->req2);
+      if (e->n_chunks)
+        with_words<2>(e->rw, [&](auto rw) { hipLaunchKernelGGL(kl_part<rw()>, dim3(e->nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->nown,
+            (const unsigned *) e->whist, e->max_chunks, e->lg.nb, e->req2); });
       HIPCHK(hipGetLastError());
       e->presorted = 3;
       return SMG_OK;
@@ -1669,11 +754,9 @@ static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
   { const char *v = test_hook("SMG_FILTER_SORT_MIN"); if (v) sort_min = atoll(v); if (sort_min < SORT_MIN) sort_min = SORT_MIN; }
   if (!(e->rw == 1 && nslots >= sort_min && e->kmer < 32)) return SMG_OK;
   hipLaunchKernelGGL(kf_fill_holes, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
-  if ((rc = grow(&e->req2, &e->req2_cap, nslots * (int64_t) sizeof(u64), errbuf, errlen))) return rc;
-  size_t tmp = 0;
-  HIPCHK(rocprim::radix_sort_keys<smg_sort_config>(nullptr, tmp, e->req, e->req2, (size_t) nslots, 56u, 64u, e->stream));
-  if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
-  HIPCHK(rocprim::radix_sort_keys<smg_sort_config>(e->sort_tmp, tmp, e->req, e->req2, (size_t) nslots, 56u, 64u, e->stream));
+  HIPCHK(e->req2.reserve(nslots * (int64_t) sizeof(u64)));
+  HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
+    { return rocprim::radix_sort_keys<smg_sort_config>(tmp, bytes, (u64 *) e->req, (u64 *) e->req2, (size_t) nslots, 56u, 64u, e->stream); }));
   e->presorted = 1;
   return SMG_OK;
 }
@@ -1681,10 +764,7 @@ static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
 // smg_lookup.hpp: filter the partitioned requests against `map`; list = false: look the survivors up at once
 static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned maxout, char *errbuf, size_t errlen)
 { const bool two = e->bm2 != 0;                             // (a map that came from outside was built by the same rule)
-  unsigned grid = 256;
-  { int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus > 0) grid = (unsigned) cus;
-  }
+  unsigned grid = (unsigned) e->cus;
   const unsigned nbk = 1u << e->lg.nb;
   FastArgs a = make_fast(e);
   // The fused probe + look-up of a single shard has two forms.  kl_probe (a bucket per workgroup, the bucket's map folded
@@ -1701,8 +781,7 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
     const int64_t share = e->one_way ? 14 : 28;
     const bool auto_x = (e->st.nbig > 0 && e->st.nbig * 400 > e->n) || e->st.nemitted * 100 > e->n * share;
     if (!list && e->lg.nb >= 3 && (px ? atoi(px) != 0 : auto_x))
-      { int rc2;
-        if ((rc2 = grow(&e->xtick, &e->xtick_cap, (int64_t) PX_NXCD * PX_TICKW * 4, errbuf, errlen))) return rc2;
+      { HIPCHK(e->xtick.reserve((int64_t) PX_NXCD * PX_TICKW * 4));
         HIPCHK(hipMemsetAsync(e->xtick, 0, (size_t) PX_NXCD * PX_TICKW * 4, e->stream));
         // tickets of 2048 requests where many requests survive (polyploid tables: one in seven, all real hits -- half as many
         // buckets in flight per XCD keep more of a bucket's k-mer lines in reach: -0.25 ms on the hexaploid table), 4096 where the
@@ -1742,33 +821,28 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   const int nbits = bm_id_bits(e->kmer, e->bm_cap);
   // two workgroups per CU, chunks dealt round-robin: the chunks in flight then span one or two of the 256 sorted
   // buckets, i.e. <= 1 MB of the map (measured: 512 workgroups 3.0 ms, 256 / 1024 / 2048 workgroups 3.4-3.7 ms)
-  unsigned grid = 512;
-  { int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus > 0) grid = 2u * (unsigned) cus;
-  }
+  unsigned grid = 2u * (unsigned) e->cus;
   if (grid > e->n_chunks) grid = e->n_chunks;
   unsigned maxout = e->n_chunks + grid + 16;
   if (e->lg.nb)
     { // kl_probe: every wave of every workgroup (one per CU, lookup_probe) fills chunks of its own, each to the brim
       // but for the < 64 records that did not fit: size the list from the launch and the request count, not from 256 CUs
-      int cus = 256;
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus < 1) cus = 256;
-      const int64_t need = (int64_t) cus * PB_WAVES + e->st.nrequests / (F_CH - 63) + 16;
+      const int64_t need = (int64_t) e->cus * PB_WAVES + e->st.nrequests / (F_CH - 63) + 16;
       maxout = need < 0x7FFFFFFFll ? (unsigned) need : 0x7FFFFFFFu;
       if (maxout < e->n_chunks + 16) maxout = e->n_chunks + 16;
     }
   // (the two chunk lists swap roles after every filter: keep them the same size, or pass 1 would reallocate)
   { int64_t want = (int64_t) maxout * F_CH * (int64_t) sizeof(u64) * e->rw, wantf = (int64_t) maxout * 4 + 4;
-    if (want < e->req_cap) want = e->req_cap;
-    if (wantf < e->chunk_cap) wantf = e->chunk_cap;
-    if ((rc = grow(&e->reqf, &e->reqf_cap, want, errbuf, errlen))) return rc;
-    if ((rc = grow(&e->chunk_fillf, &e->chunk_capf, wantf, errbuf, errlen))) return rc;
+    if (want < (int64_t) e->req.bytes) want = (int64_t) e->req.bytes;
+    if (wantf < (int64_t) e->chunk_fill.bytes) wantf = (int64_t) e->chunk_fill.bytes;
+    HIPCHK(e->reqf.reserve(want));
+    HIPCHK(e->chunk_fillf.reserve(wantf));
   }
   if (e->rp_active)
     { // replayed step: WHICH chunks the waves of the probe kernel fill is decided by an atomic counter, and how many by the
       // way the buckets fall to the workgroups -- so the routing kernels walk the whole list, and a chunk nobody opened must
       // read as empty
-      hipEventRecord(e->ev[11], e->stream);
+      hipEventRecord(e->ev[EV_REPLAY_FILTER_BEG], e->stream);
       // (as many chunks as the recorded step's filter filled, and some: the device checks that this step stayed inside)
       if (e->rp_seen_chunks + 64u < maxout) maxout = e->rp_seen_chunks + 64u;
       HIPCHK(hipMemsetAsync(e->chunk_fillf, 0, (size_t) maxout * 4, e->stream));
@@ -1780,33 +854,21 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   else if (e->presorted == 1)
     hipLaunchKernelGGL(kf_filter<1>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req2, (const uint32_t *) NULL, e->n_chunks, nslots,
                        map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
-  else if (e->rw == 1)
-    hipLaunchKernelGGL(kf_filter<1>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
-                       map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
-  else if (e->rw == 2)
-    hipLaunchKernelGGL(kf_filter<2>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
-                       map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
-  else if (e->rw == 3)
-    hipLaunchKernelGGL(kf_filter<3>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
-                       map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
   else
-    hipLaunchKernelGGL(kf_filter<4>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
-                       map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
-  hipEventRecord(e->ev[5], e->stream);
+    with_words<4>(e->rw, [&](auto rw) { hipLaunchKernelGGL(kf_filter<rw()>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
+        map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast); });
+  hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
   HIPCHK(hipGetLastError());
   if (e->rp_active)
     { // replayed step: the kept list is as long as last time (the device checks it: smg_engine_proof) -- nothing is read
-      hipEventRecord(e->ev[12], e->stream);
+      hipEventRecord(e->ev[EV_REPLAY_FILTER_END], e->stream);
       e->rp_nf_chunks = maxout;             // (the device checks that the probe kernel stayed inside the list)
     }
   else
     { if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       if (e->h_ctrl->fast.nf_chunks > maxout) return fail(errbuf, errlen, SMG_ENODEV, "request filter overflowed its chunk list%s");
     }
-  { u64 *t = e->req; e->req = e->reqf; e->reqf = t; }
-  { int64_t t = e->req_cap; e->req_cap = e->reqf_cap; e->reqf_cap = t; }
-  { uint32_t *t = e->chunk_fill; e->chunk_fill = e->chunk_fillf; e->chunk_fillf = t; }
-  { int64_t t = e->chunk_cap; e->chunk_cap = e->chunk_capf; e->chunk_capf = t; }
+  e->req.swap(e->reqf); e->chunk_fill.swap(e->chunk_fillf);
   if (e->rp_active)
     { e->n_chunks = e->rp_nf_chunks; e->st.nrequests = e->rp_nf_req; e->filtered = true;
       return SMG_OK;
@@ -1814,9 +876,8 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   e->n_chunks = e->h_ctrl->fast.nf_chunks;
   e->st.nrequests = (int64_t) e->h_ctrl->fast.nf_req;
   e->filtered = true;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
-  e->st.ms_rclookup += ms;
-  e->st.ms_filter = ms;
+  e->st.ms_filter = ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
+  e->st.ms_rclookup += e->st.ms_filter;
   // what a replayed step on this table may take for granted (key-only records through the look-up chain, k <= 64)
   e->rp_have = e->rp_want && e->presorted == 3 && e->W <= 2 && e->rw == e->W;
   if (e->rp_have)
@@ -1828,15 +889,11 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
 
 // squeeze the request chunks (ragged fills) into the dense array e->dense: exclusive scan of the fills + one copy
 static int compact_chunks(smg_engine *e, int64_t nreq, char *errbuf, size_t errlen)
-{ int rc;
-  if ((rc = grow(&e->dense, &e->dense_cap, nreq * (int64_t) sizeof(u64) * e->rw, errbuf, errlen))) return rc;
-  if ((rc = grow(&e->chunk_off, &e->chunk_off_cap, (int64_t) e->n_chunks * 4 + 4, errbuf, errlen))) return rc;
-  size_t tmp = 0;
-  HIPCHK(rocprim::exclusive_scan(nullptr, tmp, e->chunk_fill, e->chunk_off, 0u, (size_t) e->n_chunks,
-                                 rocprim::plus<uint32_t>(), e->stream));
-  if ((rc = grow((char **) &e->sort_tmp, &e->sort_tmp_cap, (int64_t) tmp + 16, errbuf, errlen))) return rc;
-  HIPCHK(rocprim::exclusive_scan(e->sort_tmp, tmp, e->chunk_fill, e->chunk_off, 0u, (size_t) e->n_chunks,
-                                 rocprim::plus<uint32_t>(), e->stream));
+{ HIPCHK(e->dense.reserve(nreq * (int64_t) sizeof(u64) * e->rw));
+  HIPCHK(e->chunk_off.reserve((int64_t) e->n_chunks * 4 + 4));
+  HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
+    { return rocprim::exclusive_scan(tmp, bytes, (uint32_t *) e->chunk_fill, (uint32_t *) e->chunk_off, 0u, (size_t) e->n_chunks,
+                                     rocprim::plus<uint32_t>(), e->stream); }));
   hipLaunchKernelGGL(kf_compact, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->chunk_off, e->rw, e->dense);
   return SMG_OK;
 }
@@ -1850,14 +907,12 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
     { // own requests, own map: partition, then filter and look-ups in one kernel (no survivor list, no sort)
       if (e->n_chunks == 0 || e->st.nrequests == 0) { if (missing) *missing = 0; return SMG_OK; }
       if (!e->presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
-      hipEvent_t mid = e->ev[10];
-      hipEventRecord(mid, e->stream);
+      hipEventRecord(e->ev[EV_PROBE_BEG], e->stream);
       if ((rc = lookup_probe(e, e->bmap, false, 0u, errbuf, errlen))) return rc;
-      hipEventRecord(e->ev[5], e->stream);
+      hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
-      float ms = 0;
-      hipEventElapsedTime(&ms, e->ev[4], mid); e->st.ms_filter = ms;       // scan + partition
-      hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); e->st.ms_rclookup += ms;
+      e->st.ms_filter = ms_between(e, EV_LOOKUP_BEG, EV_PROBE_BEG);       // scan + partition
+      e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
       e->st.nrequests = (int64_t) e->h_ctrl->fast.nf_req;
       e->filtered = true;
       e->n_chunks = 0;                                            // nothing left to route or to look up
@@ -1865,7 +920,7 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
       return SMG_OK;
     }
   if (!flat && e->bm_bits && !e->filtered && (rc = fast_filter(e, NULL, errbuf, errlen))) return rc;
-  hipEventRecord(e->ev[4], e->stream);
+  hipEventRecord(e->ev[EV_LOOKUP_BEG], e->stream);
   const bool keys_only = e->W == 1 && e->rw == 1;
   const int64_t nreq = e->st.nrequests;
   if (flat)
@@ -1886,14 +941,13 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
         }
     }
   if (rc) return rc;
-  hipEventRecord(e->ev[5], e->stream);
+  hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
   HIPCHK(hipGetLastError());
   if (!missing && flat)                   // (sharded run: the count of missing complements stays on the device -- smg_engine_proof)
     { e->lookup_pending = true; return SMG_OK; }
   rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[4], e->ev[5]);
-  e->st.ms_rclookup += ms;
+  e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
   if (missing) *missing = e->h_ctrl->fast.missing;
   return SMG_OK;
 }
@@ -1901,32 +955,29 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
 static int fast_pass2(smg_engine *e, int64_t *d_plot, bool with_sum, char *errbuf, size_t errlen)
 { HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
   FastArgs a = make_fast(e);
-  hipEventRecord(e->ev[6], e->stream);
+  hipEventRecord(e->ev[EV_PASS2_BEG], e->stream);
   if (e->n > 0)
     { int64_t nb = (e->n + P2_TPB - 1) / P2_TPB;
       if (nb > P2_GRID) nb = P2_GRID;
       { const char *v = test_hook("SMG_P2_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= P2_GRID && atoi(v) < nb) nb = atoi(v); }
-#define CALL(WW) hipLaunchKernelGGL(kf_pass2<WW>, dim3((unsigned) nb), dim3(P2_TPB), 0, e->stream, a, (u64 *) d_plot)
-      DISPATCH_W3(e, CALL)
-#undef CALL
+      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2<w()>, dim3((unsigned) nb), dim3(P2_TPB), 0, e->stream, a, (u64 *) d_plot); });
       // entries whose unique partner is out of the code's reach: from the list of deferred entries that pass 1 of one-
       // and two-word k-mers leaves, else (three words: the generic pass 1) from a scan of the code bytes
       if (e->far_listed && e->W <= 2)
         { const unsigned nl = (unsigned) e->st.nbig;
           unsigned fb = (nl + 255) / 256;
           if (fb > 4096) fb = 4096;
-          if (nl && e->W == 1) hipLaunchKernelGGL(kf_pass2_far<1>, dim3(fb), dim3(256), 0, e->stream, a, (const uint32_t *) e->biglist, (const uint32_t *) e->farp, nl, (u64 *) d_plot);
-          else if (nl)         hipLaunchKernelGGL(kf_pass2_far<2>, dim3(fb), dim3(256), 0, e->stream, a, (const uint32_t *) e->biglist, (const uint32_t *) e->farp, nl, (u64 *) d_plot);
+          if (nl)
+            with_words<2>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_far<w()>, dim3(fb), dim3(256), 0, e->stream, a, (const uint32_t *) e->biglist,
+                (const uint32_t *) e->farp, nl, (u64 *) d_plot); });
         }
       else
         { int64_t fb = ((e->n + 15) / 16 + 255) / 256;
           if (fb > 4096) fb = 4096;
-#define CALL(WW) hipLaunchKernelGGL(kf_pass2_farscan<WW>, dim3((unsigned) fb), dim3(256), 0, e->stream, a, (u64 *) d_plot)
-          DISPATCH_W3(e, CALL)
-#undef CALL
+          with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_farscan<w()>, dim3((unsigned) fb), dim3(256), 0, e->stream, a, (u64 *) d_plot); });
         }
     }
-  hipEventRecord(e->ev[7], e->stream);
+  hipEventRecord(e->ev[EV_PASS2_END], e->stream);
   HIPCHK(hipGetLastError());
   int rc = SMG_OK;
   e->st.path = 1;
@@ -1934,8 +985,7 @@ static int fast_pass2(smg_engine *e, int64_t *d_plot, bool with_sum, char *errbu
     { e->st.npairs = 0; e->st.ms_pass2 = -1.0; return SMG_OK; }
   rc = plot_sum(e, d_plot, errbuf, errlen);                         // (one more kernel and a host round trip)
   if (rc) return rc;
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[6], e->ev[7]);
-  e->st.ms_pass2 = ms;
+  e->st.ms_pass2 = ms_between(e, EV_PASS2_BEG, EV_PASS2_END);
   return SMG_OK;
 }
 
@@ -1950,7 +1000,7 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
   e->fast = true; e->counted_done = false; e->general_done = false; e->lookup_pending = false;
-  if ((rc = grow(&e->deg, &e->deg_cap, ((e->n + 15) & ~15ll) + 32, errbuf, errlen))) return rc;
+  HIPCHK(e->deg.reserve(((e->n + 15) & ~15ll) + 32));
   if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_codes, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
   e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
   e->use_sig = false; e->bm_bits = 0; e->bm2 = 0; e->lg.nb = 0; e->one_way = 0;
@@ -1963,27 +1013,10 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
       if (e->n > 0)
         { Tab t = make_tab(e);
           const unsigned nblk = (unsigned) ((e->n + 1 + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_directory<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl)
-          DISPATCH_W(e, CALL)
-#undef CALL
+          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_directory<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl); });
           HIPCHK(hipGetLastError());
         }
     }
-  e->prepared = true;
-  return SMG_OK;
-}
-
-// the same for k > 85 (round 6): the byte a shard left behind is its array of counted degrees (S_all of every entry, uint8 with the
-// reference's wrap); the look-ups of the received requests add S_hi of the complements on top (k_apply) and pass 2 reads the sums
-static int counted_resume(smg_engine *e, const uint8_t *d_degs, char *errbuf, size_t errlen)
-{ HIPCHK(hipSetDevice(e->device));
-  int rc = counted_prepare(e, errbuf, errlen);               // control words, geometry, zeroed degrees, directory
-  if (rc) return rc;
-  if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_degs, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
-  e->rw = e->W + 1;
-  e->lookup_pending = false; e->n_chunks = 0; e->bm_bits = 0; e->filtered = false; e->presorted = 0;
-  e->st.nrequests = 0; e->st.ms_rclookup = 0; e->st.path = 1;
-  memset(e->fp, 0, sizeof(e->fp));
   e->prepared = true;
   return SMG_OK;
 }
@@ -2042,10 +1075,9 @@ extern "C" int smg_engine_replay_done(smg_engine *e, int ok, char *errbuf, size_
   memset(e->fp, 0, sizeof(e->fp));
   for (unsigned b = 0; b < e->rp_grid; b++)
     for (int q = 0; q < 4; q++) e->fp[q] ^= e->h_partials[b * 4 + q];
-  float ms = 0;
-  hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); e->st.ms_pass1 = ms;
-  hipEventElapsedTime(&ms, e->ev[0], e->ev[3]); e->st.ms_bigfix = ms;
-  hipEventElapsedTime(&ms, e->ev[11], e->ev[12]); e->st.ms_filter = ms; e->st.ms_rclookup += ms;
+  e->st.ms_pass1 = ms_between(e, EV_PASS1_BEG, EV_PASS1_END);
+  e->st.ms_bigfix = ms_between(e, EV_DECODE_BEG, EV_PASS1_END);
+  e->st.ms_filter = ms_between(e, EV_REPLAY_FILTER_BEG, EV_REPLAY_FILTER_END); e->st.ms_rclookup += e->st.ms_filter;
   return SMG_OK;
 }
 
@@ -2155,7 +1187,7 @@ extern "C" int smg_engine_set_blockmap_bits(smg_engine *e, int id_bits)
 extern "C" int smg_engine_blockmap(smg_engine *e, int *id_bits, int64_t *nwords)
 { if (!e || !id_bits || !nwords) return SMG_EINVAL;
   *id_bits = e->prepared ? e->bm_bits : 0;
-  *nwords = *id_bits ? (((1ll << *id_bits) + 31) >> 5) << e->bm2 : 0;      // (two-bit map: 64 bits per 32 block ids)
+  *nwords = *id_bits ? bm_words(*id_bits, e->bm2) : 0;
   return SMG_OK;
 }
 
@@ -2163,7 +1195,7 @@ extern "C" int smg_engine_blockmap_copy(smg_engine *e, int64_t word_lo, int64_t 
                                         char *errbuf, size_t errlen)
 { NEED_FAST(e)
   if (!e->prepared || !e->bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
-  const int64_t nwords = (((1ll << e->bm_bits) + 31) >> 5) << e->bm2;
+  const int64_t nwords = bm_words(e->bm_bits, e->bm2);
   if (word_lo < 0 || nw < 0 || word_lo + nw > nwords || (nw > 0 && !d_dst))
     return fail(errbuf, errlen, SMG_EINVAL, "block map range out of bounds%s");
   HIPCHK(hipSetDevice(e->device));
@@ -2195,7 +1227,7 @@ extern "C" int smg_engine_merge_maps(smg_engine *e, const uint32_t *d_parts, int
   if (!e->prepared || !e->bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
   if (!d_parts || !d_full || !word_lo || !nwords_of || nranks < 1 || nranks > 16 || width < 1)
     return fail(errbuf, errlen, SMG_EINVAL, "bad merge_maps arguments (1..16 ranks)%s");
-  const int64_t nwords = (((1ll << e->bm_bits) + 31) >> 5) << e->bm2;
+  const int64_t nwords = bm_words(e->bm_bits, e->bm2);
   MapGeo geo;
   for (int r = 0; r < 16; r++) { geo.lo[r] = r < nranks ? word_lo[r] : 0; geo.ln[r] = r < nranks ? nwords_of[r] : 0; }
   for (int r = 0; r < nranks; r++)
@@ -2242,24 +1274,19 @@ static int route_records(smg_engine *e, const u64 *req, const uint32_t *chunk_fi
     { if (d_counts) HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int64_t) * nranks, e->stream));
       return SMG_OK;
     }
-  int rc;
   if (nranks > 1)
     HIPCHK(hipMemcpyAsync(e->d_split, splitters, sizeof(u64) * (nranks - 1) * e->W,
                           hipMemcpyHostToDevice, e->stream));
-  if ((rc = grow(&e->route_cnt, &e->route_cnt_cap, (int64_t) nc * nranks * 4, errbuf, errlen))) return rc;
-  if ((rc = grow(&e->route_off, &e->route_off_cap, ((int64_t) nc * nranks + 16) * 8, errbuf, errlen))) return rc;
+  HIPCHK(e->route_cnt.reserve((int64_t) nc * nranks * 4));
+  HIPCHK(e->route_off.reserve(((int64_t) nc * nranks + 16) * 8));
   u64 *totals = e->route_off + (size_t) nc * nranks;           // [nranks], behind the offsets
-#define CALL(WW) hipLaunchKernelGGL(kf_route_count<WW>, dim3(nc), dim3(F_TPB), 0, e->stream, req, \
-                   chunk_fill, rw, e->d_split, nranks, e->route_cnt)
-  DISPATCH_W(e, CALL)
-#undef CALL
+  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_route_count<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
+      chunk_fill, rw, e->d_split, nranks, e->route_cnt); });
   // offsets and scatter follow on the device; the host only learns the totals (what the exchange needs): ONE round trip
   hipLaunchKernelGGL(kf_route_offsets, dim3(nranks), dim3(1024), 0, e->stream, (const uint32_t *) e->route_cnt, nc, nranks, e->route_off, totals);
-#define CALL(WW) hipLaunchKernelGGL(kf_route_scatter<WW>, dim3(nc), dim3(F_TPB), 0, e->stream, req, \
-                   chunk_fill, rw, e->d_split, nranks, (const u64 *) e->route_off, (const u64 *) totals, (u64 *) d_send, \
-                   (u64) (capacity < 0 ? 0 : capacity))
-  DISPATCH_W(e, CALL)
-#undef CALL
+  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_route_scatter<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
+      chunk_fill, rw, e->d_split, nranks, (const u64 *) e->route_off, (const u64 *) totals, (u64 *) d_send,
+      (u64) (capacity < 0 ? 0 : capacity)); });
   HIPCHK(hipGetLastError());
   if (d_counts)
     { HIPCHK(hipMemcpyAsync(d_counts, totals, sizeof(u64) * nranks, hipMemcpyDeviceToDevice, e->stream));
@@ -2298,7 +1325,7 @@ extern "C" int smg_engine_route_device(smg_engine *e, const uint64_t *splitters,
   if (rc || !e->rp_want || !e->fast) return rc;
   // replay: the per-destination totals of a plain step are kept, those of a replayed step are put beside them -- the verdict
   // kernel (smg_engine_proof) compares the two: the caller splits its exchange by the RECORDED totals
-  if (!e->rp_totals) HIPCHK(hipMalloc(&e->rp_totals, sizeof(u64) * 32));
+  if (!e->rp_totals) HIPCHK(e->rp_totals.alloc(sizeof(u64) * 32));
   const bool rep = e->rp_active;
   if (rep && e->rp_nranks != nranks) { e->rp_routed = false; return SMG_OK; }
   HIPCHK(hipMemcpyAsync(e->rp_totals + (rep ? 16 : 0), d_counts, sizeof(u64) * nranks, hipMemcpyDeviceToDevice, e->stream));
@@ -2317,16 +1344,13 @@ extern "C" int smg_engine_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, si
 extern "C" int smg_engine_stats(smg_engine *e, smg_stats *stats)
 { if (!e || !stats) return SMG_EINVAL;
   if (e->lookup_pending)                 // look-ups of received requests were queued without a wait
-    { float ms = 0;
-      hipSetDevice(e->device);
-      if (hipEventSynchronize(e->ev[5]) == hipSuccess && hipEventElapsedTime(&ms, e->ev[4], e->ev[5]) == hipSuccess) e->st.ms_rclookup += ms;
+    { hipSetDevice(e->device);
+      if (hipEventSynchronize(e->ev[EV_LOOKUP_END]) == hipSuccess) e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
       e->lookup_pending = false;
     }
   if (e->st.ms_pass2 < 0)                // pass 2 of the phase API was queued without a wait
-    { float ms = 0;
-      hipSetDevice(e->device);
-      if (hipEventSynchronize(e->ev[7]) == hipSuccess && hipEventElapsedTime(&ms, e->ev[6], e->ev[7]) == hipSuccess) e->st.ms_pass2 = ms;
-      else e->st.ms_pass2 = 0;
+    { hipSetDevice(e->device);
+      e->st.ms_pass2 = hipEventSynchronize(e->ev[EV_PASS2_END]) == hipSuccess ? ms_between(e, EV_PASS2_BEG, EV_PASS2_END) : 0;
     }
   *stats = e->st;
   return SMG_OK;
@@ -2337,7 +1361,7 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
 { if (!e || !d_plot) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
   HIPCHK(hipSetDevice(e->device));
   int rc;
-  hipEventRecord(e->ev[8], e->stream);
+  hipEventRecord(e->ev[EV_RUN_BEG], e->stream);
   e->st.ms_pass1 = e->st.ms_rclookup = e->st.ms_pass2 = 0;
   bool symmetric = false;
   if (symcheck != SMG_SYM_NONE && e->kmer <= FAST_MAX_K)
@@ -2361,460 +1385,14 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
   else if (symcheck != SMG_SYM_NONE)
     { if ((rc = counted_symmetric(e, symcheck, d_plot, &symmetric, errbuf, errlen))) return rc; }
   if (!symmetric && (rc = run_general(e, d_plot, errbuf, errlen))) return rc;
-  hipEventRecord(e->ev[9], e->stream);
+  hipEventRecord(e->ev[EV_RUN_END], e->stream);
   HIPCHK(hipStreamSynchronize(e->stream));
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[8], e->ev[9]);
-  e->st.ms_total = ms;
+  e->st.ms_total = ms_between(e, EV_RUN_BEG, EV_RUN_END);
   if (stats) *stats = e->st;
   return SMG_OK;
 }
 
-// ---- table conditioning on device ----------------------------------------
-// The reference shells out to FastK's Logex / Symmex (PloidyPlot.c:1381-1414), which are neither vendored
-// nor pinned.  Restated semantics:
-//   trim        : keep the entries with count >= ethresh                    (Logex 'A[e-]')
-//   symmetrise  : add rc(x) with the count of x for every entry x, sort, keep one copy of a k-mer that
-//                 occurs twice (a self-complementary k-mer, or -- only on input that is neither canonical
-//                 nor symmetric -- a k-mer whose complement was already present: the original entry wins)
-// The sort, the scans and the buffers are those of the k-mer counter (smg_keysort.hpp).
-
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_append_rc(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k,
-             u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  const Key<W> x = load_key<W>(keys, i);
-  const Key<W> r = revcomp<W>(x, k);
-#pragma unroll
-  for (int w = 0; w < W; w++) { okeys[i * W + w] = x.w[w]; okeys[(n + i) * W + w] = r.w[w]; }
-  ocnt[i] = cnt[i]; ocnt[n + i] = cnt[i];
-}
-
-// flag[i] = 1 when the i-th entry in sorted order survives (first of its k-mer)
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_flag_first(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, int64_t n,
-              uint32_t *__restrict__ flag)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  bool first = i == 0;
-  if (i > 0) first = !key_eq<W>(load_key<W>(keys, perm[i]), load_key<W>(keys, perm[i - 1]));
-  flag[i] = first;
-}
-
-__global__ void __launch_bounds__(TPB)
-kc_flag_trim(const uint16_t *__restrict__ cnt, int64_t n, unsigned ethresh, uint32_t *__restrict__ flag)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i < n) flag[i] = cnt[i] >= ethresh;
-}
-
-// out[pos[i]] = in[perm ? perm[i] : i] for the flagged i
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_compact(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint32_t *__restrict__ perm,
-           const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
-           u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const int64_t src = perm ? (int64_t) perm[i] : i;
-  const int64_t dst = pos[i];
-#pragma unroll
-  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
-  ocnt[dst] = cnt[src];
-}
-
-// like kc_compact, for a sorted permutation in which a k-mer occurs at most twice (once as an entry, once as a
-// complement): the survivor is the first of the two, its count the ENTRY's
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_compact_pref(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, const uint8_t *__restrict__ copy,
-                const uint32_t *__restrict__ perm, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos,
-                int64_t n, u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const int64_t src = perm[i];
-  int64_t csrc = src;
-  if (copy[src] && i + 1 < n && !flag[i + 1]) csrc = perm[i + 1];        // (the next one is the same k-mer: the entry)
-  const int64_t dst = pos[i];
-#pragma unroll
-  for (int w = 0; w < W; w++) okeys[dst * W + w] = keys[src * W + w];
-  ocnt[dst] = cnt[csrc];
-}
-
-// the engine's table has n entries now and is another table: what a run, the prefix index and the ends said is gone
-static void table_changed(smg_engine *e, int64_t n)
-{ e->n = n;
-  e->prepared = false; e->counted_done = false; e->general_done = false;
-  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
-  e->st.nels = n;
-}
-
-// (k, c), n finished entries, leave their buffers and become the engine's own table.  The stream is idle: the old one is freed.
-static void adopt_table(smg_engine *e, Dev &k, Dev &c, int64_t n)
-{ hipFree(e->own_keys); hipFree(e->own_cnt);
-  e->own_keys = (u64 *) k.release(); e->own_cnt = (uint16_t *) c.release();
-  e->keys = e->own_keys; e->cnt = e->own_cnt;
-  table_changed(e, n);
-}
-
-// sorted, duplicate-free table from 2-copies-at-most material: keys[n2 * W], counts, copy flags (NULL: the first of two
-// equal k-mers in INPUT order wins, as the stable sort leaves it) -> the engine's own table.  Frees nothing of the caller's.
-static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, const uint8_t *copy, int64_t n2,
-                            int64_t *kept_out, char *errbuf, size_t errlen)
-{ const int W = e->W;
-  if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
-  const unsigned nblk2 = (unsigned) ((n2 + TPB - 1) / TPB);
-  Dev perm, flag, pos, ko, co;
-  int64_t kept = 0;
-  HIPCHK(sort_permutation(k2, W, n2, e->stream, &e->sort_tmp, &e->sort_tmp_cap, perm));
-  HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n2));
-  HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n2));
-#define CALL(WW) hipLaunchKernelGGL(kc_flag_first<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm.as<uint32_t>(), n2, flag.as<uint32_t>())
-  DISPATCH_W(e, CALL)
-#undef CALL
-  HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n2, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &kept));
-  HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
-  HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
-  if (copy)
-    {
-#define CALL(WW) hipLaunchKernelGGL(kc_compact_pref<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm.as<uint32_t>(), \
-                   flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  else
-    {
-#define CALL(WW) hipLaunchKernelGGL(kc_compact<WW>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm.as<uint32_t>(), \
-                   flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-    }
-  HIPCHK(hipStreamSynchronize(e->stream));
-  adopt_table(e, ko, co, kept);
-  *kept_out = kept;
-  return SMG_OK;
-}
-
-extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
-                                    int64_t *new_nels, char *errbuf, size_t errlen)
-{ if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  const int W = e->W;
-  int rc;
-  int64_t n = e->n;
-  hipEventRecord(e->ev[0], e->stream);                 // (the decode pair: conditioning is booked under ms_decode)
-
-  if (do_trim && n > 0)
-    { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
-      Dev flag, pos, ko, co;
-      HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n));
-      HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n));
-      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->cnt, n, (unsigned) ethresh, flag.as<uint32_t>());
-      int64_t kept = 0;
-      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &kept));
-      HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
-      HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
-#define CALL(WW) hipLaunchKernelGGL(kc_compact<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, \
-                   (const uint32_t *) NULL, flag.as<uint32_t>(), pos.as<uint32_t>(), n, ko.as<u64>(), co.as<uint16_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-      HIPCHK(hipStreamSynchronize(e->stream));
-      adopt_table(e, ko, co, kept);
-      n = kept;
-    }
-
-  if (do_symm && n > 0)
-    { const int64_t n2 = 2 * n;
-      if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
-      const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
-      Dev k2, c2;
-      HIPCHK(dev_alloc(k2, sizeof(u64) * (size_t) n2 * W));
-      HIPCHK(dev_alloc(c2, sizeof(uint16_t) * (size_t) n2));
-#define CALL(WW) hipLaunchKernelGGL(kc_append_rc<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, n, e->kmer, \
-                   k2.as<u64>(), c2.as<uint16_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-      // (entries first, complements behind them: the stable sort keeps the entry in front of an equal complement)
-      if ((rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), NULL, n2, &n, errbuf, errlen))) return rc;
-    }
-  hipEventRecord(e->ev[1], e->stream);
-  HIPCHK(hipStreamSynchronize(e->stream));
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
-  table_changed(e, n);                                 // (also where nothing was asked for, or of an empty table)
-  e->rp_have = false; e->rp_active = false;
-  e->st.ms_decode += ms;
-  if (new_nels) *new_nels = n;
-  return SMG_OK;
-}
-
-// ---- closure of a CANONICAL table by merge ------------------------------------------------------------------------------
-// A table as the k-mer counter leaves it holds, of every k-mer and its reverse complement, the smaller one only (x <= rc x),
-// sorted.  The complements R of its entries that are not their own complement are then disjoint from the table C (were
-// rc x = y in C, y <= rc y = x and x <= rc x = y would make them equal), so the closure is C merged with sorted R: one sort
-// of m <= n k-mers where smg_engine_condition sorts 2 n, nothing to de-duplicate, no count to choose.  Entry for entry the
-// table smg_engine_condition(e, 0, 0, 1) leaves.
-
-// rc[i] = the reverse complement of entry i, flag[i] = it is another k-mer; *bad is set where it is the SMALLER one
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_rc_flag(const u64 *__restrict__ keys, int64_t n, int k, u64 *__restrict__ rc, uint32_t *__restrict__ flag, uint32_t *__restrict__ bad)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  const Key<W> x = load_key<W>(keys, i);
-  const Key<W> r = revcomp<W>(x, k);
-#pragma unroll
-  for (int w = 0; w < W; w++) rc[i * W + w] = r.w[w];
-  flag[i] = !key_eq<W>(x, r);
-  if (key_lt<W>(r, x)) *bad = 1u;
-}
-
-// the flagged complements, compacted, and the entry each came from
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_rc_compact(const u64 *__restrict__ rc, const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, int64_t n,
-              u64 *__restrict__ okeys, uint32_t *__restrict__ osrc)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const int64_t dst = pos[i];
-#pragma unroll
-  for (int w = 0; w < W; w++) okeys[dst * W + w] = rc[i * W + w];
-  osrc[dst] = (uint32_t) i;
-}
-
-extern "C" int smg_engine_merge_tile(int key_words)
-{ return key_words >= 1 && key_words <= 4 ? ks_merge_tile(key_words) : 0; }
-
-// *not_canonical tells that refusal (SMG_EINVAL like the others, the table untouched) from every other one
-static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical, char *errbuf, size_t errlen)
-{ *not_canonical = false;
-  if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  const int W = e->W;
-  const int64_t n = e->n;
-  int64_t m = 0;
-  hipEventRecord(e->ev[0], e->stream);                 // (booked under ms_decode, like smg_engine_condition)
-  if (n > 0)
-    { const unsigned nblk = (unsigned) ((n + TPB - 1) / TPB);
-      Dev rc, flag, pos, bad, rk, rsrc, perm, split, ko, co;
-      uint32_t h_bad = 0;
-      HIPCHK(dev_alloc(rc, sizeof(u64) * (size_t) n * W));
-      HIPCHK(dev_alloc(flag, sizeof(uint32_t) * (size_t) n));
-      HIPCHK(dev_alloc(pos, sizeof(uint32_t) * (size_t) n));
-      HIPCHK(dev_alloc(bad, 16));
-      HIPCHK(hipMemsetAsync(bad.p, 0, 16, e->stream));
-#define CALL(WW) hipLaunchKernelGGL(kc_rc_flag<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, n, e->kmer, rc.as<u64>(), \
-                   flag.as<uint32_t>(), bad.as<uint32_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-      HIPCHK(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, &e->sort_tmp, &e->sort_tmp_cap, &m));    // (waits)
-      if (h_bad)
-        { *not_canonical = true;
-          return fail(errbuf, errlen, SMG_EINVAL, "table is not canonical: an entry is larger than its reverse complement "
-                      "(smg_engine_condition closes any sorted table)%s");
-        }
-      if (n + m >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "table too large to symmetrise in one shard%s");
-      HIPCHK(dev_alloc(ko, sizeof(u64) * (size_t) (n + m) * W));
-      HIPCHK(dev_alloc(co, sizeof(uint16_t) * (size_t) (n + m) + 16));
-      if (m == 0)                                      // every entry is its own complement: the closure is a copy
-        { HIPCHK(hipMemcpyAsync(ko.p, e->keys, sizeof(u64) * (size_t) n * W, hipMemcpyDeviceToDevice, e->stream));
-          HIPCHK(hipMemcpyAsync(co.p, e->cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToDevice, e->stream));
-        }
-      else
-        { HIPCHK(dev_alloc(rk, sizeof(u64) * (size_t) m * W));
-          HIPCHK(dev_alloc(rsrc, sizeof(uint32_t) * (size_t) m));
-#define CALL(WW) hipLaunchKernelGGL(kc_rc_compact<WW>, dim3(nblk), dim3(TPB), 0, e->stream, rc.as<u64>(), flag.as<uint32_t>(), \
-                   pos.as<uint32_t>(), n, rk.as<u64>(), rsrc.as<uint32_t>())
-          DISPATCH_W(e, CALL)
-#undef CALL
-          HIPCHK(hipStreamSynchronize(e->stream));
-          rc.reset(); flag.reset(); pos.reset();
-          HIPCHK(sort_permutation(rk.as<u64>(), W, m, e->stream, &e->sort_tmp, &e->sort_tmp_cap, perm));
-          const int64_t ntiles = (n + m + ks_merge_tile(W) - 1) / ks_merge_tile(W);
-          HIPCHK(dev_alloc(split, sizeof(uint32_t) * (size_t) (ntiles + 1)));
-#define CALL(WW) hipLaunchKernelGGL(ks_merge_split<WW>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, e->keys, n, \
-                   rk.as<u64>(), perm.as<uint32_t>(), m, ntiles, split.as<uint32_t>())
-          DISPATCH_W(e, CALL)
-#undef CALL
-#define CALL(WW) hipLaunchKernelGGL(ks_merge<WW>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, e->keys, e->cnt, n, rk.as<u64>(), \
-                   perm.as<uint32_t>(), rsrc.as<uint32_t>(), m, split.as<uint32_t>(), ko.as<u64>(), co.as<uint16_t>())
-          DISPATCH_W(e, CALL)
-#undef CALL
-          HIPCHK(hipGetLastError());
-        }
-      HIPCHK(hipStreamSynchronize(e->stream));
-      adopt_table(e, ko, co, n + m);
-    }
-  hipEventRecord(e->ev[1], e->stream);
-  HIPCHK(hipStreamSynchronize(e->stream));
-  float ms = 0; hipEventElapsedTime(&ms, e->ev[0], e->ev[1]);
-  table_changed(e, n + m);
-  e->rp_have = false; e->rp_active = false;
-  e->st.ms_decode += ms;
-  if (new_nels) *new_nels = n + m;
-  return SMG_OK;
-}
-
-extern "C" int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char *errbuf, size_t errlen)
-{ bool not_canonical;
-  return close_canonical(e, new_nels, &not_canonical, errbuf, errlen);
-}
-
-extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
-{ if (!e) return SMG_EINVAL;
-  if (nels) *nels = e->n;
-  if (d_keys) *d_keys = (const uint64_t *) e->keys;
-  if (d_counts) *d_counts = e->cnt;
-  return SMG_OK;
-}
-
-// the same table copied to the host (tests and tools that want to look at a conditioned table): two copies and a wait
-extern "C" int smg_engine_table_host(smg_engine *e, uint64_t *keys, uint16_t *counts, int64_t capacity, char *errbuf, size_t errlen)
-{ NEED_ENGINE(e)
-  if (capacity < e->n || (e->n > 0 && (!keys || !counts)))
-    return fail(errbuf, errlen, SMG_EINVAL, "table_host: the buffers must hold every entry of the table%s");
-  if (e->n == 0) return SMG_OK;
-  if (!e->keys || !e->cnt) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(keys, e->keys, sizeof(u64) * (size_t) e->n * e->W, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(counts, e->cnt, sizeof(uint16_t) * (size_t) e->n, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));
-  return SMG_OK;
-}
-
-// ---- symmetrising a table that is cut into prefix shards (several GPUs, or one device and more than 2^32 entries) -----
-// The reference's Symmex has no size limit (PloidyPlot.c:1395-1414 hands it any table).  Here every shard
-//   1. counts its own entries and their reverse complements per leading `bits` k-mer bits (smg_engine_symm_hist): the
-//      sum over the shards is the shape of the CLOSED table, from which the caller takes balanced splitters -- a table
-//      of canonical k-mers crowds the low end of the k-mer space (7/8 of the k-mers that start with an a are canonical,
-//      1/8 of those that start with a t), its closure does not;
-//   2. writes one record per entry and one per complement, grouped by the shard whose range holds the k-mer
-//      (smg_engine_symm_route; records of W + 1 words: the k-mer, then count | is-a-complement << 16);
-//   3. after the exchange sorts what it received and keeps one entry per k-mer (smg_engine_symm_finish; a k-mer that
-//      arrives as an entry AND as a complement keeps the entry's count -- self-complementary k-mers, or input that was
-//      neither canonical nor closed: the same rule as the single-shard code above).
-
-#define SY_MAXBITS 12
-
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_symm_hist(const u64 *__restrict__ keys, int64_t n, int k, int bits, u64 *__restrict__ hist /* [2 << bits]: own, complements */)
-{ __shared__ unsigned h[2 << SY_MAXBITS];
-  const int nb = 1 << bits;
-  for (int b = threadIdx.x; b < 2 * nb; b += TPB) h[b] = 0;
-  __syncthreads();
-  for (int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t) gridDim.x * TPB)
-    { const Key<W> x = load_key<W>(keys, i);
-      const Key<W> r = revcomp<W>(x, k);
-      atomicAdd(&h[(unsigned) (x.w[0] >> (64 - bits))], 1u);
-      atomicAdd(&h[nb + (unsigned) (r.w[0] >> (64 - bits))], 1u);
-    }
-  __syncthreads();
-  for (int b = threadIdx.x; b < 2 * nb; b += TPB)
-    if (h[b]) atomicAdd(&hist[b], (u64) h[b]);
-}
-
-// record i = (entry i, count), record n + i = (its reverse complement, count | 1 << 16)
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_symm_records(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k, u64 *__restrict__ rec)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  const Key<W> x = load_key<W>(keys, i);
-  const Key<W> r = revcomp<W>(x, k);
-  u64 *a = rec + (size_t) i * (W + 1), *b = rec + (size_t) (n + i) * (W + 1);
-#pragma unroll
-  for (int w = 0; w < W; w++) { a[w] = x.w[w]; b[w] = r.w[w]; }
-  a[W] = (u64) cnt[i];
-  b[W] = (u64) cnt[i] | (1ull << 16);
-}
-
-// records -> separate k-mer / count / is-a-complement arrays
-template <int W> __global__ void __launch_bounds__(TPB)
-kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, uint16_t *__restrict__ cnt, uint8_t *__restrict__ copy)
-{ const int64_t i = (int64_t) blockIdx.x * TPB + threadIdx.x;
-  if (i >= n) return;
-  const u64 *q = rec + (size_t) i * (W + 1);
-#pragma unroll
-  for (int w = 0; w < W; w++) keys[i * W + w] = q[w];
-  cnt[i] = (uint16_t) q[W];
-  copy[i] = (uint8_t) ((q[W] >> 16) & 1u);
-}
-
-extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
-{ if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
-  Dev d;
-  HIPCHK(dev_alloc(d, bytes));
-  hipError_t he = hipMemsetAsync(d.p, 0, bytes, e->stream);
-  if (he == hipSuccess && e->n > 0)
-    { int64_t nb = (e->n + TPB - 1) / TPB;
-      if (nb > 2048) nb = 2048;
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_hist<WW>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->keys, e->n, e->kmer, bits, d.as<u64>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-      he = hipGetLastError();
-    }
-  if (he == hipSuccess) he = hipMemcpyAsync(hist, d.p, bytes, hipMemcpyDeviceToHost, e->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-  if (he != hipSuccess) return fail(errbuf, errlen, SMG_ENODEV, "symm_hist: %s", hipGetErrorString(he));
-  return SMG_OK;
-}
-
-extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, int nranks, uint64_t *d_send,
-                                     int64_t capacity, int64_t *counts, char *errbuf, size_t errlen)
-{ if (!e || !counts || nranks < 1 || nranks > 16) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_route arguments (1..16 ranks)%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  const int64_t n2 = 2 * e->n;
-  if (capacity < n2 || (n2 > 0 && !d_send)) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: the send buffer must hold two records per entry%s");
-  for (int r = 0; r < nranks; r++) counts[r] = 0;
-  if (n2 == 0) return SMG_OK;
-  HIPCHK(hipSetDevice(e->device));
-  const int rw = e->W + 1;
-  const int64_t nc = (n2 + F_CH - 1) / F_CH;
-  if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: shard too large%s");
-  Dev rec, fill;
-  int rc = SMG_OK;
-  if (dev_alloc(rec, sizeof(u64) * (size_t) n2 * rw) != hipSuccess || dev_alloc(fill, sizeof(uint32_t) * (size_t) nc) != hipSuccess)
-    return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
-  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_records<WW>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, e->n, e->kmer, rec.as<u64>())
-  DISPATCH_W(e, CALL)
-#undef CALL
-  hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill.as<uint32_t>(), nc, (uint32_t) F_CH,
-                     (uint32_t) (n2 - (nc - 1) * F_CH));
-  if (hipGetLastError() != hipSuccess) rc = fail(errbuf, errlen, SMG_ENODEV, "symm_route: launch failed%s");
-  if (rc == SMG_OK) rc = route_records(e, rec.as<u64>(), fill.as<uint32_t>(), (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
-  hipStreamSynchronize(e->stream);                     // (the records are freed on return)
-  return rc;
-}
-
-extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int64_t nrecv, int64_t *new_nels,
-                                      char *errbuf, size_t errlen)
-{ if (!e || nrecv < 0 || (nrecv > 0 && !d_recv)) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_finish arguments%s");
-  if (e->kmer < 1) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  int64_t kept = 0;
-  if (nrecv == 0)
-    { Dev ko, co;
-      HIPCHK(dev_alloc(ko, sizeof(u64) * e->W)); HIPCHK(dev_alloc(co, 16));
-      adopt_table(e, ko, co, 0);
-    }
-  else
-    { if (nrecv >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
-      Dev k2, c2, cp;
-      if (dev_alloc(k2, sizeof(u64) * (size_t) nrecv * e->W) != hipSuccess || dev_alloc(c2, sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
-          || dev_alloc(cp, (size_t) nrecv + 16) != hipSuccess)
-        return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
-      const unsigned nblk = (unsigned) ((nrecv + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(kc_symm_unpack<WW>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2.as<u64>(), \
-                   c2.as<uint16_t>(), cp.as<uint8_t>())
-      DISPATCH_W(e, CALL)
-#undef CALL
-      const int rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), cp.as<uint8_t>(), nrecv, &kept, errbuf, errlen);
-      if (rc) return rc;
-    }
-  if (new_nels) *new_nels = kept;
-  return SMG_OK;
-}
+#include "smg_condition.hpp"
 
 // ---- extract: the unique pairs of the labelled pixels (next row of the scope table: extract_kmer_pairs) ------
 
@@ -2829,38 +1407,32 @@ static int engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_o
   HIPCHK(hipSetDevice(e->device));
   u64 *d_total = &e->ctrl->plot_sum;
   HIPCHK(hipMemsetAsync(d_total, 0, sizeof(u64), e->stream));
-  hipEventRecord(e->ev[13], e->stream);
+  hipEventRecord(e->ev[EV_EXTRACT_BEG], e->stream);
   if (e->n > 0 && general)
     { Tab t = make_tab(e);
       const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_extract_general<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out, \
-                   (u64) (d_out ? capacity : 0), d_total, d_set)
-      DISPATCH_W(e, CALL)
-#undef CALL
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_extract_general<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
+          (u64) (d_out ? capacity : 0), d_total, d_set); });
     }
   else if (e->n > 0 && counted)
     { Tab t = make_tab(e);
       const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-#define CALL(WW) hipLaunchKernelGGL(k_extract<WW>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out, \
-                   (u64) (d_out ? capacity : 0), d_total)
-      DISPATCH_W(e, CALL)
-#undef CALL
+      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_extract<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
+          (u64) (d_out ? capacity : 0), d_total); });
     }
   else if (e->n > 0)
     { FastArgs a = make_fast(e);
       int64_t nb = (e->n + F_TPB - 1) / F_TPB;
       if (nb > EX_GRID) nb = EX_GRID;
       { const char *v = test_hook("SMG_EXTRACT_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= EX_GRID && atoi(v) < nb) nb = atoi(v); }
-#define CALL(WW) hipLaunchKernelGGL(kf_extract<WW>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, d_labels, \
-                   (u64 *) d_out, (u64) (d_out ? capacity : 0), d_total)
-      DISPATCH_W3(e, CALL)
-#undef CALL
+      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_extract<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, d_labels,
+          (u64 *) d_out, (u64) (d_out ? capacity : 0), d_total); });
     }
-  hipEventRecord(e->ev[14], e->stream);
+  hipEventRecord(e->ev[EV_EXTRACT_END], e->stream);
   HIPCHK(hipGetLastError());
   int rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
-  hipEventElapsedTime(&e->ms_extract, e->ev[13], e->ev[14]);
+  e->ms_extract = ms_between(e, EV_EXTRACT_BEG, EV_EXTRACT_END);
   *nrec = (int64_t) e->h_ctrl->plot_sum;
   return SMG_OK;
 }
@@ -3023,12 +1595,12 @@ static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *p
   { // the index goes first (asynchronously from pageable memory: staged by the runtime); the records stream behind it,
     // piece by piece through a pinned ring, and every piece is decoded on the device as soon as its copy has landed
     if (hipMemcpyAsync(d_index, tv->prefix_index, ixbytes, hipMemcpyHostToDevice, e->stream) != hipSuccess
-        || hipEventRecord(e->ev[0], e->stream) != hipSuccess)
+        || hipEventRecord(e->ev[EV_DECODE_BEG], e->stream) != hipSuccess)
       BAIL(SMG_ENODEV, "host to device copy failed")
     clock_gettime(CLOCK_MONOTONIC, &w2);
     alloc_s = SECS(w1, w2);
     DecodeHook hk; hk.e = e; hk.d_index = d_index; hk.ibyte = tv->ibyte; hk.ibase = 0;
-    if ((rc = ingest_records(tv, pbyte, 0, tv->nels, NULL, device, tv->host_threads, &h2d_s, errbuf, errlen, decode_hook, &hk, e->ev[0]))) goto done;
+    if ((rc = ingest_records(tv, pbyte, 0, tv->nels, NULL, device, tv->host_threads, &h2d_s, errbuf, errlen, decode_hook, &hk, e->ev[EV_DECODE_BEG]))) goto done;
     if (hipStreamSynchronize(e->stream) != hipSuccess) BAIL(SMG_ENODEV, "host to device copy failed")
   }
   clock_gettime(CLOCK_MONOTONIC, &w1);

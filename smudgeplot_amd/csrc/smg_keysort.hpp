@@ -1,5 +1,5 @@
-// smg_keysort.hpp -- what the k-mer counter (smg_count.hip) and table conditioning (smg_hetmers.hip) share: a device
-// buffer that frees itself, the stable sort of W-word k-mers as a permutation, the scan that turns flags into
+// smg_keysort.hpp -- what the k-mer counter (smg_count.hip) and table conditioning (smg_condition.hpp) share: the device
+// buffer of both and of the engine, rocPRIM's scratch around a call, the stable sort of W-word k-mers as a permutation, the scan that turns flags into
 // positions, and the merge of two sorted lists of k-mers.  No state of its own; every function returns the HIP error and the caller gives it its own code and message.
 
 #pragma once
@@ -13,31 +13,44 @@
 #define KS_TPB 256
 #define KS_TRY(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return _e; } while (0)
 
-struct Dev                                                     // a device allocation that frees itself
+#define KS_SLACK 256                                            // bytes past what rocPRIM asks for (with_scratch)
+
+// A device allocation that frees itself and knows its size.  reserve() is grow-only: an allocation that is large enough
+// stays, any other is freed and made anew with exactly the bytes asked for -- the contents are lost, and on failure the
+// buffer is empty.  alloc() always allocates anew.
+struct Dev
 { void *p = nullptr;
-  ~Dev() { if (p) (void) hipFree(p); }
-  void reset() { if (p) (void) hipFree(p); p = nullptr; }
-  void take(Dev &o) { reset(); p = o.p; o.p = nullptr; }
-  void *release() { void *q = p; p = nullptr; return q; }     // the caller owns the allocation from here on
+  size_t bytes = 0;
+  Dev() = default;
+  Dev(const Dev &) = delete;
+  Dev &operator=(const Dev &) = delete;
+  ~Dev() { reset(); }
+  void reset() { if (p) (void) hipFree(p); p = nullptr; bytes = 0; }
+  void swap(Dev &o) { void *q = p; p = o.p; o.p = q; const size_t b = bytes; bytes = o.bytes; o.bytes = b; }
+  void take(Dev &o) { reset(); swap(o); }
+  void *release() { void *q = p; p = nullptr; bytes = 0; return q; }     // the caller owns the allocation from here on
+  hipError_t reserve(size_t need)
+  { if (p && bytes >= need) return hipSuccess;
+    reset();
+    const hipError_t e = hipMalloc(&p, need);
+    if (e != hipSuccess) p = nullptr; else bytes = need;
+    return e;
+  }
+  hipError_t alloc(size_t need) { reset(); return reserve(need ? need : 16); }
   template <class T> T *as() const { return (T *) p; }
 };
 
-static inline hipError_t dev_alloc(Dev &d, size_t bytes)
-{ d.reset();
-  const hipError_t e = hipMalloc(&d.p, bytes ? bytes : 16);
-  if (e != hipSuccess) d.p = nullptr;
-  return e;
-}
+template <class T> struct DevBuf : Dev                          // ... that reads as the T * it holds
+{ operator T *() const { return (T *) p; }
+  T *operator->() const { return (T *) p; }
+};
 
-// the caller's grow-only rocPRIM scratch: at least `bytes` behind *tmp afterwards
-static inline hipError_t ks_scratch(void **tmp, int64_t *cap, size_t bytes)
-{ if (*tmp && (int64_t) bytes <= *cap) return hipSuccess;
-  if (*tmp) (void) hipFree(*tmp);
-  *tmp = nullptr; *cap = 0;
-  const hipError_t e = hipMalloc(tmp, bytes + 256);
-  if (e != hipSuccess) { *tmp = nullptr; return e; }
-  *cap = (int64_t) bytes + 256;
-  return hipSuccess;
+// rocPRIM's two calls -- ask for the scratch size, run with that much -- around the caller's grow-only scratch
+template <class F> static inline hipError_t with_scratch(Dev &tmp, F &&run)
+{ size_t bytes = 0;
+  KS_TRY(run((void *) nullptr, bytes));
+  KS_TRY(tmp.reserve(bytes + KS_SLACK));
+  return run(tmp.p, bytes);
 }
 
 __global__ void __launch_bounds__(KS_TPB) ks_iota(uint32_t *__restrict__ p, int64_t n)
@@ -57,21 +70,18 @@ ks_gather_word(const u64 *__restrict__ keys, const uint32_t *__restrict__ perm, 
 // wrong with a partial bit range (garbage, or runs of 1024 keys left unmerged with a begin bit above 0), while the full
 // range is exact on every path -- and costs a W-word k-mer nothing, since all 64 bits of a word count.  The four work
 // buffers are freed on return, hence the wait for the stream.
-static inline hipError_t sort_permutation(const u64 *keys, int W, int64_t n, hipStream_t stream, void **tmp, int64_t *tmp_cap, Dev &perm)
+static inline hipError_t sort_permutation(const u64 *keys, int W, int64_t n, hipStream_t stream, Dev &tmp, Dev &perm)
 { if (n < 1 || n >= 0xFFFFFFF0ll) return hipErrorInvalidValue;              // (uint32 permutation: the callers say so first)
   const unsigned nblk = (unsigned) ((n + KS_TPB - 1) / KS_TPB);
   Dev w1, w2, p1, p2;
-  KS_TRY(dev_alloc(w1, sizeof(u64) * (size_t) n)); KS_TRY(dev_alloc(w2, sizeof(u64) * (size_t) n));
-  KS_TRY(dev_alloc(p1, sizeof(uint32_t) * (size_t) n)); KS_TRY(dev_alloc(p2, sizeof(uint32_t) * (size_t) n));
+  KS_TRY(w1.alloc(sizeof(u64) * (size_t) n)); KS_TRY(w2.alloc(sizeof(u64) * (size_t) n));
+  KS_TRY(p1.alloc(sizeof(uint32_t) * (size_t) n)); KS_TRY(p2.alloc(sizeof(uint32_t) * (size_t) n));
   rocprim::double_buffer<uint32_t> pb(p1.as<uint32_t>(), p2.as<uint32_t>());
   hipLaunchKernelGGL(ks_iota, dim3(nblk), dim3(KS_TPB), 0, stream, pb.current(), n);
   for (int w = W - 1; w >= 0; w--)
     { rocprim::double_buffer<u64> word(w1.as<u64>(), w2.as<u64>());
       hipLaunchKernelGGL(ks_gather_word, dim3(nblk), dim3(KS_TPB), 0, stream, keys, pb.current(), W, w, n, word.current());
-      size_t bytes = 0;
-      KS_TRY(rocprim::radix_sort_pairs(nullptr, bytes, word, pb, (size_t) n, 0u, 64u, stream));
-      KS_TRY(ks_scratch(tmp, tmp_cap, bytes));
-      KS_TRY(rocprim::radix_sort_pairs(*tmp, bytes, word, pb, (size_t) n, 0u, 64u, stream));
+      KS_TRY(with_scratch(tmp, [&](void *t, size_t &bytes) { return rocprim::radix_sort_pairs(t, bytes, word, pb, (size_t) n, 0u, 64u, stream); }));
     }
   KS_TRY(hipGetLastError());
   KS_TRY(hipStreamSynchronize(stream));
@@ -80,11 +90,9 @@ static inline hipError_t sort_permutation(const u64 *keys, int W, int64_t n, hip
 }
 
 // pos[] = exclusive scan of flag[0 .. n), n > 0; *total = the number of set flags (one wait for the stream)
-static inline hipError_t scan_flags(uint32_t *flag, uint32_t *pos, int64_t n, hipStream_t stream, void **tmp, int64_t *tmp_cap, int64_t *total)
-{ size_t bytes = 0;
-  KS_TRY(rocprim::exclusive_scan(nullptr, bytes, flag, pos, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
-  KS_TRY(ks_scratch(tmp, tmp_cap, bytes));
-  KS_TRY(rocprim::exclusive_scan(*tmp, bytes, flag, pos, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream));
+static inline hipError_t scan_flags(uint32_t *flag, uint32_t *pos, int64_t n, hipStream_t stream, Dev &tmp, int64_t *total)
+{ KS_TRY(with_scratch(tmp, [&](void *t, size_t &bytes)
+    { return rocprim::exclusive_scan(t, bytes, flag, pos, 0u, (size_t) n, rocprim::plus<uint32_t>(), stream); }));
   uint32_t last[2] = { 0, 0 };
   KS_TRY(hipMemcpyAsync(&last[0], flag + n - 1, 4, hipMemcpyDeviceToHost, stream));
   KS_TRY(hipMemcpyAsync(&last[1], pos + n - 1, 4, hipMemcpyDeviceToHost, stream));

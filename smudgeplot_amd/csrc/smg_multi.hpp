@@ -122,7 +122,7 @@ static int multi_filter(MultiCtx *c, int r, smg_engine *e, const u64 *splitters,
   for (int s = 0; s < n; s++) if (c->bm_bits[s] != bits) return SMG_OK;       // (cannot happen: a function of k and the proof)
   if (!bits) return SMG_OK;
   const int two = e->bm2;                            // 64-bit map words (two-bit map): twice the 32-bit words per id range
-  const int64_t nwords = (((1ll << bits) + 31) >> 5) << two;
+  const int64_t nwords = bm_words(bits, two);
   int64_t wlo[SMG_MAXGPU], wlen[SMG_MAXGPU], width = 1;
   for (int s = 0; s < n; s++)
     { const u64 a = s == 0 ? 0 : splitters[(size_t) (s - 1) * c->W] >> (64 - bits);

@@ -323,7 +323,7 @@ def test_condition_executable(tmp_path):
 
 @pytest.mark.parametrize("k", [32, 65])
 def test_both_strands_with_different_counts(k):
-    """smg_hetmers.hip, "table conditioning on device" and "symmetrising a table that is cut into prefix shards": every input
+    """smg_condition.hpp, "table conditioning on device" and "symmetrising a table that is cut into prefix shards": every input
     entry keeps its own count, and a complement is added (with its entry's count) only where the table does not hold it"""
     import torch
     from smudgeplot_amd import sharded
