@@ -375,6 +375,11 @@ void    smg_engine_pass2_limits(int32_t out[8]);
    [10] slices of the owners per kl_tot / kl_woff workgroup, [11] rows a thread of them loads together.              */
 void    smg_engine_lookup_limits(int32_t out[12]);
 
+/* the tile of kf_pass1_d, pass 1 of k <= 64 (read-only, needs no device; for tests): out[0] entries a tile owns -- tile t owns
+   the entries t * out[0] .. (t + 1) * out[0] - 1 --, [1] entries it stages in front of the first one it owns, [2] entries it
+   stages in all, [3] the distance up to which partners are searched (longer window blocks are redone by kf_bigfix).          */
+void    smg_engine_pass1_limits(int32_t out[4]);
+
 /* what the last pass 1 / filter / look-up of this engine did (plain host fields; for tests): out[0] id bits of the
    block map, [1] bucket bits (0: the chain did not run), [2] two-bit map, [3] one-way requests, [4] words per record,
    [5] workgroups of pass 1 (test hook SMG_P1_GRID=<g> lowers them), [6] owners of the request list, [7] chunk slots

@@ -1452,6 +1452,11 @@ extern "C" void smg_engine_lookup_limits(int32_t out[12])
   memcpy(out, v, sizeof(v));
 }
 
+extern "C" void smg_engine_pass1_limits(int32_t out[4])
+{ const int32_t v[4] = { D_OWN, D_LEAD, D_SLOTS, D_WIN };
+  memcpy(out, v, sizeof(v));
+}
+
 extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])
 { if (!e || !out) return SMG_EINVAL;
   const bool chain = e->prepared && e->fast && e->lg.nb > 0;

@@ -69,7 +69,7 @@ EXPORTS = [
     "smg_engine_table_host",
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
-    "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form",
+    "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
 ]
 
 _lib = None
@@ -131,6 +131,9 @@ def load_library():
     lib.smg_engine_lookup_state.argtypes = [vp, C.POINTER(i64)]
     if hasattr(lib, "smg_engine_pass1_form"):          # (SMG_LIB / tools/ab_libs.py load the libraries of earlier commits too)
         lib.smg_engine_pass1_form.argtypes = [vp, C.POINTER(C.c_int32)]
+    if hasattr(lib, "smg_engine_pass1_limits"):
+        lib.smg_engine_pass1_limits.argtypes = [C.POINTER(C.c_int32)]
+        lib.smg_engine_pass1_limits.restype = None
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
@@ -245,6 +248,17 @@ def lookup_limits() -> dict:
     out = (C.c_int32 * 12)()
     load_library().smg_engine_lookup_limits(out)
     return dict(zip(LOOKUP_LIMITS, (int(v) for v in out)))
+
+
+PASS1_LIMITS = ("D_OWN", "D_LEAD", "D_SLOTS", "D_WIN")
+
+
+def pass1_limits() -> dict:
+    """the tile of kf_pass1_d (smg_engine_pass1_limits; no device needed): entries a tile owns (tile t owns t * D_OWN and the
+    D_OWN - 1 behind it), entries staged in front of the first owned one, entries staged in all, the partner window"""
+    out = (C.c_int32 * 4)()
+    load_library().smg_engine_pass1_limits(out)
+    return dict(zip(PASS1_LIMITS, (int(v) for v in out)))
 
 
 def _table_view(table):
