@@ -393,6 +393,18 @@ int     smg_engine_lookup_state(smg_engine *e, int64_t out[10]);
    of inner tiles only).                                                                                                  */
 int     smg_engine_pass1_form(smg_engine *e, int32_t out[4]);
 
+/* what pass 1 of the fast path (k <= 85) WOULD decide for a table of `nels` entries (read-only, needs no engine and no device;
+   for tests: the function the engine itself calls).  symcheck: SMG_SYM_HASH or SMG_SYM_EXACT; own_lookups: the caller is
+   smg_engine_run (1) or the phase API (0); have_index: a 3-byte prefix index was handed over; bm_cap: id bits of the map at
+   most (smg_engine_run: 32, the phase API: 30 or what smg_engine_set_blockmap_bits asked for); no_filter: out-of-core shards.
+   The test hooks SMG_TWO_WAY, SMG_NO_FILTER, SMG_ONE_BIT_MAP, SMG_SIG and SMG_BM_BITS are read as the engine reads them.
+   out[0] words per request record, [1] one-way requests, [2] kf_pass1_d (k <= 64), [3] entries per directory bucket,
+   [4] the index serves as directory, [5] id bits of the candidate map (0: none), [6] two-bit map, [7] bucket bits of the look-up
+   chain (0: no chain), [8] signatures, [9] the form (smg_engine_pass1_form's out[0]), [10] template argument KF, [11] words
+   per k-mer.  SMG_EINVAL for k outside 1 .. 85, nels < 0 or SMG_SYM_NONE.                                                  */
+int     smg_engine_pass1_plan(int kmer, int64_t nels, int symcheck, int own_lookups, int have_index, int bm_cap, int no_filter,
+                              int32_t out[12]);
+
 /* library / build identification, e.g. "smudgeplot_amd 0.1 gfx950" */
 const char *smg_version(void);
 

@@ -73,18 +73,10 @@ kc_compact_pref(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, 
   ocnt[dst] = cnt[csrc];
 }
 
-// the engine's table has n entries now and is another table: what a run, the prefix index and the ends said is gone
-static void table_changed(smg_engine *e, int64_t n)
-{ e->n = n;
-  e->prepared = false; e->counted_done = false; e->general_done = false;
-  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;
-  e->st.nels = n;
-}
-
 // (k, c), n finished entries, leave their buffers and become the engine's own table.  The stream is idle: the old one is freed.
 static void adopt_table(smg_engine *e, Dev &k, Dev &c, int64_t n)
 { e->own_keys.take(k); e->own_cnt.take(c);
-  e->keys = e->own_keys; e->cnt = e->own_cnt;
+  e->tab.keys = e->own_keys; e->tab.cnt = e->own_cnt;
   table_changed(e, n);
 }
 
@@ -92,7 +84,7 @@ static void adopt_table(smg_engine *e, Dev &k, Dev &c, int64_t n)
 // equal k-mers in INPUT order wins, as the stable sort leaves it) -> the engine's own table.  Frees nothing of the caller's.
 static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, const uint8_t *copy, int64_t n2,
                             int64_t *kept_out, char *errbuf, size_t errlen)
-{ const int W = e->W;
+{ const int W = e->tab.W;
   if (n2 >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
   const unsigned nblk2 = (unsigned) ((n2 + TPB - 1) / TPB);
   Dev perm, flag, pos, ko, co;
@@ -100,18 +92,18 @@ static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, co
   HIPCHK(sort_permutation(k2, W, n2, e->stream, e->sort_tmp, perm));
   HIPCHK(flag.alloc(sizeof(uint32_t) * (size_t) n2));
   HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n2));
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_flag_first<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm.as<uint32_t>(), n2, flag.as<uint32_t>()); });
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_flag_first<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, perm.as<uint32_t>(), n2, flag.as<uint32_t>()); });
   HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n2, e->stream, e->sort_tmp, &kept));
   HIPCHK(ko.alloc(sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
   HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
   if (copy)
     {
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact_pref<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm.as<uint32_t>(),
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_compact_pref<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, copy, perm.as<uint32_t>(),
           flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>()); });
     }
   else
     {
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm.as<uint32_t>(),
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk2), dim3(TPB), 0, e->stream, k2, c2, perm.as<uint32_t>(),
           flag.as<uint32_t>(), pos.as<uint32_t>(), n2, ko.as<u64>(), co.as<uint16_t>()); });
     }
   HIPCHK(hipStreamSynchronize(e->stream));
@@ -123,11 +115,11 @@ static int cond_sort_dedupe(smg_engine *e, const u64 *k2, const uint16_t *c2, co
 extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
                                     int64_t *new_nels, char *errbuf, size_t errlen)
 { if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
-  const int W = e->W;
+  const int W = e->tab.W;
   int rc;
-  int64_t n = e->n;
+  int64_t n = e->tab.n;
   hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);                 // (the decode pair: conditioning is booked under ms_decode)
 
   if (do_trim && n > 0)
@@ -135,12 +127,12 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
       Dev flag, pos, ko, co;
       HIPCHK(flag.alloc(sizeof(uint32_t) * (size_t) n));
       HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n));
-      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->cnt, n, (unsigned) ethresh, flag.as<uint32_t>());
+      hipLaunchKernelGGL(kc_flag_trim, dim3(nblk), dim3(TPB), 0, e->stream, e->tab.cnt, n, (unsigned) ethresh, flag.as<uint32_t>());
       int64_t kept = 0;
       HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, e->sort_tmp, &kept));
       HIPCHK(ko.alloc(sizeof(u64) * (size_t) (kept > 0 ? kept : 1) * W));
       HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (kept > 0 ? kept : 1) + 16));
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt,
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->tab.keys, e->tab.cnt,
           (const uint32_t *) NULL, flag.as<uint32_t>(), pos.as<uint32_t>(), n, ko.as<u64>(), co.as<uint16_t>()); });
       HIPCHK(hipStreamSynchronize(e->stream));
       adopt_table(e, ko, co, kept);
@@ -154,7 +146,7 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
       Dev k2, c2;
       HIPCHK(k2.alloc(sizeof(u64) * (size_t) n2 * W));
       HIPCHK(c2.alloc(sizeof(uint16_t) * (size_t) n2));
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_append_rc<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, n, e->kmer,
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_append_rc<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->tab.keys, e->tab.cnt, n, e->tab.kmer,
           k2.as<u64>(), c2.as<uint16_t>()); });
       // (entries first, complements behind them: the stable sort keeps the entry in front of an equal complement)
       if ((rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), NULL, n2, &n, errbuf, errlen))) return rc;
@@ -163,7 +155,7 @@ extern "C" int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int
   HIPCHK(hipStreamSynchronize(e->stream));
   const float ms = ms_between(e, EV_DECODE_BEG, EV_DECODE_END);
   table_changed(e, n);                                 // (also where nothing was asked for, or of an empty table)
-  e->rp_have = false; e->rp_active = false;
+  e->rp.have = false; e->rp.active = false;
   e->st.ms_decode += ms;
   if (new_nels) *new_nels = n;
   return SMG_OK;
@@ -208,10 +200,10 @@ extern "C" int smg_engine_merge_tile(int key_words)
 static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical, char *errbuf, size_t errlen)
 { *not_canonical = false;
   if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
-  const int W = e->W;
-  const int64_t n = e->n;
+  const int W = e->tab.W;
+  const int64_t n = e->tab.n;
   int64_t m = 0;
   hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);                 // (booked under ms_decode, like smg_engine_condition)
   if (n > 0)
@@ -223,7 +215,7 @@ static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical
       HIPCHK(pos.alloc(sizeof(uint32_t) * (size_t) n));
       HIPCHK(bad.alloc(16));
       HIPCHK(hipMemsetAsync(bad.p, 0, 16, e->stream));
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_rc_flag<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, n, e->kmer, rc.as<u64>(),
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_rc_flag<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->tab.keys, n, e->tab.kmer, rc.as<u64>(),
           flag.as<uint32_t>(), bad.as<uint32_t>()); });
       HIPCHK(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(scan_flags(flag.as<uint32_t>(), pos.as<uint32_t>(), n, e->stream, e->sort_tmp, &m));    // (waits)
@@ -236,22 +228,22 @@ static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical
       HIPCHK(ko.alloc(sizeof(u64) * (size_t) (n + m) * W));
       HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (n + m) + 16));
       if (m == 0)                                      // every entry is its own complement: the closure is a copy
-        { HIPCHK(hipMemcpyAsync(ko.p, e->keys, sizeof(u64) * (size_t) n * W, hipMemcpyDeviceToDevice, e->stream));
-          HIPCHK(hipMemcpyAsync(co.p, e->cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToDevice, e->stream));
+        { HIPCHK(hipMemcpyAsync(ko.p, e->tab.keys, sizeof(u64) * (size_t) n * W, hipMemcpyDeviceToDevice, e->stream));
+          HIPCHK(hipMemcpyAsync(co.p, e->tab.cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToDevice, e->stream));
         }
       else
         { HIPCHK(rk.alloc(sizeof(u64) * (size_t) m * W));
           HIPCHK(rsrc.alloc(sizeof(uint32_t) * (size_t) m));
-          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_rc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, rc.as<u64>(), flag.as<uint32_t>(),
+          with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_rc_compact<w()>, dim3(nblk), dim3(TPB), 0, e->stream, rc.as<u64>(), flag.as<uint32_t>(),
               pos.as<uint32_t>(), n, rk.as<u64>(), rsrc.as<uint32_t>()); });
           HIPCHK(hipStreamSynchronize(e->stream));
           rc.reset(); flag.reset(); pos.reset();
           HIPCHK(sort_permutation(rk.as<u64>(), W, m, e->stream, e->sort_tmp, perm));
           const int64_t ntiles = (n + m + ks_merge_tile(W) - 1) / ks_merge_tile(W);
           HIPCHK(split.alloc(sizeof(uint32_t) * (size_t) (ntiles + 1)));
-          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(ks_merge_split<w()>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, e->keys, n,
+          with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(ks_merge_split<w()>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, e->tab.keys, n,
               rk.as<u64>(), perm.as<uint32_t>(), m, ntiles, split.as<uint32_t>()); });
-          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(ks_merge<w()>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, e->keys, e->cnt, n, rk.as<u64>(),
+          with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(ks_merge<w()>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, e->tab.keys, e->tab.cnt, n, rk.as<u64>(),
               perm.as<uint32_t>(), rsrc.as<uint32_t>(), m, split.as<uint32_t>(), ko.as<u64>(), co.as<uint16_t>()); });
           HIPCHK(hipGetLastError());
         }
@@ -262,7 +254,7 @@ static int close_canonical(smg_engine *e, int64_t *new_nels, bool *not_canonical
   HIPCHK(hipStreamSynchronize(e->stream));
   const float ms = ms_between(e, EV_DECODE_BEG, EV_DECODE_END);
   table_changed(e, n + m);
-  e->rp_have = false; e->rp_active = false;
+  e->rp.have = false; e->rp.active = false;
   e->st.ms_decode += ms;
   if (new_nels) *new_nels = n + m;
   return SMG_OK;
@@ -275,22 +267,22 @@ extern "C" int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char
 
 extern "C" int smg_engine_table(smg_engine *e, int64_t *nels, const uint64_t **d_keys, const uint16_t **d_counts)
 { if (!e) return SMG_EINVAL;
-  if (nels) *nels = e->n;
-  if (d_keys) *d_keys = (const uint64_t *) e->keys;
-  if (d_counts) *d_counts = e->cnt;
+  if (nels) *nels = e->tab.n;
+  if (d_keys) *d_keys = (const uint64_t *) e->tab.keys;
+  if (d_counts) *d_counts = e->tab.cnt;
   return SMG_OK;
 }
 
 // the same table copied to the host (tests and tools that want to look at a conditioned table): two copies and a wait
 extern "C" int smg_engine_table_host(smg_engine *e, uint64_t *keys, uint16_t *counts, int64_t capacity, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (capacity < e->n || (e->n > 0 && (!keys || !counts)))
+  if (capacity < e->tab.n || (e->tab.n > 0 && (!keys || !counts)))
     return fail(errbuf, errlen, SMG_EINVAL, "table_host: the buffers must hold every entry of the table%s");
-  if (e->n == 0) return SMG_OK;
-  if (!e->keys || !e->cnt) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  if (e->tab.n == 0) return SMG_OK;
+  if (!e->tab.keys || !e->tab.cnt) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
-  HIPCHK(hipMemcpyAsync(keys, e->keys, sizeof(u64) * (size_t) e->n * e->W, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(hipMemcpyAsync(counts, e->cnt, sizeof(uint16_t) * (size_t) e->n, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(keys, e->tab.keys, sizeof(u64) * (size_t) e->tab.n * e->tab.W, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipMemcpyAsync(counts, e->tab.cnt, sizeof(uint16_t) * (size_t) e->tab.n, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(hipStreamSynchronize(e->stream));
   return SMG_OK;
 }
@@ -354,17 +346,17 @@ kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, u
 
 extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
 { if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->tab.kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
+  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
   const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
   Dev d;
   HIPCHK(d.alloc(bytes));
   hipError_t he = hipMemsetAsync(d.p, 0, bytes, e->stream);
-  if (he == hipSuccess && e->n > 0)
-    { int64_t nb = (e->n + TPB - 1) / TPB;
+  if (he == hipSuccess && e->tab.n > 0)
+    { int64_t nb = (e->tab.n + TPB - 1) / TPB;
       if (nb > 2048) nb = 2048;
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_hist<w()>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->keys, e->n, e->kmer, bits, d.as<u64>()); });
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_symm_hist<w()>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->tab.keys, e->tab.n, e->tab.kmer, bits, d.as<u64>()); });
       he = hipGetLastError();
     }
   if (he == hipSuccess) he = hipMemcpyAsync(hist, d.p, bytes, hipMemcpyDeviceToHost, e->stream);
@@ -376,21 +368,21 @@ extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char
 extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, int nranks, uint64_t *d_send,
                                      int64_t capacity, int64_t *counts, char *errbuf, size_t errlen)
 { if (!e || !counts || nranks < 1 || nranks > 16) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_route arguments (1..16 ranks)%s");
-  if (!e->keys && e->n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  const int64_t n2 = 2 * e->n;
+  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  const int64_t n2 = 2 * e->tab.n;
   if (capacity < n2 || (n2 > 0 && !d_send)) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: the send buffer must hold two records per entry%s");
   for (int r = 0; r < nranks; r++) counts[r] = 0;
   if (n2 == 0) return SMG_OK;
   HIPCHK(hipSetDevice(e->device));
-  const int rw = e->W + 1;
+  const int rw = e->tab.W + 1;
   const int64_t nc = (n2 + F_CH - 1) / F_CH;
   if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "symm_route: shard too large%s");
   Dev rec, fill;
   int rc = SMG_OK;
   if (rec.alloc(sizeof(u64) * (size_t) n2 * rw) != hipSuccess || fill.alloc(sizeof(uint32_t) * (size_t) nc) != hipSuccess)
     return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
-  const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_records<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->keys, e->cnt, e->n, e->kmer, rec.as<u64>()); });
+  const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_symm_records<w()>, dim3(nblk), dim3(TPB), 0, e->stream, e->tab.keys, e->tab.cnt, e->tab.n, e->tab.kmer, rec.as<u64>()); });
   hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill.as<uint32_t>(), nc, (uint32_t) F_CH,
                      (uint32_t) (n2 - (nc - 1) * F_CH));
   if (hipGetLastError() != hipSuccess) rc = fail(errbuf, errlen, SMG_ENODEV, "symm_route: launch failed%s");
@@ -402,22 +394,22 @@ extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, i
 extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int64_t nrecv, int64_t *new_nels,
                                       char *errbuf, size_t errlen)
 { if (!e || nrecv < 0 || (nrecv > 0 && !d_recv)) return fail(errbuf, errlen, SMG_EINVAL, "bad symm_finish arguments%s");
-  if (e->kmer < 1) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  if (e->tab.kmer < 1) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
   HIPCHK(hipSetDevice(e->device));
   int64_t kept = 0;
   if (nrecv == 0)
     { Dev ko, co;
-      HIPCHK(ko.alloc(sizeof(u64) * e->W)); HIPCHK(co.alloc(16));
+      HIPCHK(ko.alloc(sizeof(u64) * e->tab.W)); HIPCHK(co.alloc(16));
       adopt_table(e, ko, co, 0);
     }
   else
     { if (nrecv >= 0xFFFFFFF0ll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large to symmetrise (2^32 entries per shard)%s");
       Dev k2, c2, cp;
-      if (k2.alloc(sizeof(u64) * (size_t) nrecv * e->W) != hipSuccess || c2.alloc(sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
+      if (k2.alloc(sizeof(u64) * (size_t) nrecv * e->tab.W) != hipSuccess || c2.alloc(sizeof(uint16_t) * (size_t) nrecv + 16) != hipSuccess
           || cp.alloc((size_t) nrecv + 16) != hipSuccess)
         return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
       const unsigned nblk = (unsigned) ((nrecv + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kc_symm_unpack<w()>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2.as<u64>(),
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_symm_unpack<w()>, dim3(nblk), dim3(TPB), 0, e->stream, (const u64 *) d_recv, nrecv, k2.as<u64>(),
           c2.as<uint16_t>(), cp.as<uint8_t>()); });
       const int rc = cond_sort_dedupe(e, k2.as<u64>(), c2.as<uint16_t>(), cp.as<uint8_t>(), nrecv, &kept, errbuf, errlen);
       if (rc) return rc;

@@ -450,23 +450,23 @@ k_extract_general(Tab t, const uint16_t *__restrict__ labels, u64 *__restrict__ 
 
 static Tab make_tab(smg_engine *e)
 { Tab t;
-  t.keys = e->keys; t.cnt = e->cnt; t.deg = e->deg; t.n = e->n; t.g = e->geo; t.dir = e->dir;
+  t.keys = e->tab.keys; t.cnt = e->tab.cnt; t.deg = e->deg; t.n = e->tab.n; t.g = e->tab.geo; t.dir = e->run.dir;
   return t;
 }
 
-static int counted_prepare(smg_engine *e, char *errbuf, size_t errlen)
-{ HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
+static int counted_prepare(smg_engine *e, RunKind kind, char *errbuf, size_t errlen)
+{ begin_run(e, kind);
+  HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
-  e->fast = false; e->counted_done = false; e->general_done = false;
-  const int64_t dbytes = ((e->n + 3) & ~3ll) + 4;
+  const int64_t dbytes = ((e->tab.n + 3) & ~3ll) + 4;
   HIPCHK(e->deg.reserve(dbytes));
   HIPCHK(hipMemsetAsync(e->deg, 0, (size_t) dbytes, e->stream));
   const int rc = dir_geometry(e, 8, errbuf, errlen);
   if (rc) return rc;
-  HIPCHK(hipMemsetAsync(e->bstart, 0xFF, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
+  HIPCHK(hipMemsetAsync(e->bstart, 0xFF, sizeof(uint32_t) * ((size_t) e->run.dir.nb + 2), e->stream));
   Tab t = make_tab(e);
-  const unsigned nblk = (unsigned) ((e->n + 1 + TPB - 1) / TPB);
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_directory<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl); });
+  const unsigned nblk = (unsigned) ((e->tab.n + 1 + TPB - 1) / TPB);
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_directory<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl); });
   HIPCHK(hipGetLastError());
   return SMG_OK;
 }
@@ -481,13 +481,13 @@ __global__ void __launch_bounds__(TPB) kc_fill_u32(uint32_t *__restrict__ p, int
 
 // k_pass1<W, SYM>: events 2, 3
 template <bool SYM> static void launch_pass1(smg_engine *e, int emit_all, int want_fp, u64 *req, int64_t cap, const TabSet *d_set)
-{ const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
+{ const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
   Tab t = make_tab(e);
   hipEventRecord(e->ev[EV_PASS1_BEG], e->stream);
-  if (e->n > 0)
+  if (e->tab.n > 0)
     {
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL((k_pass1<w(), SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t,
-          (int64_t) 0, e->n, emit_all, want_fp, req, cap, e->ctrl, d_set); });
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL((k_pass1<w(), SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t,
+          (int64_t) 0, e->tab.n, emit_all, want_fp, req, cap, e->ctrl, d_set); });
     }
   hipEventRecord(e->ev[EV_PASS1_END], e->stream);
 }
@@ -498,11 +498,11 @@ static void launch_apply(smg_engine *e, const u64 *rec, int64_t nrec, bool verif
   hipEventRecord(e->ev[EV_LOOKUP_BEG], e->stream);
   if (nrec > 0)
     { const unsigned rb = (unsigned) ((nrec + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_apply<w()>, dim3(rb), dim3(TPB), 0, e->stream, t, rec, nrec, e->ctrl); });
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_apply<w()>, dim3(rb), dim3(TPB), 0, e->stream, t, rec, nrec, e->ctrl); });
     }
-  if (verify && e->n > 0)
-    { const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_verify<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, (int64_t) 0, e->n, e->ctrl); });
+  if (verify && e->tab.n > 0)
+    { const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_verify<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, (int64_t) 0, e->tab.n, e->ctrl); });
     }
   hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
 }
@@ -511,11 +511,11 @@ static void launch_apply(smg_engine *e, const u64 *rec, int64_t nrec, bool verif
 template <bool SYM> static int launch_pass2(smg_engine *e, int64_t *d_plot, const TabSet *d_set, char *errbuf, size_t errlen)
 { HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
   hipEventRecord(e->ev[EV_PASS2_BEG], e->stream);
-  if (e->n > 0)
+  if (e->tab.n > 0)
     { Tab t = make_tab(e);
-      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL((k_pass2<w(), SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t,
-          (int64_t) 0, e->n, (u64 *) d_plot, d_set); });
+      const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL((k_pass2<w(), SYM>), dim3(nblk), dim3(TPB), 0, e->stream, t,
+          (int64_t) 0, e->tab.n, (u64 *) d_plot, d_set); });
     }
   hipEventRecord(e->ev[EV_PASS2_END], e->stream);
   HIPCHK(hipGetLastError());
@@ -527,9 +527,9 @@ template <bool SYM> static int launch_pass2(smg_engine *e, int64_t *d_plot, cons
 // where pass 1 counted more, that many on the second attempt.
 static int counted_pass1(smg_engine *e, int emit_all, int symcheck, int64_t cap, char *errbuf, size_t errlen)
 { int rc;
-  if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
+  if ((rc = counted_prepare(e, RUN_COUNTED, errbuf, errlen))) return rc;
   for (int attempt = 0; attempt < 2; attempt++)
-    { HIPCHK(e->req.reserve(cap * (int64_t) sizeof(u64) * (e->W + 1)));
+    { HIPCHK(e->req.reserve(cap * (int64_t) sizeof(u64) * (e->tab.W + 1)));
       launch_pass1<true>(e, emit_all, symcheck == SMG_SYM_HASH, e->req, cap, NULL);
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       if (e->h_ctrl->unsorted)
@@ -548,7 +548,7 @@ static int counted_pass1(smg_engine *e, int emit_all, int symcheck, int64_t cap,
 static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool *symmetric,
                              char *errbuf, size_t errlen)
 { int rc;
-  if ((rc = counted_pass1(e, 0, symcheck, e->n / 4 + 1024, errbuf, errlen))) return rc;
+  if ((rc = counted_pass1(e, 0, symcheck, e->tab.n / 4 + 1024, errbuf, errlen))) return rc;
   launch_apply(e, e->req, e->st.nrequests, symcheck == SMG_SYM_EXACT);
   if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
   e->st.ms_rclookup = ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
@@ -560,7 +560,7 @@ static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool 
   if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
   e->st.ms_pass2 = ms_between(e, EV_PASS2_BEG, EV_PASS2_END);
   e->st.path = 1;
-  e->counted_done = true;
+  e->run.completed = true;
   return SMG_OK;
 }
 
@@ -569,11 +569,11 @@ static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool 
 // and proves that the k-mer is there with the same count.  The exact proof emits from every entry instead of k_verify.
 static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
 { const int emit_all = symcheck == SMG_SYM_EXACT;
-  e->rw = e->W + 1;
-  int rc = counted_pass1(e, emit_all, symcheck, (emit_all ? e->n : e->n / 4) + 1024, errbuf, errlen);
+  int rc = counted_pass1(e, emit_all, symcheck, (emit_all ? e->tab.n : e->tab.n / 4) + 1024, errbuf, errlen);
   if (rc) return rc;
+  e->run.rw = e->tab.W + 1;
   const int64_t nreq = e->st.nrequests;
-  for (int i = 0; i < 4; i++) e->fp[i] = e->h_ctrl->fp[i];
+  for (int i = 0; i < 4; i++) e->run.fp[i] = e->h_ctrl->fp[i];
   const int64_t nc = (nreq + F_CH - 1) / F_CH;
   if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large%s");
   HIPCHK(e->chunk_fill.reserve(nc * 4 + 4));
@@ -581,16 +581,16 @@ static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t
     hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->chunk_fill, nc, (uint32_t) F_CH,
                        (uint32_t) (nreq - (nc - 1) * F_CH));
   HIPCHK(hipGetLastError());
-  e->n_chunks = (unsigned) nc; e->bm_bits = 0; e->filtered = false; e->presorted = false;
+  e->run.n_chunks = (unsigned) nc;
   e->st.path = 1; e->st.ms_filter = 0;
-  e->prepared = true;                     // (with e->fast == false: the counted steps)
+  e->run.pass1_done = true;
   return SMG_OK;
 }
 
 static int counted_phase_apply(smg_engine *e, const u64 *rec, int64_t nrec, int64_t *missing, char *errbuf, size_t errlen)
 { launch_apply(e, rec, nrec, false);
   HIPCHK(hipGetLastError());
-  if (!missing) { e->lookup_pending = true; return SMG_OK; }
+  if (!missing) { e->run.lookup_pending = true; return SMG_OK; }
   const int rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
   e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
@@ -602,14 +602,14 @@ static int counted_phase_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, siz
 { const int rc = launch_pass2<true>(e, d_plot, NULL, errbuf, errlen);
   if (rc) return rc;
   e->st.path = 1; e->st.npairs = 0; e->st.ms_pass2 = -1.0;      // (no host wait: smg_engine_stats resolves the events)
-  e->counted_done = true;
+  e->run.completed = true;
   return SMG_OK;
 }
 
 // general (assumption-free) path: both passes over every position
 static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
 { int rc;
-  if ((rc = counted_prepare(e, errbuf, errlen))) return rc;
+  if ((rc = counted_prepare(e, RUN_GENERAL, errbuf, errlen))) return rc;
   launch_pass1<false>(e, 0, 0, NULL, 0, NULL);
   if ((rc = launch_pass2<false>(e, d_plot, NULL, errbuf, errlen))) return rc;
   if ((rc = plot_sum(e, d_plot, errbuf, errlen))) return rc;
@@ -618,7 +618,7 @@ static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errl
   e->st.ms_pass1 += ms_between(e, EV_PASS1_BEG, EV_PASS1_END);
   e->st.ms_pass2 = ms_between(e, EV_PASS2_BEG, EV_PASS2_END);
   e->st.path = 2;
-  e->general_done = true;
+  e->run.completed = true;
   return SMG_OK;
 }
 
@@ -626,7 +626,7 @@ static int run_general(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errl
 // builds the directory and the degree array (then the caller collects the Tabs of all shards into a TabSet on the
 // device), step 2 = pass 1 (degrees, over all positions), step 3 = pass 2 -- a barrier between the steps is the caller's.
 static int general_shard_prepare(smg_engine *e, Tab *out, char *errbuf, size_t errlen)
-{ int rc = counted_prepare(e, errbuf, errlen);
+{ int rc = counted_prepare(e, RUN_GENERAL, errbuf, errlen);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(e->stream));
   *out = make_tab(e);
@@ -642,7 +642,7 @@ static int general_shard_pass(smg_engine *e, const TabSet *d_set, int pass, int6
   if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
   if (e->h_ctrl->unsorted) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
   if (pass == 1) { e->st.ms_pass1 += ms_between(e, EV_PASS1_BEG, EV_PASS1_END); }
-  else { e->st.ms_pass2 = ms_between(e, EV_PASS2_BEG, EV_PASS2_END); e->st.path = 2; e->general_done = true; }
+  else { e->st.ms_pass2 = ms_between(e, EV_PASS2_BEG, EV_PASS2_END); e->st.path = 2; e->run.completed = true; }
   return SMG_OK;
 }
 
@@ -651,13 +651,11 @@ static int general_shard_pass(smg_engine *e, const TabSet *d_set, int pass, int6
 // on top (k_apply) and pass 2 reads the sums
 static int counted_resume(smg_engine *e, const uint8_t *d_degs, char *errbuf, size_t errlen)
 { HIPCHK(hipSetDevice(e->device));
-  int rc = counted_prepare(e, errbuf, errlen);               // control words, geometry, zeroed degrees, directory
+  int rc = counted_prepare(e, RUN_COUNTED, errbuf, errlen);  // control words, geometry, zeroed degrees, directory
   if (rc) return rc;
-  if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_degs, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
-  e->rw = e->W + 1;
-  e->lookup_pending = false; e->n_chunks = 0; e->bm_bits = 0; e->filtered = false; e->presorted = 0;
+  if (e->tab.n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_degs, (size_t) e->tab.n, hipMemcpyDeviceToDevice, e->stream));
+  e->run.rw = e->tab.W + 1;
   e->st.nrequests = 0; e->st.ms_rclookup = 0; e->st.path = 1;
-  memset(e->fp, 0, sizeof(e->fp));
-  e->prepared = true;
+  e->run.pass1_done = true;
   return SMG_OK;
 }

@@ -160,9 +160,9 @@ static int decode_begin(smg_engine *e, int kmer, int ibyte, int64_t nels, char *
   const int kbyte = (kmer + 3) >> 2;
   if (kbyte <= ibyte) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
   e->own_keys.reset(); e->own_cnt.reset();
-  HIPCHK(e->own_keys.alloc(sizeof(u64) * (size_t) (nels > 0 ? nels : 1) * e->W));
+  HIPCHK(e->own_keys.alloc(sizeof(u64) * (size_t) (nels > 0 ? nels : 1) * e->tab.W));
   HIPCHK(e->own_cnt.alloc(sizeof(uint16_t) * (size_t) (nels > 0 ? nels : 1) + 16));
-  e->keys = e->own_keys; e->cnt = e->own_cnt;
+  e->tab.keys = e->own_keys; e->tab.cnt = e->own_cnt;
   return SMG_OK;
 }
 
@@ -171,10 +171,10 @@ static int decode_begin(smg_engine *e, int kmer, int ibyte, int64_t nels, char *
 static int decode_piece(smg_engine *e, hipStream_t stream, int ibyte, const uint8_t *d_records, const int64_t *d_prefix_index,
                         int64_t ibase, int64_t first, int64_t nent)
 { if (nent <= 0) return 0;
-  const int kbyte = (e->kmer + 3) >> 2;
+  const int kbyte = (e->tab.kmer + 3) >> 2;
   const unsigned nblk = (unsigned) ((nent + DEC_TILE - 1) / DEC_TILE);
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_decode<w()>, dim3(nblk), dim3(TPB), dec_lds_bytes(kbyte + 2 - ibyte), stream, d_records,
-      d_prefix_index, 1 << (8 * ibyte), ibyte, kbyte, nent, ibase + first, e->own_keys + first * e->W, e->own_cnt + first); });
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_decode<w()>, dim3(nblk), dim3(TPB), dec_lds_bytes(kbyte + 2 - ibyte), stream, d_records,
+      d_prefix_index, 1 << (8 * ibyte), ibyte, kbyte, nent, ibase + first, e->own_keys + first * e->tab.W, e->own_cnt + first); });
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -223,13 +223,13 @@ extern "C" int smg_engine_set_prefix_index(smg_engine *e, const int64_t *d_prefi
                                            char *errbuf, size_t errlen)
 { if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
   if (ibyte < 1 || ibyte > 3 || !d_prefix_index) return fail(errbuf, errlen, SMG_EINVAL, "prefix index: ibyte must be 1, 2 or 3%s");
-  e->have_ixdir = false;
-  if (ibyte != 3 || e->kmer < 12 || test_hook("SMG_NO_INDEX_DIR")) return SMG_OK;     // (a coarser index is of no use as a directory)
+  e->tab.have_ixdir = false;
+  if (ibyte != 3 || e->tab.kmer < 12 || test_hook("SMG_NO_INDEX_DIR")) return SMG_OK;     // (a coarser index is of no use as a directory)
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(e->ixdir.reserve((int64_t) sizeof(uint32_t) * ((1ll << IXDIR_BITS) + 2)));
   hipLaunchKernelGGL(k_index_dir, dim3((unsigned) (((1ll << IXDIR_BITS) + 1 + TPB - 1) / TPB)), dim3(TPB), 0, e->stream,
-                     d_prefix_index, first_entry, e->n, e->ixdir);
+                     d_prefix_index, first_entry, e->tab.n, e->ixdir);
   HIPCHK(hipGetLastError());
-  e->have_ixdir = true;
+  e->tab.have_ixdir = true;
   return SMG_OK;
 }

@@ -58,6 +58,9 @@
 //                       smg_engine_lookup_limits and smg_engine_lookup_state).
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
+// host: f(std::true_type) or f(std::false_type) -- with_words (smg_device.hpp) for a template argument that is a bool
+template <class F> static inline void with_bool(bool b, F &&f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+
 #define WIN_LIM   32          // window blocks up to this many entries are walked linearly
 #define TPB       256
 
@@ -102,13 +105,77 @@ typedef void (*P1Kernel)(P1Hot, const P1Cold *);          // an instantiation of
 enum Ev { EV_DECODE_BEG, EV_DECODE_END, EV_PASS1_BEG, EV_PASS1_END, EV_LOOKUP_BEG, EV_LOOKUP_END, EV_PASS2_BEG, EV_PASS2_END,
           EV_RUN_BEG, EV_RUN_END, EV_PROBE_BEG, EV_REPLAY_FILTER_BEG, EV_REPLAY_FILTER_END, EV_EXTRACT_BEG, EV_EXTRACT_END, EV_COUNT };
 
+// The engine's scalar state, by lifetime.  Four groups, each reset in one place:
+//   Settings    what the caller asked for: survives every table and every run
+//   TableState  the bound table: table_changed()
+//   RunState    what the last pass 1 decided and how far its run has got: begin_run(), which table_changed() calls as well
+//   Replay      the record a replayed step of the phase API runs from (below)
+struct Settings
+{ bool no_filter;             // pass 1 builds no candidate map and nothing is filtered (out-of-core shards: smg_multi.hpp, host_run_sequential)
+  int  bm_cap;                // id bits of the block map: 32 on one GPU, 30 when the maps of several shards are exchanged
+  int  bm_want;               //   ... as asked for by smg_engine_set_blockmap_bits (0: default)
+  bool rp_want;               // replayed steps asked for (smg_engine_set_replay)
+};
+
+struct TableState
+{ int             kmer, W;
+  int64_t         n;
+  const u64      *keys;       // bound or owned
+  const uint16_t *cnt;
+  bool            have_ixdir; // ixdir holds this table's prefix index (smg_engine_set_prefix_index)
+  bool            have_ends;  u64 end_first, end_last;     // leading words of the first and the last entry (read once)
+  Geo             geo;        // (set_geo: a function of k)
+};
+
+enum RunKind { RUN_NONE, RUN_FAST, RUN_COUNTED, RUN_GENERAL };    // k <= 85 / k > 85 / every position, nothing assumed
+// the request list before the filter: not looked at yet / req2 holds it bucketed on its leading 8 bits / left as it is /
+// req2 holds it partitioned into the buckets of the look-up chain
+enum Presort { PRESORT_NONE, PRESORT_BUCKETED, PRESORT_ASIS, PRESORT_CHAIN };
+enum ProbeForm { PROBE_NONE = 0, PROBE_FUSED = 1, PROBE_X = 2, PROBE_LIST = 3 };   // kl_probe fused / kl_probe_x / kl_probe to a list (exported)
+
+struct RunState
+{ RunKind   kind;             // the path of the pass 1 that ran last on this table
+  bool      pass1_done;       // ... and it left its requests to the phase calls (the one-shot counted and general runs never do)
+  bool      completed;        // pass 2 has run: deg[] holds finished code bytes (fast) or degrees (counted, general)
+  int       rw;               // 64-bit words per request record
+  int       one_way;          // the requests are one-way (smg_fast.hpp): smg_engine_run only, never the phase API
+  bool      use_sig;          // pass 1 writes the 2-byte look-up signatures (not worth their 5 GB when the filter leaves 1 request in 115)
+  int       bm_bits, bm2;     // leading k-mer bits per block id of the candidate map (0: none built); a two-bit map (smg_fast.hpp)
+  LookupGeo lg;               // the look-up chain (lg.nb = 0: not used)
+  Dir       dir;  bool dir_preset;      // the directory; it is the table's own index (ixdir): pass 1 writes none
+  bool      filtered;         // the request list has been filtered
+  Presort   presorted;
+  ProbeForm probe_form;  unsigned probe_part;   // the probe kernel of the filter / look-up, requests per ticket of kl_probe_x (else 0)
+  bool      far_listed;       // biglist[0 .. st.nbig) holds pass 1's deferred entries: pass 2 finishes the far partners from it
+  bool      lookup_pending;   // look-ups of received requests were queued without a host wait (their time is read later)
+  unsigned  n_chunks, max_chunks;       // chunks of the request list in use; its capacity
+  unsigned  p1grid, nown;     // workgroups of pass 1; owners of the request list (+ BF_MAXGRID for kf_bigfix):
+                              //   owner w fills the chunk slots w, w + nown, w + 2 nown, ..
+  int       p1_var, p1_w, p1_rw;        // VAR of kf_pass1_d (0: the wide or the counted kernels), W, RW (smg_engine_pass1_form)
+  u64       fp[4];            // fingerprints of the table and of its complement
+};
+
+// Replay of the PHASE calls (sharded runs, smg_engine_set_replay): a step on a table whose last step went through pass1 ->
+// filter (hash proof, look-up chain) is queued without a read-back -- the counts the host needs are last step's (functions
+// of the table and of the exchanged maps), the device compares them with this step's and reports through smg_engine_proof.
+// The record is dropped (have = false) when the table changes, by smg_engine_set_replay(0) and by smg_engine_replay_done(!ok).
+struct Replay
+{ bool     have, active;      // a record exists / the current step runs from it
+  int64_t  nreq, nbig, nf_req;          // pass 1: requests, deferred entries; filter: requests kept
+  unsigned nf_chunks, grid;   // filter: chunks of the kept list (the list the routing kernels walk); pass-1 grid (rows of `partials`)
+  unsigned seen_chunks;       // chunks the plain step's filter filled (a replayed step walks that many + slack)
+  int      nranks;  bool routed;        // router: ranks of the recorded totals (rp_totals); this step's are there to be compared
+  int      bm_bits, sym;      // map geometry and proof the record belongs to
+};
+
 struct smg_engine
 { int          device;
   hipStream_t  stream;
-  int          kmer, W;
-  int64_t      n;
-  const u64   *keys;          // bound or owned
-  const uint16_t *cnt;
+  Settings     set;
+  TableState   tab;
+  RunState     run;
+  Replay       rp;
+  DevBuf<u64>  rp_totals;     // replay: per-destination totals of the recorded step (16 words) and of this step (16 more)
   // (every device allocation is a DevBuf: grown where it is used by reserve(), freed with the engine)
   DevBuf<u64>  own_keys;      // owned copies (decode path)
   DevBuf<uint16_t> own_cnt;
@@ -116,20 +183,6 @@ struct smg_engine
   DevBuf<uint16_t> sig;       // k <= 32: look-up signatures (2 bytes per entry)
   DevBuf<uint32_t> bstart;
   DevBuf<uint32_t> ixdir;     // the table's own FastK prefix index (2^24 + 1 bucket starts, relative to this shard) as directory
-  bool         have_ixdir;                   //   ... handed over with the current table (smg_engine_set_prefix_index); gone when the table changes
-  bool         dir_preset;                   //   the current run looks up through ixdir: pass 1 writes no directory
-  bool         have_ends;  u64 end_first, end_last;     // leading words of the first and the last entry of the bound table (read once)
-  bool         no_filter;    // pass 1 builds no candidate map and nothing is filtered (out-of-core shards: smg_multi.hpp, host_run_sequential)
-  // replay of the PHASE calls (sharded runs, smg_engine_set_replay): a step on a table whose last step went through pass1 ->
-  // filter (hash proof, look-up chain) is queued without a read-back -- the counts the host needs are last step's (functions
-  // of the table and of the exchanged maps), the device compares them with this step's and reports through smg_engine_proof
-  bool         rp_want, rp_have, rp_active;    // asked for / a record exists / the current step runs from the record
-  int64_t      rp_nreq, rp_nbig, rp_nf_req;    //   pass 1: requests, deferred entries; filter: requests kept
-  unsigned     rp_nf_chunks, rp_grid;          //   filter: chunks of the kept list (the list the routing kernels walk); pass-1 grid (rows of `partials`)
-  unsigned     rp_seen_chunks;                 //   chunks the plain step's filter filled (a replayed step walks that many + slack)
-  DevBuf<u64>  rp_totals; int rp_nranks;      //   router: per-destination totals of the recorded step (device, 16 words) and of this step (16 more)
-  bool         rp_routed;                      //   ... this step's totals are there to be compared
-  int          rp_bm_bits, rp_sym;             //   map geometry and proof the record belongs to
   DevBuf<u64>  req;
   DevBuf<u64>  req2;          // radix sort output
   Dev          sort_tmp;      // rocPRIM's scratch (with_scratch)
@@ -143,13 +196,8 @@ struct smg_engine
   DevBuf<unsigned> p1tick;    // tile tickets of kf_pass1_d
   DevBuf<unsigned> xtick;     // (bucket, part) tickets of kl_probe_x, one counter per XCD
   DevBuf<uint32_t> farp;      // beside it: the partner of a listed entry whose code is CODE_FAR (kf_bigfix -> kf_pass2_far)
-  int          rw;                           // 64-bit words per request record
   DevBuf<uint32_t> chunk_fill;
-  unsigned     max_chunks;
   DevBuf<uint32_t> bmap;      // candidate block map (request filter)
-  int          bm_bits;                      //   leading k-mer bits per block id (0 = not built by the last pass 1)
-  bool         filtered;                     //   the request list of the last pass 1 has been filtered
-  int          presorted;                    //   0 not decided, 1 req2 holds the list bucketed on its leading 8 bits, 2 left as it is
   DevBuf<u64>  reqf;          // filtered request chunks (swapped with req)
   DevBuf<uint32_t> chunk_fillf;
   DevBuf<uint32_t> route_cnt;
@@ -157,39 +205,18 @@ struct smg_engine
   DevBuf<u64>  partials;   // [P1_MAXGRID][4]
   DevBuf<unsigned> ghist;  // look-up chain: requests per bucket [L_BK], bucket cursor `bnext` behind it
   DevBuf<unsigned> whist;  //   requests per owner and bucket [owners][L_BK] (owner = a workgroup of pass 1 / kf_bigfix)
-  unsigned     p1grid, nown; //  workgroups of the last pass 1; owners of the request list (+ BF_MAXGRID for kf_bigfix):
-                           //   owner w fills the chunk slots w, w + nown, w + 2 nown, ..
   DevBuf<u64>  boff;       //   bucket offsets [L_BK + 1] and scatter cursors [L_BK] behind them
-  LookupGeo    lg;         //   geometry of the current run (lg.nb = 0: the round-1 chain is used)
-  int          probe_form; //   the probe kernel of the last filter / look-up: 0 none, 1 kl_probe fused, 2 kl_probe_x, 3 kl_probe list
-  unsigned     probe_part; //   ... and the requests per ticket it passed to kl_probe_x (0 otherwise): smg_engine_lookup_state
-  bool         far_listed;   // pass 1 left the list of its deferred entries in biglist[0 .. st.nbig): pass 2 finishes the far partners from it
-  bool         counted_done; // the counted path (k > 85) has run on a closed table: deg[] holds the wrapped degrees
-  bool         lookup_pending; // look-ups of received requests were queued without a host wait (their time is read later)
-  bool         use_sig;    // pass 1 writes the 2-byte look-up signatures (not worth their 5 GB when the filter leaves 1 request in 115)
-  int          bm2;        //   the map is a two-bit map (smg_fast.hpp): 64-bit words, private to this engine
-  int          one_way;    //   this run's requests are one-way (smg_fast.hpp): set by fast_pass1 for smg_engine_run, never by the phase API
-  int          bm_cap;     //   id bits of the block map: 32 on one GPU, 30 when the maps of several shards are exchanged
-  int          bm_want;    //   ... as asked for by smg_engine_set_blockmap_bits (0: default)
   DevBuf<P1Cold> p1cold;   // rarely used arguments of kf_pass1_d (device copy)
   P1Cold      *h_p1cold;   // pinned staging
   DevBuf<u64>  d_split;
   DevBuf<Ctrl> ctrl;
   Ctrl        *h_ctrl;        // pinned mirror
   u64         *h_partials;    // pinned
-  Geo          geo;
-  Dir          dir;
-  bool         prepared;      // pass 1 of the current table has run
-  bool         fast;          // fast path in use
   P1Kernel     p1_asked;      // the instantiation of kf_pass1_d whose resident workgroups were asked for last (NULL: none yet) ..
   unsigned     p1_resident;   //   .. and the answer
-  int          p1_var, p1_w, p1_rw;   // the last pass 1: VAR of kf_pass1_d (0: the wide or the counted kernels), W, RW (smg_engine_pass1_form)
-  unsigned     n_chunks;
-  u64          fp[4];
   smg_stats    st;
   int          cus;           // compute units of the device (256 where it does not say)
   hipEvent_t   ev[EV_COUNT];
-  bool         general_done;  // the general path has run (st.path == 2): deg[] holds the degrees over all positions
   float        ms_extract;    // device time of the last extract launch
 };
 
@@ -232,7 +259,7 @@ extern "C" smg_engine *smg_engine_create(int device, void *stream, char *errbuf,
   if (!e) { fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s"); return NULL; }
   e->device = device;
   e->stream = (hipStream_t) stream;
-  e->bm_cap = 30;
+  e->set.bm_cap = 30;
   if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || e->cus < 1) e->cus = 256;
   for (int i = 0; i < EV_COUNT; i++) hipEventCreate(&e->ev[i]);
   if (e->ctrl.alloc(sizeof(Ctrl)) != hipSuccess
@@ -259,35 +286,52 @@ extern "C" void smg_engine_destroy(smg_engine *e)
   delete e;                                  // (frees every device buffer)
 }
 
+// which pass 1 the engine's byte array, lists and map belong to (ran_fast: with its requests there for the phase calls)
+static inline bool ran_fast(const smg_engine *e)    { return e->run.kind == RUN_FAST && e->run.pass1_done; }
+static inline bool ran_counted(const smg_engine *e) { return e->run.kind == RUN_COUNTED; }
+static inline bool ran_general(const smg_engine *e) { return e->run.kind == RUN_GENERAL; }
+static inline bool has_chain(const smg_engine *e)   { return ran_fast(e) && e->run.lg.nb > 0; }
+
+// a pass 1 of `kind` starts (RUN_NONE: none has run on this table): nothing an earlier run decided or reached is left
+static void begin_run(smg_engine *e, RunKind kind)
+{ e->run = RunState{};
+  e->run.kind = kind;
+}
+
+// the engine's table has n entries now and is another table: what a run, the prefix index and the ends said is gone
+static void table_changed(smg_engine *e, int64_t n)
+{ e->tab.n = n;
+  e->tab.have_ixdir = false; e->tab.have_ends = false;
+  begin_run(e, RUN_NONE);
+  e->st.nels = n;
+}
+
 static int set_table(smg_engine *e, int kmer, int64_t nels, char *errbuf, size_t errlen)
 { if (kmer < 1 || kmer > SMG_MAX_KMER)
     return fail(errbuf, errlen, SMG_EINVAL, "k-mer length out of range (1..128)%s");
   if (nels < 0 || nels >= 0xFFFFFFF0ll)
     return fail(errbuf, errlen, SMG_EINVAL, "table shard too large (entries per GPU must be < 2^32-16)%s");
-  e->kmer = kmer;
-  e->W = (kmer + 31) / 32;
-  e->n = nels;
-  e->prepared = false; e->counted_done = false; e->general_done = false; e->lookup_pending = false;
-  e->have_ixdir = false; e->dir_preset = false; e->have_ends = false;        // (properties of the table that was bound before)
-  e->rp_have = false; e->rp_active = false;
+  e->tab.kmer = kmer;
+  e->tab.W = (kmer + 31) / 32;
   memset(&e->st, 0, sizeof(e->st));
-  e->st.nels = nels;
-  e->st.key_words = e->W;
+  table_changed(e, nels);
+  e->rp.have = false; e->rp.active = false;
+  e->st.key_words = e->tab.W;
   return SMG_OK;
 }
 
 static void set_geo(smg_engine *e)
-{ Geo &g = e->geo;
-  g.k = e->kmer;
+{ Geo &g = e->tab.geo;
+  g.k = e->tab.kmer;
   // first scanned position p0 = ceil((k-1)/2) = k/2 (integer division) for both parities: on
   // the symmetric path positions below it are the mirror images of the scanned ones, on the
   // general path they are resolved by directory look-ups
-  g.p0 = e->kmer / 2;
+  g.p0 = e->tab.kmer / 2;
   g.pw = g.p0 >> 5;
   const int r = g.p0 & 31;
   g.pmask = r ? ~0ull << (64 - 2 * r) : 0ull;
-  g.mid = (e->kmer & 1) ? (e->kmer - 1) / 2 : -1;
-  g.wrap = e->kmer > FAST_MAX_K;
+  g.mid = (e->tab.kmer & 1) ? (e->tab.kmer - 1) / 2 : -1;
+  g.wrap = e->tab.kmer > FAST_MAX_K;
 }
 
 extern "C" int smg_engine_bind(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys,
@@ -299,8 +343,8 @@ extern "C" int smg_engine_bind(smg_engine *e, int kmer, int64_t nels, const uint
   HIPCHK(hipSetDevice(e->device));
   int rc = set_table(e, kmer, nels, errbuf, errlen);
   if (rc) return rc;
-  e->keys = (const u64 *) d_keys;
-  e->cnt = d_counts;
+  e->tab.keys = (const u64 *) d_keys;
+  e->tab.cnt = d_counts;
   return SMG_OK;
 }
 
@@ -317,32 +361,32 @@ static int read_ctrl(smg_engine *e, char *errbuf, size_t errlen)
 // million look-ups: their bisection still stays inside one or two lines of signatures, while pass 1 writes -- and every
 // run clears -- an eighth of the directory (1 GB -> 128 MB at 2.5e9 entries: -0.5 ms per run).
 static int dir_geometry(smg_engine *e, int per, char *errbuf, size_t errlen, bool index_ok = false)
-{ e->dir_preset = false;
-  if (index_ok && e->have_ixdir && e->n > 0)
-    { e->dir.bstart = e->ixdir; e->dir.b0 = 0; e->dir.dsh = 32 - IXDIR_BITS; e->dir.nb = 1u << IXDIR_BITS;
-      e->dir_preset = true;
+{ e->run.dir_preset = false;
+  if (index_ok && e->tab.have_ixdir && e->tab.n > 0)
+    { e->run.dir.bstart = e->ixdir; e->run.dir.b0 = 0; e->run.dir.dsh = 32 - IXDIR_BITS; e->run.dir.nb = 1u << IXDIR_BITS;
+      e->run.dir_preset = true;
       return SMG_OK;
     }
   u64 first = 0, last = 0;
-  if (e->n > 0 && !e->have_ends)      // (read once per bound table: a host round trip)
-    { HIPCHK(hipMemcpyAsync(&e->end_first, e->keys, 8, hipMemcpyDeviceToHost, e->stream));
-      HIPCHK(hipMemcpyAsync(&e->end_last, e->keys + (size_t) (e->n - 1) * e->W, 8, hipMemcpyDeviceToHost, e->stream));
+  if (e->tab.n > 0 && !e->tab.have_ends)      // (read once per bound table: a host round trip)
+    { HIPCHK(hipMemcpyAsync(&e->tab.end_first, e->tab.keys, 8, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(hipMemcpyAsync(&e->tab.end_last, e->tab.keys + (size_t) (e->tab.n - 1) * e->tab.W, 8, hipMemcpyDeviceToHost, e->stream));
       HIPCHK(hipStreamSynchronize(e->stream));
-      e->have_ends = true;
+      e->tab.have_ends = true;
     }
-  if (e->n > 0) { first = e->end_first; last = e->end_last; }
+  if (e->tab.n > 0) { first = e->tab.end_first; last = e->tab.end_last; }
   if (last < first) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
   int bits = 4;
   { const char *v = test_hook("SMG_DIR_PER"); if (v && atoi(v) >= 1) per = atoi(v); }       // tuning override
-  while (bits < 30 && (1ll << (bits + 1)) <= e->n / per) bits++;
+  while (bits < 30 && (1ll << (bits + 1)) <= e->tab.n / per) bits++;
   const uint32_t hf = (uint32_t) (first >> 32), hl = (uint32_t) (last >> 32);
   int dsh = 0;
   while (dsh < 31 && ((hl >> dsh) - (hf >> dsh)) >= (1u << bits)) dsh++;
-  e->dir.b0 = hf >> dsh;
-  e->dir.dsh = dsh;
-  e->dir.nb = (hl >> dsh) - (hf >> dsh) + 1;
-  HIPCHK(e->bstart.reserve((int64_t) sizeof(uint32_t) * ((int64_t) e->dir.nb + 2)));
-  e->dir.bstart = e->bstart;
+  e->run.dir.b0 = hf >> dsh;
+  e->run.dir.dsh = dsh;
+  e->run.dir.nb = (hl >> dsh) - (hf >> dsh) + 1;
+  HIPCHK(e->bstart.reserve((int64_t) sizeof(uint32_t) * ((int64_t) e->run.dir.nb + 2)));
+  e->run.dir.bstart = e->bstart;
   return SMG_OK;
 }
 
@@ -361,14 +405,14 @@ static int plot_sum(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
 
 static FastArgs make_fast(smg_engine *e)
 { FastArgs a;
-  a.keys = e->keys; a.cnt = e->cnt; a.n = e->n; a.g = e->geo; a.dir = e->dir;
+  a.keys = e->tab.keys; a.cnt = e->tab.cnt; a.n = e->tab.n; a.g = e->tab.geo; a.dir = e->run.dir;
   a.code = e->deg;
-  a.sig = (e->W <= 2 && e->use_sig) ? e->sig : NULL;
-  a.sigsh = 16 + e->dir.dsh;               // the 16 bits right below the directory's bucket bits
-  a.bmap = e->bm_bits ? e->bmap : NULL;
-  a.bmsh = 32 - e->bm_bits;
-  a.bm2 = e->bm2;
-  a.ow = e->one_way;
+  a.sig = (e->tab.W <= 2 && e->run.use_sig) ? e->sig : NULL;
+  a.sigsh = 16 + e->run.dir.dsh;               // the 16 bits right below the directory's bucket bits
+  a.bmap = e->run.bm_bits ? e->bmap : NULL;
+  a.bmsh = 32 - e->run.bm_bits;
+  a.bm2 = e->run.bm2;
+  a.ow = e->run.one_way;
   return a;
 }
 
@@ -394,257 +438,298 @@ static P1Kernel p1_kernel(int W, int rw, bool odd, bool kf, int var)
 #undef P1_K
 }
 
-static int bm_id_bits(int kmer, int cap);
 // 32-bit words of a block map of 2^bits ids (two-bit map, smg_fast.hpp: 64 bits per 32 ids)
 static inline int64_t bm_words(int bits, int two_bit) { return (((1ll << bits) + 31) >> 5) << two_bit; }
-// (k = 1 has no prefix bases to name a block by)
-static bool filter_ok(const smg_engine *e)
-{ return e->kmer >= 2 && ((e->W == 1 && e->rw == 1) || (e->W == 2 && e->rw != 1) || (e->W == 3 && e->rw == 4)); }
 
-// replay: a step of the phase API on the table of the step before (smg_engine_set_replay).  Everything is launched as ever, but
-// nothing is read back here: the lists are as large as last time, the counts that later launches take from the host (requests,
-// deferred entries) are the recorded step's -- they are functions of the table -- and the device checks all of it against the
-// control words at the end of the step (k_proof_replay).
+// block ids of the request filter = the leading bm_id_bits(k) bits of a k-mer (a function of k alone, so that the
+// maps of all the shards of a table line up): window blocks, coarsened to 2^30 ids (128 MB of bits) at most
+// cap: 30 when the maps of several shards are exchanged (128 MB in total), 32 on one GPU, where the probes of the
+// first 30 bits are LDS reads (smg_lookup.hpp) and a finer map only costs its memset; SMG_BM_BITS overrides (8..32).
+// An id never runs past the k-mer (2k bits) nor past its leading 32 bits.
+static int bm_id_bits(int kmer, int cap)
+{ { const char *v = test_hook("SMG_BM_BITS"); if (v && atoi(v) >= 8 && atoi(v) <= 32) cap = atoi(v); }
+  int nbits = cap > 30 ? 2 * kmer : 2 * (kmer / 2);
+  if (nbits > cap) nbits = cap;
+  return nbits;
+}
+
+// records the request filter covers (k = 1 has no prefix bases to name a block by)
+static bool filter_ok(int kmer, int W, int rw)
+{ return kmer >= 2 && ((W == 1 && rw == 1) || (W == 2 && rw != 1) || (W == 3 && rw == 4)); }
+static bool filter_ok(const smg_engine *e) { return filter_ok(e->tab.kmer, e->tab.W, e->run.rw); }
+
+static GeoR p1_geor(int kmer, int W)
+{ GeoR gr;
+  const int p0 = kmer / 2, sbits = 2 * (kmer - p0);
+  gr.k = kmer;
+  gr.kshift = (W == 1 ? 64 : 128) - 2 * kmer;           // (W = 2, 33 <= k <= 64: 0 .. 62)
+  gr.pshift = (W == 1 ? 32 : 64) - 2 * p0;              // (W = 2: p0 = 16 .. 32)
+  gr.smask = sbits >= 64 ? ~0ull : ((1ull << sbits) - 1ull);
+  gr.mshift = sbits - 2;
+  return gr;
+}
+
+// ---- pass 1 of the fast path: decide (p1_plan, p1_form), size (p1_reserve), launch (p1_attempt), retry (fast_pass1) --------
+// What a pass 1 is going to do, as a function of k, n, the proof, the caller and the test hooks: no device, no engine
+// (smg_engine_pass1_plan hands it to the tests).  SMG_TWO_WAY, SMG_NO_FILTER, SMG_ONE_BIT_MAP, SMG_SIG and SMG_BM_BITS are read here.
+struct P1Plan
+{ int     kmer, W, rw;            // record = the complement k-mer (W words) [+ one word: count | has-hi-pair << 16]
+  bool    emit_all, want_fp;      // exact proof: every entry sends; hash proof: the fingerprints
+  bool    one_way;                // one request per complement class (smg_fast.hpp)
+  bool    narrow, odd, kf;        // k <= 64: kf_pass1_d (blocked register scan); its template arguments ODD and KF (17 <= k <= 32)
+  int     dir_per;  bool index_ok;          // entries per directory bucket (dir_geometry); the table's own index may be the directory
+  int     bm_bits, bm2;           // the candidate map: id bits (0: none, nothing is filtered), two-bit
+  bool    chain, use_sig;         // the look-up chain of smg_lookup.hpp; pass 1 writes signatures
+  GeoR    gr;
+  int64_t ntiles, want_rec, want_big, dwords;     // tiles; first guess of the request list (without the grid's slack) and of the
+};                                                //   list of deferred entries; 32-bit words of their bit map
+
 // one_way_ok: the caller looks this engine's requests up itself, with this engine's map (smg_engine_run): odd k <= 63 with key-only
-// records under the hash proof then sends one request per complement class (smg_fast.hpp); the test hook SMG_TWO_WAY=1 keeps the
-// two-way protocol.  The phase API never passes it: its requests leave the engine, and the sender is not local to the look-up.
-static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, char *errbuf, size_t errlen, bool replay = false,
-                      bool one_way_ok = false)
-{ int rc;
-  // record = the complement k-mer (W words) [+ one word: count | has-hi-pair << 16]
+// records under the hash proof then sends one request per complement class; the test hook SMG_TWO_WAY=1 keeps the two-way
+// protocol.  The phase API never passes it: its requests leave the engine, and the sender is not local to the look-up.
+static P1Plan p1_plan(int kmer, int64_t n, bool emit_all, bool with_meta, bool want_fp, bool one_way_ok, int bm_cap, bool no_filter)
+{ P1Plan p = {};
+  p.kmer = kmer; p.W = (kmer + 31) / 32; p.emit_all = emit_all; p.want_fp = want_fp;
+  p.narrow = p.W <= 2; p.odd = (kmer & 1) != 0;
   // (two-word k-mers send key-only records for the hash proof as one-word ones do: 16 instead of 24 bytes for 21.6 % of
   //  the entries at k = 51; three-word k-mers go through the generic kernel, whose records always carry the count word)
-  e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
-  e->one_way = (one_way_ok && (e->kmer & 1) && e->kmer >= 3 && e->kmer <= 63 && e->W <= 2 && e->rw == e->W && want_fp && !emit_all
-                && !test_hook("SMG_TWO_WAY")) ? 1 : 0;
-  HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
-  set_geo(e);
-  e->fast = true; e->counted_done = false; e->general_done = false;
-  e->p1_var = 0; e->p1_w = e->W; e->p1_rw = e->rw;
-  HIPCHK(e->deg.reserve(((e->n + 15) & ~15ll) + 32));
-  const int64_t pbytes = ((e->n + 15) & ~15ll) + 32;
-  e->use_sig = e->W <= 2;
+  p.rw = p.W + ((with_meta || p.W > 2) ? 1 : 0);
+  p.one_way = one_way_ok && p.odd && kmer >= 3 && kmer <= 63 && p.rw == p.W && want_fp && !emit_all && !test_hook("SMG_TWO_WAY");
   // (hash proof of one- and two-word k-mers: the table's own prefix index, when it came with one, is the directory)
-  if ((rc = dir_geometry(e, (emit_all || e->W > 1) ? 8 : 64, errbuf, errlen, !emit_all && e->W <= 2))) return rc;
+  p.dir_per = (emit_all || p.W > 1) ? 8 : 64; p.index_ok = !emit_all && p.narrow;
+  p.use_sig = p.narrow;
   // request filter: the candidate block map (an empty shard has one too -- all zero -- so that every rank of a
   // sharded run reports the same geometry and takes part in the exchange of the maps)
-  e->bm_bits = 0; e->bm2 = 0;
-  e->filtered = false; e->presorted = 0;
-  e->lg.nb = 0; e->probe_form = 0; e->probe_part = 0;
-  if (filter_ok(e) && !emit_all && !e->no_filter && !test_hook("SMG_NO_FILTER"))
-    { const int nbits = bm_id_bits(e->kmer, e->bm_cap);
-      // the look-up chain of smg_lookup.hpp: one-word k-mers, key-only records, a map of >= 12 id bits
-      const bool chain = nbits >= 12 && e->W <= 2 && e->rw == e->W;
+  if (filter_ok(kmer, p.W, p.rw) && !emit_all && !no_filter && !test_hook("SMG_NO_FILTER"))
+    { p.bm_bits = bm_id_bits(kmer, bm_cap);
+      // the look-up chain of smg_lookup.hpp: one- and two-word k-mers, key-only records, a map of >= 12 id bits
+      p.chain = p.bm_bits >= 12 && p.narrow && p.rw == p.W;
       // ... with the two-bit map (smg_fast.hpp) when the k-mer has bits below the id to hash (a function of k and the
       // environment alone: every shard of a table decides the same)
-      e->bm2 = (chain && e->kmer >= 24 && !test_hook("SMG_ONE_BIT_MAP")) ? 1 : 0;
-      const int64_t bytes = 4 * bm_words(nbits, e->bm2) + ((4 * D_BMW + 64) << e->bm2);
-      HIPCHK(e->bmap.reserve(bytes));
-      HIPCHK(hipMemsetAsync(e->bmap, 0, (size_t) bytes, e->stream));
-      e->bm_bits = nbits;
-      if (chain) e->lg = lookup_geo(nbits);
+      p.bm2 = (p.chain && kmer >= 24 && !test_hook("SMG_ONE_BIT_MAP")) ? 1 : 0;
       // Signatures (2 bytes per entry written by pass 1, so that a look-up bisects 2-byte instead of 8-byte words)
       // pay when most requests are looked up.  With the 32-bit two-bit map of a single-GPU run 1 request in 115
       // survives the filter: 3.9e6 look-ups at 2.5e9 entries, which can afford the k-mer lines of their bucket, while
       // the signatures cost pass 1 5 GB of stores and four instructions per entry.  SMG_SIG=0/1 overrides.
-      if (chain && e->bm2 && nbits >= 32) e->use_sig = false;
+      if (p.chain && p.bm2 && p.bm_bits >= 32) p.use_sig = false;
     }
-  { const char *v = test_hook("SMG_SIG"); if (v && e->W <= 2) e->use_sig = atoi(v) != 0; }
-  if (e->use_sig) HIPCHK(e->sig.reserve(2 * pbytes));
-  if (e->n > 0 && !e->dir_preset)
-    HIPCHK(hipMemsetAsync(e->bstart, 0xFF, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
-  if (e->n == 0)
-    { HIPCHK(hipMemsetAsync(e->bstart, 0, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
-      e->n_chunks = 0; e->prepared = true;
-      memset(e->fp, 0, sizeof(e->fp));
-      return SMG_OK;
+  { const char *v = test_hook("SMG_SIG"); if (v && p.narrow) p.use_sig = atoi(v) != 0; }
+  p.gr = p1_geor(kmer, p.W);
+  p.kf = p.W == 1 && p.gr.pshift < 32 && p.gr.kshift < 32;
+  p.ntiles = p.narrow ? (n + D_OWN - 1) / D_OWN : (n + F_TILE - 1) / F_TILE;
+  p.want_rec = emit_all ? n + n / 24 : p.one_way ? n / 8 : n / 4;      // (one-way requests: half the senders)
+  p.want_big = n / 16 + 4096;               // deferred entries: 0.13 % of the diploid table, 0.4 % with 5 % repeats
+  p.dwords = ((((n + 31) >> 5) + 2) + 3) & ~3ll;                       // (kf_bigfix reads the map four words at a time)
+  return p;
+}
+
+// The form of kf_pass1_d (VAR of smg_pass1d.hpp), settled once dir_geometry has said whether the index serves.  The hot form:
+// key-only records through the look-up chain with the two-bit map and the fingerprint, on a table that came with its index (no
+// directory, no signatures); where k is odd it has the protocol compiled in, one-way (2) or two-way (6: the phase API, the hook
+// SMG_TWO_WAY).  Everything else: the general form (1).  0: the generic kf_pass1 of three-word k-mers, or no launch at all.
+static int p1_form(const P1Plan &p, bool dir_preset, int64_t n)
+{ if (!p.narrow || n == 0) return 0;
+  const bool hot = p.rw == p.W && dir_preset && !p.use_sig && p.bm2 && p.bm_bits && p.want_fp && !p.emit_all && p.chain;
+  return !hot ? 1 : (p.odd && !p.one_way) ? 6 : 2;
+}
+
+extern "C" int smg_engine_pass1_plan(int kmer, int64_t nels, int symcheck, int own_lookups, int have_index, int bm_cap, int no_filter,
+                                     int32_t out[12])
+{ if (kmer < 1 || kmer > FAST_MAX_K || nels < 0 || !out || symcheck == SMG_SYM_NONE) return SMG_EINVAL;
+  const bool exact = symcheck == SMG_SYM_EXACT, hash = symcheck == SMG_SYM_HASH;
+  const P1Plan p = p1_plan(kmer, nels, exact, exact, hash, own_lookups && hash, bm_cap, no_filter != 0);
+  const bool preset = p.index_ok && have_index && nels > 0;               // (dir_geometry)
+  const int32_t v[12] = { p.rw, p.one_way, p.narrow, p.dir_per, preset, p.bm_bits, p.bm2, p.chain ? lookup_geo(p.bm_bits).nb : 0,
+                          p.use_sig, p1_form(p, preset, nels), p.kf, p.W };
+  memcpy(out, v, sizeof(v));
+  return SMG_OK;
+}
+
+// everything pass 1 writes besides its lists, in the order the stream sees it: code bytes, directory, map, signatures; then
+// the kernel and its grid, and the bit map of deferred entries.  n = 0: no launch follows.
+static int p1_reserve(smg_engine *e, const P1Plan &p, P1Kernel *p1k, unsigned *grid_out, char *errbuf, size_t errlen)
+{ int rc;
+  const int64_t n = e->tab.n, pbytes = ((n + 15) & ~15ll) + 32;
+  HIPCHK(e->deg.reserve(pbytes));
+  if ((rc = dir_geometry(e, p.dir_per, errbuf, errlen, p.index_ok))) return rc;
+  if (p.bm_bits)
+    { const int64_t bytes = 4 * bm_words(p.bm_bits, p.bm2) + ((4 * D_BMW + 64) << p.bm2);
+      HIPCHK(e->bmap.reserve(bytes));
+      HIPCHK(hipMemsetAsync(e->bmap, 0, (size_t) bytes, e->stream));
     }
-  const bool narrow = e->W <= 2;                       // k <= 64: kf_pass1_d (blocked register scan)
-  const int64_t ntiles = narrow ? (e->n + D_OWN - 1) / D_OWN : (e->n + F_TILE - 1) / F_TILE;
-  GeoR gr;
-  { const int p0 = e->kmer / 2, sbits = 2 * (e->kmer - p0);
-    gr.k = e->kmer;
-    if (e->W == 1)
-      { gr.kshift = 64 - 2 * e->kmer;
-        gr.pshift = 32 - 2 * p0;
-      }
-    else
-      { gr.kshift = 128 - 2 * e->kmer;                 // 33 <= k <= 64: 0 .. 62
-        gr.pshift = 64 - 2 * p0;                        // p0 = 16 .. 32
-      }
-    gr.smask = sbits >= 64 ? ~0ull : ((1ull << sbits) - 1ull);
-    gr.mshift = sbits - 2;
-  }
-  const bool odd = (e->kmer & 1) != 0;
+  if (p.use_sig) HIPCHK(e->sig.reserve(2 * pbytes));
+  if (!e->run.dir_preset)
+    HIPCHK(hipMemsetAsync(e->bstart, n > 0 ? 0xFF : 0, sizeof(uint32_t) * ((size_t) e->run.dir.nb + 2), e->stream));
+  if (n == 0) return SMG_OK;
+  e->run.p1_var = p1_form(p, e->run.dir_preset, n);
   unsigned grid = P1_GRID;
-  P1Kernel p1k = NULL;
-  if (narrow)
-    { // The form of kf_pass1_d (VAR of smg_pass1d.hpp).  The hot form: key-only records through the look-up chain with the
-      // two-bit map and the fingerprint, on a table that came with its index (no directory, no signatures); where k is odd it has
-      // the protocol compiled in, one-way (2) or two-way (6: the phase API, the hook SMG_TWO_WAY).  Everything else: the general form.
-      const bool hot_form = e->rw == e->W && e->dir_preset && !(e->W <= 2 && e->use_sig) && e->bm2 && e->bm_bits && want_fp && !emit_all && e->lg.nb;
-      const int var = !hot_form ? 1 : (odd && !e->one_way) ? 6 : 2;
-      p1k = p1_kernel(e->W, e->rw, odd, gr.pshift < 32 && gr.kshift < 32, var);
-      if (!p1k) return fail(errbuf, errlen, SMG_EINVAL, "pass 1: no kernel for this table%s");
-      e->p1_var = var;
+  if (p.narrow)
+    { if (!(*p1k = p1_kernel(p.W, p.rw, p.odd, p.kf, e->run.p1_var))) return fail(errbuf, errlen, SMG_EINVAL, "pass 1: no kernel for this table%s");
       // persistent workgroups: exactly what is resident (a static tile stride must not have stragglers)
-      if (e->p1_asked != p1k)
+      if (e->p1_asked != *p1k)
         { int nb = 0;
-          const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, p1k, D_TPB, 0);
+          const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, *p1k, D_TPB, 0);
           if (he != hipSuccess || nb < 1) nb = 3;
           if (nb > 8) nb = 8;
           e->p1_resident = (unsigned) (nb * e->cus);
-          e->p1_asked = p1k;
+          e->p1_asked = *p1k;
         }
       grid = e->p1_resident;
     }
   if (grid > P1_MAXGRID) grid = P1_MAXGRID;
-  if ((int64_t) grid > ntiles) grid = (unsigned) ntiles;
+  if ((int64_t) grid > p.ntiles) grid = (unsigned) p.ntiles;
   // (tests: fewer workgroups, never more -- and the cached occupancy above stays what the device said.  The chunk slots of an
   //  owner are strided by the number of owners, grid + BF_MAXGRID, so with ONE workgroup the list below holds 513 times the chunks
   //  of that owner plus the usual slack: by this arithmetic ~5 GB for a table of 4e5 one-word entries, ~11 GB for 1e6 two-word ones,
   //  and the filtered list takes the same again.  Sized, not measured; a hook for small tables on a device with room to spare.)
   { const char *v = test_hook("SMG_P1_GRID"); if (v && atoi(v) >= 1 && (unsigned) atoi(v) < grid) grid = (unsigned) atoi(v); }
-  // a chunk is closed as soon as the next tile's batch (<= one tile of records) does not fit, so
-  // chunks fill to >= 75 %: size the list for that, and never below what is already allocated
-  // (an engine that is reused on the same table must not redo pass 1 every time)
-  // (one-way requests: half the senders)
-  int64_t want_rec = (emit_all ? e->n + e->n / 24 : e->one_way ? e->n / 8 : e->n / 4) + (int64_t) (grid + 16 + 256) * F_CH;
-  const int64_t dwords = ((((e->n + 31) >> 5) + 2) + 3) & ~3ll;          // (kf_bigfix reads the map four words at a time)
-  if (narrow)
-    { if ((int64_t) e->dbits.bytes < dwords * 4) e->dbits_dirty = true;                 // (fresh memory)
-      HIPCHK(e->dbits.reserve(dwords * 4));
+  if (p.narrow)
+    { if ((int64_t) e->dbits.bytes < p.dwords * 4) e->dbits_dirty = true;               // (fresh memory)
+      HIPCHK(e->dbits.reserve(p.dwords * 4));
     }
-  int64_t want_big = e->n / 16 + 4096;      // deferred entries: 0.13 % of the diploid table, 0.4 % with 5 % repeats
+  *grid_out = grid;
+  return SMG_OK;
+}
+
+// ONE attempt, straight through: the request list for want_rec records and the list of deferred entries for want_big, the
+// clears, pass 1 over `grid` workgroups, kf_collect + kf_bigfix.  *maxc, *bigcap: the capacities the kernels were given.
+static int p1_attempt(smg_engine *e, const P1Plan &p, P1Kernel p1k, unsigned grid, int64_t want_rec, int64_t want_big,
+                      unsigned *maxc_out, unsigned *bigcap_out, char *errbuf, size_t errlen)
+{ RunState &r = e->run;
+  // a chunk is closed as soon as the next tile's batch (<= one tile of records) does not fit, so chunks fill to >= 75 %: size
+  // the list for that, and never below what is already allocated (an engine reused on the same table must not redo pass 1)
+  unsigned maxc = (unsigned) ((want_rec + F_CH - 1) / F_CH);
+  if (r.lg.nb)
+    { // look-up chain: owner w fills the slots w, w + G, w + 2G, .. (G = workgroups of this launch + those of kf_bigfix),
+      // so the list must hold G times the chunks of the busiest owner -- pass 1 deals its tiles round-robin, the owners
+      // are balanced to a few per cent -- and the slots of the kf_bigfix owners stay empty on a table without long blocks
+      const int64_t G = (int64_t) grid + BF_MAXGRID;
+      const int64_t per = ((int64_t) maxc + grid - 1) / grid + 2;
+      if (per * G > (int64_t) maxc && per * G < 0x7FFFFFFFll) maxc = (unsigned) (per * G);
+    }
+  { const int64_t have = (int64_t) e->req.bytes / ((int64_t) F_CH * (int64_t) sizeof(u64) * r.rw);
+    if (e->req && have > (int64_t) maxc && have < 0x7FFFFFFFll) maxc = (unsigned) have;
+  }
+  HIPCHK(e->req.reserve((int64_t) maxc * F_CH * (int64_t) sizeof(u64) * r.rw));
+  HIPCHK(e->chunk_fill.reserve((int64_t) maxc * 4 + 4));
+  *maxc_out = r.max_chunks = maxc;
+  if (p.narrow && e->dbits_dirty)
+    { HIPCHK(hipMemsetAsync(e->dbits, 0, e->dbits.bytes, e->stream)); e->dbits_dirty = false; }
+  FastArgs a = make_fast(e);
+  if (r.lg.nb)
+    { // owners of the request chunks: the workgroups of this launch, then those of kf_bigfix (rows zero unless it runs)
+      HIPCHK(e->whist.reserve((int64_t) (grid + BF_MAXGRID) * L_BK * 4));
+      HIPCHK(hipMemsetAsync(e->whist + (size_t) grid * L_BK, 0, sizeof(unsigned) * BF_MAXGRID * L_BK, e->stream));
+      HIPCHK(hipMemsetAsync(e->chunk_fill, 0, (size_t) maxc * 4, e->stream));      // (a slot that stays empty has fill 0)
+      r.p1grid = grid; r.nown = grid + BF_MAXGRID;
+    }
+  hipEventRecord(e->ev[EV_PASS1_BEG], e->stream);
+  if (!p.narrow)
+    with_words<3>(p.W, [&](auto w) { hipLaunchKernelGGL(kf_pass1<w()>, dim3(grid), dim3(F_TPB), 0, e->stream, a, e->bstart,
+        e->req, e->chunk_fill, maxc, (int) p.emit_all, (int) p.want_fp, e->partials, &e->ctrl->fast, p.ntiles); });
+  else
+    { P1Hot hot;
+      hot.keys = a.keys; hot.cnt = a.cnt; hot.n = a.n; hot.code = a.code; hot.sig = a.sig; hot.bstart = r.dir_preset ? (uint32_t *) NULL : e->bstart;
+      hot.bmap = a.bmap; hot.b0 = r.dir.b0; hot.nb = r.dir.nb;
+      hot.shifts = P1Hot::pack(r.dir.dsh, a.sigsh, a.bmsh, p.emit_all, p.want_fp, r.lg.nb, r.bm2 != 0, r.one_way != 0);
+      hot.G = p.gr; hot.ntiles = p.ntiles;
+      P1Cold &c = *e->h_p1cold;
+      c.req = e->req; c.chunk_fill = e->chunk_fill; c.dbits = e->dbits;
+      e->dbits_dirty = true;                                               // until kf_bigfix has cleared the bits again
+      c.partials = e->partials; c.ctl = &e->ctrl->fast; c.max_chunks = maxc; c.whist = e->whist; c.owners = grid + BF_MAXGRID;
+      HIPCHK(e->p1tick.reserve((int64_t) D_NCLS * D_TICKW * 4));
+      HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
+      c.tick = e->p1tick;
+      HIPCHK(hipMemcpyAsync(e->p1cold, e->h_p1cold, sizeof(P1Cold), hipMemcpyHostToDevice, e->stream));
+      // (the hot forms take these for granted: what chose them is what the kernel argument says)
+      if (r.p1_var != 1 && (hot.bstart != NULL || hot.sig != NULL || hot.bmap == NULL))
+        return fail(errbuf, errlen, SMG_EINVAL, "pass 1: the hot form without its preconditions%s");
+      hipLaunchKernelGGL(p1k, dim3(grid), dim3(D_TPB), 0, e->stream, hot, (const P1Cold *) e->p1cold);
+    }
+  hipEventRecord(e->ev[EV_PASS1_END], e->stream);
+  HIPCHK(hipGetLastError());
+  if (p.want_fp)
+    HIPCHK(hipMemcpyAsync(e->h_partials, e->partials, sizeof(u64) * 4 * grid, hipMemcpyDeviceToHost, e->stream));
+  *bigcap_out = 0;
+  if (!p.narrow) return SMG_OK;
+  // exact redo of the deferred entries (a pair at distance 4..30, or a window block longer than the window): kf_collect compacts
+  // the bit map pass 1 marked them in into a list (and clears it), kf_bigfix redoes the list.  Launched without waiting for pass 1's
+  // control words (a list that overflowed is guarded on the device; the run is redone either way, as for too short a biglist).
+  if (want_big < (int64_t) e->biglist.bytes / 4) want_big = (int64_t) e->biglist.bytes / 4;
+  if (want_big > 0xFFFFFFF0ll) want_big = 0xFFFFFFF0ll;
+  HIPCHK(e->biglist.reserve(want_big * 4));
+  HIPCHK(e->farp.reserve(e->biglist.bytes));
+  const unsigned bigcap = (unsigned) (e->biglist.bytes / 4 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : e->biglist.bytes / 4);
+  const int64_t cb = (p.dwords / 4 + BF_TPB - 1) / BF_TPB;
+  hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);
+  hipLaunchKernelGGL(kf_collect, dim3((unsigned) (cb > BF_MAXGRID ? BF_MAXGRID : cb)), dim3(BF_TPB), 0, e->stream, e->dbits, p.dwords, e->biglist, bigcap, &e->ctrl->fast.nbig);
+  unsigned *const bf_hist = r.lg.nb ? e->whist + (size_t) grid * L_BK : (unsigned *) NULL;
+  with_bool(p.W == 2, [&](auto two_words) { with_bool(r.rw == p.W, [&](auto key_only)
+    { hipLaunchKernelGGL((kf_bigfix<two_words() ? 2 : 1, (two_words() ? 2 : 1) + (key_only() ? 0 : 1)>), dim3(BF_MAXGRID), dim3(BF_TPB), 0, e->stream, a, e->biglist,
+          &e->ctrl->fast.nbig, bigcap, e->req, e->chunk_fill, maxc, &e->ctrl->fast, bf_hist, grid, grid + BF_MAXGRID, r.lg.nb, e->farp); }); });
+  hipEventRecord(e->ev[EV_PASS1_END], e->stream);
+  HIPCHK(hipGetLastError());
+  *bigcap_out = bigcap;
+  return SMG_OK;
+}
+
+// the table's fingerprints: XOR of the partial words of pass 1's workgroups (smg_device.hpp)
+static void fold_fp(smg_engine *e, unsigned grid)
+{ memset(e->run.fp, 0, sizeof(e->run.fp));
+  for (unsigned b = 0; b < grid; b++)
+    for (int q = 0; q < 4; q++) e->run.fp[q] ^= e->h_partials[b * 4 + q];
+}
+
+// replay: a step of the phase API on the table of the step before (smg_engine_set_replay).  Everything is launched as ever, but
+// nothing is read back here: the lists are as large as last time, the counts that later launches take from the host (requests,
+// deferred entries) are the recorded step's -- they are functions of the table -- and the device checks all of it against the
+// control words at the end of the step (k_proof_replay).
+static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, char *errbuf, size_t errlen, bool replay = false,
+                      bool one_way_ok = false)
+{ int rc;
+  begin_run(e, RUN_FAST);
+  RunState &r = e->run;
+  const P1Plan p = p1_plan(e->tab.kmer, e->tab.n, emit_all != 0, with_meta != 0, want_fp != 0, one_way_ok, e->set.bm_cap, e->set.no_filter);
+  r.rw = r.p1_rw = p.rw; r.p1_w = p.W; r.one_way = p.one_way; r.use_sig = p.use_sig; r.bm_bits = p.bm_bits; r.bm2 = p.bm2;
+  if (p.chain) r.lg = lookup_geo(p.bm_bits);
+  HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
+  set_geo(e);
+  P1Kernel p1k = NULL;
+  unsigned grid = 0, maxc = 0, bigcap = 0;
+  if ((rc = p1_reserve(e, p, &p1k, &grid, errbuf, errlen))) return rc;
+  if (e->tab.n == 0) { r.pass1_done = true; return SMG_OK; }
+  int64_t want_rec = p.want_rec + (int64_t) (grid + 16 + 256) * F_CH, want_big = p.want_big;
+  const FastCtl &f = e->h_ctrl->fast;
   bool done = false;
   for (int attempt = 0; attempt < 5 && !done; attempt++)
-    { unsigned maxc = (unsigned) ((want_rec + F_CH - 1) / F_CH);
-      if (e->lg.nb)
-        { // look-up chain: owner w fills the slots w, w + G, w + 2G, .. (G = workgroups of this launch + those of kf_bigfix),
-          // so the list must hold G times the chunks of the busiest owner -- pass 1 deals its tiles round-robin, the owners
-          // are balanced to a few per cent -- and the slots of the kf_bigfix owners stay empty on a table without long blocks
-          const int64_t G = (int64_t) grid + BF_MAXGRID;
-          const int64_t per = ((int64_t) maxc + grid - 1) / grid + 2;
-          if (per * G > (int64_t) maxc && per * G < 0x7FFFFFFFll) maxc = (unsigned) (per * G);
-        }
-      { const int64_t have = (int64_t) e->req.bytes / ((int64_t) F_CH * (int64_t) sizeof(u64) * e->rw);
-        if (e->req && have > (int64_t) maxc && have < 0x7FFFFFFFll) maxc = (unsigned) have;
-      }
-      HIPCHK(e->req.reserve((int64_t) maxc * F_CH * (int64_t) sizeof(u64) * e->rw));
-      HIPCHK(e->chunk_fill.reserve((int64_t) maxc * 4 + 4));
-      e->max_chunks = maxc;
-      if (narrow && e->dbits_dirty)
-        { HIPCHK(hipMemsetAsync(e->dbits, 0, e->dbits.bytes, e->stream)); e->dbits_dirty = false; }
-      FastArgs a = make_fast(e);
-      if (e->lg.nb)
-        { // owners of the request chunks: the workgroups of this launch, then those of kf_bigfix (rows zero unless it runs)
-          HIPCHK(e->whist.reserve((int64_t) (grid + BF_MAXGRID) * L_BK * 4));
-          HIPCHK(hipMemsetAsync(e->whist + (size_t) grid * L_BK, 0, sizeof(unsigned) * BF_MAXGRID * L_BK, e->stream));
-          HIPCHK(hipMemsetAsync(e->chunk_fill, 0, (size_t) maxc * 4, e->stream));      // (a slot that stays empty has fill 0)
-          e->p1grid = grid; e->nown = grid + BF_MAXGRID;
-        }
-      hipEventRecord(e->ev[EV_PASS1_BEG], e->stream);
-      if (narrow)
-        {
-          P1Hot hot;
-          hot.keys = a.keys; hot.cnt = a.cnt; hot.n = a.n; hot.code = a.code; hot.sig = a.sig; hot.bstart = e->dir_preset ? (uint32_t *) NULL : e->bstart;
-          hot.bmap = a.bmap; hot.b0 = e->dir.b0; hot.nb = e->dir.nb; hot.shifts = (unsigned) e->dir.dsh | ((unsigned) a.sigsh << 6) | (((unsigned) a.bmsh & 31u) << 12)
-                       | ((emit_all ? 1u : 0u) << 18) | ((want_fp ? 1u : 0u) << 19) | ((unsigned) e->lg.nb << 20) | ((unsigned) e->bm2 << 24)
-                       | ((unsigned) e->one_way << 25);
-          hot.G = gr; hot.ntiles = ntiles;
-          e->h_p1cold->req = e->req; e->h_p1cold->chunk_fill = e->chunk_fill; e->h_p1cold->dbits = e->dbits;
-          e->dbits_dirty = true;                                               // until kf_bigfix has cleared the bits again
-          e->h_p1cold->partials = e->partials; e->h_p1cold->ctl = &e->ctrl->fast; e->h_p1cold->max_chunks = maxc;
-          e->h_p1cold->whist = e->whist; e->h_p1cold->owners = grid + BF_MAXGRID;
-          HIPCHK(e->p1tick.reserve((int64_t) D_NCLS * D_TICKW * 4));
-          HIPCHK(hipMemsetAsync(e->p1tick, 0, (size_t) D_NCLS * D_TICKW * 4, e->stream));
-          e->h_p1cold->tick = e->p1tick;
-          HIPCHK(hipMemcpyAsync(e->p1cold, e->h_p1cold, sizeof(P1Cold), hipMemcpyHostToDevice, e->stream));
-          // (the hot forms take these for granted: what chose them above is what the kernel argument says)
-          if (e->p1_var != 1 && (hot.bstart != NULL || hot.sig != NULL || hot.bmap == NULL))
-            return fail(errbuf, errlen, SMG_EINVAL, "pass 1: the hot form without its preconditions%s");
-          hipLaunchKernelGGL(p1k, dim3(grid), dim3(D_TPB), 0, e->stream, hot, (const P1Cold *) e->p1cold);
-        }
-      else
-        {
-          with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass1<w()>, dim3(grid), dim3(F_TPB), 0, e->stream, a, e->bstart,
-              e->req, e->chunk_fill, maxc, emit_all, want_fp, e->partials, &e->ctrl->fast, ntiles); });
-        }
-      hipEventRecord(e->ev[EV_PASS1_END], e->stream);
-      HIPCHK(hipGetLastError());
-      if (want_fp)
-        HIPCHK(hipMemcpyAsync(e->h_partials, e->partials, sizeof(u64) * 4 * grid, hipMemcpyDeviceToHost, e->stream));
-      unsigned bigcap = 0;
-      if (narrow)
-        { // exact redo of the deferred entries (a pair at distance 4..30, or a window block longer than the window):
-          // kf_collect compacts the bit map pass 1 marked them in into a list (and clears it), kf_bigfix redoes the list.
-          // Launched without waiting for pass 1's control words (a request list that overflowed is guarded on the
-          // device; the run is redone below either way, and so it is when the list of deferred entries was too short).
-          if (want_big < (int64_t) e->biglist.bytes / 4) want_big = (int64_t) e->biglist.bytes / 4;
-          if (want_big > 0xFFFFFFF0ll) want_big = 0xFFFFFFF0ll;
-          HIPCHK(e->biglist.reserve(want_big * 4));
-          HIPCHK(e->farp.reserve(e->biglist.bytes));
-          bigcap = (unsigned) (e->biglist.bytes / 4 > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : e->biglist.bytes / 4);
-          unsigned cb = (unsigned) ((dwords / 4 + BF_TPB - 1) / BF_TPB);
-          if (cb > BF_MAXGRID) cb = BF_MAXGRID;
-          hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);
-          hipLaunchKernelGGL(kf_collect, dim3(cb), dim3(BF_TPB), 0, e->stream, e->dbits, dwords, e->biglist, bigcap, &e->ctrl->fast.nbig);
-#define BIGFIX(W_, RW_) hipLaunchKernelGGL((kf_bigfix<W_, RW_>), dim3(BF_MAXGRID), dim3(BF_TPB), 0, e->stream, a, e->biglist, &e->ctrl->fast.nbig, bigcap, e->req, \
-                              e->chunk_fill, maxc, &e->ctrl->fast, e->lg.nb ? e->whist + (size_t) grid * L_BK : (unsigned *) NULL, \
-                              grid, grid + BF_MAXGRID, e->lg.nb, e->farp)
-          if (e->W == 2 && e->rw == 2) BIGFIX(2, 2); else if (e->W == 2) BIGFIX(2, 3); else if (e->rw == 1) BIGFIX(1, 1); else BIGFIX(1, 2);
-#undef BIGFIX
-          hipEventRecord(e->ev[EV_PASS1_END], e->stream);
-          HIPCHK(hipGetLastError());
-        }
-      if (replay) { done = true; break; }
+    { if ((rc = p1_attempt(e, p, p1k, grid, want_rec, want_big, &maxc, &bigcap, errbuf, errlen))) return rc;
+      if (replay) break;
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       e->dbits_dirty = false;
-      if (e->h_ctrl->fast.unsorted)
-        return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
-      if (narrow && e->h_ctrl->fast.nbig > bigcap)
-        { // more deferred entries than the list holds (a repeat-dominated table): size it from the count and redo
-          want_big = (int64_t) e->h_ctrl->fast.nbig + (int64_t) e->h_ctrl->fast.nbig / 8 + 4096;
-          e->dbits_dirty = true;                  // (the bits of the entries that did not fit are still set)
-          HIPCHK(hipMemsetAsync(&e->ctrl->fast, 0, sizeof(FastCtl), e->stream));
-          continue;
+      if (f.unsorted) return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
+      // each redo sizes its list from the count the failed attempt reported, so the second attempt fits
+      if (p.narrow && f.nbig > bigcap)        // more deferred entries than the list holds (a repeat-dominated table)
+        { want_big = (int64_t) f.nbig + (int64_t) f.nbig / 8 + 4096;
+          e->dbits_dirty = true;              // (the bits of the entries that did not fit are still set)
         }
-      if (e->h_ctrl->fast.n_chunks > maxc)
-        { // the request list outgrew its first-guess capacity: size it from the count and redo
-          want_rec = (int64_t) (e->h_ctrl->fast.n_chunks + 16 + 256) * F_CH;
-          HIPCHK(hipMemsetAsync(&e->ctrl->fast, 0, sizeof(FastCtl), e->stream));
-          continue;
-        }
-      done = true;
+      else if (f.n_chunks > maxc) want_rec = (int64_t) (f.n_chunks + 16 + 256) * F_CH;       // the request list outgrew its first guess
+      else done = true;
+      if (!done) HIPCHK(hipMemsetAsync(&e->ctrl->fast, 0, sizeof(FastCtl), e->stream));
     }
-  // (each redo sizes the lists from the counts the failed attempt reported, so the second attempt fits; a list that
-  //  still overflows after that is a bug, and must not be read as a complete request list)
-  if (replay)
-    { e->rp_grid = grid;
-      e->n_chunks = 1;                      // (> 0: "there are requests"; the real number is checked at the end of the step)
-      e->st.nrequests = e->st.nemitted = e->rp_nreq;
-      e->st.nbig = e->rp_nbig;
-      e->st.ms_filter = 0; e->st.ms_bigfix = 0;
-      e->far_listed = narrow;
-      e->prepared = true;
-      return SMG_OK;
-    }
-  if (!done || e->h_ctrl->fast.n_chunks > e->max_chunks)
+  // (a list that still overflows is a bug, and must not be read as a complete request list)
+  if (!replay && (!done || f.n_chunks > r.max_chunks))
     return fail(errbuf, errlen, SMG_ENODEV, "pass 1: the request list overflowed its capacity on every attempt%s");
-  e->n_chunks = e->h_ctrl->fast.n_chunks;
-  memset(e->fp, 0, sizeof(e->fp));
-  if (want_fp)
-    for (unsigned b = 0; b < grid; b++)
-      for (int q = 0; q < 4; q++) e->fp[q] ^= e->h_partials[b * 4 + q];     // (XOR fingerprint: smg_device.hpp)
-  e->st.ms_pass1 = ms_between(e, EV_PASS1_BEG, EV_PASS1_END);
-  e->st.nrequests = (int64_t) e->h_ctrl->fast.nreq;
-  e->st.nemitted = e->st.nrequests;
+  // the counts: this step's, or (replay) the recorded step's -- the real ones are checked at the end of the step, the
+  // fingerprints and the times are read then (smg_engine_replay_done)
+  if (replay) e->rp.grid = grid;
+  else { fold_fp(e, want_fp ? grid : 0); e->st.ms_pass1 = ms_between(e, EV_PASS1_BEG, EV_PASS1_END); }
+  r.n_chunks = replay ? 1 : f.n_chunks;                 // (replay: > 0, "there are requests")
+  e->st.nrequests = e->st.nemitted = replay ? e->rp.nreq : (int64_t) f.nreq;
+  e->st.nbig = replay ? e->rp.nbig : p.narrow ? (int64_t) f.nbig : 0;
   e->st.ms_filter = 0;
-  e->st.nbig = narrow ? (int64_t) e->h_ctrl->fast.nbig : 0;
-  e->far_listed = narrow;
-  e->st.ms_bigfix = 0;
-  if (narrow) e->st.ms_bigfix = ms_between(e, EV_DECODE_BEG, EV_PASS1_END);
-  e->prepared = true;
+  e->st.ms_bigfix = (!replay && p.narrow) ? ms_between(e, EV_DECODE_BEG, EV_PASS1_END) : 0;
+  r.far_listed = p.narrow;
+  r.pass1_done = true;
   return SMG_OK;
 }
 
@@ -697,33 +782,21 @@ static int apply_indexed(smg_engine *e, const u64 *rec, int64_t n, int check_cou
   if (nb > 16384) nb = 16384;
   if (n < SORT_MIN || n >= 0xFFFFFFF0ll)
     {
-      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_apply<w()>, dim3((unsigned) (nb > 8192 ? 8192 : nb)), dim3(F_TPB), 0, e->stream, a, rec,
-          (const uint32_t *) NULL, n, check_count, &e->ctrl->fast, e->rw); });
+      with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_apply<w()>, dim3((unsigned) (nb > 8192 ? 8192 : nb)), dim3(F_TPB), 0, e->stream, a, rec,
+          (const uint32_t *) NULL, n, check_count, &e->ctrl->fast, e->run.rw); });
       return SMG_OK;
     }
   for (int q = 0; q < 2; q++)
     { HIPCHK(e->skey[q].reserve(n * 4 + 16));
       HIPCHK(e->sidx[q].reserve(n * 4 + 16));
     }
-  hipLaunchKernelGGL(kf_sortkey, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, rec, e->rw, n, e->skey[0], e->sidx[0]);
+  hipLaunchKernelGGL(kf_sortkey, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, rec, e->run.rw, n, e->skey[0], e->sidx[0]);
   uint32_t *const ki = e->skey[0], *const ko = e->skey[1], *const vi = e->sidx[0], *const vo = e->sidx[1];
   HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
     { return rocprim::radix_sort_pairs<smg_sort_config>(tmp, bytes, ki, ko, vi, vo, (size_t) n, 8u, 32u, e->stream); }));
-  with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_apply_indexed<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, rec, e->sidx[1], n,
-      check_count, &e->ctrl->fast, e->rw); });
+  with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_apply_indexed<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, rec, e->sidx[1], n,
+      check_count, &e->ctrl->fast, e->run.rw); });
   return SMG_OK;
-}
-
-// block ids of the request filter = the leading bm_id_bits(k) bits of a k-mer (a function of k alone, so that the
-// maps of all the shards of a table line up): window blocks, coarsened to 2^30 ids (128 MB of bits) at most
-// cap: 30 when the maps of several shards are exchanged (128 MB in total), 32 on one GPU, where the probes of the
-// first 30 bits are LDS reads (smg_lookup.hpp) and a finer map only costs its memset; SMG_BM_BITS overrides (8..32).
-// An id never runs past the k-mer (2k bits) nor past its leading 32 bits.
-static int bm_id_bits(int kmer, int cap)
-{ { const char *v = test_hook("SMG_BM_BITS"); if (v && atoi(v) >= 8 && atoi(v) <= 32) cap = atoi(v); }
-  int nbits = cap > 30 ? 2 * kmer : 2 * (kmer / 2);
-  if (nbits > cap) nbits = cap;
-  return nbits;
 }
 
 // first half of the request filter, which does not need the map (a sharded run overlaps it with the exchange of the
@@ -732,40 +805,40 @@ static int bm_id_bits(int kmer, int cap)
 // array as sentinels, as for the look-ups) keeps the map words that the resident workgroups probe inside the L2s.
 static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
 { hipEventRecord(e->ev[EV_LOOKUP_BEG], e->stream);                      // start of the filter's time
-  if (e->lg.nb)
+  if (e->run.lg.nb)
     { // smg_lookup.hpp: bucket offsets from pass 1's histogram, one-pass partition into the dense array req2
       const int64_t nreq = e->st.nrequests;
-      HIPCHK(e->req2.reserve((nreq > 0 ? nreq : 1) * (int64_t) sizeof(u64) * e->rw));
-      const int nbk = 1 << e->lg.nb;
+      HIPCHK(e->req2.reserve((nreq > 0 ? nreq : 1) * (int64_t) sizeof(u64) * e->run.rw));
+      const int nbk = 1 << e->run.lg.nb;
       // bucket sizes = column sums of the owners' histogram rows -> bucket offsets -> first slot of every owner in every bucket
-      hipLaunchKernelGGL(kl_tot, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, (const unsigned *) e->whist, e->nown, e->ghist);
+      hipLaunchKernelGGL(kl_tot, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, (const unsigned *) e->whist, e->run.nown, e->ghist);
       hipLaunchKernelGGL(kl_scan, dim3(1), dim3(L_BK), 0, e->stream, e->ghist, nbk, e->boff, e->boff + L_BK + 2, e->ghist + L_BK);
-      hipLaunchKernelGGL(kl_woff, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, e->whist, e->nown, (const u64 *) e->boff);
-      if (e->n_chunks)
-        with_words<2>(e->rw, [&](auto rw) { hipLaunchKernelGGL(kl_part<rw()>, dim3(e->nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->nown,
-            (const unsigned *) e->whist, e->max_chunks, e->lg.nb, e->req2); });
+      hipLaunchKernelGGL(kl_woff, dim3(L_BK / LW_BPW), dim3(LW_SL * LW_BPW), 0, e->stream, e->whist, e->run.nown, (const u64 *) e->boff);
+      if (e->run.n_chunks)
+        with_words<2>(e->run.rw, [&](auto rw) { hipLaunchKernelGGL(kl_part<rw()>, dim3(e->run.nown), dim3(PT_TPB), 0, e->stream, e->req, e->chunk_fill, e->run.nown,
+            (const unsigned *) e->whist, e->run.max_chunks, e->run.lg.nb, e->req2); });
       HIPCHK(hipGetLastError());
-      e->presorted = 3;
+      e->run.presorted = PRESORT_CHAIN;
       return SMG_OK;
     }
-  e->presorted = 2;
-  const int64_t nslots = (int64_t) e->n_chunks * F_CH;
+  e->run.presorted = PRESORT_ASIS;
+  const int64_t nslots = (int64_t) e->run.n_chunks * F_CH;
   int64_t sort_min = 1 << 22;               // below this the probes are too few to matter
   { const char *v = test_hook("SMG_FILTER_SORT_MIN"); if (v) sort_min = atoll(v); if (sort_min < SORT_MIN) sort_min = SORT_MIN; }
-  if (!(e->rw == 1 && nslots >= sort_min && e->kmer < 32)) return SMG_OK;
-  hipLaunchKernelGGL(kf_fill_holes, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
+  if (!(e->run.rw == 1 && nslots >= sort_min && e->tab.kmer < 32)) return SMG_OK;
+  hipLaunchKernelGGL(kf_fill_holes, dim3(e->run.n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
   HIPCHK(e->req2.reserve(nslots * (int64_t) sizeof(u64)));
   HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
     { return rocprim::radix_sort_keys<smg_sort_config>(tmp, bytes, (u64 *) e->req, (u64 *) e->req2, (size_t) nslots, 56u, 64u, e->stream); }));
-  e->presorted = 1;
+  e->run.presorted = PRESORT_BUCKETED;
   return SMG_OK;
 }
 
 // smg_lookup.hpp: filter the partitioned requests against `map`; list = false: look the survivors up at once
 static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned maxout, char *errbuf, size_t errlen)
-{ const bool two = e->bm2 != 0;                             // (a map that came from outside was built by the same rule)
+{ const bool two = e->run.bm2 != 0;                             // (a map that came from outside was built by the same rule)
   unsigned grid = (unsigned) e->cus;
-  const unsigned nbk = 1u << e->lg.nb;
+  const unsigned nbk = 1u << e->run.lg.nb;
   FastArgs a = make_fast(e);
   // The fused probe + look-up of a single shard has two forms.  kl_probe (a bucket per workgroup, the bucket's map folded
   // into LDS) is the faster one on a table without long window blocks: 2.5 against 2.7 ms at 2.5e9 entries.  kl_probe_x
@@ -778,123 +851,119 @@ static int lookup_probe(smg_engine *e, const uint32_t *map, bool list, unsigned 
     // ... and so does the share of entries that sent a request: 17.5 % on the diploid tables, a third on the polyploid ones, where
     // one request in seven survives the filter (2.5e7 look-ups at 6.4e8 entries) and kl_probe_x is 7-8 % ahead as well
     // (a one-way run sends one request per complement class: half the share says the same about the table)
-    const int64_t share = e->one_way ? 14 : 28;
-    const bool auto_x = (e->st.nbig > 0 && e->st.nbig * 400 > e->n) || e->st.nemitted * 100 > e->n * share;
-    if (!list && e->lg.nb >= 3 && (px ? atoi(px) != 0 : auto_x))
+    const int64_t share = e->run.one_way ? 14 : 28;
+    const bool auto_x = (e->st.nbig > 0 && e->st.nbig * 400 > e->tab.n) || e->st.nemitted * 100 > e->tab.n * share;
+    if (!list && e->run.lg.nb >= 3 && (px ? atoi(px) != 0 : auto_x))
       { HIPCHK(e->xtick.reserve((int64_t) PX_NXCD * PX_TICKW * 4));
         HIPCHK(hipMemsetAsync(e->xtick, 0, (size_t) PX_NXCD * PX_TICKW * 4, e->stream));
         // tickets of 2048 requests where many requests survive (polyploid tables: one in seven, all real hits -- half as many
         // buckets in flight per XCD keep more of a bucket's k-mer lines in reach: -0.25 ms on the hexaploid table), 4096 where the
         // kernel is mostly streaming (a table with repeats: 1 request in 50 survives, and a ticket's fixed cost shows: +0.5 ms at 2048)
-        unsigned part = e->st.nemitted * 100 > e->n * share ? PX_PART : 2 * PX_PART;
+        unsigned part = e->st.nemitted * 100 > e->tab.n * share ? PX_PART : 2 * PX_PART;
         if (test_hook("SMG_PX_ONE_XCC")) part |= 0x80000000u;                      // (tests: every workgroup claims XCD 0)
         const unsigned xg = grid * PX_WGS;
-#define PROBEX(TWO_, RW_) hipLaunchKernelGGL((kl_probe_x<TWO_, RW_>), dim3(xg), dim3(PX_TPB), 0, e->stream, a, (const u64 *) e->req2, \
-                            (const u64 *) e->boff, map, e->lg, e->xtick, &e->ctrl->fast, part)
-        if (two) { if (e->rw == 1) PROBEX(true, 1); else PROBEX(true, 2); }
-        else     { if (e->rw == 1) PROBEX(false, 1); else PROBEX(false, 2); }
-#undef PROBEX
+        with_bool(two, [&](auto t) { with_words<2>(e->run.rw, [&](auto rw)
+          { hipLaunchKernelGGL((kl_probe_x<t(), rw()>), dim3(xg), dim3(PX_TPB), 0, e->stream, a, (const u64 *) e->req2,
+                               (const u64 *) e->boff, map, e->run.lg, e->xtick, &e->ctrl->fast, part); }); });
         HIPCHK(hipGetLastError());
-        e->probe_form = 2; e->probe_part = part & 0x7FFFFFFFu;
+        e->run.probe_form = PROBE_X; e->run.probe_part = part & 0x7FFFFFFFu;
         return SMG_OK;
       }
   }
   if (grid > nbk) grid = nbk;
-#define PROBE(LIST_, TWO_, RW_, OUT_, FILL_, MAX_) hipLaunchKernelGGL((kl_probe<LIST_, TWO_, RW_>), dim3(grid), dim3(PB_TPB), 0, e->stream, a, \
-                       (const u64 *) e->req2, (const u64 *) e->boff, map, e->lg, e->ghist + L_BK, OUT_, FILL_, MAX_, &e->ctrl->fast)
-#define PROBE_RW(LIST_, TWO_, OUT_, FILL_, MAX_) { if (e->rw == 1) PROBE(LIST_, TWO_, 1, OUT_, FILL_, MAX_); else PROBE(LIST_, TWO_, 2, OUT_, FILL_, MAX_); }
-  if (list) { if (two) PROBE_RW(true, true, e->reqf, e->chunk_fillf, maxout) else PROBE_RW(true, false, e->reqf, e->chunk_fillf, maxout) }
-  else      { if (two) PROBE_RW(false, true, (u64 *) NULL, (uint32_t *) NULL, 0u) else PROBE_RW(false, false, (u64 *) NULL, (uint32_t *) NULL, 0u) }
-#undef PROBE_RW
-#undef PROBE
+  u64 *const out = list ? (u64 *) e->reqf : (u64 *) NULL;                  // (the fused form keeps no survivor list)
+  uint32_t *const fill = list ? (uint32_t *) e->chunk_fillf : (uint32_t *) NULL;
+  with_bool(list, [&](auto l) { with_bool(two, [&](auto t) { with_words<2>(e->run.rw, [&](auto rw)
+    { hipLaunchKernelGGL((kl_probe<l(), t(), rw()>), dim3(grid), dim3(PB_TPB), 0, e->stream, a, (const u64 *) e->req2, (const u64 *) e->boff,
+                         map, e->run.lg, e->ghist + L_BK, out, fill, list ? maxout : 0u, &e->ctrl->fast); }); }); });
   HIPCHK(hipGetLastError());
-  e->probe_form = list ? 3 : 1; e->probe_part = 0;
+  e->run.probe_form = list ? PROBE_LIST : PROBE_FUSED; e->run.probe_part = 0;
   return SMG_OK;
 }
 
 // drop the requests whose target window block holds no candidate (kf_filter); map = NULL: this engine's own map
 static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t errlen)
 { int rc;
-  if (!filter_ok(e) || e->n_chunks == 0) return SMG_OK;
-  if (!map) map = e->bm_bits ? e->bmap : NULL;
+  if (!filter_ok(e) || e->run.n_chunks == 0) return SMG_OK;
+  if (!map) map = e->run.bm_bits ? e->bmap : NULL;
   if (!map) return SMG_OK;
-  const int nbits = bm_id_bits(e->kmer, e->bm_cap);
+  const int nbits = bm_id_bits(e->tab.kmer, e->set.bm_cap);
   // two workgroups per CU, chunks dealt round-robin: the chunks in flight then span one or two of the 256 sorted
   // buckets, i.e. <= 1 MB of the map (measured: 512 workgroups 3.0 ms, 256 / 1024 / 2048 workgroups 3.4-3.7 ms)
   unsigned grid = 2u * (unsigned) e->cus;
-  if (grid > e->n_chunks) grid = e->n_chunks;
-  unsigned maxout = e->n_chunks + grid + 16;
-  if (e->lg.nb)
+  if (grid > e->run.n_chunks) grid = e->run.n_chunks;
+  unsigned maxout = e->run.n_chunks + grid + 16;
+  if (e->run.lg.nb)
     { // kl_probe: every wave of every workgroup (one per CU, lookup_probe) fills chunks of its own, each to the brim
       // but for the < 64 records that did not fit: size the list from the launch and the request count, not from 256 CUs
       const int64_t need = (int64_t) e->cus * PB_WAVES + e->st.nrequests / (F_CH - 63) + 16;
       maxout = need < 0x7FFFFFFFll ? (unsigned) need : 0x7FFFFFFFu;
-      if (maxout < e->n_chunks + 16) maxout = e->n_chunks + 16;
+      if (maxout < e->run.n_chunks + 16) maxout = e->run.n_chunks + 16;
     }
   // (the two chunk lists swap roles after every filter: keep them the same size, or pass 1 would reallocate)
-  { int64_t want = (int64_t) maxout * F_CH * (int64_t) sizeof(u64) * e->rw, wantf = (int64_t) maxout * 4 + 4;
+  { int64_t want = (int64_t) maxout * F_CH * (int64_t) sizeof(u64) * e->run.rw, wantf = (int64_t) maxout * 4 + 4;
     if (want < (int64_t) e->req.bytes) want = (int64_t) e->req.bytes;
     if (wantf < (int64_t) e->chunk_fill.bytes) wantf = (int64_t) e->chunk_fill.bytes;
     HIPCHK(e->reqf.reserve(want));
     HIPCHK(e->chunk_fillf.reserve(wantf));
   }
-  if (e->rp_active)
+  if (e->rp.active)
     { // replayed step: WHICH chunks the waves of the probe kernel fill is decided by an atomic counter, and how many by the
       // way the buckets fall to the workgroups -- so the routing kernels walk the whole list, and a chunk nobody opened must
       // read as empty
       hipEventRecord(e->ev[EV_REPLAY_FILTER_BEG], e->stream);
       // (as many chunks as the recorded step's filter filled, and some: the device checks that this step stayed inside)
-      if (e->rp_seen_chunks + 64u < maxout) maxout = e->rp_seen_chunks + 64u;
+      if (e->rp.seen_chunks + 64u < maxout) maxout = e->rp.seen_chunks + 64u;
       HIPCHK(hipMemsetAsync(e->chunk_fillf, 0, (size_t) maxout * 4, e->stream));
     }
-  if (!e->presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
-  const int64_t nslots = (int64_t) e->n_chunks * F_CH;
-  if (e->presorted == 3)
+  if (!e->run.presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
+  const int64_t nslots = (int64_t) e->run.n_chunks * F_CH;
+  if (e->run.presorted == PRESORT_CHAIN)
     { if ((rc = lookup_probe(e, map, true, maxout, errbuf, errlen))) return rc; }
-  else if (e->presorted == 1)
-    hipLaunchKernelGGL(kf_filter<1>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req2, (const uint32_t *) NULL, e->n_chunks, nslots,
+  else if (e->run.presorted == PRESORT_BUCKETED)
+    hipLaunchKernelGGL(kf_filter<1>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req2, (const uint32_t *) NULL, e->run.n_chunks, nslots,
                        map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast);
   else
-    with_words<4>(e->rw, [&](auto rw) { hipLaunchKernelGGL(kf_filter<rw()>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->n_chunks, (int64_t) 0,
+    with_words<4>(e->run.rw, [&](auto rw) { hipLaunchKernelGGL(kf_filter<rw()>, dim3(grid), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->run.n_chunks, (int64_t) 0,
         map, 64 - nbits, e->reqf, e->chunk_fillf, maxout, &e->ctrl->fast); });
   hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
   HIPCHK(hipGetLastError());
-  if (e->rp_active)
+  if (e->rp.active)
     { // replayed step: the kept list is as long as last time (the device checks it: smg_engine_proof) -- nothing is read
       hipEventRecord(e->ev[EV_REPLAY_FILTER_END], e->stream);
-      e->rp_nf_chunks = maxout;             // (the device checks that the probe kernel stayed inside the list)
+      e->rp.nf_chunks = maxout;             // (the device checks that the probe kernel stayed inside the list)
     }
   else
     { if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       if (e->h_ctrl->fast.nf_chunks > maxout) return fail(errbuf, errlen, SMG_ENODEV, "request filter overflowed its chunk list%s");
     }
   e->req.swap(e->reqf); e->chunk_fill.swap(e->chunk_fillf);
-  if (e->rp_active)
-    { e->n_chunks = e->rp_nf_chunks; e->st.nrequests = e->rp_nf_req; e->filtered = true;
+  if (e->rp.active)
+    { e->run.n_chunks = e->rp.nf_chunks; e->st.nrequests = e->rp.nf_req; e->run.filtered = true;
       return SMG_OK;
     }
-  e->n_chunks = e->h_ctrl->fast.nf_chunks;
+  e->run.n_chunks = e->h_ctrl->fast.nf_chunks;
   e->st.nrequests = (int64_t) e->h_ctrl->fast.nf_req;
-  e->filtered = true;
+  e->run.filtered = true;
   e->st.ms_filter = ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
   e->st.ms_rclookup += e->st.ms_filter;
   // what a replayed step on this table may take for granted (key-only records through the look-up chain, k <= 64)
-  e->rp_have = e->rp_want && e->presorted == 3 && e->W <= 2 && e->rw == e->W;
-  if (e->rp_have)
-    { e->rp_nreq = e->st.nemitted; e->rp_nbig = e->st.nbig; e->rp_nf_req = e->st.nrequests; e->rp_bm_bits = e->bm_bits;
-      e->rp_seen_chunks = e->n_chunks; e->rp_nranks = 0;
+  e->rp.have = e->set.rp_want && e->run.presorted == PRESORT_CHAIN && e->tab.W <= 2 && e->run.rw == e->tab.W;
+  if (e->rp.have)
+    { e->rp.nreq = e->st.nemitted; e->rp.nbig = e->st.nbig; e->rp.nf_req = e->st.nrequests; e->rp.bm_bits = e->run.bm_bits;
+      e->rp.seen_chunks = e->run.n_chunks; e->rp.nranks = 0;
     }
   return SMG_OK;
 }
 
 // squeeze the request chunks (ragged fills) into the dense array e->dense: exclusive scan of the fills + one copy
 static int compact_chunks(smg_engine *e, int64_t nreq, char *errbuf, size_t errlen)
-{ HIPCHK(e->dense.reserve(nreq * (int64_t) sizeof(u64) * e->rw));
-  HIPCHK(e->chunk_off.reserve((int64_t) e->n_chunks * 4 + 4));
+{ HIPCHK(e->dense.reserve(nreq * (int64_t) sizeof(u64) * e->run.rw));
+  HIPCHK(e->chunk_off.reserve((int64_t) e->run.n_chunks * 4 + 4));
   HIPCHK(with_scratch(e->sort_tmp, [&](void *tmp, size_t &bytes)
-    { return rocprim::exclusive_scan(tmp, bytes, (uint32_t *) e->chunk_fill, (uint32_t *) e->chunk_off, 0u, (size_t) e->n_chunks,
+    { return rocprim::exclusive_scan(tmp, bytes, (uint32_t *) e->chunk_fill, (uint32_t *) e->chunk_off, 0u, (size_t) e->run.n_chunks,
                                      rocprim::plus<uint32_t>(), e->stream); }));
-  hipLaunchKernelGGL(kf_compact, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->chunk_off, e->rw, e->dense);
+  hipLaunchKernelGGL(kf_compact, dim3(e->run.n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill, e->chunk_off, e->run.rw, e->dense);
   return SMG_OK;
 }
 
@@ -903,10 +972,10 @@ static int compact_chunks(smg_engine *e, int64_t nreq, char *errbuf, size_t errl
 static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_count, int64_t *missing,
                       char *errbuf, size_t errlen)
 { int rc = SMG_OK;
-  if (!flat && e->lg.nb && e->bm_bits && !e->filtered)
+  if (!flat && e->run.lg.nb && e->run.bm_bits && !e->run.filtered)
     { // own requests, own map: partition, then filter and look-ups in one kernel (no survivor list, no sort)
-      if (e->n_chunks == 0 || e->st.nrequests == 0) { if (missing) *missing = 0; return SMG_OK; }
-      if (!e->presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
+      if (e->run.n_chunks == 0 || e->st.nrequests == 0) { if (missing) *missing = 0; return SMG_OK; }
+      if (!e->run.presorted && (rc = filter_presort(e, errbuf, errlen))) return rc;
       hipEventRecord(e->ev[EV_PROBE_BEG], e->stream);
       if ((rc = lookup_probe(e, e->bmap, false, 0u, errbuf, errlen))) return rc;
       hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
@@ -914,23 +983,23 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
       e->st.ms_filter = ms_between(e, EV_LOOKUP_BEG, EV_PROBE_BEG);       // scan + partition
       e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
       e->st.nrequests = (int64_t) e->h_ctrl->fast.nf_req;
-      e->filtered = true;
-      e->n_chunks = 0;                                            // nothing left to route or to look up
+      e->run.filtered = true;
+      e->run.n_chunks = 0;                                            // nothing left to route or to look up
       if (missing) *missing = e->h_ctrl->fast.missing;
       return SMG_OK;
     }
-  if (!flat && e->bm_bits && !e->filtered && (rc = fast_filter(e, NULL, errbuf, errlen))) return rc;
+  if (!flat && e->run.bm_bits && !e->run.filtered && (rc = fast_filter(e, NULL, errbuf, errlen))) return rc;
   hipEventRecord(e->ev[EV_LOOKUP_BEG], e->stream);
-  const bool keys_only = e->W == 1 && e->rw == 1;
+  const bool keys_only = e->tab.W == 1 && e->run.rw == 1;
   const int64_t nreq = e->st.nrequests;
   if (flat)
     { if (nflat > 0) rc = keys_only ? apply_sorted(e, flat, nflat, 0, errbuf, errlen) : apply_indexed(e, flat, nflat, check_count, errbuf, errlen); }
-  else if (nreq > 0 && e->n_chunks > 0)
-    { const int64_t nslots = (int64_t) e->n_chunks * F_CH;
-      if (keys_only && nslots <= nreq + nreq / 8 && nslots >= SORT_MIN && e->kmer < 32)
+  else if (nreq > 0 && e->run.n_chunks > 0)
+    { const int64_t nslots = (int64_t) e->run.n_chunks * F_CH;
+      if (keys_only && nslots <= nreq + nreq / 8 && nslots >= SORT_MIN && e->tab.kmer < 32)
         { // nearly every chunk is full (pass 1 and the filter split their batches): sort the chunk array as it is,
           // holes as sentinels behind the requests, instead of compacting it first
-          hipLaunchKernelGGL(kf_fill_holes, dim3(e->n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
+          hipLaunchKernelGGL(kf_fill_holes, dim3(e->run.n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
           rc = apply_sorted(e, e->req, nslots, 1, errbuf, errlen);
         }
       else
@@ -944,7 +1013,7 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
   hipEventRecord(e->ev[EV_LOOKUP_END], e->stream);
   HIPCHK(hipGetLastError());
   if (!missing && flat)                   // (sharded run: the count of missing complements stays on the device -- smg_engine_proof)
-    { e->lookup_pending = true; return SMG_OK; }
+    { e->run.lookup_pending = true; return SMG_OK; }
   rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
   e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
@@ -956,32 +1025,32 @@ static int fast_pass2(smg_engine *e, int64_t *d_plot, bool with_sum, char *errbu
 { HIPCHK(hipMemsetAsync(d_plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS, e->stream));
   FastArgs a = make_fast(e);
   hipEventRecord(e->ev[EV_PASS2_BEG], e->stream);
-  if (e->n > 0)
-    { int64_t nb = (e->n + P2_TPB - 1) / P2_TPB;
+  if (e->tab.n > 0)
+    { int64_t nb = (e->tab.n + P2_TPB - 1) / P2_TPB;
       if (nb > P2_GRID) nb = P2_GRID;
       { const char *v = test_hook("SMG_P2_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= P2_GRID && atoi(v) < nb) nb = atoi(v); }
-      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2<w()>, dim3((unsigned) nb), dim3(P2_TPB), 0, e->stream, a, (u64 *) d_plot); });
+      with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_pass2<w()>, dim3((unsigned) nb), dim3(P2_TPB), 0, e->stream, a, (u64 *) d_plot); });
       // entries whose unique partner is out of the code's reach: from the list of deferred entries that pass 1 of one-
       // and two-word k-mers leaves, else (three words: the generic pass 1) from a scan of the code bytes
-      if (e->far_listed && e->W <= 2)
+      if (e->run.far_listed && e->tab.W <= 2)
         { const unsigned nl = (unsigned) e->st.nbig;
           unsigned fb = (nl + 255) / 256;
           if (fb > 4096) fb = 4096;
           if (nl)
-            with_words<2>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_far<w()>, dim3(fb), dim3(256), 0, e->stream, a, (const uint32_t *) e->biglist,
+            with_words<2>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_far<w()>, dim3(fb), dim3(256), 0, e->stream, a, (const uint32_t *) e->biglist,
                 (const uint32_t *) e->farp, nl, (u64 *) d_plot); });
         }
       else
-        { int64_t fb = ((e->n + 15) / 16 + 255) / 256;
+        { int64_t fb = ((e->tab.n + 15) / 16 + 255) / 256;
           if (fb > 4096) fb = 4096;
-          with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_farscan<w()>, dim3((unsigned) fb), dim3(256), 0, e->stream, a, (u64 *) d_plot); });
+          with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_pass2_farscan<w()>, dim3((unsigned) fb), dim3(256), 0, e->stream, a, (u64 *) d_plot); });
         }
     }
   hipEventRecord(e->ev[EV_PASS2_END], e->stream);
   HIPCHK(hipGetLastError());
   int rc = SMG_OK;
-  e->st.path = 1;
-  if (!with_sum)                         // (phase API: no host wait here; smg_engine_stats reads the events once they have fired)
+  e->st.path = 1; e->run.completed = true;
+  if (!with_sum)                        // (phase API: no host wait here; smg_engine_stats reads the events once they have fired)
     { e->st.npairs = 0; e->st.ms_pass2 = -1.0; return SMG_OK; }
   rc = plot_sum(e, d_plot, errbuf, errlen);                         // (one more kernel and a host round trip)
   if (rc) return rc;
@@ -997,27 +1066,24 @@ static int fast_pass2(smg_engine *e, int64_t *d_plot, bool with_sum, char *errbu
 static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, char *errbuf, size_t errlen)
 { int rc;
   HIPCHK(hipSetDevice(e->device));
+  begin_run(e, RUN_FAST);
   HIPCHK(hipMemsetAsync(e->ctrl, 0, sizeof(Ctrl), e->stream));
   set_geo(e);
-  e->fast = true; e->counted_done = false; e->general_done = false; e->lookup_pending = false;
-  HIPCHK(e->deg.reserve(((e->n + 15) & ~15ll) + 32));
-  if (e->n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_codes, (size_t) e->n, hipMemcpyDeviceToDevice, e->stream));
-  e->rw = e->W + ((with_meta || e->W > 2) ? 1 : 0);
-  e->use_sig = false; e->bm_bits = 0; e->bm2 = 0; e->lg.nb = 0; e->one_way = 0;
-  e->filtered = false; e->presorted = 0; e->n_chunks = 0; e->far_listed = false;
+  HIPCHK(e->deg.reserve(((e->tab.n + 15) & ~15ll) + 32));
+  if (e->tab.n > 0) HIPCHK(hipMemcpyAsync(e->deg, d_codes, (size_t) e->tab.n, hipMemcpyDeviceToDevice, e->stream));
+  e->run.rw = e->tab.W + ((with_meta || e->tab.W > 2) ? 1 : 0);
   e->st.nrequests = 0; e->st.ms_rclookup = 0;
-  memset(e->fp, 0, sizeof(e->fp));
   if ((rc = dir_geometry(e, 8, errbuf, errlen, true))) return rc;
-  if (!e->dir_preset)
-    { HIPCHK(hipMemsetAsync(e->bstart, e->n > 0 ? 0xFF : 0, sizeof(uint32_t) * ((size_t) e->dir.nb + 2), e->stream));
-      if (e->n > 0)
+  if (!e->run.dir_preset)
+    { HIPCHK(hipMemsetAsync(e->bstart, e->tab.n > 0 ? 0xFF : 0, sizeof(uint32_t) * ((size_t) e->run.dir.nb + 2), e->stream));
+      if (e->tab.n > 0)
         { Tab t = make_tab(e);
-          const unsigned nblk = (unsigned) ((e->n + 1 + TPB - 1) / TPB);
-          with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_directory<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl); });
+          const unsigned nblk = (unsigned) ((e->tab.n + 1 + TPB - 1) / TPB);
+          with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_directory<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, e->bstart, e->ctrl); });
           HIPCHK(hipGetLastError());
         }
     }
-  e->prepared = true;
+  e->run.pass1_done = true;
   return SMG_OK;
 }
 
@@ -1027,54 +1093,52 @@ static int fast_resume(smg_engine *e, const uint8_t *d_codes, int with_meta, cha
 
 #define NEED_FAST(e)                                                                          \
   if (!(e)) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");                          \
-  if ((e)->kmer > FAST_MAX_K)                                                                 \
+  if ((e)->tab.kmer > FAST_MAX_K)                                                                \
     return fail(errbuf, errlen, SMG_EINVAL, "no block map and no request filter above k = 85%s");
 #define NEED_ENGINE(e)  if (!(e)) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
 
 extern "C" int smg_engine_pass1(smg_engine *e, int symcheck, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
   HIPCHK(hipSetDevice(e->device));
-  e->st.ms_rclookup = 0; e->lookup_pending = false;
-  if (e->kmer > FAST_MAX_K) return counted_phase_pass1(e, symcheck, errbuf, errlen);
-  e->bm_cap = e->bm_want ? e->bm_want : 30;  // default: the maps of the shards are exchanged, 128 MB in total
-  e->rp_active = false;
-  if (e->rp_want && e->rp_have && symcheck == SMG_SYM_HASH && e->rp_sym == symcheck && e->n > 0
-      && e->rp_bm_bits == bm_id_bits(e->kmer, e->bm_cap))
+  e->st.ms_rclookup = 0;
+  if (e->tab.kmer > FAST_MAX_K) return counted_phase_pass1(e, symcheck, errbuf, errlen);
+  e->set.bm_cap = e->set.bm_want ? e->set.bm_want : 30;  // default: the maps of the shards are exchanged, 128 MB in total
+  e->rp.active = false;
+  if (e->set.rp_want && e->rp.have && symcheck == SMG_SYM_HASH && e->rp.sym == symcheck && e->tab.n > 0
+      && e->rp.bm_bits == bm_id_bits(e->tab.kmer, e->set.bm_cap))
     { // the step before this one, on this very table, went through the look-up chain: queue this one from its counts
       const int rc = fast_pass1(e, 0, 0, 1, errbuf, errlen, true);
       if (rc) return rc;
-      e->rp_active = true; e->rp_routed = false;
+      e->rp.active = true; e->rp.routed = false;
       return SMG_OK;
     }
-  e->rp_sym = symcheck;
+  e->rp.sym = symcheck;
   return fast_pass1(e, symcheck == SMG_SYM_EXACT, symcheck == SMG_SYM_EXACT, symcheck == SMG_SYM_HASH, errbuf, errlen);
 }
 
 extern "C" int smg_engine_set_replay(smg_engine *e, int on)
 { if (!e) return SMG_EINVAL;
-  e->rp_want = on != 0;
-  if (!on) e->rp_have = false;
+  e->set.rp_want = on != 0;
+  if (!on) e->rp.have = false;
   return SMG_OK;
 }
 
 // is the current step a replayed one (1), and did the LAST finished step leave a record (2)?
-extern "C" int smg_engine_replay_state(smg_engine *e) { return e ? (e->rp_active ? 1 : 0) | (e->rp_have ? 2 : 0) : 0; }
+extern "C" int smg_engine_replay_state(smg_engine *e) { return e ? (e->rp.active ? 1 : 0) | (e->rp.have ? 2 : 0) : 0; }
 
 // after the caller has read the proof words of a replayed step: ok != 0 = the device found every count as recorded (the
 // run stands: the engine's bookkeeping is brought up to date from the control words, which are complete by now),
 // ok == 0 = the record is dropped and the next step runs the plain way
 extern "C" int smg_engine_replay_done(smg_engine *e, int ok, char *errbuf, size_t errlen)
 { if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
-  if (!e->rp_active) return SMG_OK;
-  e->rp_active = false;
+  if (!e->rp.active) return SMG_OK;
+  e->rp.active = false;
   HIPCHK(hipSetDevice(e->device));
-  if (!ok) { e->rp_have = false; e->dbits_dirty = true; e->lookup_pending = false; return SMG_OK; }
+  if (!ok) { e->rp.have = false; e->dbits_dirty = true; e->run.lookup_pending = false; return SMG_OK; }
   int rc = read_ctrl(e, errbuf, errlen);
   if (rc) return rc;
   e->dbits_dirty = false;
-  memset(e->fp, 0, sizeof(e->fp));
-  for (unsigned b = 0; b < e->rp_grid; b++)
-    for (int q = 0; q < 4; q++) e->fp[q] ^= e->h_partials[b * 4 + q];
+  fold_fp(e, e->rp.grid);
   e->st.ms_pass1 = ms_between(e, EV_PASS1_BEG, EV_PASS1_END);
   e->st.ms_bigfix = ms_between(e, EV_DECODE_BEG, EV_PASS1_END);
   e->st.ms_filter = ms_between(e, EV_REPLAY_FILTER_BEG, EV_REPLAY_FILTER_END); e->st.ms_rclookup += e->st.ms_filter;
@@ -1082,14 +1146,14 @@ extern "C" int smg_engine_replay_done(smg_engine *e, int ok, char *errbuf, size_
 }
 
 extern "C" int64_t smg_engine_nreq(smg_engine *e) { return e ? e->st.nrequests : 0; }
-extern "C" int smg_engine_record_words(smg_engine *e) { return e ? e->rw : 0; }
+extern "C" int smg_engine_record_words(smg_engine *e) { return e ? e->run.rw : 0; }
 
 extern "C" int smg_engine_apply(smg_engine *e, const uint64_t *d_recv, int64_t nrecv,
                                 int64_t *missing, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "apply before pass1%s");
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "apply before pass1%s");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->fast) return counted_phase_apply(e, (const u64 *) d_recv, nrecv, missing, errbuf, errlen);
+  if (!ran_fast(e)) return counted_phase_apply(e, (const u64 *) d_recv, nrecv, missing, errbuf, errlen);
   return fast_apply(e, (const u64 *) d_recv, nrecv, 1, missing, errbuf, errlen);
 }
 
@@ -1136,66 +1200,66 @@ k_proof_tail(const u64 *__restrict__ src, int nslots, int slot, int replayed, u6
 }
 
 static int proof_words(smg_engine *e, u64 *d_dst, char *errbuf, size_t errlen)
-{ if (e->rp_active)
+{ if (e->rp.active)
     { ReplayExpect x;
-      x.nreq = (u64) e->rp_nreq; x.nf_req = (u64) e->rp_nf_req; x.nbig = (unsigned) e->rp_nbig; x.nf_chunks = e->rp_nf_chunks;
-      x.max_chunks = e->max_chunks; x.grid = e->rp_grid;
-      x.totals = e->rp_routed ? e->rp_totals : (const u64 *) NULL; x.nranks = e->rp_nranks;     // (not routed: nothing to vouch for the split)
+      x.nreq = (u64) e->rp.nreq; x.nf_req = (u64) e->rp.nf_req; x.nbig = (unsigned) e->rp.nbig; x.nf_chunks = e->rp.nf_chunks;
+      x.max_chunks = e->run.max_chunks; x.grid = e->rp.grid;
+      x.totals = e->rp.routed ? e->rp_totals : (const u64 *) NULL; x.nranks = e->rp.nranks;     // (not routed: nothing to vouch for the split)
       hipLaunchKernelGGL(k_proof_replay, dim3(1), dim3(64), 0, e->stream, (const Ctrl *) e->ctrl, (const u64 *) e->partials, x, d_dst);
     }
   else
     hipLaunchKernelGGL(k_proof_words, dim3(1), dim3(64), 0, e->stream,
-                       (const Ctrl *) e->ctrl, e->fast ? 1 : 0, e->fp[0] ^ e->fp[2], e->fp[1] ^ e->fp[3], d_dst);
+                       (const Ctrl *) e->ctrl, ran_fast(e) ? 1 : 0, e->run.fp[0] ^ e->run.fp[2], e->run.fp[1] ^ e->run.fp[3], d_dst);
   HIPCHK(hipGetLastError());
   return SMG_OK;
 }
 
 extern "C" int smg_engine_proof(smg_engine *e, uint64_t *d_dst, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared || !d_dst) return fail(errbuf, errlen, SMG_EINVAL, "proof before pass1%s");
+  if (!e->run.pass1_done || !d_dst) return fail(errbuf, errlen, SMG_EINVAL, "proof before pass1%s");
   HIPCHK(hipSetDevice(e->device));
   return proof_words(e, (u64 *) d_dst, errbuf, errlen);
 }
 
 extern "C" int smg_engine_proof_tail(smg_engine *e, uint64_t *d_tail, int nslots, int slot, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared || !d_tail || nslots < 1 || nslots > 16 || slot < 0 || slot >= nslots)
+  if (!e->run.pass1_done || !d_tail || nslots < 1 || nslots > 16 || slot < 0 || slot >= nslots)
     return fail(errbuf, errlen, SMG_EINVAL, "proof_tail: 1..16 slots, after pass1%s");
   HIPCHK(hipSetDevice(e->device));
   u64 *tmp = e->partials + (size_t) 4 * P1_MAXGRID;           // (the row behind the workgroups' partial sums)
   int rc = proof_words(e, tmp, errbuf, errlen);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_proof_tail, dim3(1), dim3(64), 0, e->stream, (const u64 *) tmp, nslots, slot, e->rp_active ? 1 : 0, (u64 *) d_tail);
+  hipLaunchKernelGGL(k_proof_tail, dim3(1), dim3(64), 0, e->stream, (const u64 *) tmp, nslots, slot, e->rp.active ? 1 : 0, (u64 *) d_tail);
   HIPCHK(hipGetLastError());
   return SMG_OK;
 }
 
 extern "C" int smg_engine_apply_own(smg_engine *e, int64_t *missing, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "apply before pass1%s");
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "apply before pass1%s");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->fast) return counted_phase_apply(e, e->req, e->st.nrequests, missing, errbuf, errlen);
+  if (!ran_fast(e)) return counted_phase_apply(e, e->req, e->st.nrequests, missing, errbuf, errlen);
   return fast_apply(e, NULL, 0, 1, missing, errbuf, errlen);
 }
 
 extern "C" int smg_engine_set_blockmap_bits(smg_engine *e, int id_bits)
 { if (!e || (id_bits != 0 && (id_bits < 8 || id_bits > 32))) return SMG_EINVAL;
-  e->bm_want = id_bits;
+  e->set.bm_want = id_bits;
   return SMG_OK;
 }
 
 extern "C" int smg_engine_blockmap(smg_engine *e, int *id_bits, int64_t *nwords)
 { if (!e || !id_bits || !nwords) return SMG_EINVAL;
-  *id_bits = e->prepared ? e->bm_bits : 0;
-  *nwords = *id_bits ? bm_words(*id_bits, e->bm2) : 0;
+  *id_bits = e->run.pass1_done ? e->run.bm_bits : 0;
+  *nwords = *id_bits ? bm_words(*id_bits, e->run.bm2) : 0;
   return SMG_OK;
 }
 
 extern "C" int smg_engine_blockmap_copy(smg_engine *e, int64_t word_lo, int64_t nw, uint32_t *d_dst,
                                         char *errbuf, size_t errlen)
 { NEED_FAST(e)
-  if (!e->prepared || !e->bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
-  const int64_t nwords = bm_words(e->bm_bits, e->bm2);
+  if (!e->run.pass1_done || !e->run.bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
+  const int64_t nwords = bm_words(e->run.bm_bits, e->run.bm2);
   if (word_lo < 0 || nw < 0 || word_lo + nw > nwords || (nw > 0 && !d_dst))
     return fail(errbuf, errlen, SMG_EINVAL, "block map range out of bounds%s");
   HIPCHK(hipSetDevice(e->device));
@@ -1224,10 +1288,10 @@ extern "C" int smg_engine_merge_maps(smg_engine *e, const uint32_t *d_parts, int
                                      const int64_t *word_lo, const int64_t *nwords_of, uint32_t *d_full,
                                      char *errbuf, size_t errlen)
 { NEED_FAST(e)
-  if (!e->prepared || !e->bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
+  if (!e->run.pass1_done || !e->run.bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map: pass 1 (hash proof, k <= 85) has not run%s");
   if (!d_parts || !d_full || !word_lo || !nwords_of || nranks < 1 || nranks > 16 || width < 1)
     return fail(errbuf, errlen, SMG_EINVAL, "bad merge_maps arguments (1..16 ranks)%s");
-  const int64_t nwords = bm_words(e->bm_bits, e->bm2);
+  const int64_t nwords = bm_words(e->run.bm_bits, e->run.bm2);
   MapGeo geo;
   for (int r = 0; r < 16; r++) { geo.lo[r] = r < nranks ? word_lo[r] : 0; geo.ln[r] = r < nranks ? nwords_of[r] : 0; }
   for (int r = 0; r < nranks; r++)
@@ -1241,26 +1305,26 @@ extern "C" int smg_engine_merge_maps(smg_engine *e, const uint32_t *d_parts, int
 
 extern "C" int smg_engine_presort(smg_engine *e, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "presort before pass1%s");
-  if (!e->fast || !filter_ok(e) || !e->bm_bits || e->filtered || e->presorted || e->n_chunks == 0) return SMG_OK;
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "presort before pass1%s");
+  if (!ran_fast(e) || !filter_ok(e) || !e->run.bm_bits || e->run.filtered || e->run.presorted || e->run.n_chunks == 0) return SMG_OK;
   HIPCHK(hipSetDevice(e->device));
   return filter_presort(e, errbuf, errlen);
 }
 
 extern "C" int smg_engine_filter(smg_engine *e, const uint32_t *d_map, int64_t *kept, char *errbuf, size_t errlen)
 { NEED_FAST(e)
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "filter before pass1%s");
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "filter before pass1%s");
   if (!filter_ok(e)) return fail(errbuf, errlen, SMG_EINVAL, "the request filter covers the hash proof at k <= 85%s");
-  if (!d_map && !e->bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map to filter with%s");
+  if (!d_map && !e->run.bm_bits) return fail(errbuf, errlen, SMG_EINVAL, "no block map to filter with%s");
   HIPCHK(hipSetDevice(e->device));
-  int rc = e->filtered ? SMG_OK : fast_filter(e, d_map, errbuf, errlen);
+  int rc = e->run.filtered ? SMG_OK : fast_filter(e, d_map, errbuf, errlen);
   if (kept) *kept = e->st.nrequests;
   return rc;
 }
 
 extern "C" int smg_engine_symhash(smg_engine *e, uint64_t out[4], char *errbuf, size_t errlen)
 { if (!e || !out) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  for (int i = 0; i < 4; i++) out[i] = e->fp[i];
+  for (int i = 0; i < 4; i++) out[i] = e->run.fp[i];
   return SMG_OK;
 }
 
@@ -1275,16 +1339,16 @@ static int route_records(smg_engine *e, const u64 *req, const uint32_t *chunk_fi
       return SMG_OK;
     }
   if (nranks > 1)
-    HIPCHK(hipMemcpyAsync(e->d_split, splitters, sizeof(u64) * (nranks - 1) * e->W,
+    HIPCHK(hipMemcpyAsync(e->d_split, splitters, sizeof(u64) * (nranks - 1) * e->tab.W,
                           hipMemcpyHostToDevice, e->stream));
   HIPCHK(e->route_cnt.reserve((int64_t) nc * nranks * 4));
   HIPCHK(e->route_off.reserve(((int64_t) nc * nranks + 16) * 8));
   u64 *totals = e->route_off + (size_t) nc * nranks;           // [nranks], behind the offsets
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_route_count<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_route_count<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
       chunk_fill, rw, e->d_split, nranks, e->route_cnt); });
   // offsets and scatter follow on the device; the host only learns the totals (what the exchange needs): ONE round trip
   hipLaunchKernelGGL(kf_route_offsets, dim3(nranks), dim3(1024), 0, e->stream, (const uint32_t *) e->route_cnt, nc, nranks, e->route_off, totals);
-  with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_route_scatter<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
+  with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_route_scatter<w()>, dim3(nc), dim3(F_TPB), 0, e->stream, req,
       chunk_fill, rw, e->d_split, nranks, (const u64 *) e->route_off, (const u64 *) totals, (u64 *) d_send,
       (u64) (capacity < 0 ? 0 : capacity)); });
   HIPCHK(hipGetLastError());
@@ -1305,11 +1369,11 @@ extern "C" int smg_engine_route(smg_engine *e, const uint64_t *splitters, int nr
 { NEED_ENGINE(e)
   if (!counts || nranks < 1 || nranks > 16)
     return fail(errbuf, errlen, SMG_EINVAL, "bad route arguments (1..16 ranks)%s");
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
-  if (e->one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
+  if (e->run.one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
   HIPCHK(hipSetDevice(e->device));
   if (e->st.nrequests > capacity) return fail(errbuf, errlen, SMG_EINVAL, "send buffer too small%s");
-  return route_records(e, e->req, e->chunk_fill, e->n_chunks, e->rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
+  return route_records(e, e->req, e->chunk_fill, e->run.n_chunks, e->run.rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
 }
 
 extern "C" int smg_engine_route_device(smg_engine *e, const uint64_t *splitters, int nranks, uint64_t *d_send, int64_t capacity,
@@ -1317,36 +1381,36 @@ extern "C" int smg_engine_route_device(smg_engine *e, const uint64_t *splitters,
 { NEED_ENGINE(e)
   if (!d_counts || nranks < 1 || nranks > 16)
     return fail(errbuf, errlen, SMG_EINVAL, "bad route arguments (1..16 ranks)%s");
-  if (!e->prepared) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
-  if (e->one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
+  if (!e->run.pass1_done) return fail(errbuf, errlen, SMG_EINVAL, "route before pass1%s");
+  if (e->run.one_way) return fail(errbuf, errlen, SMG_EINVAL, "one-way requests cannot be routed: their senders are local to this engine%s");
   HIPCHK(hipSetDevice(e->device));
   if (e->st.nrequests > capacity) return fail(errbuf, errlen, SMG_EINVAL, "send buffer too small%s");
-  int rc = route_records(e, e->req, e->chunk_fill, e->n_chunks, e->rw, splitters, nranks, d_send, capacity, NULL, errbuf, errlen, d_counts);
-  if (rc || !e->rp_want || !e->fast) return rc;
+  int rc = route_records(e, e->req, e->chunk_fill, e->run.n_chunks, e->run.rw, splitters, nranks, d_send, capacity, NULL, errbuf, errlen, d_counts);
+  if (rc || !e->set.rp_want || !ran_fast(e)) return rc;
   // replay: the per-destination totals of a plain step are kept, those of a replayed step are put beside them -- the verdict
   // kernel (smg_engine_proof) compares the two: the caller splits its exchange by the RECORDED totals
   if (!e->rp_totals) HIPCHK(e->rp_totals.alloc(sizeof(u64) * 32));
-  const bool rep = e->rp_active;
-  if (rep && e->rp_nranks != nranks) { e->rp_routed = false; return SMG_OK; }
+  const bool rep = e->rp.active;
+  if (rep && e->rp.nranks != nranks) { e->rp.routed = false; return SMG_OK; }
   HIPCHK(hipMemcpyAsync(e->rp_totals + (rep ? 16 : 0), d_counts, sizeof(u64) * nranks, hipMemcpyDeviceToDevice, e->stream));
-  if (rep) e->rp_routed = true; else e->rp_nranks = nranks;
+  if (rep) e->rp.routed = true; else e->rp.nranks = nranks;
   return SMG_OK;
 }
 
 extern "C" int smg_engine_pass2(smg_engine *e, int64_t *d_plot, char *errbuf, size_t errlen)
 { NEED_ENGINE(e)
-  if (!e->prepared || !d_plot) return fail(errbuf, errlen, SMG_EINVAL, "pass2 before pass1%s");
+  if (!e->run.pass1_done || !d_plot) return fail(errbuf, errlen, SMG_EINVAL, "pass2 before pass1%s");
   HIPCHK(hipSetDevice(e->device));
-  if (!e->fast) return counted_phase_pass2(e, d_plot, errbuf, errlen);
+  if (!ran_fast(e)) return counted_phase_pass2(e, d_plot, errbuf, errlen);
   return fast_pass2(e, d_plot, false, errbuf, errlen);
 }
 
 extern "C" int smg_engine_stats(smg_engine *e, smg_stats *stats)
 { if (!e || !stats) return SMG_EINVAL;
-  if (e->lookup_pending)                 // look-ups of received requests were queued without a wait
+  if (e->run.lookup_pending)                 // look-ups of received requests were queued without a wait
     { hipSetDevice(e->device);
       if (hipEventSynchronize(e->ev[EV_LOOKUP_END]) == hipSuccess) e->st.ms_rclookup += ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
-      e->lookup_pending = false;
+      e->run.lookup_pending = false;
     }
   if (e->st.ms_pass2 < 0)                // pass 2 of the phase API was queued without a wait
     { hipSetDevice(e->device);
@@ -1364,12 +1428,12 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
   hipEventRecord(e->ev[EV_RUN_BEG], e->stream);
   e->st.ms_pass1 = e->st.ms_rclookup = e->st.ms_pass2 = 0;
   bool symmetric = false;
-  if (symcheck != SMG_SYM_NONE && e->kmer <= FAST_MAX_K)
+  if (symcheck != SMG_SYM_NONE && e->tab.kmer <= FAST_MAX_K)
     { // hash : requests from the entries that own a hi-side pair; closure proven by the fingerprint
       // exact: EVERY entry sends (rc(kmer), count) and the look-up compares the count -- the same records the
       //        sharded protocol exchanges, index-sorted look-ups (kf_apply_indexed)
       const int exact = symcheck == SMG_SYM_EXACT;
-      e->bm_cap = 32;
+      e->set.bm_cap = 32;
       // (Rounds 3-5 queued a re-run on the same table from the counts of the run before -- "run_speculative", one host wait
       //  instead of four.  Measured twice without a gain, 17.94 against 17.7-18.0 ms per step, profiles/r05_lookup_experiments.txt:
       //  taken out in round 6.  The one mechanism of that kind left is the replayed step of the phase API, for sharded runs.)
@@ -1379,7 +1443,7 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
       if ((rc = fast_apply(e, NULL, 0, exact, &missing, errbuf, errlen))) return rc;
       symmetric = (missing == 0);
       if (symmetric && symcheck == SMG_SYM_HASH)
-        symmetric = e->fp[0] == e->fp[2] && e->fp[1] == e->fp[3];
+        symmetric = e->run.fp[0] == e->run.fp[2] && e->run.fp[1] == e->run.fp[3];
       if (symmetric && (rc = fast_pass2(e, d_plot, true, errbuf, errlen))) return rc;
     }
   else if (symcheck != SMG_SYM_NONE)
@@ -1400,32 +1464,32 @@ extern "C" int smg_engine_run(smg_engine *e, int symcheck, int64_t *d_plot, smg_
 static int engine_extract(smg_engine *e, const uint16_t *d_labels, uint64_t *d_out, int64_t capacity, int64_t *nrec,
                           const TabSet *d_set, char *errbuf, size_t errlen)
 { if (!e || !d_labels || !nrec) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  const bool general = e->general_done && !e->fast && e->st.path == 2;        // the table failed the proof: all positions
-  const bool counted = e->counted_done && !e->fast && e->st.path == 1;        // k > 85: degrees instead of code bytes
-  if (!general && !counted && (!e->prepared || !e->fast || e->st.path != 1))
+  const bool general = ran_general(e);        // the table failed the proof: all positions
+  const bool counted = ran_counted(e);        // k > 85: degrees instead of code bytes
+  if (!e->run.completed)
     return fail(errbuf, errlen, SMG_EINVAL, "extract needs a completed run on the engine's current table%s");
   HIPCHK(hipSetDevice(e->device));
   u64 *d_total = &e->ctrl->plot_sum;
   HIPCHK(hipMemsetAsync(d_total, 0, sizeof(u64), e->stream));
   hipEventRecord(e->ev[EV_EXTRACT_BEG], e->stream);
-  if (e->n > 0 && general)
+  if (e->tab.n > 0 && general)
     { Tab t = make_tab(e);
-      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_extract_general<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
+      const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_extract_general<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
           (u64) (d_out ? capacity : 0), d_total, d_set); });
     }
-  else if (e->n > 0 && counted)
+  else if (e->tab.n > 0 && counted)
     { Tab t = make_tab(e);
-      const unsigned nblk = (unsigned) ((e->n + TPB - 1) / TPB);
-      with_words<4>(e->W, [&](auto w) { hipLaunchKernelGGL(k_extract<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
+      const unsigned nblk = (unsigned) ((e->tab.n + TPB - 1) / TPB);
+      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(k_extract<w()>, dim3(nblk), dim3(TPB), 0, e->stream, t, d_labels, (u64 *) d_out,
           (u64) (d_out ? capacity : 0), d_total); });
     }
-  else if (e->n > 0)
+  else if (e->tab.n > 0)
     { FastArgs a = make_fast(e);
-      int64_t nb = (e->n + F_TPB - 1) / F_TPB;
+      int64_t nb = (e->tab.n + F_TPB - 1) / F_TPB;
       if (nb > EX_GRID) nb = EX_GRID;
       { const char *v = test_hook("SMG_EXTRACT_GRID"); if (v && atoi(v) >= 1 && atoi(v) <= EX_GRID && atoi(v) < nb) nb = atoi(v); }
-      with_words<3>(e->W, [&](auto w) { hipLaunchKernelGGL(kf_extract<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, d_labels,
+      with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_extract<w()>, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, a, d_labels,
           (u64 *) d_out, (u64) (d_out ? capacity : 0), d_total); });
     }
   hipEventRecord(e->ev[EV_EXTRACT_END], e->stream);
@@ -1459,18 +1523,18 @@ extern "C" void smg_engine_pass1_limits(int32_t out[4])
 
 extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])
 { if (!e || !out) return SMG_EINVAL;
-  const bool chain = e->prepared && e->fast && e->lg.nb > 0;
-  out[0] = e->prepared ? e->bm_bits : 0; out[1] = chain ? e->lg.nb : 0; out[2] = e->bm2; out[3] = e->one_way; out[4] = e->rw;
-  out[5] = chain ? e->p1grid : 0; out[6] = chain ? e->nown : 0;
+  const bool chain = has_chain(e);
+  out[0] = e->run.pass1_done ? e->run.bm_bits : 0; out[1] = chain ? e->run.lg.nb : 0; out[2] = e->run.bm2; out[3] = e->run.one_way; out[4] = e->run.rw;
+  out[5] = chain ? e->run.p1grid : 0; out[6] = chain ? e->run.nown : 0;
   out[7] = chain ? (int64_t) e->h_ctrl->fast.n_chunks : 0;       // (pass 1's counter: the filter counts in nf_chunks)
-  out[8] = e->probe_form; out[9] = e->probe_part;
+  out[8] = e->run.probe_form; out[9] = e->run.probe_part;
   return SMG_OK;
 }
 
 extern "C" int smg_engine_pass1_form(smg_engine *e, int32_t out[4])
 { if (!e || !out) return SMG_EINVAL;
-  const bool ran = e->prepared && e->fast;
-  out[0] = ran ? e->p1_var : 0; out[1] = ran ? e->p1_w : 0; out[2] = ran ? e->p1_rw : 0;
+  const bool ran = ran_fast(e);
+  out[0] = ran ? e->run.p1_var : 0; out[1] = ran ? e->run.p1_w : 0; out[2] = ran ? e->run.p1_rw : 0;
   out[3] = 0;                                // (no launch is an INNER-only grid)
   return SMG_OK;
 }
@@ -1624,7 +1688,7 @@ static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *p
       // path 2 counts and writes every pair once)
       int64_t want = 0, got = 0;
       for (int c = 0; c < SMG_PLOT_CELLS; c++) if (labels[c]) want += plot[c];
-      const int rw = e->W + 1;
+      const int rw = e->tab.W + 1;
       if (hipMalloc(&d_labels, sizeof(uint16_t) * SMG_PLOT_CELLS) != hipSuccess
           || hipMalloc(&d_out, sizeof(uint64_t) * (size_t) (want > 0 ? want : 1) * rw) != hipSuccess)
         BAIL(SMG_ENOMEM, "out of device memory for the pair list")
@@ -1793,14 +1857,14 @@ extern "C" int smg_condition_table(const smg_table_view *tv, const smg_opts *opt
       && (rc = smg_engine_condition(e, opts->ethresh, opts->condition & SMG_COND_TRIM, opts->condition & SMG_COND_SYMM,
                                     NULL, errbuf, errlen)))
     goto done;
-  { const int64_t n = e->n;
-    hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (n > 0 ? n : 1) * e->W);
+  { const int64_t n = e->tab.n;
+    hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (n > 0 ? n : 1) * e->tab.W);
     hc = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (n > 0 ? n : 1));
     if (!hk || !hc) BAIL(SMG_ENOMEM, "out of host memory for the conditioned table")
-    if (n > 0 && (hipMemcpy(hk, e->keys, sizeof(uint64_t) * (size_t) n * e->W, hipMemcpyDeviceToHost) != hipSuccess
-                  || hipMemcpy(hc, e->cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess))
+    if (n > 0 && (hipMemcpy(hk, e->tab.keys, sizeof(uint64_t) * (size_t) n * e->tab.W, hipMemcpyDeviceToHost) != hipSuccess
+                  || hipMemcpy(hc, e->tab.cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess))
       BAIL(SMG_ENODEV, "device to host copy failed")
-    *keys_out = hk; *counts_out = hc; *nels_out = n; *words_out = e->W;
+    *keys_out = hk; *counts_out = hc; *nels_out = n; *words_out = e->tab.W;
     hk = NULL; hc = NULL;
   }
 done:

@@ -121,7 +121,7 @@ static int multi_filter(MultiCtx *c, int r, smg_engine *e, const u64 *splitters,
 { const int n = c->n, bits = c->bm_bits[r];
   for (int s = 0; s < n; s++) if (c->bm_bits[s] != bits) return SMG_OK;       // (cannot happen: a function of k and the proof)
   if (!bits) return SMG_OK;
-  const int two = e->bm2;                            // 64-bit map words (two-bit map): twice the 32-bit words per id range
+  const int two = e->run.bm2;                            // 64-bit map words (two-bit map): twice the 32-bit words per id range
   const int64_t nwords = bm_words(bits, two);
   int64_t wlo[SMG_MAXGPU], wlen[SMG_MAXGPU], width = 1;
   for (int s = 0; s < n; s++)
@@ -253,7 +253,7 @@ static void *multi_worker(void *argp)
       for (int s = 1; s < n; s++) memcpy(splitters + (size_t) (s - 1) * W, c->first[s], sizeof(u64) * W);
       // S3: two records per entry (itself, its complement), grouped by destination
       const int rw = W + 1;
-      const int64_t n2 = MOK ? 2 * e->n : 0;
+      const int64_t n2 = MOK ? 2 * e->tab.n : 0;
       if (MOK && hipMalloc(&c->send[r], sizeof(uint64_t) * (size_t) (n2 > 0 ? n2 : 1) * rw) != hipSuccess)
         MFAIL(SMG_ENOMEM, "out of device memory while symmetrising");
       if (MOK && (c->rc[r] = smg_engine_symm_route(e, (const uint64_t *) splitters, n, c->send[r], n2, c->counts[r], eb, el))) c->failed = 1;
@@ -274,13 +274,13 @@ static void *multi_worker(void *argp)
           if (c->virt) pthread_mutex_unlock(&c->big_mu);
         }
       if (recv) { hipFree(recv); recv = NULL; }
-      if (MOK) c->nshard[r] = e->n;
+      if (MOK) c->nshard[r] = e->tab.n;
       pthread_barrier_wait(&c->bar);                                                     // A: shards ready (splitters = first[])
     }
   else
     { if (MOK)
-        { c->nshard[r] = e->n;
-          if (e->n > 0 && hipMemcpy(c->first[r], e->keys, sizeof(u64) * W, hipMemcpyDeviceToHost) != hipSuccess)
+        { c->nshard[r] = e->tab.n;
+          if (e->tab.n > 0 && hipMemcpy(c->first[r], e->tab.keys, sizeof(u64) * W, hipMemcpyDeviceToHost) != hipSuccess)
             MFAIL(SMG_ENODEV, "device to host copy failed");
         }
       pthread_barrier_wait(&c->bar);                                                     // A: shards + first k-mers
@@ -298,7 +298,7 @@ static void *multi_worker(void *argp)
       if ((c->rc[r] = smg_engine_pass1(e, c->symcheck, eb, el))) c->failed = 1;
     }
   c->bmap[r] = NULL; c->bm_bits[r] = 0;
-  if (MOK && e->bm_bits) { c->bmap[r] = e->bmap; c->bm_bits[r] = e->bm_bits; hipStreamSynchronize(e->stream); }
+  if (MOK && e->run.bm_bits) { c->bmap[r] = e->bmap; c->bm_bits[r] = e->run.bm_bits; hipStreamSynchronize(e->stream); }
   pthread_barrier_wait(&c->bar);                                                         // A3: block maps complete
   if (MOK && (c->rc[r] = multi_filter(c, r, e, splitters, eb, el))) c->failed = 1;
   if (MOK)
@@ -492,10 +492,10 @@ static int host_condition_sequential(const smg_table_source *tv, const smg_opts 
   };
   auto take = [&](int d) -> int            // the engine's table -> shard d on the host
   { HostShard &h = out[(size_t) d];
-    h.n = e->n;
-    h.keys.resize((size_t) (e->n > 0 ? e->n : 0) * W); h.cnt.resize((size_t) (e->n > 0 ? e->n : 0));
-    if (e->n > 0 && (hipMemcpy(h.keys.data(), e->keys, sizeof(u64) * (size_t) e->n * W, hipMemcpyDeviceToHost) != hipSuccess
-                     || hipMemcpy(h.cnt.data(), e->cnt, sizeof(uint16_t) * (size_t) e->n, hipMemcpyDeviceToHost) != hipSuccess))
+    h.n = e->tab.n;
+    h.keys.resize((size_t) (e->tab.n > 0 ? e->tab.n : 0) * W); h.cnt.resize((size_t) (e->tab.n > 0 ? e->tab.n : 0));
+    if (e->tab.n > 0 && (hipMemcpy(h.keys.data(), e->tab.keys, sizeof(u64) * (size_t) e->tab.n * W, hipMemcpyDeviceToHost) != hipSuccess
+                     || hipMemcpy(h.cnt.data(), e->tab.cnt, sizeof(uint16_t) * (size_t) e->tab.n, hipMemcpyDeviceToHost) != hipSuccess))
       return fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s");
     return SMG_OK;
   };
@@ -533,7 +533,7 @@ static int host_condition_sequential(const smg_table_source *tv, const smg_opts 
   std::vector<int64_t> counts((size_t) n);
   for (int s = 0; s < n && rc == SMG_OK; s++)                                  // sweep 2
     { if ((rc = load(s))) break;
-      const int64_t n2 = 2 * e->n;
+      const int64_t n2 = 2 * e->tab.n;
       uint64_t *send = NULL;
       if (hipMalloc(&send, sizeof(uint64_t) * (size_t) (n2 > 0 ? n2 : 1) * rw) != hipSuccess)
         return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory while symmetrising%s");
@@ -600,7 +600,7 @@ static int host_run_sequential(const smg_table_source *tv, const smg_opts *opts,
   }
   smg_engine *e = smg_engine_create(opts->device, NULL, errbuf, errlen);
   if (!e) return SMG_ENODEV;
-  e->no_filter = true;                    // (k <= 85: no candidate map out of core -- the filter would need the maps of the shards not read yet)
+  e->set.no_filter = true;                    // (k <= 85: no candidate map out of core -- the filter would need the maps of the shards not read yet)
   // extract leg (round 5): the two members of a pair share a window block, hence a shard -- every shard lists the pairs behind
   // the labelled pixels while it is resident for its second round; the lists are only handed out if the whole table proves closed
   std::vector<uint64_t> xrec;
@@ -639,7 +639,7 @@ static int host_run_sequential(const smg_table_source *tv, const smg_opts *opts,
           }
         if (hipStreamSynchronize(e->stream) != hipSuccess) SBAIL(SMG_ENODEV, "decode failed")
         if (round == 1)
-          { e->bm_want = 32;
+          { e->set.bm_want = 32;
             if ((rc = smg_engine_pass1(e, symcheck, errbuf, errlen))) break;
             rw = smg_engine_record_words(e);
             nreq[sh] = smg_engine_nreq(e);
@@ -648,7 +648,7 @@ static int host_run_sequential(const smg_table_source *tv, const smg_opts *opts,
               SBAIL(SMG_ENOMEM, "out of device memory for what a shard leaves behind (1 byte per entry and its requests)")
             if ((rc = smg_engine_route(e, (const uint64_t *) splitters.data(), n, send[sh], nreq[sh], &counts[(size_t) sh * n], errbuf, errlen))) break;
             if (ns > 0 && hipMemcpy(codes[sh], e->deg, (size_t) ns, hipMemcpyDeviceToDevice) != hipSuccess) SBAIL(SMG_ENODEV, "device copy failed")
-            for (int q = 0; q < 4; q++) fp[q] ^= e->fp[q];
+            for (int q = 0; q < 4; q++) fp[q] ^= e->run.fp[q];
             ms_p1 += e->st.ms_pass1; nels += ns; nemit += e->st.nemitted;
           }
         else

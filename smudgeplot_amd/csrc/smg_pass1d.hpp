@@ -203,6 +203,10 @@ struct P1Hot                              // kernel argument: what every tile to
   SMG_DEV bool two() const { return (shifts >> 24 & 1u) != 0; }         // two-bit block map (BM2_* in smg_fast.hpp)
   SMG_DEV bool ow() const { return (shifts >> 25 & 1u) != 0; }          // one-way requests (smg_fast.hpp; odd k, key-only records):
                                                                         //   read by the general form only, the hot forms have it compiled in
+  static unsigned pack(int dsh, int sigsh, int bmsh, bool emit_all, bool want_fp, int hbits, bool two, bool ow)      // (host: what the accessors take apart)
+  { return (unsigned) dsh | ((unsigned) sigsh << 6) | (((unsigned) bmsh & 31u) << 12) | ((emit_all ? 1u : 0u) << 18) | ((want_fp ? 1u : 0u) << 19)
+           | ((unsigned) hbits << 20) | ((two ? 1u : 0u) << 24) | ((ow ? 1u : 0u) << 25);
+  }
 };
 
 struct P1Cold                             // in device memory: what only a flush touches (kept out of the register file)

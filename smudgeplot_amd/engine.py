@@ -70,6 +70,7 @@ EXPORTS = [
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
     "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
+    "smg_engine_pass1_plan",
 ]
 
 _lib = None
@@ -134,6 +135,8 @@ def load_library():
     if hasattr(lib, "smg_engine_pass1_limits"):
         lib.smg_engine_pass1_limits.argtypes = [C.POINTER(C.c_int32)]
         lib.smg_engine_pass1_limits.restype = None
+    if hasattr(lib, "smg_engine_pass1_plan"):
+        lib.smg_engine_pass1_plan.argtypes = [i32, i64, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
@@ -259,6 +262,22 @@ def pass1_limits() -> dict:
     out = (C.c_int32 * 4)()
     load_library().smg_engine_pass1_limits(out)
     return dict(zip(PASS1_LIMITS, (int(v) for v in out)))
+
+
+PASS1_PLAN = ("rw", "one_way", "narrow", "dir_per", "dir_preset", "bm_bits", "bm2", "nb", "use_sig", "var", "kf", "w")
+
+
+def pass1_plan(k: int, nels: int, symcheck: str = "hash", own_lookups: bool = True, have_index: bool = True, bm_cap: int = 32,
+               no_filter: bool = False) -> dict:
+    """what pass 1 of the fast path would decide (smg_engine_pass1_plan; no engine, no device: the function the engine calls):
+    words per record, one-way requests, kf_pass1_d or the generic kernel, entries per directory bucket, the index as directory,
+    id bits of the candidate map, two-bit map, bucket bits of the look-up chain, signatures, the form (pass1_form's "var"),
+    KF, words per k-mer.  own_lookups: smg_engine_run (bm_cap 32); the phase API passes False (bm_cap 30 by default)."""
+    out = (C.c_int32 * 12)()
+    rc = load_library().smg_engine_pass1_plan(k, nels, _SYM[symcheck], int(own_lookups), int(have_index), bm_cap, int(no_filter), out)
+    if rc:
+        raise EngineError(rc, "pass1_plan")
+    return dict(zip(PASS1_PLAN, (int(v) for v in out)))
 
 
 def _table_view(table):
