@@ -128,7 +128,24 @@ int smg_hetmers_run(const smg_table_view *table, const smg_opts *opts, int64_t *
 int smg_hetmers_run_source(const smg_table_source *source, const smg_opts *opts, int64_t *plot,
                            smg_stats *stats, char *errbuf, size_t errlen);
 
-/* the same from a table that is ALREADY IN DEVICE MEMORY, decoded: what the k-mer counter's _device entries leave there
+/* Which path smg_hetmers_run / smg_hetmers_extract would take for a table of `nels` entries of k = kmer under `opts` (NULL:
+   the defaults): the function they themselves call, and the only reader of the environment that bears on the choice --
+   SMG_VIRTUAL_SHARDS=<n> (n shards on one device), SMG_SHARD_LIMIT=<entries> (the size from which a table is cut into
+   shards, 2^32 - 32 otherwise), SMG_SEQUENTIAL_SHARDS=<n> (out of core in n shards), SMG_HBM_LIMIT=<bytes> (stands in for
+   the free device memory) and SMG_FORCE_MULTI=1 (a one-rank RCCL group).  free_bytes: the free memory of the device;
+   <= 0 asks opts->device, and then only where the choice depends on it.  With free_bytes > 0 no device is touched.
+   out[0] SMG_MODE_*, out[1] the shards or GPUs that would run (1 in core), out[2] the prefix shards a table was cut into
+   because of its size alone (0: it was not).  SMG_EINVAL (more than 16 shards of 3e9 entries) and SMG_ENOMEM (does not fit
+   the device even shard by shard) with the messages of the run itself.                                              */
+#define SMG_MODE_CORE             0   /* one engine, the whole table on one device                                  */
+#define SMG_MODE_VIRTUAL          1   /* prefix shards that all live on one device, exchanging by device copies     */
+#define SMG_MODE_SEQUENTIAL       2   /* out of core: prefix shards one after the other, the table read twice       */
+#define SMG_MODE_MULTI            3   /* one prefix shard per GPU, exchanging through RCCL                          */
+#define SMG_MODE_ONE_RANK_FORCED  4   /* the RCCL path with one GPU (SMG_FORCE_MULTI)                               */
+int smg_hetmers_run_mode(int kmer, int64_t nels, const smg_opts *opts, double free_bytes, int32_t out[3],
+                         char *errbuf, size_t errlen);
+
+/* smg_hetmers_run from a table that is ALREADY IN DEVICE MEMORY, decoded: what the k-mer counter's _device entries leave there
    (smg_count.h), or any sorted, duplicate-free table in the layout of smg_engine_bind -- d_keys = nels * ceil(kmer / 32)
    words, 16-byte aligned; d_counts = nels uint16, 8-byte aligned.  The table is borrowed and not changed.  opts->condition:
    SMG_COND_TRIM keeps the entries with count >= opts->ethresh; SMG_COND_SYMM closes the table under reverse complement,

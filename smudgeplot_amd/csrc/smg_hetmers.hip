@@ -758,13 +758,12 @@ static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int ho
         { return rocprim::radix_sort_keys<smg_sort_config>(tmp, bytes, (u64 *) keys_in, (u64 *) e->req2, (size_t) nsort, lobit, 64u, e->stream); }));
       src = e->req2;
       if (test_hook("SMG_VERIFY_SORT"))
-        { u64 *d_chk = NULL, h[4];
-          HIPCHK(hipMalloc(&d_chk, 32));
+        { DevBuf<u64> d_chk; u64 h[4];
+          HIPCHK(d_chk.alloc(32));
           HIPCHK(hipMemsetAsync(d_chk, 0, 32, e->stream));
           hipLaunchKernelGGL(kf_check_sorted, dim3((unsigned) nb), dim3(F_TPB), 0, e->stream, keys_in, e->req2, nsort, (int) lobit, d_chk);
           HIPCHK(hipMemcpyAsync(h, d_chk, 32, hipMemcpyDeviceToHost, e->stream));
           HIPCHK(hipStreamSynchronize(e->stream));
-          hipFree(d_chk);
           if (h[0] || h[1] != h[2] || h[3])
             return fail(errbuf, errlen, SMG_ENODEV, "request sort self-check failed (rocPRIM radix sort)%s");
         }
@@ -1540,172 +1539,62 @@ extern "C" int smg_engine_pass1_form(smg_engine *e, int32_t out[4])
 }
 
 #include "smg_ingest.hpp"
+#include "smg_shards.hpp"
 #include "smg_multi.hpp"
 
 // ---- one-shot host entry ----------------------------------------------------------------------
 
-// labels == NULL: hetmers.  labels != NULL: additionally the extract leg; *records receives a malloc'ed
-// array of *nrec records of (words + 1) uint64 each.
-static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *plot, smg_stats *stats,
-                    const uint16_t *labels, uint64_t **records, int64_t *nrec, int *rec_words,
-                    char *errbuf, size_t errlen)
-{ if (!tv || !plot || !tv->read) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  struct timespec w0, w1, w2;
-  clock_gettime(CLOCK_MONOTONIC, &w0);       // (the first HIP call of the process -- the free-memory query below -- starts the runtime)
-  const int device = opts ? opts->device : 0;
-  const int symcheck = opts ? opts->symcheck : SMG_SYM_EXACT;
-  const int verbose = opts ? opts->verbose : 0;
-  if (tv->ibyte < 1 || tv->ibyte > 3) return fail(errbuf, errlen, SMG_EINVAL, "ibyte must be 1, 2 or 3%s");
-  const int kbyte = (tv->kmer + 3) >> 2, pbyte = kbyte + 2 - tv->ibyte;
-  if (pbyte < 3) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
-  int64_t sum = 0;
-  for (int p = 0; p < tv->nparts; p++) sum += tv->part_nels[p];
-  if (sum != tv->nels) return fail(errbuf, errlen, SMG_EFORMAT, "part sizes do not add up to nels%s");
-  { // several GPUs of the node (smg_multi.hpp); SMG_VIRTUAL_SHARDS is the 1-GPU test hook of that path
-    int ng = opts ? opts->ngpus : 0;
-    bool virt = false;
-    const char *v = getenv("SMG_VIRTUAL_SHARDS");
-    if (v && atoi(v) > 1) { ng = atoi(v); virt = true; }
-    // A shard addresses its entries with 32 bits.  A table beyond that is cut into prefix shards that all live on
-    // this one device (288 GB of HBM hold ~1.5e10 k=31 entries with their side arrays) -- the same code path as
-    // several GPUs, with device-to-device copies for the exchange: the reference streams a table of any size
-    // (PloidyPlot.c:931-1038), this engine must not refuse one just because of an index width.
-    // SMG_SHARD_LIMIT (tests) lowers the threshold.
-    { int64_t limit = 0xFFFFFFF0ll - 16;
-      const char *sl = getenv("SMG_SHARD_LIMIT");
-      if (sl && atoll(sl) > 0) limit = atoll(sl);
-      // (a table that still has to be symmetrised closes to at most twice its entries: shard it for that size)
-      const bool want_symm = opts && (opts->condition & SMG_COND_SYMM);
-      const int64_t closed = want_symm ? 2 * tv->nels : tv->nels;
-      if (ng <= 1 && closed >= limit)
-        { int64_t per = limit > 3000000000ll ? 3000000000ll : limit;     // ~3e9 entries per shard
-          if (per < 1) per = 1;
-          ng = (int) ((closed + per - 1) / per);
-          if (ng < 2) ng = 2;
-          if (ng > SMG_MAXGPU)
-            return fail(errbuf, errlen, SMG_EINVAL, "table too large for one GPU (more than 16 shards of 3e9 entries): use SMUDGEPLOT_GPUS%s");
-          virt = true;
-          if (verbose) fprintf(stderr, "  [smg] %lld entries%s: %d prefix shards on one device\n", (long long) tv->nels,
-                               want_symm ? " before the table is symmetrised" : "", ng);
-        }
-    }
-    // Out of core (smg_multi.hpp, host_run_sequential): a table whose shards do not fit the device TOGETHER -- keys, counts and
-    // the lists of a run take ~8 W + 12 bytes per entry -- is run shard after shard, the table read twice; what stays between
-    // the two rounds is a code byte per entry and the requests.  SMG_HBM_LIMIT=<bytes> (tests) stands in for the free device
-    // memory, SMG_SEQUENTIAL_SHARDS=<n> forces the mode.
-    if (ng <= 1 || virt)
-      { const int W = (tv->kmer + 31) / 32;
-        int seq = 0;
-        { const char *sv = getenv("SMG_SEQUENTIAL_SHARDS"); if (sv && atoi(sv) > 1) seq = atoi(sv); }
-        if (!seq)
-          { size_t fr = 0, tot = 0;
-            double limit = 0;
-            { const char *hl = getenv("SMG_HBM_LIMIT"); if (hl && atof(hl) > 0) limit = atof(hl); }
-            if (limit <= 0 && hipSetDevice(device) == hipSuccess && hipMemGetInfo(&fr, &tot) == hipSuccess) limit = 0.9 * (double) fr;
-            // what a run in core takes per entry: k-mers 8 W, count 2, code byte 1, deferred-entry map and lists 0.6, the request
-            // list (a quarter of the entries + slack) and its partitioned copy ~2.6 W -- and the candidate map (1 GiB at most)
-            // (a raw table: the size of the CLOSED table counts -- at most twice the entries -- and conditioning a shard takes
-            //  more than running it: its records (2 (W + 1) words per entry of the piece), the sort's copies and scratch)
-            const bool raw = opts && opts->condition, want_symm = opts && (opts->condition & SMG_COND_SYMM);
-            const double ne = (double) tv->nels * (want_symm ? 2.0 : 1.0);
-            const double per_run = 10.6 * W + 5.5, per_cond = raw ? (want_symm ? 24.0 * W + 30.0 : 8.0 * W + 12.0) : 0.0;
-            const double all = ne * (per_run > per_cond ? per_run : per_cond) + 1.1e9;
-            if (limit > 0 && all > limit)
-              { // what a shard leaves behind: its code bytes and its requests -- every entry's (W + 1 words) under the exact
-                // proof, those of the owners of a pair at p > k-1-p otherwise (17 % of a diploid table, 36 % of a polyploid one)
-                const bool exact = symcheck == SMG_SYM_EXACT;
-                const double keep = ne * (1.0 + (exact ? 8.0 * (W + 1) : 0.36 * 8.0 * (tv->kmer > FAST_MAX_K ? W + 1 : W)));     // (k > 85: records carry a count word)
-                for (int q = 2; q <= SMG_MAXGPU && !seq; q++)
-                  if (keep + ne / q * per_run <= limit && ne / q * per_cond <= limit && ne / q < 0xFFFFFFF0ll - 16) seq = q;     // (no map out of core)
-                if (!seq)
-                  return fail(errbuf, errlen, SMG_ENOMEM, "the table does not fit the device even shard by shard (16 shards, a code byte and "
-                              "the requests of every entry resident): use SMUDGEPLOT_GPUS%s");
-              }
-          }
-        if (seq)
-          { if (verbose) fprintf(stderr, "  [smg] %lld entries do not fit the device together: %d prefix shards one after the other\n",
-                                 (long long) tv->nels, seq);
-            smg_opts o; memset(&o, 0, sizeof(o));
-            if (opts) o = *opts; else o.symcheck = SMG_SYM_HASH;
-            return host_run_sequential(tv, &o, seq, plot, stats, errbuf, errlen, labels, records, nrec, rec_words);
-          }
-      }
-    // SMG_FORCE_MULTI=1 (tests): take the multi-GPU code path even with one GPU -- a one-rank RCCL
-    // communicator, send/recv to self, all-reduce: checks the dlopen'ed RCCL entry points on a 1-GPU box
-    if (ng <= 1 && getenv("SMG_FORCE_MULTI") && !v) ng = -1;
-    if (ng > 1 || ng == -1)
-      { { smg_opts o; memset(&o, 0, sizeof(o));
-            if (opts) o = *opts; else o.symcheck = SMG_SYM_HASH;
-            const int mrc = host_run_multi(tv, &o, ng == -1 ? 1 : ng, virt, plot, stats, errbuf, errlen, labels, records, nrec, rec_words);
-            // a table that fails the symmetry proof: shards on ONE device run the general path together (smg_multi.hpp,
-            // TabSet); several real GPUs hand the table to one of them, which can hold it as long as it has < 2^32 entries
-            if (mrc != SMG_ENOTSYM) return mrc;
-            if (tv->nels >= 0xFFFFFFF0ll - 16)
-              return fail(errbuf, errlen, SMG_ENOTSYM, "the table is not closed under reverse complement and has more than 2^32 entries: "
-                          "the general path for such a table runs on one device (unset SMUDGEPLOT_GPUS), or condition the table%s");
-            if (verbose) fprintf(stderr, "  [smg] the table is not closed under reverse complement: general path on one GPU\n");
-          }
-      }
-  }
+#define SECS(a, b) ((double) ((b).tv_sec - (a).tv_sec) + 1e-9 * (double) ((b).tv_nsec - (a).tv_nsec))
 
-  smg_engine *e = smg_engine_create(device, NULL, errbuf, errlen);
+// the table in core on one device: ingest, condition or take the index, run, and -- labels != NULL -- the extract leg.
+// w0: when the call began (the wall-time line of the verbose output).
+static int host_run_core(const smg_table_source *tv, const smg_opts *opts, int64_t *plot, smg_stats *stats, const uint16_t *labels,
+                         uint64_t **records, int64_t *nrec, int *rec_words, const struct timespec &w0, char *errbuf, size_t errlen)
+{ const int device = opts ? opts->device : 0;
+  const int symcheck = opts ? opts->symcheck : SMG_SYM_EXACT;
+  const int pbyte = ((tv->kmer + 3) >> 2) + 2 - tv->ibyte;
+  struct timespec w1, w2;
+  EngineOwner eng;                           // (in front of the buffers: destroyed after them)
+  smg_engine *e = eng.create(device, errbuf, errlen);
   if (!e) return SMG_ENODEV;
   clock_gettime(CLOCK_MONOTONIC, &w1);       // (the first HIP call of the process: runtime start-up + code object load)
   int rc = SMG_OK;
-  int64_t *d_index = NULL, *d_plot = NULL;
-  uint16_t *d_labels = NULL; uint64_t *d_out = NULL;
+  DevBuf<int64_t> d_index, d_plot;
   const size_t ixbytes = sizeof(int64_t) << (8 * tv->ibyte);
   double h2d_s = 0, alloc_s = 0, cond_s = 0, run_s = 0, out_s = 0;
-#define BAIL(code, msg) { rc = fail(errbuf, errlen, code, msg "%s"); goto done; }
-#define SECS(a, b) ((double) ((b).tv_sec - (a).tv_sec) + 1e-9 * (double) ((b).tv_nsec - (a).tv_nsec))
-  if (hipMalloc(&d_index, ixbytes) != hipSuccess || hipMalloc(&d_plot, sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess)
-    BAIL(SMG_ENOMEM, "out of device memory for the table")
-  if ((rc = decode_begin(e, tv->kmer, tv->ibyte, tv->nels, errbuf, errlen))) goto done;
-  { // the index goes first (asynchronously from pageable memory: staged by the runtime); the records stream behind it,
-    // piece by piece through a pinned ring, and every piece is decoded on the device as soon as its copy has landed
-    if (hipMemcpyAsync(d_index, tv->prefix_index, ixbytes, hipMemcpyHostToDevice, e->stream) != hipSuccess
-        || hipEventRecord(e->ev[EV_DECODE_BEG], e->stream) != hipSuccess)
-      BAIL(SMG_ENODEV, "host to device copy failed")
-    clock_gettime(CLOCK_MONOTONIC, &w2);
-    alloc_s = SECS(w1, w2);
-    DecodeHook hk; hk.e = e; hk.d_index = d_index; hk.ibyte = tv->ibyte; hk.ibase = 0;
-    if ((rc = ingest_records(tv, pbyte, 0, tv->nels, NULL, device, tv->host_threads, &h2d_s, errbuf, errlen, decode_hook, &hk, e->ev[EV_DECODE_BEG]))) goto done;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) BAIL(SMG_ENODEV, "host to device copy failed")
-  }
+  if (d_index.alloc(ixbytes) != hipSuccess || d_plot.alloc(sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess)
+    return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the table%s");
+  // the index goes first (asynchronously from pageable memory: staged by the runtime); the records stream behind it,
+  // piece by piece through a pinned ring, and every piece is decoded on the device as soon as its copy has landed
+  if (hipMemcpyAsync(d_index, tv->prefix_index, ixbytes, hipMemcpyHostToDevice, e->stream) != hipSuccess
+      || hipEventRecord(e->ev[EV_DECODE_BEG], e->stream) != hipSuccess)
+    return fail(errbuf, errlen, SMG_ENODEV, "host to device copy failed%s");
+  if ((rc = ingest_range(e, tv, 0, tv->nels, d_index, device, tv->host_threads, &h2d_s, e->ev[EV_DECODE_BEG], errbuf, errlen))) return rc;
+  clock_gettime(CLOCK_MONOTONIC, &w2);
+  alloc_s = SECS(w1, w2) - h2d_s;            // (the engine's table is allocated inside ingest_range, in front of the first copy)
+  if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(errbuf, errlen, SMG_ENODEV, "host to device copy failed%s");
   clock_gettime(CLOCK_MONOTONIC, &w1);
   if (opts && opts->condition)
-    { if ((rc = smg_engine_condition(e, opts->ethresh, opts->condition & SMG_COND_TRIM, opts->condition & SMG_COND_SYMM,
-                                     NULL, errbuf, errlen))) goto done;
-    }
-  else if ((rc = smg_engine_set_prefix_index(e, d_index, tv->ibyte, 0, errbuf, errlen))) goto done;   // the table's index = its directory
+    rc = smg_engine_condition(e, opts->ethresh, opts->condition & SMG_COND_TRIM, opts->condition & SMG_COND_SYMM, NULL, errbuf, errlen);
+  else rc = smg_engine_set_prefix_index(e, d_index, tv->ibyte, 0, errbuf, errlen);   // the table's index = its directory
+  if (rc) return rc;
   clock_gettime(CLOCK_MONOTONIC, &w2); cond_s = SECS(w1, w2);
-  if ((rc = smg_engine_run(e, symcheck, d_plot, NULL, errbuf, errlen))) goto done;
+  if ((rc = smg_engine_run(e, symcheck, d_plot, NULL, errbuf, errlen))) return rc;
   clock_gettime(CLOCK_MONOTONIC, &w1); run_s = SECS(w2, w1);
   if (hipMemcpy(plot, d_plot, sizeof(int64_t) * SMG_PLOT_CELLS, hipMemcpyDeviceToHost) != hipSuccess)
-    BAIL(SMG_ENODEV, "device to host copy failed")
+    return fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s");
   if (labels)
-    { // exact record count = plot weight on the labelled pixels (path 1 counts a mirrored pair twice and writes it twice,
-      // path 2 counts and writes every pair once)
-      int64_t want = 0, got = 0;
-      for (int c = 0; c < SMG_PLOT_CELLS; c++) if (labels[c]) want += plot[c];
-      const int rw = e->tab.W + 1;
-      if (hipMalloc(&d_labels, sizeof(uint16_t) * SMG_PLOT_CELLS) != hipSuccess
-          || hipMalloc(&d_out, sizeof(uint64_t) * (size_t) (want > 0 ? want : 1) * rw) != hipSuccess)
-        BAIL(SMG_ENOMEM, "out of device memory for the pair list")
-      if (hipMemcpy(d_labels, labels, sizeof(uint16_t) * SMG_PLOT_CELLS, hipMemcpyHostToDevice) != hipSuccess)
-        BAIL(SMG_ENODEV, "host to device copy failed")
-      if ((rc = smg_engine_extract(e, d_labels, d_out, want, &got, errbuf, errlen))) goto done;
-      if (got != want) BAIL(SMG_ENODEV, "internal error: pair list and plot disagree")
-      uint64_t *h = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (want > 0 ? want : 1) * rw);
-      if (!h) BAIL(SMG_ENOMEM, "out of host memory for the pair list")
-      if (want && hipMemcpy(h, d_out, sizeof(uint64_t) * (size_t) want * rw, hipMemcpyDeviceToHost) != hipSuccess)
-        { free(h); BAIL(SMG_ENODEV, "device to host copy failed") }
-      *records = h; *nrec = want; *rec_words = rw;
+    { // one launch: the number of records is known, it is the plot's weight on the labelled pixels
+      DevBuf<uint16_t> d_labels;
+      std::vector<uint64_t> rec;
+      if ((rc = upload_labels(labels, d_labels, errbuf, errlen))) return rc;
+      if ((rc = extract_to_host(e, d_labels, NULL, pair_weight(labels, plot), rec, errbuf, errlen))) return rc;
+      if ((rc = records_to_caller(rec, e->tab.W + 1, labels, plot, records, nrec, rec_words, errbuf, errlen))) return rc;
     }
   clock_gettime(CLOCK_MONOTONIC, &w2); out_s = SECS(w1, w2);
   e->st.ms_h2d = h2d_s * 1e3;
   if (stats) *stats = e->st;
-  if (verbose)
+  if (opts && opts->verbose)
     { fprintf(stderr, "  [smg] n=%lld k=%d path=%s  read+h2d+decode %.2f ms (%.1f GB/s, %d readers; the decode of a piece runs behind its copy), "
               "pass1 %.2f, rc-lookup %.2f, pass2 %.2f, total(device) %.2f ms => %.3g k-mers/s\n",
               (long long) e->st.nels, tv->kmer, e->st.path == 1 ? "rc-half-scan" : "general",
@@ -1720,16 +1609,51 @@ static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *p
               SECS(w0, w2) * 1e3, (SECS(w0, w2) - alloc_s - h2d_s - cond_s - run_s - out_s) * 1e3, alloc_s * 1e3, h2d_s * 1e3,
               cond_s * 1e3, run_s * 1e3, out_s * 1e3);
     }
-done:
-#undef BAIL
-#undef SECS
-  if (d_index) hipFree(d_index);
-  if (d_plot) hipFree(d_plot);
-  if (d_labels) hipFree(d_labels);
-  if (d_out) hipFree(d_out);
-  smg_engine_destroy(e);
-  return rc;
+  return SMG_OK;
 }
+
+// ---- one-shot host entry ----------------------------------------------------------------------
+// validate, plan (run_mode_plan, smg_shards.hpp), dispatch to the shard drivers (smg_multi.hpp) -- or run in core.
+// labels == NULL: hetmers.  labels != NULL: additionally the extract leg; *records receives a malloc'ed
+// array of *nrec records of (words + 1) uint64 each.
+static int host_run(const smg_table_source *tv, const smg_opts *opts, int64_t *plot, smg_stats *stats,
+                    const uint16_t *labels, uint64_t **records, int64_t *nrec, int *rec_words,
+                    char *errbuf, size_t errlen)
+{ if (!tv || !plot || !tv->read) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
+  struct timespec w0;
+  clock_gettime(CLOCK_MONOTONIC, &w0);       // (the first HIP call of the process -- the plan's free-memory query -- starts the runtime)
+  const int verbose = opts ? opts->verbose : 0;
+  if (tv->ibyte < 1 || tv->ibyte > 3) return fail(errbuf, errlen, SMG_EINVAL, "ibyte must be 1, 2 or 3%s");
+  if (((tv->kmer + 3) >> 2) + 2 - tv->ibyte < 3) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
+  int64_t sum = 0;
+  for (int p = 0; p < tv->nparts; p++) sum += tv->part_nels[p];
+  if (sum != tv->nels) return fail(errbuf, errlen, SMG_EFORMAT, "part sizes do not add up to nels%s");
+  RunMode m;
+  int rc = run_mode_plan(tv->kmer, tv->nels, opts ? opts->ngpus : 0, opts ? opts->condition : 0, opts ? opts->symcheck : SMG_SYM_EXACT,
+                         opts ? opts->device : 0, 0, &m, errbuf, errlen);
+  if (verbose && m.cut_by_limit)
+    fprintf(stderr, "  [smg] %lld entries%s: %d prefix shards on one device\n", (long long) tv->nels,
+            opts && (opts->condition & SMG_COND_SYMM) ? " before the table is symmetrised" : "", m.cut_by_limit);
+  if (rc) return rc;
+  if (m.mode == SMG_MODE_CORE) return host_run_core(tv, opts, plot, stats, labels, records, nrec, rec_words, w0, errbuf, errlen);
+  smg_opts o; memset(&o, 0, sizeof(o));
+  if (opts) o = *opts; else o.symcheck = SMG_SYM_HASH;
+  if (m.mode == SMG_MODE_SEQUENTIAL)
+    { if (verbose) fprintf(stderr, "  [smg] %lld entries do not fit the device together: %d prefix shards one after the other\n",
+                           (long long) tv->nels, m.count);
+      return host_run_sequential(tv, &o, m.count, plot, stats, errbuf, errlen, labels, records, nrec, rec_words);
+    }
+  rc = host_run_multi(tv, &o, m.count, m.mode == SMG_MODE_VIRTUAL, plot, stats, errbuf, errlen, labels, records, nrec, rec_words);
+  // a table that fails the symmetry proof: shards on ONE device run the general path together (smg_multi.hpp,
+  // TabSet); several real GPUs hand the table to one of them, which can hold it as long as it has < 2^32 entries
+  if (rc != SMG_ENOTSYM) return rc;
+  if (tv->nels >= SMG_ONE_SHARD_MAX)
+    return fail(errbuf, errlen, SMG_ENOTSYM, "the table is not closed under reverse complement and has more than 2^32 entries: "
+                "the general path for such a table runs on one device (unset SMUDGEPLOT_GPUS), or condition the table%s");
+  if (verbose) fprintf(stderr, "  [smg] the table is not closed under reverse complement: general path on one GPU\n");
+  return host_run_core(tv, opts, plot, stats, labels, records, nrec, rec_words, w0, errbuf, errlen);
+}
+#undef SECS
 
 extern "C" int smg_hetmers_run(const smg_table_view *tv, const smg_opts *opts, int64_t *plot,
                                smg_stats *stats, char *errbuf, size_t errlen)
@@ -1763,21 +1687,13 @@ extern "C" int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_
   if (kmer < 1 || kmer > SMG_MAX_KMER) return fail(errbuf, errlen, SMG_EINVAL, "k-mer length out of range (1..128)%s");
   if (nels < 0) return fail(errbuf, errlen, SMG_EINVAL, "negative number of entries%s");
   { // in core or not at all: the closed table next to the lists of a run, or next to the buffers of its own closure
-    // (host_run's prices per entry); the table handed in is in device memory already and not part of what is free
+    // (core_bytes); the table handed in is in device memory already and not part of what is free
     const int W = (kmer + 31) / 32;
-    const double ne = (double) nels * ((cond & SMG_COND_SYMM) ? 2.0 : 1.0);
-    if (ne >= (double) (0xFFFFFFF0ll - 16))
+    if ((double) nels * ((cond & SMG_COND_SYMM) ? 2.0 : 1.0) >= (double) SMG_ONE_SHARD_MAX)
       return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 - 32 entries in the closed table: one engine does not address them%s", two_step);
-    size_t fr = 0, tot = 0;
-    double limit = 0;
-    { const char *hl = getenv("SMG_HBM_LIMIT"); if (hl && atof(hl) > 0) limit = atof(hl); }
-    if (limit <= 0)
-      { if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&fr, &tot) != hipSuccess)
-          return fail(errbuf, errlen, SMG_ENODEV, "no usable HIP device%s");
-        limit = 0.9 * (double) fr;
-      }
-    const double per_run = 10.6 * W + 5.5, per_cond = cond ? ((cond & SMG_COND_SYMM) ? 24.0 * W + 30.0 : 8.0 * W + 12.0) : 0.0;
-    const double need = ne * (per_run > per_cond ? per_run : per_cond) + 1.1e9 - (cond ? 0.0 : (double) nels * (8.0 * W + 2.0));
+    const double limit = memory_limit(device, 0);
+    if (limit <= 0) return fail(errbuf, errlen, SMG_ENODEV, "no usable HIP device%s");
+    const double need = core_bytes(W, nels, cond) - (cond ? 0.0 : (double) nels * (8.0 * W + 2.0));
     if (need > limit)
       { char msg[256];
         snprintf(msg, sizeof(msg), "the table does not fit the device in core: %lld entries need %.3f GB, %.3f GB are free",
@@ -1786,32 +1702,29 @@ extern "C" int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_
         return SMG_ENOMEM;
       }
   }
-  smg_engine *e = smg_engine_create(device, NULL, errbuf, errlen);
+  EngineOwner eng;                           // (in front of the buffer: destroyed after it)
+  smg_engine *e = eng.create(device, errbuf, errlen);
   if (!e) return SMG_ENODEV;
   int rc = SMG_OK;
-  int64_t *d_plot = NULL;
-  if (hipMalloc(&d_plot, sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess)
-    { rc = fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the plot%s"); goto done; }
-  if ((rc = smg_engine_bind(e, kmer, nels, d_keys, d_counts, errbuf, errlen))) goto done;
-  if ((cond & SMG_COND_TRIM) && (rc = smg_engine_condition(e, opts->ethresh, 1, 0, NULL, errbuf, errlen))) goto done;
+  DevBuf<int64_t> d_plot;
+  if (d_plot.alloc(sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess) return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the plot%s");
+  if ((rc = smg_engine_bind(e, kmer, nels, d_keys, d_counts, errbuf, errlen))) return rc;
+  if ((cond & SMG_COND_TRIM) && (rc = smg_engine_condition(e, opts->ethresh, 1, 0, NULL, errbuf, errlen))) return rc;
   if (cond & SMG_COND_SYMM)
     { bool generic = !RUN_DEVICE_CLOSE_BY_MERGE;
       if (!generic) rc = close_canonical(e, NULL, &generic, errbuf, errlen);     // (not canonical: left as it was, the generic closure takes it)
       if (generic) rc = smg_engine_condition(e, 0, 0, 1, NULL, errbuf, errlen);
-      if (rc) goto done;
+      if (rc) return rc;
     }
-  if ((rc = smg_engine_run(e, symcheck, d_plot, NULL, errbuf, errlen))) goto done;
+  if ((rc = smg_engine_run(e, symcheck, d_plot, NULL, errbuf, errlen))) return rc;
   if (hipMemcpy(plot, d_plot, sizeof(int64_t) * SMG_PLOT_CELLS, hipMemcpyDeviceToHost) != hipSuccess)
-    { rc = fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s"); goto done; }
+    return fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s");
   if (stats) *stats = e->st;
   if (opts && opts->verbose)
     fprintf(stderr, "  [smg] n=%lld k=%d path=%s  conditioning %.2f ms, pass1 %.2f, rc-lookup %.2f, pass2 %.2f, total(device) %.2f ms\n",
             (long long) e->st.nels, kmer, e->st.path == 1 ? "rc-half-scan" : "general", e->st.ms_decode, e->st.ms_pass1,
             e->st.ms_rclookup, e->st.ms_pass2, e->st.ms_total);
-done:
-  if (d_plot) hipFree(d_plot);
-  smg_engine_destroy(e);
-  return rc;
+  return SMG_OK;
 }
 
 extern "C" int smg_hetmers_extract(const smg_table_view *tv, const smg_opts *opts, const uint16_t *labels,
@@ -1835,44 +1748,30 @@ extern "C" int smg_condition_table(const smg_table_view *tv, const smg_opts *opt
     return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
   *keys_out = NULL; *counts_out = NULL; *nels_out = 0; *words_out = 0;
   if (tv->ibyte < 1 || tv->ibyte > 3) return fail(errbuf, errlen, SMG_EINVAL, "ibyte must be 1, 2 or 3%s");
-  const int kbyte = (tv->kmer + 3) >> 2, pbyte = kbyte + 2 - tv->ibyte;
-  if (pbyte < 3) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
-  smg_engine *e = smg_engine_create(opts->device, NULL, errbuf, errlen);
+  if (((tv->kmer + 3) >> 2) + 2 - tv->ibyte < 3) return fail(errbuf, errlen, SMG_EINVAL, "k-mer shorter than the index prefix%s");
+  EngineOwner eng;                           // (in front of the buffer: destroyed after it)
+  smg_engine *e = eng.create(opts->device, errbuf, errlen);
   if (!e) return SMG_ENODEV;
-  int rc = SMG_OK;
-  uint8_t *d_rec = NULL; int64_t *d_index = NULL;
-  uint64_t *hk = NULL; uint16_t *hc = NULL;
-  const size_t ixbytes = sizeof(int64_t) << (8 * tv->ibyte);
-#define BAIL(code, msg) { rc = fail(errbuf, errlen, code, msg "%s"); goto done; }
-  if (hipMalloc(&d_index, ixbytes) != hipSuccess) BAIL(SMG_ENOMEM, "out of device memory for the table")
-  if ((rc = decode_begin(e, tv->kmer, tv->ibyte, tv->nels, errbuf, errlen))) goto done;
-  { ViewCtx vc; smg_table_source src;
-    view_source(tv, &vc, &src);
-    if (hipMemcpy(d_index, tv->prefix_index, ixbytes, hipMemcpyHostToDevice) != hipSuccess)
-      BAIL(SMG_ENODEV, "host to device copy failed")
-    DecodeHook hk; hk.e = e; hk.d_index = d_index; hk.ibyte = tv->ibyte; hk.ibase = 0;
-    if ((rc = ingest_records(&src, pbyte, 0, tv->nels, NULL, opts->device, 4, NULL, errbuf, errlen, decode_hook, &hk))) goto done;
-  }
+  int rc;
+  DevBuf<int64_t> d_index;
+  ViewCtx vc; smg_table_source src;
+  view_source(tv, &vc, &src);
+  if ((rc = upload_index(&src, d_index, "the table", errbuf, errlen))) return rc;
+  if ((rc = ingest_range(e, &src, 0, tv->nels, d_index, opts->device, 4, NULL, NULL, errbuf, errlen))) return rc;
   if (opts->condition
       && (rc = smg_engine_condition(e, opts->ethresh, opts->condition & SMG_COND_TRIM, opts->condition & SMG_COND_SYMM,
                                     NULL, errbuf, errlen)))
-    goto done;
-  { const int64_t n = e->tab.n;
-    hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (n > 0 ? n : 1) * e->tab.W);
-    hc = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (n > 0 ? n : 1));
-    if (!hk || !hc) BAIL(SMG_ENOMEM, "out of host memory for the conditioned table")
-    if (n > 0 && (hipMemcpy(hk, e->tab.keys, sizeof(uint64_t) * (size_t) n * e->tab.W, hipMemcpyDeviceToHost) != hipSuccess
-                  || hipMemcpy(hc, e->tab.cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess))
-      BAIL(SMG_ENODEV, "device to host copy failed")
-    *keys_out = hk; *counts_out = hc; *nels_out = n; *words_out = e->tab.W;
-    hk = NULL; hc = NULL;
-  }
-done:
-#undef BAIL
-  free(hk); free(hc);
-  if (d_rec) hipFree(d_rec);
-  if (d_index) hipFree(d_index);
-  smg_engine_destroy(e);
-  return rc;
+    return rc;
+  // (the two arrays go to the caller, who releases them with smg_free: malloc)
+  const int64_t n = e->tab.n;
+  uint64_t *hk = (uint64_t *) malloc(sizeof(uint64_t) * (size_t) (n > 0 ? n : 1) * e->tab.W);
+  uint16_t *hc = (uint16_t *) malloc(sizeof(uint16_t) * (size_t) (n > 0 ? n : 1));
+  if (!hk || !hc) rc = fail(errbuf, errlen, SMG_ENOMEM, "out of host memory for the conditioned table%s");
+  else if (n > 0 && (hipMemcpy(hk, e->tab.keys, sizeof(uint64_t) * (size_t) n * e->tab.W, hipMemcpyDeviceToHost) != hipSuccess
+                     || hipMemcpy(hc, e->tab.cnt, sizeof(uint16_t) * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess))
+    rc = fail(errbuf, errlen, SMG_ENODEV, "device to host copy failed%s");
+  if (rc) { free(hk); free(hc); return rc; }
+  *keys_out = hk; *counts_out = hc; *nels_out = n; *words_out = e->tab.W;
+  return SMG_OK;
 }
 

@@ -70,7 +70,7 @@ EXPORTS = [
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
     "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
-    "smg_engine_pass1_plan",
+    "smg_engine_pass1_plan", "smg_hetmers_run_mode",
 ]
 
 _lib = None
@@ -137,6 +137,8 @@ def load_library():
         lib.smg_engine_pass1_limits.restype = None
     if hasattr(lib, "smg_engine_pass1_plan"):
         lib.smg_engine_pass1_plan.argtypes = [i32, i64, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
+    if hasattr(lib, "smg_hetmers_run_mode"):
+        lib.smg_hetmers_run_mode.argtypes = [i32, i64, C.POINTER(Opts), C.c_double, C.POINTER(C.c_int32), *err]
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
@@ -278,6 +280,21 @@ def pass1_plan(k: int, nels: int, symcheck: str = "hash", own_lookups: bool = Tr
     if rc:
         raise EngineError(rc, "pass1_plan")
     return dict(zip(PASS1_PLAN, (int(v) for v in out)))
+
+
+RUN_MODES = ("core", "virtual", "sequential", "multi", "one_rank_forced")
+
+
+def run_mode(k: int, nels: int, free_bytes: float, symcheck: str = "exact", condition: int = 0, ngpus: int = 0, device: int = 0) -> dict:
+    """which path hetmers_run / hetmers_extract would take (smg_hetmers_run_mode; the function they call, and with free_bytes > 0
+    no device): {"mode": one of RUN_MODES, "count": the shards or GPUs that would run, "cut_by_limit": the prefix shards the
+    table was cut into because of its size alone}.  Reads SMG_VIRTUAL_SHARDS, SMG_SHARD_LIMIT, SMG_SEQUENTIAL_SHARDS,
+    SMG_HBM_LIMIT and SMG_FORCE_MULTI; raises EngineError with the run's own code and message where the run would refuse."""
+    out = (C.c_int32 * 3)()
+    opts = Opts(device, _SYM[symcheck], 0, condition, 0, ngpus)
+    buf = C.create_string_buffer(512)
+    _check(load_library().smg_hetmers_run_mode(k, nels, C.byref(opts), float(free_bytes), out, buf, 512), buf)
+    return {"mode": RUN_MODES[out[0]], "count": int(out[1]), "cut_by_limit": int(out[2])}
 
 
 def _table_view(table):
