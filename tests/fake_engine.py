@@ -1,16 +1,18 @@
 """Numpy stand-in for `smudgeplot_amd.sharded.TorchEngine` -- TEST INFRASTRUCTURE ONLY.
 
-It implements the same phase protocol (bind / pass1 / blockmap / filter / route / apply / symhash / pass2, and the
-general-path fallback) on CPU tensors with brute-force numpy, so that the world_size>1 orchestration of
-`sharded.hetmers_sharded` (splitter exchange, block-map all_gather, all_to_all of the complement requests,
-symmetry proof + histogram all_reduce, gather for the fallback) can run under the `gloo` backend without a GPU.
+It implements the protocol of `sharded.ShardEngine` IN FULL -- the table (_bind, nels, run_general), a step (pass1, nreq,
+record_words, blockmap, blockmap_copy, presort, merge_maps, filter, route, apply, pass2, proof_tail, stats; run_single),
+replay (set_replay, replay_state, replay_done) and closing across shards (trim, symm_hist, symm_route, symm_finish); and
+proof_into, the four words that proof_tail lays out -- on CPU tensors with brute-force numpy, so that the
+orchestration of `sharded.hetmers_sharded` (splitter exchange, block-map all_gather, all_to_all of the complement requests,
+proof tail + histogram all_reduce, replay verdict, gather for the fallback) runs under `gloo` through the driver code of a GPU run.
 Any k <= 128: a k-mer is handled as a Python integer of 64 * W bits (left aligned, like the engine's W words).
 The product path never imports this module.
 """
 import numpy as np
 import torch
 
-from smudgeplot_amd import ktab
+from smudgeplot_amd import sharded
 
 SMAX, FMAX = 1000, 500
 PLOT_COLS = FMAX + 1
@@ -25,9 +27,16 @@ def _mix(z):
     return z ^ (z >> 31)
 
 
-class NumpyEngine:
+def _general_plot(k, kw, cnt):
+    """what one GPU does with a table that fails the proof: the oracle's all-positions count (kw: uint64[n, W], left aligned)"""
+    import brute
+    packed = np.ascontiguousarray(kw.astype(">u8")).view(np.uint8).reshape(len(kw), 8 * kw.shape[1])[:, : (k + 3) // 4]
+    return torch.from_numpy(brute.hetmers_plot(np.ascontiguousarray(packed), cnt, k).reshape(-1))
+
+
+class NumpyEngine(sharded.ShardEngine):
     def __init__(self, device):
-        self.device = device
+        super().__init__(device)
         self._rp_want, self._rp_rec, self._rp_active, self._rp_bad = False, None, False, 0
 
     # ---- replay of the phase calls (smg_engine_set_replay): the stand-in does all the work every time, but hands out the
@@ -68,12 +77,17 @@ class NumpyEngine:
             v >>= 2
         return r << (bits - 2 * k)
 
-    def bind(self, k, keys, counts):
+    def _bind(self, k, keys, counts):
         self.k = k
         self.W = (k + 31) // 32
         self.keys = self._ints(keys.cpu().numpy().view(np.uint64))
         self.cnt = counts.cpu().numpy().view(np.uint16).astype(np.int64)
         self.n = len(self.cnt)
+
+    def reload_table(self, keys, counts):
+        """the stand-in copies the table when it is bound, the engine reads it in place: copy again what changed IN PLACE under
+        a bound engine -- not a bind: engine and driver keep what they know of the table"""
+        self._bind(self.k, keys, counts)
 
     def record_words(self):
         return self.W + 1
@@ -239,6 +253,11 @@ class NumpyEngine:
         out = rec[order].reshape(-1)
         send[: len(out)] = torch.from_numpy(out.view(np.int64).copy())
         counts = [int((dest == r).sum()) for r in range(nranks)]
+        # the per-destination totals: the recorded step stores them, a replayed step compares (the engine's rp_totals)
+        if self._rp_active:
+            self._rp_bad |= int(counts != self._rp_rec.get("totals"))
+        elif self._rp_rec is not None:
+            self._rp_rec["totals"] = counts
         if counts_out is not None:
             counts_out.copy_(torch.tensor(counts, dtype=torch.int64))
             return None
@@ -263,15 +282,32 @@ class NumpyEngine:
         self.missing = self._apply(recv[: nrecv * (self.W + 1)].cpu().numpy().view(np.uint64))
         return self.missing if wait else None
 
+    def _proof(self):
+        """(missing, residue word 0, word 1, a replayed step found other counts than recorded)"""
+        return [self.missing, self.fp[0] ^ self.fp[2], self.fp[1] ^ self.fp[3], self._rp_bad]
+
     def proof_into(self, dst):
-        w = np.array([self.missing, self.fp[0] ^ self.fp[2], self.fp[1] ^ self.fp[3], self._rp_bad], dtype=np.uint64)
-        dst[:4] = torch.from_numpy(w.view(np.int64).copy())
+        dst[:4] = torch.from_numpy(np.array(self._proof(), dtype=np.uint64).view(np.int64))
 
-    def apply_own(self):
-        return self._apply(self.req)
+    def proof_tail(self, tail, nslots, slot):
+        """the layout of k_proof_tail: [missing] + the residue in THIS rank's two words of 2 nslots + [verdict, replayed]"""
+        p = self._proof()
+        w = np.zeros(3 + 2 * nslots, dtype=np.uint64)
+        w[0], w[1 + 2 * slot], w[2 + 2 * slot], w[-2], w[-1] = p[0], p[1], p[2], p[3], int(self._rp_active)
+        tail[: len(w)] = torch.from_numpy(w.view(np.int64))
 
-    def symhash(self):
-        return list(self.fp)
+    def run_single(self, plot, symcheck):
+        """smg_engine_run: pass 1, its own look-ups, the proof, pass 2 -- the general path on the same table when the proof fails"""
+        self.pass1(symcheck, exchange=False)
+        self.missing = self._apply(self.req)
+        p = self._proof()
+        ok = p[0] == 0 and (symcheck != "hash" or p[1] == p[2] == 0)
+        if ok:
+            self.pass2(plot)
+        else:
+            kw = np.array([self._words(x) for x in self.keys], dtype=np.uint64).reshape(-1, self.W)
+            plot.copy_(_general_plot(self.k, kw, self.cnt.astype(np.uint16)))
+        return {"nels": self.n, "path": 1 if ok else 2, "nemitted": self.nreq()}
 
     def pass2(self, plot):
         a, b = self.pa, self.pb
@@ -285,13 +321,9 @@ class NumpyEngine:
         plot.copy_(torch.from_numpy(out))
 
     def run_general(self, k, keys, counts, plot):
-        """what one GPU does with a table that fails the proof: the oracle's all-positions count"""
-        import brute
-        W = (k + 31) // 32
-        kw = keys.cpu().numpy().view(np.uint64).reshape(-1, W)
-        packed = np.ascontiguousarray(kw.astype(">u8")).view(np.uint8).reshape(len(kw), 8 * W)[:, : (k + 3) // 4]
-        cnt = counts.cpu().numpy().view(np.uint16)
-        plot.copy_(torch.from_numpy(brute.hetmers_plot(np.ascontiguousarray(packed), cnt, k).reshape(-1)))
+        self.state.table_changed()                # (as the engine: not on the shard any more)
+        kw = keys.cpu().numpy().view(np.uint64).reshape(-1, (k + 31) // 32)
+        plot.copy_(_general_plot(k, kw, counts.cpu().numpy().view(np.uint16)))
 
     def stats(self):
         return {"nels": self.n, "path": 1}

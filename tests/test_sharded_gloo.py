@@ -264,8 +264,7 @@ def _replay_worker(rank, world, port, k, keys, cnt, cuts, edits, q):
                 for e_, v in edit[1:]:
                     if lo <= e_ < hi:
                         tc[e_ - lo] = v
-                eng.bind(k, tk, tc)                       # (the stand-in copies the table at bind; the engine reads it in place)
-                eng._rp_want = True                       # ... and must keep its record, as an engine that was not re-bound would
+                eng.reload_table(tk, tc)                  # (the engine reads the table in place; the stand-in copied it at bind)
             plot, st = sharded.hetmers_sharded(k, tk, tc, symcheck="hash", engine_factory=NumpyEngine, eng=eng, prebound=True)
             out.append((st["path"], bool(st.get("replayed")), plot.numpy().copy()))
         q.put((rank, out))
