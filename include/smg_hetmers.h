@@ -205,6 +205,13 @@ int smg_engine_decode(smg_engine *e, int kmer, int ibyte, int64_t nels,
                       const uint8_t *d_records, const int64_t *d_prefix_index,
                       char *errbuf, size_t errlen);
 
+/* The same for a shard of a table: d_records holds the `nels` records of the entries first_entry .. first_entry + nels - 1
+   of the table that d_prefix_index belongs to (smg_engine_decode is first_entry = 0).  The engine's table then holds
+   those entries as its entries 0 .. nels - 1.                                                                        */
+int smg_engine_decode_at(smg_engine *e, int kmer, int ibyte, int64_t nels, int64_t first_entry,
+                         const uint8_t *d_records, const int64_t *d_prefix_index,
+                         char *errbuf, size_t errlen);
+
 /* Bind an already decoded device table (not copied; must outlive the engine's use of it):
    d_keys  = nels * words 64-bit words, k-mer left aligned (base 0 in bits 63..62 of word 0),
              words = ceil(k/32), entries strictly increasing;
@@ -396,6 +403,16 @@ void    smg_engine_lookup_limits(int32_t out[12]);
    the entries t * out[0] .. (t + 1) * out[0] - 1 --, [1] entries it stages in front of the first one it owns, [2] entries it
    stages in all, [3] the distance up to which partners are searched (longer window blocks are redone by kf_bigfix).          */
 void    smg_engine_pass1_limits(int32_t out[4]);
+
+/* where the record decoder and the piece-wise ingest change regime (read-only, needs no device; for tests): out[0] entries
+   a workgroup of k_decode decodes (a tile), [1] entries per thread, [2] the buckets of the prefix index a tile may span and
+   still walk its slice of the index in LDS (a tile that spans more bisects the whole index per entry), [3] KiB per piece
+   of the ingest (a piece holds whole tiles: the largest multiple of 1024 records that fits).                          */
+void    smg_engine_decode_limits(int32_t out[4]);
+
+/* readers (and, plus two, pinned and device slots at most) of the ingest of a table that lies in host memory:
+   smg_hetmers_run, smg_hetmers_extract and smg_condition_table on a smg_table_view                                    */
+int     smg_engine_ingest_readers(void);
 
 /* what the last pass 1 / filter / look-up of this engine did (plain host fields; for tests): out[0] id bits of the
    block map, [1] bucket bits (0: the chain did not run), [2] two-bit map, [3] one-way requests, [4] words per record,

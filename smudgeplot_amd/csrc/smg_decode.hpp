@@ -203,6 +203,14 @@ extern "C" int smg_engine_decode(smg_engine *e, int kmer, int ibyte, int64_t nel
                                  char *errbuf, size_t errlen)
 { return decode_at(e, kmer, ibyte, nels, 0, d_records, d_prefix_index, errbuf, errlen); }
 
+// the same for a shard: d_records holds the entries first_entry .. first_entry + nels - 1 of the table the index belongs to
+extern "C" int smg_engine_decode_at(smg_engine *e, int kmer, int ibyte, int64_t nels, int64_t first_entry,
+                                    const uint8_t *d_records, const int64_t *d_prefix_index,
+                                    char *errbuf, size_t errlen)
+{ if (first_entry < 0) return fail(errbuf, errlen, SMG_EINVAL, "decode: first_entry must not be negative%s");
+  return decode_at(e, kmer, ibyte, nels, first_entry, d_records, d_prefix_index, errbuf, errlen);
+}
+
 // ---- the table's own prefix index as look-up directory -------------------------------------------------------------
 // A FastK table carries the number of entries up to every 3-byte prefix (libfastk.c:841, `index[p]` = entries whose first
 // ibyte bytes are <= p).  With ibyte = 3 that IS a bucket directory over the leading 24 k-mer bits (bucket = hi32 >> 8;

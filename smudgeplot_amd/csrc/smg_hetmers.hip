@@ -1757,7 +1757,7 @@ extern "C" int smg_condition_table(const smg_table_view *tv, const smg_opts *opt
   ViewCtx vc; smg_table_source src;
   view_source(tv, &vc, &src);
   if ((rc = upload_index(&src, d_index, "the table", errbuf, errlen))) return rc;
-  if ((rc = ingest_range(e, &src, 0, tv->nels, d_index, opts->device, 4, NULL, NULL, errbuf, errlen))) return rc;
+  if ((rc = ingest_range(e, &src, 0, tv->nels, d_index, opts->device, ING_VIEW_READERS, NULL, NULL, errbuf, errlen))) return rc;
   if (opts->condition
       && (rc = smg_engine_condition(e, opts->ethresh, opts->condition & SMG_COND_TRIM, opts->condition & SMG_COND_SYMM,
                                     NULL, errbuf, errlen)))

@@ -18,6 +18,7 @@
 
 #define ING_CHUNK  ((size_t) 8 << 20)
 #define ING_MAXT   64
+#define ING_VIEW_READERS 4              // readers of a table that lies in host memory (view_source, smg_condition_table)
 
 struct IngPiece { int part; int64_t first, nent; size_t dst; };
 
@@ -188,5 +189,13 @@ static void view_source(const smg_table_view *tv, ViewCtx *ctx, smg_table_source
 { ctx->tv = tv; ctx->pbyte = ((tv->kmer + 3) >> 2) + 2 - tv->ibyte;
   src->kmer = tv->kmer; src->ibyte = tv->ibyte; src->nparts = tv->nparts; src->minval = tv->minval; src->nels = tv->nels;
   src->part_nels = tv->part_nels; src->prefix_index = tv->prefix_index;
-  src->read = view_read; src->ctx = ctx; src->host_threads = 4;
+  src->read = view_read; src->ctx = ctx; src->host_threads = ING_VIEW_READERS;
 }
+
+// where the decoder and the ingest change regime (smg_hetmers.h)
+extern "C" void smg_engine_decode_limits(int32_t out[4])
+{ const int32_t v[4] = { DEC_TILE, DEC_EPT, DEC_IX, (int32_t) (ING_CHUNK >> 10) };
+  memcpy(out, v, sizeof(v));
+}
+
+extern "C" int smg_engine_ingest_readers(void) { return ING_VIEW_READERS; }

@@ -70,7 +70,8 @@ EXPORTS = [
     "smg_engine_extract", "smg_hetmers_extract", "smg_free", "smg_condition_table", "smg_version",
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
     "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
-    "smg_engine_pass1_plan", "smg_hetmers_run_mode",
+    "smg_engine_pass1_plan", "smg_hetmers_run_mode", "smg_engine_decode_at", "smg_engine_decode_limits",
+    "smg_engine_ingest_readers",
 ]
 
 _lib = None
@@ -120,6 +121,12 @@ def load_library():
     lib.smg_engine_create.argtypes = [i32, vp, *err]
     lib.smg_engine_destroy.argtypes = [vp]
     lib.smg_engine_decode.argtypes = [vp, i32, i32, i64, vp, vp, *err]
+    if hasattr(lib, "smg_engine_decode_at"):
+        lib.smg_engine_decode_at.argtypes = [vp, i32, i32, i64, i64, vp, vp, *err]
+        lib.smg_engine_decode_limits.argtypes = [C.POINTER(C.c_int32)]
+        lib.smg_engine_decode_limits.restype = None
+        lib.smg_engine_ingest_readers.argtypes = []
+        lib.smg_engine_ingest_readers.restype = i32
     lib.smg_engine_bind.argtypes = [vp, i32, i64, vp, vp, *err]
     lib.smg_engine_set_prefix_index.argtypes = [vp, vp, i32, i64, *err]
     lib.smg_engine_condition.argtypes = [vp, i32, i32, i32, C.POINTER(i64), *err]
@@ -266,6 +273,42 @@ def pass1_limits() -> dict:
     return dict(zip(PASS1_LIMITS, (int(v) for v in out)))
 
 
+DECODE_LIMITS = ("DEC_TILE", "DEC_EPT", "DEC_IX", "ING_CHUNK_KIB")
+
+
+def decode_limits() -> dict:
+    """where k_decode and the ingest in front of it change regime (smg_engine_decode_limits, smg_engine_ingest_readers; no
+    device needed): entries per decode tile, entries per thread, the index buckets a tile may span and still walk its slice
+    of the index in LDS, KiB per ingested piece; and "READERS", the readers of a table in host memory (the pinned and the
+    device ring have READERS + 2 slots, fewer where the table has fewer pieces than readers)"""
+    lib = load_library()
+    out = (C.c_int32 * 4)()
+    lib.smg_engine_decode_limits(out)
+    d = dict(zip(DECODE_LIMITS, (int(v) for v in out)))
+    d["READERS"] = int(lib.smg_engine_ingest_readers())
+    return d
+
+
+def condition_table(table, condition: int = 0, ethresh: int = 0, device: int = 0):
+    """Host FastK table (`ktab.KTable`) -> (k-mers uint64[n, W], left aligned words; counts uint16[n]) after ingest, decode
+    and the conditioning steps asked for (smg_condition_table; condition as for hetmers_run, 0: the decoded table as it is)"""
+    lib = load_library()
+    tv, keep = _table_view(table)
+    opts = Opts(device, SYM_EXACT, 0, condition, ethresh, 0)
+    keys, cnt, n, w = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int(0)
+    buf = C.create_string_buffer(512)
+    rc = lib.smg_condition_table(C.byref(tv), C.byref(opts), C.byref(keys), C.byref(cnt), C.byref(n), C.byref(w), buf, 512)
+    _check(rc, buf)
+    n, w = int(n.value), int(w.value)
+    try:
+        hk = np.ctypeslib.as_array(C.cast(keys, C.POINTER(C.c_uint64)), shape=(max(n * w, 1),))[: n * w].copy().reshape(n, w)
+        hc = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint16)), shape=(max(n, 1),))[:n].copy()
+    finally:
+        lib.smg_free(keys)
+        lib.smg_free(cnt)
+    return hk, hc
+
+
 PASS1_PLAN = ("rw", "one_way", "narrow", "dir_per", "dir_preset", "bm_bits", "bm2", "nb", "use_sig", "var", "kf", "w")
 
 
@@ -403,9 +446,14 @@ class Engine:
         """the FastK prefix index of the bound table (int64[2^(8 ibyte)] on the device): the engine's look-up directory"""
         _check(self.lib.smg_engine_set_prefix_index(self.h, index_ptr, ibyte, first_entry, self._buf, 512), self._buf)
 
-    def decode(self, k: int, ibyte: int, nels: int, records_ptr: int, index_ptr: int):
+    def decode(self, k: int, ibyte: int, nels: int, records_ptr: int, index_ptr: int, first_entry: int = 0):
+        """format-F records on the device -> the engine's own table; first_entry: the number, in the table the index
+        belongs to, of the first record at records_ptr (a shard)"""
         self.k = k
-        _check(self.lib.smg_engine_decode(self.h, k, ibyte, nels, records_ptr, index_ptr, self._buf, 512),
+        if first_entry == 0 and not hasattr(self.lib, "smg_engine_decode_at"):       # (the library of an earlier commit)
+            _check(self.lib.smg_engine_decode(self.h, k, ibyte, nels, records_ptr, index_ptr, self._buf, 512), self._buf)
+            return
+        _check(self.lib.smg_engine_decode_at(self.h, k, ibyte, nels, first_entry, records_ptr, index_ptr, self._buf, 512),
                self._buf)
 
     def condition(self, ethresh: int, trim: bool, symm: bool) -> int:
