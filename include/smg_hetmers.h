@@ -404,6 +404,14 @@ void    smg_engine_lookup_limits(int32_t out[12]);
    stages in all, [3] the distance up to which partners are searched (longer window blocks are redone by kf_bigfix).          */
 void    smg_engine_pass1_limits(int32_t out[4]);
 
+/* the generic pass 1 and the record kernels behind it, which three-word k-mers (k = 65 .. 85) run through (read-only, needs
+   no device; for tests): out[0] entries per kf_pass1 tile, [1] entries it stages on either side of the tile (a window block
+   that reaches this far is walked by bisection), [2] records per request chunk, [3] records kf_filter stages per flush when a
+   record is wider than one word, [4] records from which the look-ups of a flat list are index-sorted first, [5] the distance
+   up to which a code byte names the partner, [6] entries at which the block walk stops narrowing and reads linearly, [7] the
+   first step of its gallop to the block's bounds.  Test hook SMG_FILTER_GRID=<g> (>= 1): kf_filter with at most g workgroups. */
+void    smg_engine_wide_limits(int32_t out[8]);
+
 /* where the record decoder and the piece-wise ingest change regime (read-only, needs no device; for tests): out[0] entries
    a workgroup of k_decode decodes (a tile), [1] entries per thread, [2] the buckets of the prefix index a tile may span and
    still walk its slice of the index in LDS (a tile that spans more bisects the whole index per entry), [3] KiB per piece
@@ -417,8 +425,9 @@ int     smg_engine_ingest_readers(void);
 /* what the last pass 1 / filter / look-up of this engine did (plain host fields; for tests): out[0] id bits of the
    block map, [1] bucket bits (0: the chain did not run), [2] two-bit map, [3] one-way requests, [4] words per record,
    [5] workgroups of pass 1 (test hook SMG_P1_GRID=<g> lowers them), [6] owners of the request list, [7] chunk slots
-   pass 1 and kf_bigfix used (before the filter), [8] the probe kernel that ran last: 0 none, 1 kl_probe with look-ups,
-   2 kl_probe_x, 3 kl_probe writing the survivor list, [9] requests per ticket passed to kl_probe_x (else 0).       */
+   pass 1 and kf_bigfix used (before the filter; [5] and [7] are reported without the chain as well: k = 65 .. 85),
+   [8] the probe kernel that ran last: 0 none, 1 kl_probe with look-ups, 2 kl_probe_x, 3 kl_probe writing the survivor
+   list, [9] requests per ticket passed to kl_probe_x (else 0).                                                      */
 int     smg_engine_lookup_state(smg_engine *e, int64_t out[10]);
 
 /* which pass-1 kernel the last pass 1 of this engine launched (plain host fields; for tests): out[0] the form of kf_pass1_d

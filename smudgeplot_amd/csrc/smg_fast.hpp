@@ -35,6 +35,7 @@
 #define F_SPAN   (F_TILE + 2 * F_HALO)
 #define F_CH     4096                 // records per request chunk
 #define F_NOCHUNK 0xFFFFFFFFu
+#define F_FSTAGE (4 * F_TPB)          // records kf_filter stages per flush when a record is wider than one word
 
 #define CODE_NONE   0
 #define CODE_MULTI  63
@@ -42,6 +43,7 @@
 #define CODE_W2     64
 #define CODE_DEFER  0xFF                  // placeholder until kf_bigfix has redone the entry
 #define CODE_P      0x80                  // set by the look-ups: the entry has a prefix-side pair ("P flag")
+#define CODE_REACH  30                    // a code byte names a partner up to this many entries away (31 + delta: 1 .. 61)
 // The flag is a BLIND byte store (round 5; rounds 1-4 read the byte, ORed the flag in and stored it: a dependent load that
 // misses the L2 for every look-up, 7.3e7 of them on the hexaploid table).  An entry with a prefix-side pair can neither be
 // counted as a candidate nor as the partner of one -- every reader of a code byte (kf_pass2 and its far twins, kf_extract)
@@ -164,6 +166,7 @@ template <int W> SMG_DEV int first_diff(const Key<W> &x, const Key<W> &y)
 // (The first version bisected the bounds over the whole table and then looked up all 3 (k - p0) flips in the whole
 //  block one after the other: ~550 dependent loads per entry; this one needs ~40 for a block of 500 entries.)
 #define BB_LIN  24
+#define BB_STEP 64                        // first step of the gallop to the block's bounds
 
 template <int W> __device__ __forceinline__ void
 big_block_walk(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n,
@@ -172,7 +175,7 @@ big_block_walk(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, i
 { const Key<W> x = load_key<W>(keys, i);
   const unsigned c = cnt[i];
   int64_t lo, hi;
-  { int64_t in = i, out, step = 64;
+  { int64_t in = i, out, step = BB_STEP;
     for (;;)
       { out = in - step;
         if (out < 0) { out = -1; break; }
@@ -185,7 +188,7 @@ big_block_walk(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, i
         if (same_block<W>(x, load_key<W>(keys, m), g)) b = m; else a = m + 1;
       }
     lo = a;
-    in = i; step = 64;
+    in = i; step = BB_STEP;
     for (;;)
       { out = in + step;
         if (out >= n) { out = n; break; }
@@ -283,7 +286,7 @@ big_block_scan(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, i
 SMG_DEV unsigned make_code(unsigned s_all, int64_t delta, unsigned w2)
 { if (s_all == 0) return CODE_NONE;
   if (s_all >= 2) return CODE_MULTI;
-  unsigned c = (delta >= -30 && delta <= 30) ? (unsigned) (31 + delta) : CODE_FAR;
+  unsigned c = (delta >= -CODE_REACH && delta <= CODE_REACH) ? (unsigned) (31 + delta) : CODE_FAR;
   return c | (w2 ? CODE_W2 : 0);
 }
 
@@ -573,7 +576,7 @@ template <int RW> __global__ void __launch_bounds__(F_TPB)
 kf_filter(const u64 *__restrict__ req, const uint32_t *__restrict__ chunk_fill, unsigned n_chunks, int64_t nflat,
           const uint32_t *__restrict__ bmap, int idshift, u64 *__restrict__ out, uint32_t *__restrict__ out_fill,
           unsigned max_out, FastCtl *__restrict__ ctl)
-{ constexpr unsigned SL = RW == 1 ? F_CH : 4 * F_TPB;        // records staged between two flushes
+{ constexpr unsigned SL = RW == 1 ? F_CH : F_FSTAGE;       // records staged between two flushes
   __shared__ u64      stage[SL * RW];
   __shared__ unsigned s_n, s_chunk, s_used;
   __shared__ u64      s_base, s_total;

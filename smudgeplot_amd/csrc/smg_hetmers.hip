@@ -55,7 +55,10 @@
 //                       (tests/test_pass2_regimes_gpu.py); the tile sizes they are cut at are read from smg_engine_pass2_limits;
 //                       SMG_P1_GRID=<g> (>= 1) launches pass 1 with at most g workgroups, so that one owner of the request list
 //                       holds several batches of kl_part on a table of 4e5 entries (tests/test_lookup_regimes_gpu.py, with
-//                       smg_engine_lookup_limits and smg_engine_lookup_state).
+//                       smg_engine_lookup_limits and smg_engine_lookup_state);
+//                       SMG_FILTER_GRID=<g> (>= 1) launches kf_filter with at most g workgroups, so that one workgroup takes several
+//                       chunks and splits its survivors across output chunks on a table of 1e4 entries
+//                       (tests/test_wide_fast_path_gpu.py, with smg_engine_wide_limits).
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
 // host: f(std::true_type) or f(std::false_type) -- with_words (smg_device.hpp) for a template argument that is a bool
@@ -621,8 +624,9 @@ static int p1_attempt(smg_engine *e, const P1Plan &p, P1Kernel p1k, unsigned gri
       HIPCHK(e->whist.reserve((int64_t) (grid + BF_MAXGRID) * L_BK * 4));
       HIPCHK(hipMemsetAsync(e->whist + (size_t) grid * L_BK, 0, sizeof(unsigned) * BF_MAXGRID * L_BK, e->stream));
       HIPCHK(hipMemsetAsync(e->chunk_fill, 0, (size_t) maxc * 4, e->stream));      // (a slot that stays empty has fill 0)
-      r.p1grid = grid; r.nown = grid + BF_MAXGRID;
+      r.nown = grid + BF_MAXGRID;
     }
+  r.p1grid = grid;
   hipEventRecord(e->ev[EV_PASS1_BEG], e->stream);
   if (!p.narrow)
     with_words<3>(p.W, [&](auto w) { hipLaunchKernelGGL(kf_pass1<w()>, dim3(grid), dim3(F_TPB), 0, e->stream, a, e->bstart,
@@ -891,6 +895,7 @@ static int fast_filter(smg_engine *e, const uint32_t *map, char *errbuf, size_t 
   // buckets, i.e. <= 1 MB of the map (measured: 512 workgroups 3.0 ms, 256 / 1024 / 2048 workgroups 3.4-3.7 ms)
   unsigned grid = 2u * (unsigned) e->cus;
   if (grid > e->run.n_chunks) grid = e->run.n_chunks;
+  { const char *v = test_hook("SMG_FILTER_GRID"); if (v && atoi(v) >= 1 && (unsigned) atoi(v) < grid) grid = (unsigned) atoi(v); }
   unsigned maxout = e->run.n_chunks + grid + 16;
   if (e->run.lg.nb)
     { // kl_probe: every wave of every workgroup (one per CU, lookup_probe) fills chunks of its own, each to the brim
@@ -1520,12 +1525,18 @@ extern "C" void smg_engine_pass1_limits(int32_t out[4])
   memcpy(out, v, sizeof(v));
 }
 
+extern "C" void smg_engine_wide_limits(int32_t out[8])
+{ const int32_t v[8] = { F_TILE, F_HALO, F_CH, F_FSTAGE, SORT_MIN, CODE_REACH, BB_LIN, BB_STEP };
+  memcpy(out, v, sizeof(v));
+}
+
 extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])
 { if (!e || !out) return SMG_EINVAL;
   const bool chain = has_chain(e);
   out[0] = e->run.pass1_done ? e->run.bm_bits : 0; out[1] = chain ? e->run.lg.nb : 0; out[2] = e->run.bm2; out[3] = e->run.one_way; out[4] = e->run.rw;
-  out[5] = chain ? e->run.p1grid : 0; out[6] = chain ? e->run.nown : 0;
-  out[7] = chain ? (int64_t) e->h_ctrl->fast.n_chunks : 0;       // (pass 1's counter: the filter counts in nf_chunks)
+  const bool fast = ran_fast(e);                                 // (three-word k-mers run pass 1 in chunks too, without the chain)
+  out[5] = fast ? e->run.p1grid : 0; out[6] = chain ? e->run.nown : 0;
+  out[7] = fast ? (int64_t) e->h_ctrl->fast.n_chunks : 0;        // (pass 1's counter: the filter counts in nf_chunks)
   out[8] = e->run.probe_form; out[9] = e->run.probe_part;
   return SMG_OK;
 }

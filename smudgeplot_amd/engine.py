@@ -71,7 +71,7 @@ EXPORTS = [
     "smg_engine_close_canonical", "smg_engine_merge_tile", "smg_hetmers_run_device", "smg_engine_pass2_limits",
     "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
     "smg_engine_pass1_plan", "smg_hetmers_run_mode", "smg_engine_decode_at", "smg_engine_decode_limits",
-    "smg_engine_ingest_readers",
+    "smg_engine_ingest_readers", "smg_engine_wide_limits",
 ]
 
 _lib = None
@@ -127,6 +127,9 @@ def load_library():
         lib.smg_engine_decode_limits.restype = None
         lib.smg_engine_ingest_readers.argtypes = []
         lib.smg_engine_ingest_readers.restype = i32
+    if hasattr(lib, "smg_engine_wide_limits"):
+        lib.smg_engine_wide_limits.argtypes = [C.POINTER(C.c_int32)]
+        lib.smg_engine_wide_limits.restype = None
     lib.smg_engine_bind.argtypes = [vp, i32, i64, vp, vp, *err]
     lib.smg_engine_set_prefix_index.argtypes = [vp, vp, i32, i64, *err]
     lib.smg_engine_condition.argtypes = [vp, i32, i32, i32, C.POINTER(i64), *err]
@@ -271,6 +274,19 @@ def pass1_limits() -> dict:
     out = (C.c_int32 * 4)()
     load_library().smg_engine_pass1_limits(out)
     return dict(zip(PASS1_LIMITS, (int(v) for v in out)))
+
+
+WIDE_LIMITS = ("F_TILE", "F_HALO", "F_CH", "F_FSTAGE", "SORT_MIN", "CODE_REACH", "BB_LIN", "BB_STEP")
+
+
+def wide_limits() -> dict:
+    """the generic pass 1 (kf_pass1, three-word k-mers) and the record kernels behind it (smg_engine_wide_limits; no device
+    needed): entries per tile, entries staged on either side of it (a longer window block is walked by bisection), records per
+    request chunk, records kf_filter stages per flush of records wider than one word, the list length from which look-ups are
+    index-sorted, the reach of a code byte, the block length at which the walk reads linearly, the first step of its gallop"""
+    out = (C.c_int32 * 8)()
+    load_library().smg_engine_wide_limits(out)
+    return dict(zip(WIDE_LIMITS, (int(v) for v in out)))
 
 
 DECODE_LIMITS = ("DEC_TILE", "DEC_EPT", "DEC_IX", "ING_CHUNK_KIB")
@@ -618,7 +634,7 @@ class Engine:
     def lookup_state(self) -> dict:
         """the look-up chain of this engine's last pass 1 / filter / run (smg_engine_lookup_state): id bits of the map, bucket
         bits (0: the chain did not run), two-bit map, one-way requests, words per record, workgroups of pass 1, owners of the
-        request list, chunk slots used before the filter, probe kernel (0 none, 1 kl_probe with look-ups, 2 kl_probe_x,
+        request list (0 without the chain), chunk slots used before the filter, probe kernel (0 none, 1 kl_probe with look-ups, 2 kl_probe_x,
         3 kl_probe writing the kept list), requests per kl_probe_x ticket"""
         out = (C.c_int64 * 10)()
         rc = self.lib.smg_engine_lookup_state(self.h, out)
