@@ -153,11 +153,24 @@ int smg_hetmers_run_mode(int kmer, int64_t nels, const smg_opts *opts, double fr
    it is not, so the answer is right for either (a build-time switch in smg_hetmers.hip takes the generic closure
    always: the same closed table).  Whatever conditioning is asked for, the engine works on a table of its
    own from there on: the caller may free d_keys and d_counts as soon as the call returns.
-   One device (opts->ngpus > 1: SMG_EINVAL), in core only: a table that does not fit next to the buffers of its closure and
-   of a run is refused with SMG_ENOMEM and the advice to write it to disk and run `hetmers` on the file, which does run
-   out of core.                                                                                                     */
+   One device (opts->ngpus > 1: SMG_EINVAL).  In core wherever the closed table is addressed by one engine (fewer than
+   2^32 - 32 entries) and fits next to the buffers of its closure and of a run.  Elsewhere a table that is to be closed
+   runs in 2 .. 16 prefix shards of its CLOSED table, one after the other in one engine: the table is trimmed once, every
+   shard is built from it on the device by smg_engine_close_canonical_range in each of the two rounds of an out-of-core
+   run, and stats is filled as that run fills it (path 1, nels the closed entries).  Still refused, with SMG_ENOMEM and
+   the advice to write the table to disk and run `hetmers` on the file: nels >= 2^32 - 32, a table for which 16 shards do
+   not fit either, and -- beyond one engine or the memory -- a table that is not canonical or not to be closed.       */
 int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
                            const smg_opts *opts, int64_t *plot, smg_stats *stats, char *errbuf, size_t errlen);
+
+/* Which way smg_hetmers_run_device would run a table of `nels` entries: the function it calls.  Reads SMG_HBM_LIMIT=<bytes>
+   (stands in for the free device memory), SMG_DEVICE_SHARDS=<2..16> (tests: that many shards) and
+   SMG_DEVICE_SHARD_LIMIT=<entries> (tests: stands in for the 2^32 - 32 entries of one engine) -- and none of the hooks of
+   smg_hetmers_run_mode.  free_bytes as there: with free_bytes > 0 no device is touched.  out[0] SMG_MODE_CORE or
+   SMG_MODE_SEQUENTIAL, out[1] the shards (1 in core), out[2] non-zero when the size alone forced the cut.  Refusals with
+   the codes and messages of the run itself.                                                                          */
+int smg_hetmers_run_device_mode(int kmer, int64_t nels, const smg_opts *opts, double free_bytes, int32_t out[3],
+                                char *errbuf, size_t errlen);
 
 /* ---- extract: the pairs behind the labelled pixels ----------------------------------------
    Replaces the compute section of extract_kmer_pairs, src/lib/PloidyList.c:1207-1583 (same two
@@ -249,6 +262,22 @@ int smg_engine_condition(smg_engine *e, int ethresh, int do_trim, int do_symm,
 int smg_engine_close_canonical(smg_engine *e, int64_t *new_nels, char *errbuf, size_t errlen);
 /* outputs per workgroup of that merge for k-mers of key_words words, 1 .. 4 (0 otherwise): where its tiles end        */
 int smg_engine_merge_tile(int key_words);
+
+/* The same closure ONE KEY RANGE AT A TIME: the engine's table becomes the part of the closed table inside [lo, hi) -- lo and
+   hi k-mers of ceil(kmer / 32) words in the layout of smg_engine_bind, NULL for an open end -- and is engine-owned.  The
+   canonical table (d_keys, d_counts: the layout and alignment of smg_engine_bind, nels < 2^32 - 32) is borrowed and not
+   changed.  The shard is the slice of the table inside the range merged with the sorted complements, selected in one pass
+   over the table, of those of ALL its entries whose complement falls into the range; what the call allocates is
+   proportional to the shard.  The shards of ranges that tile the key space, one after the other, are the table
+   smg_engine_close_canonical leaves.  An empty range, a range with no entry of the table and a range that no complement
+   falls into are valid.  A table that is not canonical: SMG_EINVAL ("table is not canonical"), the engine's table as it was. */
+int smg_engine_close_canonical_range(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
+                                     const uint64_t *lo, const uint64_t *hi, int64_t *new_nels, char *errbuf, size_t errlen);
+/* ... with the room for the selected complements handed in instead of taken from a histogram of the table (the shard driver
+   has that histogram; tests).  Too little room: SMG_EINVAL, nothing is written behind it, the engine's table as it was. */
+int smg_engine_close_canonical_range_cap(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
+                                         const uint64_t *lo, const uint64_t *hi, int64_t capacity, int64_t *new_nels,
+                                         char *errbuf, size_t errlen);
 
 /* ---- symmetrising a table that is cut into prefix shards (several GPUs, or more than 2^32 entries) --------------
    The reference hands a table of any size to Symmex (PloidyPlot.c:1395-1414).  Sharded, the same closure takes one

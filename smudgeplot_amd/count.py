@@ -232,6 +232,8 @@ def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entri
 def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash"):
     """Reads to the het-mer plot in one process: count on the device (k-mers with count >= t), hand the table over where
     it lies, trim at e, close under reverse complement, run -> (plot int64[1001, 501], hist uint64[32768], stats dict).
+    The closed table runs in core, or, where it is beyond one engine or the memory, in prefix shards one after the other
+    (engine.run_device_mode says which).
     paths_or_bases: sequence bytes (bytes, bytearray, memoryview or a uint8 array) or one path or a list of paths.
     e < t cannot be honoured (the entries below t are gone) and raises ValueError.  The stats are the counter's, with the
     engine's under "hetmers"."""

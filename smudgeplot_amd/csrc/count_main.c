@@ -6,15 +6,15 @@
  *
  *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.  With -e it is
  *  that step and `hetmers` in one process: the counted table stays in device memory and is trimmed, closed under reverse
- *  complement and scanned for het-mer pairs there (smg_hetmers_run_device), and <output>.smu is written as `hetmers -e`
- *  writes it from the table on disk.
+ *  complement and scanned for het-mer pairs there (smg_hetmers_run_device: in core, or in prefix shards of the closed table one
+ *  after the other where it is too large for that), and <output>.smu is written as `hetmers -e` writes it from the table on disk.
  *
  *  Usage: smg_count [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
  *           -k: k-mer length, 13 .. 128          -t: keep the k-mers with count >= t
  *           -H: also write <output>.hist.txt     -T: reader threads (one input file each, at most 16)
  *           -o: root name of the table; default is the root of the first input
  *           -p: key ranges to count in: 0 as many as the data need, 1 one pass, 2 .. 4096 that many
- *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device, in core
+ *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device
  *           -n: write no table (with -e or -H only)
  *
  *  SMUDGEPLOT_GPU picks the device; SMG_COUNT_MAX_ENTRIES (test hook) is max_entries of smg_count_parts.  No CPU fallback.
@@ -72,7 +72,7 @@ int main(int argc, char *argv[])
   uint64_t *keys = NULL, *hist;
   uint16_t *cnt = NULL;
   int64_t n = 0;
-  int W = 0;
+  int W = 0, shards = 1;
   char errbuf[1024];
 
   Prog_Name = "smg_count";
@@ -165,6 +165,10 @@ int main(int argc, char *argv[])
           ho.device = opts.device; ho.symcheck = SMG_SYM_HASH; ho.verbose = verbose; ho.ethresh = ethresh;
           ho.condition = SMG_COND_SYMM | (ethresh > minval ? SMG_COND_TRIM : 0);      /* (nothing below t is left to trim) */
           rc = smg_hetmers_run_device(kmer, n, d_keys, d_cnt, &ho, plot, &hst, errbuf, sizeof(errbuf));
+          if (rc == SMG_OK && verbose)                             /* (the plan that call made, asked once more for the report) */
+            { int32_t mode[3];
+              if (smg_hetmers_run_device_mode(kmer, n, &ho, 0.0, mode, NULL, 0) == SMG_OK && mode[0] == SMG_MODE_SEQUENTIAL) shards = mode[1];
+            }
         }
       smg_count_device_free(d_keys); smg_count_device_free(d_cnt);
       if (rc != SMG_OK)
@@ -212,8 +216,11 @@ int main(int argc, char *argv[])
       fprintf(stderr, "  ms: read %.1f  extract %.3f  sort %.3f  reduce+merge %.3f  finish %.3f  wall %.1f\n", st.ms_read, st.ms_extract,
               st.ms_sort, st.ms_reduce, st.ms_finish, st.ms_wall);
       if (ethresh > 0)
-        fprintf(stderr, "  het-mers at -e%d: %lld entries in the closed table, %lld pairs; ms: conditioning %.3f  pairs %.3f\n", ethresh,
-                (long long) hst.nels, (long long) hst.npairs, hst.ms_decode, hst.ms_total);
+        { fprintf(stderr, "  het-mers at -e%d: %lld entries in the closed table, %lld pairs; ms: conditioning %.3f  pairs %.3f", ethresh,
+                  (long long) hst.nels, (long long) hst.npairs, hst.ms_decode, hst.ms_total);
+          if (shards > 1) fprintf(stderr, "; %d prefix shards one after the other", shards);
+          fprintf(stderr, "\n");
+        }
     }
   if (ethresh == 0) { smg_count_free(keys); smg_count_free(cnt); }
   else { free(keys); free(cnt); }

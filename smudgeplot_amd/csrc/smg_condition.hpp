@@ -344,25 +344,37 @@ kc_symm_unpack(const u64 *__restrict__ rec, int64_t n, u64 *__restrict__ keys, u
   copy[i] = (uint8_t) ((q[W] >> 16) & 1u);
 }
 
-extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
-{ if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
-  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->tab.kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
-  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
-  HIPCHK(hipSetDevice(e->device));
-  const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
+// bits of the leading k-mer prefix that the closed table is cut on: a boundary of <= 12 leading bits is a window-block
+// boundary too (blocks share k / 2 bases)
+static int symm_split_bits(int kmer)
+{ const int b = 2 * (kmer / 2) < SY_MAXBITS ? 2 * (kmer / 2) : SY_MAXBITS;
+  return b < 2 ? 2 : b;
+}
+
+// the histogram of any sorted table on the engine's device and stream: hist[0 .. nbin) entries, hist[nbin .. 2 nbin) complements
+static int symm_hist_of(smg_engine *e, const u64 *keys, int64_t n, int kmer, int bits, int64_t *hist, char *errbuf, size_t errlen)
+{ const size_t bytes = sizeof(u64) * ((size_t) 2 << bits);
   Dev d;
   HIPCHK(d.alloc(bytes));
   hipError_t he = hipMemsetAsync(d.p, 0, bytes, e->stream);
-  if (he == hipSuccess && e->tab.n > 0)
-    { int64_t nb = (e->tab.n + TPB - 1) / TPB;
+  if (he == hipSuccess && n > 0)
+    { int64_t nb = (n + TPB - 1) / TPB;
       if (nb > 2048) nb = 2048;
-      with_words<4>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kc_symm_hist<w()>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, e->tab.keys, e->tab.n, e->tab.kmer, bits, d.as<u64>()); });
+      with_words<4>((kmer + 31) / 32, [&](auto w) { hipLaunchKernelGGL(kc_symm_hist<w()>, dim3((unsigned) nb), dim3(TPB), 0, e->stream, keys, n, kmer, bits, d.as<u64>()); });
       he = hipGetLastError();
     }
   if (he == hipSuccess) he = hipMemcpyAsync(hist, d.p, bytes, hipMemcpyDeviceToHost, e->stream);
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
   if (he != hipSuccess) return fail(errbuf, errlen, SMG_ENODEV, "symm_hist: %s", hipGetErrorString(he));
   return SMG_OK;
+}
+
+extern "C" int smg_engine_symm_hist(smg_engine *e, int bits, int64_t *hist, char *errbuf, size_t errlen)
+{ if (!e || !hist) return fail(errbuf, errlen, SMG_EINVAL, "null argument%s");
+  if (bits < 1 || bits > SY_MAXBITS || bits > 2 * e->tab.kmer) return fail(errbuf, errlen, SMG_EINVAL, "symm_hist: 1..12 leading bits, at most 2k%s");
+  if (!e->tab.keys && e->tab.n > 0) return fail(errbuf, errlen, SMG_EINVAL, "no table bound%s");
+  HIPCHK(hipSetDevice(e->device));
+  return symm_hist_of(e, e->tab.keys, e->tab.n, e->tab.kmer, bits, hist, errbuf, errlen);
 }
 
 extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, int nranks, uint64_t *d_send,
@@ -416,4 +428,210 @@ extern "C" int smg_engine_symm_finish(smg_engine *e, const uint64_t *d_recv, int
     }
   if (new_nels) *new_nels = kept;
   return SMG_OK;
+}
+
+// ---- closure of a canonical table ONE KEY RANGE AT A TIME -----------------------------------------------------------------
+// The part of the closed table T inside a key range [lo, hi) is the slice of C in the range merged with R_s, the sorted
+// complements of those entries of ALL of C whose complement falls into the range.  The two are disjoint for the reason given
+// above close_canonical, so there is nothing to de-duplicate.  What a range allocates is proportional to the range: the
+// complements are selected in one pass over C that materialises nothing per entry of C (kc_rc_select), sorted
+// (sort_permutation) and merged with the slice (ks_merge_split, ks_merge_bcnt).  closure_price (smg_shards.hpp) prices it.
+
+template <int W> struct KeyRange { Key<W> lo, hi; int has_lo, has_hi; };      // [lo, hi); an end that is not there is open
+
+template <int W> static KeyRange<W> key_range(const uint64_t *lo, const uint64_t *hi)
+{ KeyRange<W> rg;
+  rg.has_lo = lo != NULL; rg.has_hi = hi != NULL;
+  for (int w = 0; w < W; w++) { rg.lo.w[w] = lo ? lo[w] : 0; rg.hi.w[w] = hi ? hi[w] : ~0ull; }
+  return rg;
+}
+
+// One pass over C: the complement r of entry x is appended (with x's count) when it lies in the range and is another k-mer;
+// ctl[1] is set where r < x (the table is not canonical).  A wave takes RS_ITEMS rows of 64 entries and reserves the slots of
+// all its complements with one ballot per row and ONE atomic (every wave's goes to the same word: at one row per wave a
+// closure of a quarter of a 1e8-entry table took 18.6 ms, at eight 5.9 ms, profiles/reads_to_smu.md); the order of the list
+// is of no account, it is sorted next.  ctl[0] counts every
+// selected complement, stored or not: nothing is written at or behind slot `cap`, and the host sees the overflow.
+#define RS_ITEMS 8
+template <int W> __global__ void __launch_bounds__(TPB)
+kc_rc_select(const u64 *__restrict__ keys, const uint16_t *__restrict__ cnt, int64_t n, int k, KeyRange<W> rg, u64 cap,
+             u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt, u64 *__restrict__ ctl)
+{ const int lane = threadIdx.x & 63;
+  const int64_t first = ((((int64_t) blockIdx.x * TPB + threadIdx.x) >> 6) * RS_ITEMS) * 64 + lane;     // this lane's entry of row 0
+  Key<W> r[RS_ITEMS];
+  u64 mask[RS_ITEMS];
+  unsigned total = 0;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < RS_ITEMS; j++)
+    { const int64_t i = first + 64 * j;
+      bool keep = false;
+      if (i < n)
+        { const Key<W> x = load_key<W>(keys, i);
+          r[j] = revcomp<W>(x, k);
+          keep = !key_eq<W>(x, r[j]) && !(rg.has_lo && key_lt<W>(r[j], rg.lo)) && (!rg.has_hi || key_lt<W>(r[j], rg.hi));
+          bad |= key_lt<W>(r[j], x);
+        }
+      mask[j] = __ballot(keep);
+      total += (unsigned) __popcll(mask[j]);
+    }
+  if (bad) ctl[1] = 1ull;
+  if (!total) return;                                  // (the whole wave)
+  u64 base = 0;
+  if (lane == 0) base = atomicAdd(&ctl[0], (u64) total);
+  base = __shfl(base, 0, 64);
+#pragma unroll
+  for (int j = 0; j < RS_ITEMS; j++)
+    { const u64 slot = base + (u64) __popcll(mask[j] & ((1ull << lane) - 1ull));
+      if (((mask[j] >> lane) & 1ull) && slot < cap)
+        {
+#pragma unroll
+          for (int w = 0; w < W; w++) okeys[slot * W + w] = r[j].w[w];
+          ocnt[slot] = cnt[first + 64 * j];
+        }
+      base += (u64) __popcll(mask[j]);
+    }
+}
+
+// out[0], out[1] = the slice of C in the range: the first entry >= lo, the first entry >= hi (one bisection per cut)
+template <int W> __global__ void __launch_bounds__(64)
+kc_slice_bounds(const u64 *__restrict__ keys, int64_t n, KeyRange<W> rg, u64 *__restrict__ out)
+{ if (threadIdx.x == 0) out[0] = rg.has_lo ? (u64) lower_bound_key<W>(keys, 0, n, rg.lo) : 0ull;
+  if (threadIdx.x == 1) out[1] = rg.has_hi ? (u64) lower_bound_key<W>(keys, 0, n, rg.hi) : (u64) n;
+}
+
+// the bins [*b0, *b1) of the `bits`-bit histogram that the range touches
+static void range_bins(const uint64_t *lo, const uint64_t *hi, int W, int bits, int *b0, int *b1)
+{ *b0 = lo ? (int) (lo[0] >> (64 - bits)) : 0;
+  *b1 = 1 << bits;
+  if (hi)
+    { bool on_boundary = (hi[0] << bits) == 0;
+      for (int w = 1; w < W; w++) on_boundary = on_boundary && hi[w] == 0;
+      *b1 = (int) (hi[0] >> (64 - bits)) + (on_boundary ? 0 : 1);
+    }
+}
+
+static bool range_is_empty(const uint64_t *lo, const uint64_t *hi, int W)
+{ if (!lo || !hi) return false;
+  for (int w = 0; w < W; w++) if (lo[w] != hi[w]) return lo[w] > hi[w];
+  return true;
+}
+
+// the selection pass and the slice bounds of one range on e's stream: at most `cap` complements into (rk, rcnt), which are
+// allocated here for as many; *m = how many there are, *a0, *a1 = the slice of C.  cap = 0: only the canonical check is of use.
+static int range_select(smg_engine *e, int kmer, int64_t n, const u64 *keys, const uint16_t *cnt, const uint64_t *lo, const uint64_t *hi,
+                        int64_t cap, Dev &rk, Dev &rcnt, int64_t *m, bool *bad, int64_t *a0, int64_t *a1, char *errbuf, size_t errlen)
+{ const int W = (kmer + 31) / 32;
+  Dev ctl;
+  u64 h[4] = { 0, 0, 0, 0 };
+  HIPCHK(ctl.alloc(sizeof(u64) * 4));
+  HIPCHK(rk.alloc(sizeof(u64) * (size_t) (cap > 0 ? cap : 1) * W));
+  HIPCHK(rcnt.alloc(sizeof(uint16_t) * (size_t) (cap > 0 ? cap : 1) + 16));
+  HIPCHK(hipMemsetAsync(ctl.p, 0, sizeof(u64) * 4, e->stream));
+  if (n > 0)
+    { const unsigned nblk = (unsigned) ((n + TPB * RS_ITEMS - 1) / (TPB * RS_ITEMS));
+      with_words<4>(W, [&](auto w)
+        { const KeyRange<w()> rg = key_range<w()>(lo, hi);
+          hipLaunchKernelGGL(kc_rc_select<w()>, dim3(nblk), dim3(TPB), 0, e->stream, keys, cnt, n, kmer, rg, (u64) cap, rk.as<u64>(),
+                             rcnt.as<uint16_t>(), ctl.as<u64>());
+          hipLaunchKernelGGL(kc_slice_bounds<w()>, dim3(1), dim3(64), 0, e->stream, keys, n, rg, ctl.as<u64>() + 2);
+        });
+      HIPCHK(hipGetLastError());
+    }
+  HIPCHK(hipMemcpyAsync(h, ctl.p, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  *m = (int64_t) h[0]; *bad = h[1] != 0; *a0 = (int64_t) h[2]; *a1 = (int64_t) h[3];
+  if (*a1 < *a0) *a1 = *a0;                            // (an empty range handed in with hi < lo)
+  return SMG_OK;
+}
+
+#define RANGE_NELS_MAX (0xFFFFFFF0ll - 16)             // (SMG_ONE_SHARD_MAX, smg_shards.hpp)
+
+// cap < 0: the room for the complements is taken from a histogram of C (one more pass); the shard driver, which has that
+// histogram already, hands the capacity in.  *not_canonical tells that refusal from every other one.
+static int close_canonical_range(smg_engine *e, int kmer, int64_t n, const u64 *keys, const uint16_t *cnt, const uint64_t *lo,
+                                 const uint64_t *hi, int64_t cap, int64_t *new_nels, bool *not_canonical, char *errbuf, size_t errlen)
+{ *not_canonical = false;
+  if (!e) return fail(errbuf, errlen, SMG_EINVAL, "null engine%s");
+  if (kmer < 1 || kmer > SMG_MAX_KMER) return fail(errbuf, errlen, SMG_EINVAL, "k-mer length out of range (1..128)%s");
+  if (n < 0 || n >= RANGE_NELS_MAX) return fail(errbuf, errlen, SMG_EINVAL, "range closure: the table must have fewer than 2^32 - 32 entries%s");
+  if (n > 0 && (!keys || !cnt)) return fail(errbuf, errlen, SMG_EINVAL, "null table pointer%s");
+  if (((uintptr_t) keys & 15) || ((uintptr_t) cnt & 7))
+    return fail(errbuf, errlen, SMG_EINVAL, "table pointers must be aligned (k-mers 16 bytes, counts 8 bytes)%s");
+  HIPCHK(hipSetDevice(e->device));
+  const int W = (kmer + 31) / 32;
+  const bool empty = range_is_empty(lo, hi, W);
+  int rc;
+  hipEventRecord(e->ev[EV_DECODE_BEG], e->stream);                 // (booked under ms_decode, like close_canonical)
+  if (empty) cap = 0;
+  if (cap < 0 && n > 0)
+    { const int bits = symm_split_bits(kmer), nbin = 1 << bits;
+      std::vector<int64_t> hist((size_t) 2 * nbin, 0);
+      int b0, b1;
+      if ((rc = symm_hist_of(e, keys, n, kmer, bits, hist.data(), errbuf, errlen))) return rc;
+      range_bins(lo, hi, W, bits, &b0, &b1);
+      cap = 0;
+      for (int b = b0; b < b1; b++) cap += hist[(size_t) nbin + b];
+    }
+  if (cap < 0) cap = 0;
+  Dev rk, rcnt, perm, split, ko, co;
+  int64_t m = 0, a0 = 0, a1 = 0;
+  bool bad = false;
+  if ((rc = range_select(e, kmer, n, keys, cnt, lo, hi, cap, rk, rcnt, &m, &bad, &a0, &a1, errbuf, errlen))) return rc;
+  if (bad)
+    { *not_canonical = true;
+      return fail(errbuf, errlen, SMG_EINVAL, "table is not canonical: an entry is larger than its reverse complement "
+                  "(smg_engine_condition closes any sorted table)%s");
+    }
+  if (m > cap)
+    { if (errbuf && errlen) snprintf(errbuf, errlen, "range closure: %lld complements fall into the range, room was made for %lld",
+                                     (long long) m, (long long) cap);
+      return SMG_EINVAL;
+    }
+  const int64_t na = empty ? 0 : a1 - a0, ns = na + m;
+  if (ns >= RANGE_NELS_MAX) return fail(errbuf, errlen, SMG_EINVAL, "range closure: the range holds 2^32 - 32 entries or more%s");
+  const u64 *a = keys + (size_t) a0 * W;
+  const uint16_t *ac = cnt + a0;
+  HIPCHK(ko.alloc(sizeof(u64) * (size_t) (ns > 0 ? ns : 1) * W));
+  HIPCHK(co.alloc(sizeof(uint16_t) * (size_t) (ns > 0 ? ns : 1) + 16));
+  if (m == 0 && na > 0)                                // no complement falls into the range: the shard is a copy of the slice
+    { HIPCHK(hipMemcpyAsync(ko.p, a, sizeof(u64) * (size_t) na * W, hipMemcpyDeviceToDevice, e->stream));
+      HIPCHK(hipMemcpyAsync(co.p, ac, sizeof(uint16_t) * (size_t) na, hipMemcpyDeviceToDevice, e->stream));
+    }
+  else if (m > 0)
+    { HIPCHK(sort_permutation(rk.as<u64>(), W, m, e->stream, e->sort_tmp, perm));
+      const int64_t ntiles = (ns + ks_merge_tile(W) - 1) / ks_merge_tile(W);
+      HIPCHK(split.alloc(sizeof(uint32_t) * (size_t) (ntiles + 1)));
+      with_words<4>(W, [&](auto w)
+        { hipLaunchKernelGGL(ks_merge_split<w()>, dim3((unsigned) (ntiles / KS_TPB + 1)), dim3(KS_TPB), 0, e->stream, a, na, rk.as<u64>(),
+                             perm.as<uint32_t>(), m, ntiles, split.as<uint32_t>());
+          hipLaunchKernelGGL(ks_merge_bcnt<w()>, dim3((unsigned) ntiles), dim3(KS_TPB), 0, e->stream, a, ac, na, rk.as<u64>(),
+                             perm.as<uint32_t>(), rcnt.as<uint16_t>(), m, split.as<uint32_t>(), ko.as<u64>(), co.as<uint16_t>());
+        });
+      HIPCHK(hipGetLastError());
+    }
+  hipEventRecord(e->ev[EV_DECODE_END], e->stream);
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const float ms = ms_between(e, EV_DECODE_BEG, EV_DECODE_END);
+  if ((rc = set_table(e, kmer, ns, errbuf, errlen))) return rc;
+  adopt_table(e, ko, co, ns);
+  e->st.ms_decode = ms;
+  if (new_nels) *new_nels = ns;
+  return SMG_OK;
+}
+
+extern "C" int smg_engine_close_canonical_range(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
+                                                const uint64_t *lo, const uint64_t *hi, int64_t *new_nels, char *errbuf, size_t errlen)
+{ bool not_canonical;
+  return close_canonical_range(e, kmer, nels, (const u64 *) d_keys, d_counts, lo, hi, -1, new_nels, &not_canonical, errbuf, errlen);
+}
+
+// the same with the room for the complements handed in (the shard driver's door, and the tests' for a capacity that is too
+// small: SMG_EINVAL, the engine's table as it was, nothing written behind the room)
+extern "C" int smg_engine_close_canonical_range_cap(smg_engine *e, int kmer, int64_t nels, const uint64_t *d_keys, const uint16_t *d_counts,
+                                                    const uint64_t *lo, const uint64_t *hi, int64_t capacity, int64_t *new_nels,
+                                                    char *errbuf, size_t errlen)
+{ bool not_canonical;
+  if (capacity < 0) return fail(errbuf, errlen, SMG_EINVAL, "range closure: negative capacity%s");
+  return close_canonical_range(e, kmer, nels, (const u64 *) d_keys, d_counts, lo, hi, capacity, new_nels, &not_canonical, errbuf, errlen);
 }

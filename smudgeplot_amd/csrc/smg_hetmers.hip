@@ -45,7 +45,8 @@
 #include "smg_lookup.hpp"
 
 // The environment, in two classes:
-//   documented modes    getenv(): SMG_VIRTUAL_SHARDS, SMG_SEQUENTIAL_SHARDS, SMG_SHARD_LIMIT, SMG_HBM_LIMIT, SMG_FORCE_MULTI (smg_hetmers.h);
+//   documented modes    getenv(): SMG_VIRTUAL_SHARDS, SMG_SEQUENTIAL_SHARDS, SMG_SHARD_LIMIT, SMG_HBM_LIMIT, SMG_FORCE_MULTI, and for a
+//                       table on the device SMG_DEVICE_SHARDS, SMG_DEVICE_SHARD_LIMIT (smg_hetmers.h);
 //   test hooks          test_hook(): force, on a table of any size, a code path that the engine otherwise picks from the table's
 //                       size, k or counts (the 30-bit exchanged map, the one-bit map of k < 24, kl_probe_x, the unfiltered chain,
 //                       pass 1's own directory, ..) -- tests/test_gpu_parity.py drives every one of them against the oracle;
@@ -1680,7 +1681,8 @@ extern "C" int smg_hetmers_run_source(const smg_table_source *src, const smg_opt
 
 // ---- one-shot entry: a table that is already on the device -> plot ------------------------------------------------------
 // What smg_hetmers_run does behind its ingest, for the table the k-mer counter left in device memory (smg_count.h, the
-// _device entries): bind, trim, close, run.  One device, in core.
+// _device entries): bind, trim, close, run.  One device; in core, or -- a canonical table whose closure is beyond one engine
+// or does not fit -- in prefix shards of the closed table one after the other (device_run_sequential, smg_multi.hpp).
 // 1: a canonical table is closed by smg_engine_close_canonical, any other by the generic closure (same table either way).
 // profiles/reads_to_smu.md: at 1e8 entries the merge takes 17.0 against 24.0 ms at k = 31 and 27.4 against 43.1 ms at k = 51;
 // at 1e6 entries it is 0.1 - 0.2 ms behind.  0 takes the generic closure always.
@@ -1692,31 +1694,29 @@ extern "C" int smg_hetmers_run_device(int kmer, int64_t nels, const uint64_t *d_
   const int device = opts ? opts->device : 0;
   const int symcheck = opts ? opts->symcheck : SMG_SYM_HASH;
   const int cond = opts ? opts->condition : 0;
-  static const char *two_step = ": write the table (smg_count without -e) and run hetmers on it, which runs out of core";
   if (opts && opts->ngpus > 1)
     return fail(errbuf, errlen, SMG_EINVAL, "a table that is already on one device runs on that device only (ngpus > 1)%s");
   if (kmer < 1 || kmer > SMG_MAX_KMER) return fail(errbuf, errlen, SMG_EINVAL, "k-mer length out of range (1..128)%s");
   if (nels < 0) return fail(errbuf, errlen, SMG_EINVAL, "negative number of entries%s");
-  { // in core or not at all: the closed table next to the lists of a run, or next to the buffers of its own closure
-    // (core_bytes); the table handed in is in device memory already and not part of what is free
-    const int W = (kmer + 31) / 32;
-    if ((double) nels * ((cond & SMG_COND_SYMM) ? 2.0 : 1.0) >= (double) SMG_ONE_SHARD_MAX)
-      return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 - 32 entries in the closed table: one engine does not address them%s", two_step);
-    const double limit = memory_limit(device, 0);
-    if (limit <= 0) return fail(errbuf, errlen, SMG_ENODEV, "no usable HIP device%s");
-    const double need = core_bytes(W, nels, cond) - (cond ? 0.0 : (double) nels * (8.0 * W + 2.0));
-    if (need > limit)
-      { char msg[256];
-        snprintf(msg, sizeof(msg), "the table does not fit the device in core: %lld entries need %.3f GB, %.3f GB are free",
-                 (long long) nels, need * 1e-9, limit * 1e-9);
-        if (errbuf && errlen) snprintf(errbuf, errlen, "%s%s", msg, two_step);
-        return SMG_ENOMEM;
-      }
-  }
+  // in core -- the closed table next to the lists of a run, or next to the buffers of its own closure -- or, where that is
+  // refused and the table is to be closed, in prefix shards of the closed table one after the other (run_device_plan)
+  RunMode mode;
+  int rc = run_device_plan(kmer, nels, 0, cond, symcheck, device, 0, true, &mode, errbuf, errlen);
+  if (rc) return rc;
+  if (mode.mode == SMG_MODE_SEQUENTIAL)
+    { smg_opts o = *opts;
+      bool not_canonical = false;
+      rc = device_run_sequential(kmer, nels, (const u64 *) d_keys, d_counts, &o, mode.count, plot, stats, &not_canonical, errbuf, errlen);
+      if (!not_canonical) return rc;
+      // not canonical: the generic closure, which runs in core or not at all -- as ever, whatever the hooks say
+      if ((rc = run_device_plan(kmer, nels, 0, cond, symcheck, device, 0, false, &mode, errbuf, errlen))) return rc;
+      if (mode.mode != SMG_MODE_CORE)
+        return fail(errbuf, errlen, SMG_ENOMEM, mode.cut_by_limit ? "more than 2^32 - 32 entries in the closed table: one engine does not address them%s"
+                    : "the table does not fit the device in core, and it is not canonical: no prefix shards%s", DEVICE_TWO_STEP);
+    }
   EngineOwner eng;                           // (in front of the buffer: destroyed after it)
   smg_engine *e = eng.create(device, errbuf, errlen);
   if (!e) return SMG_ENODEV;
-  int rc = SMG_OK;
   DevBuf<int64_t> d_plot;
   if (d_plot.alloc(sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess) return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the plot%s");
   if ((rc = smg_engine_bind(e, kmer, nels, d_keys, d_counts, errbuf, errlen))) return rc;

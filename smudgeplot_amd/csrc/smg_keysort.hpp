@@ -104,7 +104,8 @@ static inline hipError_t scan_flags(uint32_t *flag, uint32_t *pos, int64_t n, hi
 // ---- merge path: two sorted lists of W-word k-mers with no k-mer in common -> one ----------------------------------------
 // A is a table (k-mers a[na * W], counts acnt[na]).  B is given unsorted with its order beside it: its j-th k-mer in sorted
 // order is b[bperm[j]], and it carries the count of A's entry bsrc[bperm[j]] (B holds reverse complements of entries of A:
-// smg_engine_close_canonical).  Output tile t is the outputs [t * T, (t + 1) * T): ks_merge_split finds with one diagonal
+// smg_engine_close_canonical) -- or, in the second form ks_merge_bcnt, the count bcnt[bperm[j]] given beside it.
+// Output tile t is the outputs [t * T, (t + 1) * T): ks_merge_split finds with one diagonal
 // search per tile (mp_split, smg_mergepath.hpp, on the k-mers in device memory) how many of the outputs in front of it come
 // from A.  ks_merge stages the tile's two input spans -- T items together -- in LDS, A's span in front of B's, with their
 // counts; every thread searches its own diagonal there, merges its T / 256 items into registers, and after a barrier the
@@ -128,10 +129,11 @@ ks_merge_split(const u64 *__restrict__ a, int64_t na, const u64 *__restrict__ b,
   split[t] = (uint32_t) mp_split(diag, na, nb, [&](int64_t j, int64_t i) { return mp_key_lt<W>(b + (size_t) bperm[j] * W, a + (size_t) i * W); });
 }
 
-template <int W> __global__ void __launch_bounds__(KS_TPB)
-ks_merge(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t na, const u64 *__restrict__ b,
-         const uint32_t *__restrict__ bperm, const uint32_t *__restrict__ bsrc, int64_t nb, const uint32_t *__restrict__ split,
-         u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+// (the tile's work, for both forms of B's counts: cnt_of_b(p) is the count that goes with B's item p)
+template <int W, class CntOfB> SMG_DEV void
+ks_merge_tile_body(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t na, const u64 *__restrict__ b,
+                   const uint32_t *__restrict__ bperm, int64_t nb, const uint32_t *__restrict__ split,
+                   u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt, CntOfB cnt_of_b)
 { constexpr int T = KsMergeTile<W>::value, IPT = T / KS_TPB;
   __shared__ __attribute__((aligned(16))) u64 s_key[T * W];
   __shared__ __attribute__((aligned(16))) uint16_t s_cnt[T];
@@ -150,7 +152,7 @@ ks_merge(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t n
       const Key<W> y = load_key<W>(b, p);
 #pragma unroll
       for (int w = 0; w < W; w++) s_key[(ca + x) * W + w] = y.w[w];
-      s_cnt[ca + x] = acnt[bsrc[p]];
+      s_cnt[ca + x] = cnt_of_b(p);
     }
   __syncthreads();
 
@@ -185,5 +187,19 @@ ks_merge(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t n
   for (int x = t; x < ct / 2; x += KS_TPB) o2[x] = c2[x];
   if (t == 0 && (ct & 1)) ocnt[d0 + ct - 1] = s_cnt[ct - 1];
 }
+
+template <int W> __global__ void __launch_bounds__(KS_TPB)
+ks_merge(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t na, const u64 *__restrict__ b,
+         const uint32_t *__restrict__ bperm, const uint32_t *__restrict__ bsrc, int64_t nb, const uint32_t *__restrict__ split,
+         u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ ks_merge_tile_body<W>(a, acnt, na, b, bperm, nb, split, okeys, ocnt, [=](uint32_t p) { return acnt[bsrc[p]]; }); }
+
+// the second form: B's counts are given per item of B (bcnt[p] beside b[p]) -- A is a SLICE of a table while B's sources lie
+// anywhere in that table (smg_engine_close_canonical_range)
+template <int W> __global__ void __launch_bounds__(KS_TPB)
+ks_merge_bcnt(const u64 *__restrict__ a, const uint16_t *__restrict__ acnt, int64_t na, const u64 *__restrict__ b,
+              const uint32_t *__restrict__ bperm, const uint16_t *__restrict__ bcnt, int64_t nb, const uint32_t *__restrict__ split,
+              u64 *__restrict__ okeys, uint16_t *__restrict__ ocnt)
+{ ks_merge_tile_body<W>(a, acnt, na, b, bperm, nb, split, okeys, ocnt, [=](uint32_t p) { return bcnt[p]; }); }
 
 #undef KS_TRY

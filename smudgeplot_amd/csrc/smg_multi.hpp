@@ -657,6 +657,12 @@ struct SeqRun
   std::vector<int64_t> h_plot;
   std::vector<uint64_t> xrec;                // extract leg: handed out only if the whole table proves closed
   int rw;
+  // a third source of shards: the canonical table C that is already on the device (device_run_sequential).  Shard sh is the
+  // closure of C inside its key range, built in each of the two rounds with room for dev_cap[sh] complements
+  const u64 *dev_keys = NULL; const uint16_t *dev_cnt = NULL;
+  int64_t dev_n = -1;                        // >= 0: this source
+  std::vector<int64_t> dev_cap;
+  float ms_close = 0;                        // device time of the range closures, both rounds
   int64_t missing = 0, nels = 0, nemit = 0;
   u64 fp[4] = { 0, 0, 0, 0 };
   float ms_p1 = 0, ms_look = 0, ms_p2 = 0;
@@ -669,11 +675,23 @@ struct SeqRun
 };
 
 // shard sh in the engine: a conditioned shard from host memory (it has no prefix index: pass 1 / k_directory build a
-// directory), or its range of the part files, read and decoded
+// directory), the closure of its key range of a canonical table on the device (no prefix index either), or its range of the
+// part files, read and decoded
 static int seq_load(SeqRun &s, int sh)
 { smg_engine *e = s.e;
   const smg_table_source *tv = s.tv;
   int rc;
+  if (s.dev_n >= 0)
+    { const uint64_t *lo = sh > 0 ? (const uint64_t *) &s.splitters[(size_t) (sh - 1) * s.W] : NULL;
+      const uint64_t *hi = sh + 1 < s.n ? (const uint64_t *) &s.splitters[(size_t) sh * s.W] : NULL;
+      bool not_canonical;
+      e->own_keys.reset(); e->own_cnt.reset();           // (the shard before this one goes first: one shard at a time)
+      e->tab.keys = NULL; e->tab.cnt = NULL;
+      table_changed(e, 0);
+      rc = close_canonical_range(e, tv->kmer, s.dev_n, s.dev_keys, s.dev_cnt, lo, hi, s.dev_cap[(size_t) sh], NULL, &not_canonical, s.eb, s.el);
+      if (rc == SMG_OK) s.ms_close += (float) e->st.ms_decode;
+      return rc;
+    }
   if (s.raw)
     { const HostShard &h = s.hshard[(size_t) sh];
       if ((rc = decode_begin(e, tv->kmer, tv->ibyte, h.n, s.eb, s.el))) return rc;
@@ -788,4 +806,81 @@ static int host_run_sequential(const smg_table_source *tv, const smg_opts *opts,
   for (int sh = 0; sh < n; sh++) if ((rc = seq_round1(s, sh))) return rc;
   for (int sh = 0; sh < n; sh++) if ((rc = seq_round2(s, sh))) return rc;
   return seq_result(s, w0, stats, records, nrec_out, rec_words);
+}
+
+// ---- a canonical table that is ALREADY ON THE DEVICE, in prefix shards of its closure one after the other --------------------
+// What smg_hetmers_run_device does where the closed table is beyond one engine or does not fit in core (run_device_plan).
+// The table C is trimmed once, up front, into an engine of its own that only holds it.  The 12-bit histogram of its entries
+// and complements cuts the CLOSED table into shards of equal size (balanced_splitters); the histogram also gives every
+// shard's size -- one at or above the shard limit raises the number of shards, up to 16 -- and the room its complements need.
+// Then the two rounds of SeqRun, every shard built from C by close_canonical_range in each of them: nothing is written to
+// disk, nothing leaves the device, and what is allocated beside C is one shard, the code bytes and the requests.
+// *not_canonical: the table is not canonical (SMG_EINVAL, nothing has run): the caller takes the generic closure in core.
+static int device_run_sequential(int kmer, int64_t nels, const u64 *d_keys, const uint16_t *d_cnt, const smg_opts *opts, int nshards,
+                                 int64_t *plot, smg_stats *stats, bool *not_canonical, char *errbuf, size_t errlen)
+{ *not_canonical = false;
+  const int W = (kmer + 31) / 32, bits = symm_split_bits(kmer), nbin = 1 << bits;
+  struct timespec w0;
+  clock_gettime(CLOCK_MONOTONIC, &w0);
+  EngineOwner holder;                        // (in front of the run: destroyed after it)
+  smg_engine *te = holder.create(opts->device, errbuf, errlen);
+  if (!te) return SMG_ENODEV;
+  int rc;
+  if ((rc = smg_engine_bind(te, kmer, nels, (const uint64_t *) d_keys, d_cnt, errbuf, errlen))) return rc;
+  if ((opts->condition & SMG_COND_TRIM) && (rc = smg_engine_condition(te, opts->ethresh, 1, 0, NULL, errbuf, errlen))) return rc;
+  const int64_t n = te->tab.n;
+  { // canonical or not: the selection pass over an empty range keeps nothing and looks at every entry
+    const uint64_t zero[4] = { 0, 0, 0, 0 };
+    Dev rk, rcnt;
+    int64_t m, a0, a1;
+    if ((rc = range_select(te, kmer, n, te->tab.keys, te->tab.cnt, zero, zero, 0, rk, rcnt, &m, not_canonical, &a0, &a1, errbuf, errlen))) return rc;
+    if (*not_canonical) return fail(errbuf, errlen, SMG_EINVAL, "table is not canonical%s");
+  }
+  std::vector<int64_t> hist((size_t) 2 * nbin, 0), cap;
+  std::vector<u64> splitters;
+  if ((rc = symm_hist_of(te, te->tab.keys, n, kmer, bits, hist.data(), errbuf, errlen))) return rc;
+  const int64_t limit = device_shard_limit(true);
+  int q = nshards;
+  for (;; q++)
+    { splitters.assign((size_t) (q - 1) * W, 0);
+      cap.assign((size_t) q, 0);
+      balanced_splitters(hist.data(), nbin, bits, q, W, splitters.data());
+      int worst = 0;
+      int64_t worst_size = -1;
+      for (int sh = 0; sh < q; sh++)
+        { int b0, b1;
+          int64_t size = 0;
+          range_bins(sh > 0 ? (const uint64_t *) &splitters[(size_t) (sh - 1) * W] : NULL,
+                     sh + 1 < q ? (const uint64_t *) &splitters[(size_t) sh * W] : NULL, W, bits, &b0, &b1);
+          for (int b = b0; b < b1; b++) { size += hist[(size_t) b] + hist[(size_t) nbin + b]; cap[(size_t) sh] += hist[(size_t) nbin + b]; }
+          if (size > worst_size) { worst_size = size; worst = sh; }
+        }
+      if (worst_size < limit) break;
+      if (q == SMG_MAXGPU)
+        { if (errbuf && errlen)
+            snprintf(errbuf, errlen, "prefix shard %d of %d of the closed table would hold %lld entries, one engine addresses fewer than %lld%s",
+                     worst, q, (long long) worst_size, (long long) limit, DEVICE_TWO_STEP);
+          return SMG_ENOMEM;
+        }
+    }
+  if (opts->verbose)
+    fprintf(stderr, "  [smg] %lld entries on the device%s: the closed table in %d prefix shards one after the other, every shard closed "
+            "from the table on the device in each of the two rounds\n", (long long) n, (opts->condition & SMG_COND_TRIM) ? " after trimming" : "", q);
+  smg_table_source tv; memset(&tv, 0, sizeof(tv));
+  tv.kmer = kmer; tv.nels = n; tv.ibyte = 3;
+  SeqRun s(&tv, opts, q, plot, NULL, errbuf, errlen);
+  s.dev_keys = te->tab.keys; s.dev_cnt = te->tab.cnt; s.dev_n = n;
+  s.dev_cap = cap;
+  s.splitters = splitters;
+  if (s.splitters.empty()) s.splitters.assign((size_t) W, 0);
+  if (!(s.e = s.eng.create(opts->device, errbuf, errlen))) return SMG_ENODEV;
+  s.e->set.no_filter = true;                  // (no candidate map: the filter would need the maps of the shards not built yet)
+  if (s.d_plot.alloc(sizeof(int64_t) * SMG_PLOT_CELLS) != hipSuccess) return fail(errbuf, errlen, SMG_ENOMEM, "out of device memory for the plot%s");
+  memset(plot, 0, sizeof(int64_t) * SMG_PLOT_CELLS);
+  for (int sh = 0; sh < q; sh++) if ((rc = seq_round1(s, sh))) return rc;
+  for (int sh = 0; sh < q; sh++) if ((rc = seq_round2(s, sh))) return rc;
+  if ((rc = seq_result(s, w0, stats, NULL, NULL, NULL))) return rc;
+  if (stats) stats->ms_decode = s.ms_close;     // (conditioning, as in core: here the range closures of both rounds)
+  if (opts->verbose) fprintf(stderr, "  [smg] range closures of the %d shards, both rounds: %.2f ms on the device\n", q, s.ms_close);
+  return SMG_OK;
 }

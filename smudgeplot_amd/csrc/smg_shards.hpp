@@ -69,12 +69,7 @@ static int64_t balanced_splitters(const int64_t *hist, int nbin, int bits, int n
   return total;
 }
 
-// bits of the leading k-mer prefix that the closed table is cut on: a boundary of <= 12 leading bits is a window-block
-// boundary too (blocks share k / 2 bases)
-static int symm_split_bits(int kmer)
-{ const int b = 2 * (kmer / 2) < SY_MAXBITS ? 2 * (kmer / 2) : SY_MAXBITS;
-  return b < 2 ? 2 : b;
-}
+// (symm_split_bits, the bits of the leading k-mer prefix that the closed table is cut on: smg_condition.hpp)
 
 // ---- the pieces of a sharded run ------------------------------------------------------------------------------------------
 
@@ -283,6 +278,100 @@ extern "C" int smg_hetmers_run_mode(int kmer, int64_t nels, const smg_opts *opts
   RunMode m;
   const int rc = run_mode_plan(kmer, nels, opts ? opts->ngpus : 0, opts ? opts->condition : 0, opts ? opts->symcheck : SMG_SYM_EXACT,
                                opts ? opts->device : 0, free_bytes, &m, errbuf, errlen);
+  out[0] = m.mode; out[1] = m.count; out[2] = m.cut_by_limit;
+  return rc;
+}
+
+// ---- the run mode of a table that is ALREADY ON THE DEVICE (smg_hetmers_run_device) -------------------------------------------
+
+// What the range closure of one shard (close_canonical_range, smg_condition.hpp) allocates per entry of the SHARD, in bytes,
+// at its worst -- every entry of the shard a complement, none from the slice.  While the complements are sorted: the selected
+// k-mers and counts (8 W + 2), sort_permutation's two word and two permutation buffers (2 * 8 + 2 * 4).  While they are
+// merged: the selected k-mers and counts again, the permutation (4), the shard itself (8 W + 2).
+static double closure_price(int W)
+{ const double sorting = 8.0 * W + 2.0 + 24.0, merging = 2.0 * (8.0 * W + 2.0) + 4.0;
+  return sorting > merging ? sorting : merging;
+}
+
+// what a run of the table in core needs FREE: the table handed in is in device memory already and not part of what is free
+static double device_core_need(int W, int64_t nels, int condition)
+{ return core_bytes(W, nels, condition) - (condition ? 0.0 : (double) nels * (8.0 * W + 2.0)); }
+
+// what stays on the device for the whole of a run in shards: the trimmed copy of the table where trimming is asked for, a code
+// byte per closed entry and the requests (run_mode_plan's `keep`)
+static double device_resident_bytes(int kmer, int64_t nels, int condition, int symcheck)
+{ const int W = (kmer + 31) / 32;
+  const double ne = 2.0 * (double) nels;
+  const double keep = ne * (1.0 + (symcheck == SMG_SYM_EXACT ? 8.0 * (W + 1) : 0.36 * 8.0 * (kmer > FAST_MAX_K ? W + 1 : W)));
+  return ((condition & SMG_COND_TRIM) ? (double) nels * (8.0 * W + 2.0) : 0.0) + keep;
+}
+
+static const char *DEVICE_TWO_STEP = ": write the table (smg_count without -e) and run hetmers on it, which runs out of core";
+
+// SMG_DEVICE_SHARD_LIMIT=<entries> (tests) stands in for SMG_ONE_SHARD_MAX
+static int64_t device_shard_limit(bool hooks)
+{ const char *sl = hooks ? getenv("SMG_DEVICE_SHARD_LIMIT") : NULL;
+  return sl && atoll(sl) > 0 ? atoll(sl) : SMG_ONE_SHARD_MAX;
+}
+
+// Which way a table on the device runs: a pure function of (k, entries, options, two hooks and SMG_HBM_LIMIT, free bytes).
+//   * In core wherever the closed table is addressed by one engine and fits next to the lists of its run or the buffers of
+//     its closure: the two tests this entry has always made, with their arithmetic.
+//   * Elsewhere a table that is to be closed (SMG_COND_SYMM) runs in the smallest number q = 2 .. 16 of prefix shards of its
+//     CLOSED table, one after the other (SeqRun, smg_multi.hpp), such that 2 n / q is below the shard limit and the resident
+//     part (device_resident_bytes) plus one shard -- the larger of its closure and its run -- fits the memory.
+//   * SMG_DEVICE_SHARDS=<2..16> (tests) forces that many shards, SMG_DEVICE_SHARD_LIMIT=<entries> (tests) lowers the limit.
+//     hooks = false: neither is read (a table that turns out not to be canonical: the generic closure runs in core or not at all).
+//   The hooks of run_mode_plan are not read here.
+static int run_device_plan(int kmer, int64_t nels, int ngpus, int condition, int symcheck, int device, double free_bytes, bool hooks,
+                           RunMode *out, char *errbuf, size_t errlen)
+{ RunMode m;
+  *out = m;
+  const int W = (kmer + 31) / 32;
+  const bool want_symm = (condition & SMG_COND_SYMM) != 0;
+  if (ngpus > 1)
+    return fail(errbuf, errlen, SMG_EINVAL, "a table that is already on one device runs on that device only (ngpus > 1)%s");
+  const double ne = (double) nels * (want_symm ? 2.0 : 1.0);
+  const int64_t limit = device_shard_limit(hooks);
+  const bool by_size = ne >= (double) limit;
+  int forced = 0;
+  { const char *fs = hooks ? getenv("SMG_DEVICE_SHARDS") : NULL;
+    if (fs && atoi(fs) >= 2) forced = atoi(fs) > SMG_MAXGPU ? SMG_MAXGPU : atoi(fs);
+  }
+  if (nels >= SMG_ONE_SHARD_MAX || (by_size && !want_symm))
+    return fail(errbuf, errlen, SMG_ENOMEM, "more than 2^32 - 32 entries in the closed table: one engine does not address them%s", DEVICE_TWO_STEP);
+  const double mem = memory_limit(device, free_bytes);
+  if (mem <= 0) return fail(errbuf, errlen, SMG_ENODEV, "no usable HIP device%s");
+  const double need = device_core_need(W, nels, condition);
+  const bool by_mem = need > mem;
+  if (!by_size && !by_mem && !(forced && want_symm)) return SMG_OK;             // in core, as ever
+  int q = 0;
+  if (want_symm && forced) q = forced;
+  else if (want_symm)
+    { const double resident = device_resident_bytes(kmer, nels, condition, symcheck);
+      const EntryPrice p = entry_price(W, condition);
+      const double shard = closure_price(W) > p.run ? closure_price(W) : p.run;
+      for (int c = 2; c <= SMG_MAXGPU && !q; c++)
+        if (ne / c < (double) limit && resident + ne / c * shard <= mem) q = c;
+    }
+  if (!q)
+    { char msg[320];
+      snprintf(msg, sizeof(msg), "the table does not fit the device in core: %lld entries need %.3f GB, %.3f GB are free%s",
+               (long long) nels, need * 1e-9, mem * 1e-9, want_symm ? ", and 16 prefix shards one after the other do not fit either" : "");
+      if (errbuf && errlen) snprintf(errbuf, errlen, "%s%s", msg, DEVICE_TWO_STEP);
+      return SMG_ENOMEM;
+    }
+  m.mode = SMG_MODE_SEQUENTIAL; m.count = q; m.cut_by_limit = by_size ? q : 0;
+  *out = m;
+  return SMG_OK;
+}
+
+extern "C" int smg_hetmers_run_device_mode(int kmer, int64_t nels, const smg_opts *opts, double free_bytes, int32_t out[3],
+                                           char *errbuf, size_t errlen)
+{ if (!out || kmer < 1 || kmer > SMG_MAX_KMER || nels < 0) return fail(errbuf, errlen, SMG_EINVAL, "bad argument%s");
+  RunMode m;
+  const int rc = run_device_plan(kmer, nels, opts ? opts->ngpus : 0, opts ? opts->condition : 0, opts ? opts->symcheck : SMG_SYM_HASH,
+                                 opts ? opts->device : 0, free_bytes, true, &m, errbuf, errlen);
   out[0] = m.mode; out[1] = m.count; out[2] = m.cut_by_limit;
   return rc;
 }

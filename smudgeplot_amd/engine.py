@@ -72,6 +72,7 @@ EXPORTS = [
     "smg_engine_lookup_limits", "smg_engine_lookup_state", "smg_engine_pass1_form", "smg_engine_pass1_limits",
     "smg_engine_pass1_plan", "smg_hetmers_run_mode", "smg_engine_decode_at", "smg_engine_decode_limits",
     "smg_engine_ingest_readers", "smg_engine_wide_limits",
+    "smg_engine_close_canonical_range", "smg_engine_close_canonical_range_cap", "smg_hetmers_run_device_mode",
 ]
 
 _lib = None
@@ -150,6 +151,10 @@ def load_library():
     if hasattr(lib, "smg_hetmers_run_mode"):
         lib.smg_hetmers_run_mode.argtypes = [i32, i64, C.POINTER(Opts), C.c_double, C.POINTER(C.c_int32), *err]
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
+    if hasattr(lib, "smg_hetmers_run_device_mode"):
+        lib.smg_hetmers_run_device_mode.argtypes = [i32, i64, C.POINTER(Opts), C.c_double, C.POINTER(C.c_int32), *err]
+        lib.smg_engine_close_canonical_range.argtypes = [vp, i32, i64, vp, vp, vp, vp, C.POINTER(i64), *err]
+        lib.smg_engine_close_canonical_range_cap.argtypes = [vp, i32, i64, vp, vp, vp, vp, i64, C.POINTER(i64), *err]
     lib.smg_engine_run.argtypes = [vp, i32, vp, C.POINTER(Stats), *err]
     lib.smg_engine_pass1.argtypes = [vp, i32, *err]
     lib.smg_engine_nreq.restype = i64
@@ -223,7 +228,9 @@ def hetmers_run(table, device: int = 0, symcheck: str = "exact", verbose: int = 
 def hetmers_run_device(k: int, nels: int, keys_ptr: int, counts_ptr: int, device: int = 0, symcheck: str = "hash",
                        verbose: int = 0, condition: int = 0, ethresh: int = 0):
     """A decoded table in device memory (the layout of Engine.bind; borrowed) -> (plot int64[1001,501], stats dict).
-    condition as for hetmers_run; COND_SYMM closes a canonical table by merge and any other table the generic way."""
+    condition as for hetmers_run; COND_SYMM closes a canonical table by merge and any other table the generic way.  A
+    canonical table whose closure is beyond one engine or the memory runs in prefix shards of the closed table one after
+    the other (run_device_mode says which way a table goes)."""
     lib = load_library()
     opts = Opts(device, _SYM[symcheck], verbose, condition, ethresh, 0)
     plot = np.zeros(PLOT_CELLS, dtype=np.int64)
@@ -356,6 +363,20 @@ def run_mode(k: int, nels: int, free_bytes: float, symcheck: str = "exact", cond
     return {"mode": RUN_MODES[out[0]], "count": int(out[1]), "cut_by_limit": int(out[2])}
 
 
+def run_device_mode(k: int, nels: int, free_bytes: float, symcheck: str = "hash", condition: int = 0, ngpus: int = 0,
+                    device: int = 0) -> dict:
+    """which way hetmers_run_device would run a table of `nels` entries that is on the device (smg_hetmers_run_device_mode; the
+    function it calls, and with free_bytes > 0 no device): {"mode": "core" or "sequential", "count": the prefix shards of the
+    closed table that would run one after the other (1 in core), "cut_by_limit": non-zero when the size alone forced the cut}.
+    Reads SMG_HBM_LIMIT, SMG_DEVICE_SHARDS and SMG_DEVICE_SHARD_LIMIT -- not the hooks of run_mode; raises EngineError with
+    the run's own code and message where the run would refuse."""
+    out = (C.c_int32 * 3)()
+    opts = Opts(device, _SYM[symcheck], 0, condition, 0, ngpus)
+    buf = C.create_string_buffer(512)
+    _check(load_library().smg_hetmers_run_device_mode(k, nels, C.byref(opts), float(free_bytes), out, buf, 512), buf)
+    return {"mode": RUN_MODES[out[0]], "count": int(out[1]), "cut_by_limit": int(out[2])}
+
+
 def _table_view(table):
     """`ktab.KTable` -> (TableView, objects that must stay alive while it is used)"""
     kb = (table.k + 3) >> 2
@@ -483,6 +504,29 @@ class Engine:
         complements and a merge; raises EngineError (-2, "table is not canonical") and changes nothing otherwise"""
         n = C.c_int64(0)
         _check(self.lib.smg_engine_close_canonical(self.h, C.byref(n), self._buf, 512), self._buf)
+        return int(n.value)
+
+    def close_canonical_range(self, k: int, nels: int, keys_ptr: int, counts_ptr: int, lo=None, hi=None, capacity=None) -> int:
+        """the engine's table becomes the part inside the key range [lo, hi) of the closure of the canonical table at
+        (keys_ptr, counts_ptr) -- borrowed, not changed, fewer than 2^32 - 32 entries.  lo, hi: uint64[W] k-mers in the
+        engine's layout, None for an open end.  capacity: the room made for the complements that fall into the range (None: taken
+        from a histogram of the table); too little is an EngineError and writes nothing behind it.  Raises EngineError (-2,
+        "table is not canonical") and leaves the engine's table as it was otherwise.  Returns the entries of the shard."""
+        n = C.c_int64(0)
+        words = (k + 31) // 32
+        ends = []
+        for end in (lo, hi):
+            a = None if end is None else np.ascontiguousarray(end, dtype=np.uint64).reshape(words)
+            ends.append(a)
+        plo, phi = (None if a is None else a.ctypes.data for a in ends)
+        if capacity is None:
+            rc = self.lib.smg_engine_close_canonical_range(self.h, k, nels, keys_ptr or None, counts_ptr or None, plo, phi, C.byref(n),
+                                                           self._buf, 512)
+        else:
+            rc = self.lib.smg_engine_close_canonical_range_cap(self.h, k, nels, keys_ptr or None, counts_ptr or None, plo, phi,
+                                                               int(capacity), C.byref(n), self._buf, 512)
+        _check(rc, self._buf)
+        self.k = k
         return int(n.value)
 
     # ---- symmetrising across shards (smg_hetmers.h) ----------------------------------------

@@ -5,6 +5,7 @@ generic closure, and reads to .smu in one process against `smg_count` followed b
   python tools/reads_to_smu_time.py closure [--bases 1e6,1e8] [--k 31,51] [--repeats 5] [--warmup 1]
   python tools/reads_to_smu_time.py e2e --dir DIR [--bases 2e8] [--k 31] [--t 4] [--e 12] [--two-step-bin DIR2]
   python tools/reads_to_smu_time.py memory [--bases 2e8] [--k 31] [--t 4] [--e 12]
+  python tools/reads_to_smu_time.py shards [--bases 1e8] [--k 31,51] [--shards 4] [--repeats 5] [--warmup 1]
 
 closure  A canonical table is counted on the device from a seeded random sequence of `bases` bases (t = 1: nearly every
          window a distinct k-mer) and stays there.  Engine.close_canonical and Engine.condition(0, False, True) run on it in
@@ -14,6 +15,10 @@ closure  A canonical table is counted on the device from a seeded random sequenc
 e2e      Process wall clock, no device timing in the same command: `smg_count -e -n` against `smg_count` + `hetmers -e` on the
          reads.fq that `count_time.py gen --dir DIR` wrote, each route twice, alternating.  --two-step-bin names a directory
          with another build's bin/smg_count and bin/hetmers for the two-step route (default: this build's).
+shards   One counted table (as for closure) handed to engine.hetmers_run_device, closed and run two ways in turn: in core, and
+         forced into `shards` prefix shards of the closed table one after the other (SMG_DEVICE_SHARDS).  `warmup` + `repeats`
+         times each; per run the wall clock of the call and the engine's own times.  Prints one JSON line per k with the
+         medians and every run, and asserts that both ways give the same plot.
 memory   hipMemGetInfo before and after count.reads_to_plot on a seeded stream, and the peak the run reports on the way
          (a sampling thread: 2 ms period), next to the size of the counted table.
 """
@@ -60,6 +65,35 @@ def closure(args):
             med = {r: sorted(v)[len(v) // 2] for r, v in runs.items()}
             print(json.dumps({"step": "closure", "k": k, "bases": bases, "entries": table.nels, "closed": sizes.pop(),
                               "median_ms": med, "runs_ms": runs, "warmup": args.warmup}), flush=True)
+
+
+def shards(args):
+    from smudgeplot_amd import count, engine
+    fields = ("ms_decode", "ms_pass1", "ms_rclookup", "ms_pass2", "ms_total")
+    for k in [int(x) for x in args.k.split(",")]:
+        table, _, st = count.count_bases_device(random_stream(float(args.bases), 7), k, t=1)
+        runs = {"core": [], "shards": []}
+        plots, closed = {}, set()
+        with table:
+            for i in range(args.warmup + args.repeats):
+                for way in ("core", "shards"):
+                    os.environ.pop("SMG_DEVICE_SHARDS", None)
+                    if way == "shards":
+                        os.environ["SMG_DEVICE_SHARDS"] = str(args.shards)
+                    t0 = time.perf_counter()
+                    plot, est = engine.hetmers_run_device(k, table.nels, table.keys_ptr, table.counts_ptr, condition=engine.COND_SYMM)
+                    wall = (time.perf_counter() - t0) * 1e3
+                    os.environ.pop("SMG_DEVICE_SHARDS", None)
+                    closed.add(est["nels"])
+                    assert way not in plots or np.array_equal(plots[way], plot)
+                    plots[way] = plot
+                    if i >= args.warmup:
+                        runs[way].append(dict({f: round(est[f], 3) for f in fields}, wall_ms=round(wall, 3)))
+        assert np.array_equal(plots["core"], plots["shards"]) and len(closed) == 1, closed
+        med = {w: {f: sorted(r[f] for r in v)[len(v) // 2] for f in fields + ("wall_ms",)} for w, v in runs.items()}
+        print(json.dumps({"step": "shards", "k": k, "bases": float(args.bases), "entries": table.nels, "closed": closed.pop(),
+                          "shards": args.shards, "pairs": int(plots["core"].sum()), "median": med, "runs": runs, "warmup": args.warmup}),
+              flush=True)
 
 
 def e2e(args):
@@ -120,7 +154,7 @@ def memory(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["closure", "e2e", "memory"])
+    ap.add_argument("step", choices=["closure", "e2e", "memory", "shards"])
     ap.add_argument("--bases", default=None)
     ap.add_argument("--k", default=None)
     ap.add_argument("--t", type=int, default=4)
@@ -129,12 +163,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--two-step-bin", default=None)
+    ap.add_argument("--shards", type=int, default=4)
     args = ap.parse_args()
     if args.step == "closure":
         args.bases = args.bases or "1e6,1e8"
         args.k = args.k or "31,51"
         args.repeats = args.repeats or 5
         return closure(args)
+    if args.step == "shards":
+        args.bases = args.bases or "1e8"
+        args.k = args.k or "31,51"
+        args.repeats = args.repeats or 5
+        return shards(args)
     args.k = int(args.k or 31)
     args.bases = float(args.bases or 2e8)
     args.repeats = args.repeats or 2
