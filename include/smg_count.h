@@ -143,6 +143,16 @@ int smg_count_plan(const uint64_t *windows, int64_t budget, int32_t partitions, 
 int smg_count_plan_fine(const uint64_t *windows, const int32_t *split, int32_t nsplit, const uint64_t *sub, int64_t budget,
                         int32_t *cuts, int64_t cuts_cap, int32_t *nranges, char *errbuf, size_t errlen);
 
+/* host only: how a run shares out the device memory, before its first allocation -- the function the counting calls use
+   themselves, with nothing read from the device or the environment.  kmer: k; free_bytes: free device memory; bound: the
+   most sequence bytes the input can hold; partitions, max_entries: as in smg_count_parts; batch_bases: the value of the
+   test hook SMG_COUNT_BATCH_BASES (bases per batch), 0 for none.  *cap = positions a batch holds; *parted = 0 for one
+   pass, 1 where the batches are packed into a store and counted by key range; *store_cap = positions of that store (a
+   multiple of 4096; 0 for one pass).  SMG_ENOMEM where the store, or the batch next to it, does not fit: the message
+   names what is needed and what is free.                                                                             */
+int smg_count_memory_plan(int32_t kmer, uint64_t free_bytes, int64_t bound, int32_t partitions, int64_t max_entries,
+                          int64_t batch_bases, int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf, size_t errlen);
+
 /* host only: the stripped byte stream of one file, the sequence of every record with line ends removed
    and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).            */
 int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen);

@@ -22,7 +22,7 @@ BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
            "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
-           "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free"]
+           "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan"]
 
 
 class CountError(RuntimeError):
@@ -84,6 +84,9 @@ def load_library():
     lib.smg_count_plan.restype = C.c_int
     lib.smg_count_plan_fine.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]
     lib.smg_count_plan_fine.restype = C.c_int
+    lib.smg_count_memory_plan.argtypes = [C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_memory_plan.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_parse.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
@@ -291,6 +294,21 @@ def plan_fine(windows, split, sub, budget):
     if rc != 0:
         raise CountError(rc, err.value.decode(errors="replace"))
     return cuts[: n.value + 1].copy()
+
+
+def memory_plan(k, free_bytes, bound, partitions=0, max_entries=0, batch_bases=0):
+    """Host only: how a run would share out `free_bytes` of device memory for an input of at most `bound` sequence bytes
+    (smg_count_memory_plan; no device, no environment: the function the counting calls use) -> dict with `cap` (positions of
+    a batch), `parted` (bool: packed and counted by key range) and `store_cap` (positions of the store, 0 for one pass).
+    batch_bases is the value of the test hook SMG_COUNT_BATCH_BASES, 0 for none.  Raises CountError (-3) where it does not fit."""
+    lib = load_library()
+    cap, parted, store = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_memory_plan(int(k), int(free_bytes), int(bound), int(partitions), int(max_entries), int(batch_bases),
+                                   C.byref(cap), C.byref(parted), C.byref(store), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    return {"cap": cap.value, "parted": bool(parted.value), "store_cap": store.value}
 
 
 def parse(path) -> bytes:
