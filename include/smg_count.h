@@ -1,7 +1,10 @@
 /* smg_count.h -- C ABI of the k-mer counter (libsmg_count.so, gfx950).
  *
  * Reads in, canonical k-mer table out: what FastK does in front of `hetmers`, on one MI355X.
- *   - input: plain FASTA / FASTQ (first byte '>' or '@'); gzip is refused;
+ *   - input: FASTA / FASTQ (first byte '>' or '@'), plain or block-gzipped (BGZF, what bgzip and htslib write: a gzip
+ *     file of independent members of at most 64 KiB, found by the BC subfield of its first header), every file of a call
+ *     routed by its own header; the members of a BGZF file are inflated on the device and their CRC-32 checked there;
+ *     any other gzip file is refused (SMG_EINVAL: recompress it with bgzip, or decompress it);
  *   - bases ACGTacgt code to 0..3, every other byte ends the current stretch, no k-mer spans two records;
  *   - every window of k bases counts once for the smaller of the k-mer and its reverse complement
  *     (left-aligned big-endian words, the order of the FastK table);
@@ -11,7 +14,7 @@
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
  * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
- * return SMG_ENODEV; smg_count_parse and smg_count_version need no device.
+ * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan and smg_count_version need no device.
  */
 #ifndef SMG_COUNT_H
 #define SMG_COUNT_H
@@ -43,6 +46,8 @@ extern "C" {
 #define SMG_COUNT_BINS       4096      /* of the canonical k-mer                                  */
 #define SMG_COUNT_FINE_BITS  24        /* a bin with more windows than one merge holds is split on its next 12 bits: */
 #define SMG_COUNT_FINE_BINS  (1 << SMG_COUNT_FINE_BITS)   /* the ends of a range are values of the leading 24 bits  */
+#define SMG_COUNT_BGZF_CHUNK (16 << 20)  /* compressed bytes of a BGZF file that one launch of the inflate kernel takes (whole
+                                            members; a reader thread holds one such buffer and 4 x as much for their text) */
 
 typedef struct smg_count_opts
 { int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
@@ -153,9 +158,23 @@ int smg_count_plan_fine(const uint64_t *windows, const int32_t *split, int32_t n
 int smg_count_memory_plan(int32_t kmer, uint64_t free_bytes, int64_t bound, int32_t partitions, int64_t max_entries,
                           int64_t batch_bases, int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf, size_t errlen);
 
-/* host only: the stripped byte stream of one file, the sequence of every record with line ends removed
-   and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).            */
+/* host only: the stripped byte stream of one plain file, the sequence of every record with line ends removed
+   and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).  A BGZF file is
+   SMG_EINVAL here (no device: see smg_count_bgzf_inflate).                                         */
 int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen);
+
+/* host only: the members of a BGZF file, walked from header to header.  SMG_OK: *blocks = members (empty ones and the EOF
+   marker included), *text_bytes = the sum of their ISIZE fields.  SMG_EINVAL for a file that is not BGZF: the message of the
+   counting calls for another gzip file, "<path> is not BGZF ..." for a file that is not gzip.  SMG_EFORMAT,
+   "<path>: BGZF block at offset <o>: <reason>", for a header cut off by the end of the file, a BSIZE that reaches past it,
+   an ISIZE above 65536 and a later member that is not BGZF.  The counting calls refuse the same before they touch the device. */
+int smg_count_bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen);
+
+/* the text of a whole BGZF file, inflated by the kernel on `device` as the counting calls inflate it: *text is malloc'ed
+   (smg_count_free), *n its bytes, *ms_kernel (may be NULL) the sum of the HIP-event times of the launches.  Errors as
+   smg_count_bgzf_scan, and SMG_EFORMAT "<path>: BGZF block at offset <o>: <reason>" for the first member that does not
+   inflate to ISIZE bytes with the CRC-32 of its trailer.  SMG_ENODEV without a device.                                  */
+int smg_count_bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen);
 
 void smg_count_free(void *p);
 const char *smg_count_version(void);

@@ -1,7 +1,9 @@
 """ctypes binding of the k-mer counter (include/smg_count.h, libsmg_count.so, built in-tree).
 
 Reads in, canonical FastK-style k-mer table out: the step in front of `hetmers`.  There is no CPU
-fallback: the counting calls raise `CountError` without a HIP device; `parse` needs none.
+fallback: the counting calls raise `CountError` without a HIP device; `parse` and `bgzf_scan` need none.
+The input files are FASTA / FASTQ, plain or block-gzipped (BGZF, what `bgzip` writes); the members of a BGZF file are
+inflated on the device.  Any other gzip file is refused.
 """
 
 from __future__ import annotations
@@ -15,6 +17,7 @@ from . import ktab
 
 MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
 FINE_BINS = 1 << 24                       # the ends of a range are values of the leading 24 bits where a bin was split
+BGZF_CHUNK = 16 << 20                     # compressed bytes of a BGZF file that one launch of the inflate kernel takes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
@@ -22,7 +25,8 @@ BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
            "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
-           "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan"]
+           "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan",
+           "smg_count_bgzf_scan", "smg_count_bgzf_inflate"]
 
 
 class CountError(RuntimeError):
@@ -89,6 +93,11 @@ def load_library():
     lib.smg_count_memory_plan.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_parse.restype = C.c_int
+    lib.smg_count_bgzf_scan.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_bgzf_scan.restype = C.c_int
+    lib.smg_count_bgzf_inflate.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_char_p,
+                                           C.c_size_t]
+    lib.smg_count_bgzf_inflate.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
     lib.smg_count_free.restype = None
     lib.smg_count_version.restype = C.c_char_p
@@ -312,7 +321,8 @@ def memory_plan(k, free_bytes, bound, partitions=0, max_entries=0, batch_bases=0
 
 
 def parse(path) -> bytes:
-    """Host only: the stripped byte stream of one FASTA / FASTQ file, one '\\n' between two records."""
+    """Host only: the stripped byte stream of one plain FASTA / FASTQ file, one '\\n' between two records.  A BGZF file is
+    refused here (CountError -2): there is no device in this call, see bgzf_inflate."""
     lib = load_library()
     seq, n = C.c_void_p(), C.c_int64(0)
     err = C.create_string_buffer(1024)
@@ -323,3 +333,32 @@ def parse(path) -> bytes:
         return C.string_at(seq, n.value)
     finally:
         lib.smg_count_free(seq)
+
+
+def bgzf_scan(path) -> dict:
+    """Host only: the members of a BGZF file, walked from header to header -> {"blocks": members (empty ones and the EOF
+    marker included), "text_bytes": the sum of their ISIZE fields}.  Raises CountError: -2 for a file that is not BGZF, -4
+    with the offset of the block for a file that is cut off or whose headers do not fit it."""
+    lib = load_library()
+    blocks, text = C.c_int64(0), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_bgzf_scan(os.fsencode(path), C.byref(blocks), C.byref(text), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    return {"blocks": blocks.value, "text_bytes": text.value}
+
+
+def bgzf_inflate(path, device=0):
+    """The text of a whole BGZF file, inflated on the device as the counting calls inflate it -> (bytes, ms_kernel: the sum
+    of the HIP-event times of the launches).  Raises CountError -4 with the offset of the first member that does not
+    inflate to its ISIZE bytes with the CRC-32 of its trailer, and the reason."""
+    lib = load_library()
+    text, n, ms = C.c_void_p(), C.c_int64(0), C.c_double(0.0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_bgzf_inflate(os.fsencode(path), int(device), C.byref(text), C.byref(n), C.byref(ms), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(text, n.value), ms.value
+    finally:
+        lib.smg_count_free(text)

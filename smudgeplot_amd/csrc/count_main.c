@@ -2,7 +2,8 @@
  *
  *  smg_count -- count the canonical k-mers of FASTA / FASTQ reads on the GPU and write them as a FastK
  *               k-mer table (format F: stub + one hidden part file, 3-byte prefix index), plus the
- *               k-mer count histogram that `smudgeplot cutoff` reads.
+ *               k-mer count histogram that `smudgeplot cutoff` reads.  The reads are plain or block-gzipped (BGZF, what
+ *               bgzip writes: inflated on the device); any other gzip file is refused.
  *
  *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.  With -e it is
  *  that step and `hetmers` in one process: the counted table stays in device memory and is trimmed, closed under reverse
@@ -42,15 +43,20 @@ static void usage(void)
   exit(1);
 }
 
-/* the first input without its directory-independent suffix: reads.fq -> reads */
+/* the first input without its directory-independent suffix: reads.fq -> reads, reads.fq.gz -> reads */
 static char *default_root(const char *name)
 { static const char *suffix[] = { ".fastq", ".fasta", ".fq", ".fa", ".fna", ".fas", NULL };
-  int i;
-  for (i = 0; suffix[i] != NULL; i++)
-    { int epos = (int) strlen(name) - (int) strlen(suffix[i]);
-      if (epos > 0 && strcasecmp(name + epos, suffix[i]) == 0) return strndup(name, (size_t) epos);
+  static const char *packed[] = { ".gz", ".bgz", NULL };
+  int i, len = (int) strlen(name);
+  for (i = 0; packed[i] != NULL; i++)
+    { int epos = len - (int) strlen(packed[i]);
+      if (epos > 0 && strcasecmp(name + epos, packed[i]) == 0) { len = epos; break; }
     }
-  return strdup(name);
+  for (i = 0; suffix[i] != NULL; i++)
+    { int epos = len - (int) strlen(suffix[i]);
+      if (epos > 0 && strncasecmp(name + epos, suffix[i], strlen(suffix[i])) == 0) return strndup(name, (size_t) epos);
+    }
+  return strndup(name, (size_t) len);
 }
 
 /* remove what a run that fails half way has written */
@@ -205,7 +211,12 @@ int main(int argc, char *argv[])
         }
     }
   if (verbose)
-    { fprintf(stderr, "  %lld bases, %lld %d-mers, %lld distinct, %lld with count >= %d, %lld batch%s\n", (long long) st.bases,
+    { for (i = 1; i < j; i++)
+        { int64_t blocks = 0, text = 0;
+          if (smg_count_bgzf_scan(argv[i], &blocks, &text, NULL, 0) == SMG_OK)
+            fprintf(stderr, "  %s: BGZF, %lld blocks, %lld text bytes, inflated on the device\n", argv[i], (long long) blocks, (long long) text);
+        }
+      fprintf(stderr, "  %lld bases, %lld %d-mers, %lld distinct, %lld with count >= %d, %lld batch%s\n", (long long) st.bases,
               (long long) st.windows, kmer, (long long) st.distinct, (long long) st.kept, minval, (long long) st.batches,
               st.batches == 1 ? "" : "es");
       fprintf(stderr, "  %d key range%s, packed input %.3f GB on the device; ms: pack %.3f  plan %.3f", (int) parts.used,

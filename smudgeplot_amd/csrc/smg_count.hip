@@ -9,6 +9,8 @@
 //   merge   the batch list and the running distinct list are both duplicate free: after sorting their concatenation
 //           a k-mer occurs at most twice and kc_merge_write adds the right-hand neighbour (uint32, saturating)
 //   finish  kc_finish_flag (histogram, trim flag) + scan + kc_finish_compact (k-mers, uint16 counts clamped to 32767)
+//   A block-gzipped (BGZF) file goes the same way: its reader thread copies whole members to the device, inf_members
+//           inflates them one per wave and checks their CRC-32, and the text comes back to the same parser
 // A batch boundary never loses or doubles a window: a piece that does not continue the byte in front of it in the
 // batch buffer is preceded by a separator and the last k-1 bytes of its file's stream (no whole window fits in those).
 //
@@ -31,7 +33,9 @@
 //   smg_count_kernels.hpp  all kc_* device code.  Earlier records (profiles/*.md) name kernels that have since been merged:
 //                          kc_extract_packed<W> is kc_extract_store<W, 12>, kc_extract_fine<W> is kc_extract_store<W, 24>,
 //                          kc_bins is kc_bins<false>, kc_subbins is kc_bins<true>, kc_bin / kc_bin24 are kc_bin<12> / kc_bin<24>
-//   smg_count_reader.hpp   host only: the FASTA / FASTQ parser, the reader threads and their ring of blocks (read_files)
+//   smg_count_reader.hpp   host only: the FASTA / FASTQ parser, the reader threads and their ring of blocks (read_files), the
+//                          members of a BGZF file (bgzf_walk, bgzf_feed) and the Inflater they are handed to
+//   smg_inflate.hpp        DEFLATE, one BGZF member per wave: inf_members and the decoder it shares with the host check
 //   smg_count_plan.hpp     host only: the memory plan, how buffers grow, the cuts of the key ranges
 //   smg_count_parts.hpp    the parts of the device driver, each owning its buffers: Run (what they share), Batch, Distinct,
 //                          Store, Table
@@ -54,6 +58,7 @@
 #include "smg_count_reader.hpp"
 #include "smg_count_plan.hpp"
 #include "smg_count_parts.hpp"
+#include "smg_inflate.hpp"
 
 // where a run puts its results (the arguments of the C ABI)
 struct Out
@@ -261,6 +266,95 @@ struct Counter
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+//  the Inflater of the device: one per reader thread, on a stream of its own
+// ---------------------------------------------------------------------------------------------------------------
+
+static_assert(sizeof(InfBlock) == sizeof(BgzfBlock) && sizeof(BgzfBlock) == 20, "the kernel reads the reader's blocks as they are");
+
+struct DeviceInflater : Inflater
+{ int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uint8_t *h_text = nullptr, *d_chunk = nullptr, *d_text = nullptr;
+  uint32_t *h_status = nullptr, *d_status = nullptr;
+  InfBlock *d_blk = nullptr;
+  double ms_kernel = 0;
+  int64_t launches = 0;
+
+  // pinned and device memory for a chunk, its blocks, their text and statuses; 0 or the HIP error
+  hipError_t init(int dev)
+  { device = dev;
+    hipError_t e;
+    if ((e = hipSetDevice(dev)) != hipSuccess) return e;
+    if ((e = hipStreamCreate(&stream)) != hipSuccess) return e;
+    if ((e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **) &chunk, SMG_COUNT_BGZF_CHUNK, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **) &blk, sizeof(BgzfBlock) * BGZF_MAX_BLOCKS, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **) &h_text, BGZF_TEXT, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipHostMalloc((void **) &h_status, sizeof(uint32_t) * BGZF_MAX_BLOCKS, hipHostMallocDefault)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **) &d_chunk, SMG_COUNT_BGZF_CHUNK)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **) &d_blk, sizeof(InfBlock) * BGZF_MAX_BLOCKS)) != hipSuccess) return e;
+    if ((e = hipMalloc((void **) &d_text, BGZF_TEXT)) != hipSuccess) return e;
+    return hipMalloc((void **) &d_status, sizeof(uint32_t) * BGZF_MAX_BLOCKS);
+  }
+  ~DeviceInflater() override
+  { (void) hipFree(d_status); (void) hipFree(d_text); (void) hipFree(d_blk); (void) hipFree(d_chunk);
+    (void) hipHostFree(h_status); (void) hipHostFree(h_text); (void) hipHostFree(blk); (void) hipHostFree(chunk);
+    if (ev0) (void) hipEventDestroy(ev0);
+    if (ev1) (void) hipEventDestroy(ev1);
+    if (stream) (void) hipStreamDestroy(stream);
+  }
+
+  const char *reason(int status) const override { return inflate_reason(status); }
+
+  // H2D of the members, the kernel, D2H of statuses and text.  The reader has bounded every block: its payload lies
+  // in the chunk, its text in BGZF_TEXT bytes, and the kernel stays inside both whatever the payload says.
+  int inflate(int n, const uint8_t **text, int *bad, char *errbuf, size_t errlen) override
+  { size_t in_end = 0, out_end = 0;
+    for (int i = 0; i < n; i++)
+      { const size_t ie = (size_t) blk[i].in_off + blk[i].clen, oe = (size_t) blk[i].out_off + blk[i].isize;
+        if (ie > in_end) in_end = ie;
+        if (oe > out_end) out_end = oe;
+      }
+    if (n < 1 || n > BGZF_MAX_BLOCKS || in_end > (size_t) SMG_COUNT_BGZF_CHUNK || out_end > BGZF_TEXT)
+      return fail(errbuf, errlen, SMG_EINVAL, "internal error: %d BGZF blocks of %zu bytes with %zu bytes of text in one launch", n, in_end, out_end);
+#define ICHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) \
+      return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (%s)", hipGetErrorString(_e), #call); } while (0)
+    float ms = 0;
+    ICHK(hipSetDevice(device));                                // (a reader thread has not chosen its device yet)
+    ICHK(hipMemcpyAsync(d_chunk, chunk, in_end, hipMemcpyHostToDevice, stream));
+    ICHK(hipMemcpyAsync(d_blk, blk, sizeof(InfBlock) * (size_t) n, hipMemcpyHostToDevice, stream));
+    ICHK(hipEventRecord(ev0, stream));
+    hipLaunchKernelGGL(inf_members, dim3((unsigned) n), dim3(64), 0, stream, d_chunk, d_blk, n, d_text, d_status);
+    ICHK(hipGetLastError());
+    ICHK(hipEventRecord(ev1, stream));
+    ICHK(hipMemcpyAsync(h_status, d_status, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    if (out_end) ICHK(hipMemcpyAsync(h_text, d_text, out_end, hipMemcpyDeviceToHost, stream));
+    ICHK(hipStreamSynchronize(stream));
+    ICHK(hipEventElapsedTime(&ms, ev0, ev1));
+#undef ICHK
+    ms_kernel += ms; launches++;
+    for (int i = 0; i < n; i++)
+      if (h_status[i] != INF_OK) { *bad = i; return h_status[i] < INF_NSTATUS ? (int) h_status[i] : INF_NSTATUS; }
+    *text = h_text;
+    return 0;
+  }
+};
+
+// a device inflater, or the error: the device is checked as Counter::init checks it
+static int new_inflater(int device, std::unique_ptr<DeviceInflater> &out, char *errbuf, size_t errlen)
+{ int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(errbuf, errlen, SMG_ENODEV, "no HIP device: the k-mer counter has no CPU fallback%s", "");
+  if (device < 0 || device >= ndev) return fail(errbuf, errlen, SMG_EINVAL, "device %d of %d", device, ndev);
+  out.reset(new DeviceInflater());
+  const hipError_t e = out->init(device);
+  if (e != hipSuccess)
+    return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "cannot set up the BGZF inflater: %s", hipGetErrorString(e));
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 //  entry points
 // ---------------------------------------------------------------------------------------------------------------
 
@@ -297,9 +391,24 @@ static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, i
 
 #define RING_BLOCK ((size_t) 8 << 20)
 
+// (the inflaters of the reader threads that meet a BGZF file are set up by the survey, before Counter::init reads the
+//  free device memory, so that the plan sees what is left)
 static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
-{ return count_run(opts, io, paths && npaths >= 1, npaths,
-    [&](int64_t *bound) { return survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen); },
+{ std::vector<std::unique_ptr<DeviceInflater>> own;
+  std::vector<Inflater *> infl;
+  return count_run(opts, io, paths && npaths >= 1, npaths,
+    [&](int64_t *bound)
+      { std::vector<char> bgzf;
+        RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf));
+        const int nthr = reader_threads(opts->host_threads, npaths);
+        own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
+        for (int f = 0; f < npaths; f++)
+          if (bgzf[(size_t) f] && !own[(size_t) (f % nthr)])
+            { RCHK(new_inflater(opts->device, own[(size_t) (f % nthr)], errbuf, errlen));
+              infl[(size_t) (f % nthr)] = own[(size_t) (f % nthr)].get();
+            }
+        return 0;
+      },
     [&](Counter &c, double *t_read)
       { const int nthr = reader_threads(opts->host_threads, npaths);
         std::vector<uint8_t *> pinned;
@@ -312,7 +421,8 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
             pinned.push_back(p);
           }
         return read_files(paths, npaths, nthr, pinned.data(), (int) pinned.size(), RING_BLOCK,
-                          [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, errbuf, errlen);
+                          [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, errbuf, errlen,
+                          infl.data());
       }, errbuf, errlen);
 }
 
@@ -326,6 +436,44 @@ static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts
         *t_read = now_ms();
         return 0;
       }, errbuf, errlen);
+}
+
+// members and text bytes of a BGZF file; what is not BGZF is refused with the words of the counting calls
+static int bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen)
+{ if (!path || !blocks || !text_bytes) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  const int fd = open(path, O_RDONLY);
+  if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  uint8_t magic[2] = { 0, 0 };
+  const ssize_t got = pread(fd, magic, 2, 0);
+  int rc = bgzf_probe(fd, path, errbuf, errlen);
+  if (rc == 1)
+    rc = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b
+           ? fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path)
+           : fail(errbuf, errlen, SMG_EINVAL, "%s is not BGZF: it does not begin with a gzip header", path);
+  else if (rc == 0) rc = bgzf_walk(fd, path, blocks, text_bytes, errbuf, errlen);
+  close(fd);
+  return rc;
+}
+
+static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen)
+{ if (!text || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  int64_t blocks = 0, bytes = 0;
+  RCHK(bgzf_scan(path, &blocks, &bytes, errbuf, errlen));
+  std::unique_ptr<DeviceInflater> infl;
+  RCHK(new_inflater(device, infl, errbuf, errlen));
+  struct Fd { int fd; ~Fd() { if (fd >= 0) close(fd); } } f{ open(path, O_RDONLY) };
+  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  std::unique_ptr<uint8_t, void (*)(void *)> buf((uint8_t *) malloc((size_t) bytes + 1), free);
+  if (!buf) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
+  int64_t have = 0;
+  RCHK(bgzf_feed(f.fd, path, *infl, [&](const uint8_t *t, size_t m)
+    { if (have + (int64_t) m > bytes) return fail(errbuf, errlen, SMG_EFORMAT, "%s changed while it was read", path);
+      memcpy(buf.get() + have, t, m); have += (int64_t) m;
+      return 0;
+    }, errbuf, errlen));
+  *text = buf.release(); *n = have;
+  if (ms_kernel) *ms_kernel = infl->ms_kernel;
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -375,6 +523,12 @@ extern "C" int smg_count_memory_plan(int32_t kmer, uint64_t free_bytes, int64_t 
 
 extern "C" int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { GUARD(parse_path(path, seq, n, errbuf, errlen)) }
+
+extern "C" int smg_count_bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen)
+{ GUARD(bgzf_scan(path, blocks, text_bytes, errbuf, errlen)) }
+
+extern "C" int smg_count_bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen)
+{ GUARD(bgzf_inflate(path, device, text, n, ms_kernel, errbuf, errlen)) }
 
 extern "C" void smg_count_free(void *p) { free(p); }
 

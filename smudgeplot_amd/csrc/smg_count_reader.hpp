@@ -1,12 +1,18 @@
 // smg_count_reader.hpp -- the host side in front of the k-mer counter: FASTA / FASTQ files -> stripped sequence bytes, and
 // the reader threads that deliver them block by block (smg_count.hip holds the map of the whole counter).  Host only, no
 // HIP: `make reader_check` runs it under the address, undefined-behaviour and thread sanitizers (reader_check.cpp).
+//
+// A file may be block-gzipped (BGZF, what bgzip and htslib write): a gzip file of independent members of at most 64 KiB,
+// each with its length in its header (the BC subfield) and its CRC-32 and text length in its trailer.  This file finds
+// the members; their text comes from an Inflater, which the counter implements on the device (smg_inflate.hpp) and a
+// reader without one refuses.  Any other gzip file is refused as it always was.
 
 #pragma once
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -89,6 +95,167 @@ struct Parser
   }
 };
 
+
+// ---------------------------------------------------------------------------------------------------------------
+//  BGZF: finding the members
+// ---------------------------------------------------------------------------------------------------------------
+
+#define BGZF_MAX_ISIZE  65536                                  // text bytes of one member
+#define BGZF_MAX_BLOCKS 65536                                  // members of one call of an Inflater
+#define BGZF_TEXT       ((size_t) 4 * SMG_COUNT_BGZF_CHUNK)    // text bytes of one call of an Inflater
+
+// one member for the inflater: its DEFLATE payload at chunk[in_off .. in_off + clen), its text at text[out_off .. + isize)
+struct BgzfBlock { uint32_t in_off, clen, out_off, isize, crc; };
+
+// "These whole blocks of this buffer" -> "their text, or the first bad block and why".  The reader fills chunk (pinned
+// where the inflater is the device's) and blk[0 .. n) and calls inflate: 0 and *text (valid until the next call), or
+// > 0: the status (smg_inflate.hpp) of the first block that is not ok, *bad its index, or < 0: an error code, with message.
+struct Inflater
+{ uint8_t *chunk = nullptr;                                    // SMG_COUNT_BGZF_CHUNK bytes
+  BgzfBlock *blk = nullptr;                                    // BGZF_MAX_BLOCKS
+  virtual int inflate(int n, const uint8_t **text, int *bad, char *errbuf, size_t errlen) = 0;
+  virtual const char *reason(int status) const = 0;
+  virtual ~Inflater() {}
+};
+
+// The header of a member in p[0 .. avail): 0 BGZF (*blen bytes in all, *hlen of them header), 1 not BGZF, 2 more bytes
+// are needed to tell.  BGZF is ID1 31, ID2 139, CM 8, FLG 4 and a BC subfield of length 2 somewhere in the extra field.
+static inline int bgzf_header(const uint8_t *p, size_t avail, int64_t *blen, int *hlen)
+{ static const uint8_t magic[4] = { 31, 139, 8, 4 };
+  if (memcmp(p, magic, avail < 4 ? avail : 4) != 0) return 1;
+  if (avail < 12) return 2;
+  const size_t xlen = (size_t) p[10] | (size_t) p[11] << 8;
+  if (xlen < 6) return 1;
+  for (size_t q = 12; q + 4 <= 12 + xlen; )
+    { if (q + 4 > avail) return 2;
+      const size_t slen = (size_t) p[q + 2] | (size_t) p[q + 3] << 8;
+      if (q + 4 + slen > 12 + xlen) return 1;
+      if (p[q] == 'B' && p[q + 1] == 'C' && slen == 2)
+        { if (q + 6 > avail) return 2;
+          *blen = ((int64_t) p[q + 4] | (int64_t) p[q + 5] << 8) + 1;
+          *hlen = (int) (12 + xlen);
+          return 0;
+        }
+      q += 4 + slen;
+    }
+  return 1;
+}
+
+static inline int bgzf_bad(char *errbuf, size_t errlen, const char *path, int64_t off, const char *why)
+{ return fail(errbuf, errlen, SMG_EFORMAT, "%s: BGZF block at offset %lld: %s", path, (long long) off, why); }
+
+// what every member is checked for before anything is inflated; p[0 .. avail) are the bytes of the file from `off` on
+static inline int bgzf_member(const uint8_t *p, size_t avail, const char *path, int64_t off, int64_t fsize, int64_t *blen, int *hlen,
+                              char *errbuf, size_t errlen)
+{ const int rc = bgzf_header(p, avail, blen, hlen);
+  if (rc == 1) return bgzf_bad(errbuf, errlen, path, off, "not a BGZF member (gzip with the BC subfield)");
+  if (rc == 2) return (int64_t) avail < fsize - off ? 2 : bgzf_bad(errbuf, errlen, path, off, "the header is cut off by the end of the file");
+  if (*blen < *hlen + 8) return bgzf_bad(errbuf, errlen, path, off, "BSIZE is smaller than the header and the trailer");
+  if (off + *blen > fsize) return bgzf_bad(errbuf, errlen, path, off, "BSIZE reaches past the end of the file");
+  return 0;
+}
+
+// is the file BGZF by its first member?  0 yes, 1 no, SMG_EINVAL read error
+static inline int bgzf_probe(int fd, const char *path, char *errbuf, size_t errlen)
+{ std::vector<uint8_t> h(32);
+  for (;;)
+    { const ssize_t got = pread(fd, h.data(), h.size(), 0);
+      if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
+      int64_t blen = 0; int hlen = 0;
+      const int rc = got == 0 ? 1 : bgzf_header(h.data(), (size_t) got, &blen, &hlen);
+      if (rc != 2 || (size_t) got < h.size()) return rc == 0 ? 0 : rc == 2 && got >= 4 ? 0 : 1;      // (a cut header: the walk says where)
+      h.resize(12 + 65536);
+    }
+}
+
+// From header to header: members and the sum of their ISIZE fields, one small read a member (the trailer of one and the
+// header of the next are neighbours).  The inflater enforces that a member gives exactly ISIZE bytes, so the sum bounds
+// the text of a lying file too.
+static inline int bgzf_walk(int fd, const char *path, int64_t *blocks, int64_t *text, char *errbuf, size_t errlen)
+{ struct stat sb;
+  if (fstat(fd, &sb) != 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
+  const int64_t fsize = (int64_t) sb.st_size;
+  std::vector<uint8_t> h(8 + 12 + 65536 + 8);
+  int64_t off = 0, nb = 0, nt = 0;
+  size_t have = 0;                                             // bytes of h from `off` on
+  while (off < fsize)
+    { int64_t blen = 0; int hlen = 0;
+      int rc = have ? bgzf_member(h.data(), have, path, off, fsize, &blen, &hlen, errbuf, errlen) : 2;
+      if (rc == 2)
+        { const ssize_t got = pread(fd, h.data(), have ? 12 + 65536 : 18, off);
+          if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+          have = (size_t) got;
+          rc = bgzf_member(h.data(), have, path, off, fsize, &blen, &hlen, errbuf, errlen);
+          if (rc == 2)
+            { const ssize_t more = pread(fd, h.data(), 12 + 65536, off);
+              if (more < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+              have = (size_t) more;
+              rc = bgzf_member(h.data(), have, path, off, fsize, &blen, &hlen, errbuf, errlen);
+              if (rc == 2) return bgzf_bad(errbuf, errlen, path, off, "the header is cut off by the end of the file");
+            }
+        }
+      if (rc) return rc;
+      const ssize_t got = pread(fd, h.data(), 8 + 18, off + blen - 8);           // this trailer, the next header
+      if (got < 8) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+      const uint32_t isize = (uint32_t) h[4] | (uint32_t) h[5] << 8 | (uint32_t) h[6] << 16 | (uint32_t) h[7] << 24;
+      if (isize > BGZF_MAX_ISIZE) return bgzf_bad(errbuf, errlen, path, off, "ISIZE is above 65536");
+      nb++; nt += isize;
+      off += blen;
+      have = (size_t) got - 8;
+      memmove(h.data(), h.data() + 8, have);
+    }
+  *blocks = nb; *text = nt;
+  return 0;
+}
+
+// The text of a BGZF file, chunk after chunk: whole members into infl.chunk, as many as fit it, their text to
+// consume(text, n) -> 0 or what ends the run.
+template <class Consume>
+static inline int bgzf_feed(int fd, const char *path, Inflater &infl, Consume &&consume, char *errbuf, size_t errlen)
+{ struct stat sb;
+  if (fstat(fd, &sb) != 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
+  const int64_t fsize = (int64_t) sb.st_size;
+  std::vector<int64_t> at((size_t) BGZF_MAX_BLOCKS);
+  int64_t off = 0;
+  while (off < fsize)
+    { const int64_t want = fsize - off < (int64_t) SMG_COUNT_BGZF_CHUNK ? fsize - off : (int64_t) SMG_COUNT_BGZF_CHUNK;
+      int64_t got = 0;
+      while (got < want)
+        { const ssize_t r = pread(fd, infl.chunk + got, (size_t) (want - got), off + got);
+          if (r < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+          if (r == 0) break;
+          got += r;
+        }
+      int n = 0;
+      int64_t p = 0;
+      size_t nt = 0;
+      while (p < got && n < BGZF_MAX_BLOCKS)
+        { int64_t blen = 0; int hlen = 0;
+          const int rc = bgzf_member(infl.chunk + p, (size_t) (got - p), path, off + p, got < want ? off + got : fsize, &blen, &hlen, errbuf, errlen);
+          if (rc < 0) return rc;
+          if (rc == 2 || p + blen > got) break;                 // the member goes on in the next chunk
+          const uint8_t *t = infl.chunk + p + blen - 8;
+          const uint32_t crc = (uint32_t) t[0] | (uint32_t) t[1] << 8 | (uint32_t) t[2] << 16 | (uint32_t) t[3] << 24;
+          const uint32_t isize = (uint32_t) t[4] | (uint32_t) t[5] << 8 | (uint32_t) t[6] << 16 | (uint32_t) t[7] << 24;
+          if (isize > BGZF_MAX_ISIZE) return bgzf_bad(errbuf, errlen, path, off + p, "ISIZE is above 65536");
+          if (nt + isize > BGZF_TEXT) break;
+          infl.blk[n] = BgzfBlock{ (uint32_t) (p + hlen), (uint32_t) (blen - hlen - 8), (uint32_t) nt, isize, crc };
+          at[(size_t) n] = off + p;
+          n++; nt += isize; p += blen;
+        }
+      if (n == 0) return bgzf_bad(errbuf, errlen, path, off, "the member is cut off by the end of the file");
+      const uint8_t *text = nullptr;
+      int bad = 0;
+      const int rc = infl.inflate(n, &text, &bad, errbuf, errlen);
+      if (rc < 0) return rc;
+      if (rc > 0) return bgzf_bad(errbuf, errlen, path, at[(size_t) bad], infl.reason(rc));
+      const int crc = consume(text, nt);
+      if (crc) return crc;
+      off += p;
+    }
+  return 0;
+}
+
 static inline int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases, char *errbuf, size_t errlen)
 { std::vector<uint8_t> buf((size_t) 4 << 20);
   Parser ps(sink);
@@ -99,6 +266,21 @@ static inline int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases,
       const int rc = ps.feed(buf.data(), (size_t) got, path, errbuf, errlen);
       if (rc) return rc;
     }
+  if (bases) *bases = ps.bases;
+  return 0;
+}
+
+// one file to the sink, routed by its own header: BGZF through the inflater, anything else as it is
+static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, int64_t *bases, char *errbuf, size_t errlen)
+{ const int z = bgzf_probe(fd, path, errbuf, errlen);
+  if (z < 0) return z;
+  if (z == 1) return parse_fd(fd, path, sink, bases, errbuf, errlen);
+  if (!infl)
+    return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
+                "use smg_count_bgzf_inflate or one of the counting calls", path);
+  Parser ps(sink);
+  const int rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n) { return ps.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+  if (rc) return rc;
   if (bases) *bases = ps.bases;
   return 0;
 }
@@ -126,7 +308,7 @@ static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *
   if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
   GrowSink sink;
   int rc;
-  try { rc = parse_fd(fd, path, sink, nullptr, errbuf, errlen); }
+  try { rc = parse_file(fd, path, sink, nullptr, nullptr, errbuf, errlen); }
   catch (...) { close(fd); throw; }
   close(fd);
   if (rc) return rc;
@@ -137,20 +319,32 @@ static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *
 }
 
 // Refuse what cannot be read before anything is set up for it.  *bound = the most sequence the files can hold: their
-// sizes, and k + 1 bytes per file for the separator and the tail a batch boundary puts in front of a piece.
-static inline int survey_files(const char *const *paths, int npaths, int k, int64_t *bound, char *errbuf, size_t errlen)
+// sizes (of a BGZF file: the text its members announce), and k + 1 bytes per file for the separator and the tail a batch
+// boundary puts in front of a piece.  bgzf (may be null): per file, is it BGZF?
+static inline int survey_files(const char *const *paths, int npaths, int k, int64_t *bound, char *errbuf, size_t errlen,
+                               std::vector<char> *bgzf = nullptr)
 { *bound = 0;
+  if (bgzf) bgzf->assign((size_t) npaths, 0);
   for (int f = 0; f < npaths; f++)
     { uint8_t magic[2] = { 0, 0 };
       const int fd = open(paths[f], O_RDONLY);
       if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
       const ssize_t got = read(fd, magic, 2);
-      const off_t size = lseek(fd, 0, SEEK_END);
+      int64_t size = (int64_t) lseek(fd, 0, SEEK_END);
+      int rc = 0;
+      if (got < 0 || size < 0) rc = fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
+      else if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
+        { int64_t blocks = 0;
+          rc = bgzf_probe(fd, paths[f], errbuf, errlen);
+          if (rc == 1) rc = fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", paths[f]);
+          else if (rc == 0)
+            { rc = bgzf_walk(fd, paths[f], &blocks, &size, errbuf, errlen);
+              if (bgzf) (*bgzf)[(size_t) f] = 1;
+            }
+        }
       close(fd);
-      if (got < 0 || size < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
-      if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
-        return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", paths[f]);
-      *bound += (int64_t) size + k + 1;
+      if (rc) return rc;
+      *bound += size + k + 1;
     }
   return 0;
 }
@@ -207,7 +401,7 @@ struct RingSink : Sink
   }
 };
 
-static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step)
+static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step, Inflater *infl)
 { for (int f = first; f < npaths; f += step)
     { char eb[512]; eb[0] = 0;
       int rc = 0;
@@ -217,7 +411,7 @@ static inline void reader_main(Ring *r, const char *const *paths, int npaths, in
           const int fd = open(paths[f], O_RDONLY);
           if (fd < 0) rc = fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f]);
           else
-            { rc = parse_fd(fd, paths[f], sink, &bases, eb, sizeof(eb));
+            { rc = parse_file(fd, paths[f], sink, infl, &bases, eb, sizeof(eb));
               close(fd);
             }
           if (rc == 0) sink.done();
@@ -246,9 +440,10 @@ static inline int reader_threads(int want, int npaths)
 // After the first error, a reader's or the consumer's, nothing more is consumed; the blocks in flight are drained and
 // every thread is joined before this returns.  A reader's error (code and message) goes in front of the consumer's, whose
 // message is its own business.  *bases = sequence bytes read, *t_last = now_ms() when the last reader was done.
+// infl (may be null: BGZF files are refused): the inflater of thread j, or null where none of its files is BGZF.
 template <class Consume>
 static inline int read_files(const char *const *paths, int npaths, int nthr, uint8_t *const *blocks, int nblocks, size_t block, Consume &&consume,
-                             int64_t *bases, double *t_last, char *errbuf, size_t errlen)
+                             int64_t *bases, double *t_last, char *errbuf, size_t errlen, Inflater *const *infl = nullptr)
 { Ring ring;
   ring.block = block;
   ring.idle.assign(blocks, blocks + nblocks);
@@ -258,7 +453,7 @@ static inline int read_files(const char *const *paths, int npaths, int nthr, uin
   for (int j = 0; j < nthr && rc == 0; j++)
     { try
         { { std::unique_lock<std::mutex> lk(ring.m); ring.live++; }
-          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr);
+          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr, infl ? infl[j] : nullptr);
         }
       catch (...)
         { std::unique_lock<std::mutex> lk(ring.m);

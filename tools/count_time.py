@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """count_time.py -- stage times of the k-mer counter (libsmg_count.so) on seeded reads; the source of profiles/count_reads.md
-and profiles/count_partitioned.md.
+profiles/count_partitioned.md and profiles/count_bgzf.md.
 
   python tools/count_time.py [--bases 2e9] [--k 31] [--repeats 5] [--warmup 1] [--dir DIR]
                              [--partitions 1,2,4,8,16] [--max-entries N] [--random] [--steps gen,bases]
@@ -10,6 +10,12 @@ fails:  gen    reads of 150 bases from both strands of a seeded random genome (0
                stripped byte stream (reads.seq, one newline between reads) and as FASTQ (reads.fq)
         bases  smg_count_bases on reads.seq read into host memory: warm-up runs, then `repeats` timed runs
         files  smg_count_files on reads.fq (page cache warm after the first run), the same way
+        bgzf   (only where --steps names it) reads.fq written once more as BGZF at level 6 (reads.fq.gz, members of 65280 bytes);
+               then the survey (smg_count_bgzf_scan), smg_count_bgzf_inflate alone (kernel time, text bytes per second of kernel
+               and of wall time), smg_count_files on reads.fq.gz next to reads.fq, and as the baseline what a refused gzip file
+               used to cost: one zlib thread (`gzip -dc`, or Python's gzip where there is none) to a plain file, then the plain
+               run; and, where torch is there, the copy of the text to pinned host memory and back, which the route pays for
+               parsing on the host
 Stage times are the library's own (HIP events around extract, sort, reduce+merge, finish; host clock for read and wall).
 Printed: one JSON line per step and a markdown table of medians with the min-max spread.
 --partitions runs every timed step once per listed number of key ranges (0 = automatic); --max-entries is the library's test
@@ -84,7 +90,7 @@ def gen(args):
     # FASTQ with fixed-width records: @<10 digits>\n <read>\n +\n <quality>\n
     rec = np.empty((step, 12 + READ + 1 + 2 + READ + 1), dtype=np.uint8)
     with open(os.path.join(args.dir, "reads.fq"), "wb") as f:
-        for a in range(0, nreads if "files" in args.steps.split(",") else 0, step):
+        for a in range(0, nreads if {"files", "bgzf"} & set(args.steps.split(",")) else 0, step):
             n = min(step, nreads - a)
             r = rec[:n]
             r[:, 0] = ord("@")
@@ -131,8 +137,111 @@ def timed(args, what):
     print(json.dumps(out))
 
 
+def _bgzf_member(piece):
+    import struct
+    import zlib
+    c = zlib.compressobj(6, zlib.DEFLATED, -15)
+    z = c.compress(piece) + c.flush()
+    return (struct.pack("<4BI2BH2sHH", 31, 139, 8, 4, 0, 0, 255, 6, b"BC", 2, len(z) + 25) + z +
+            struct.pack("<II", zlib.crc32(piece), len(piece)))
+
+
+def bgzf(args):
+    import multiprocessing
+    import shutil as sh
+    from smudgeplot_amd import count
+    fq, gz, back = (os.path.join(args.dir, n) for n in ("reads.fq", "reads.fq.gz", "reads.back.fq"))
+    data = open(fq, "rb").read()
+    t0 = time.perf_counter()
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool, open(gz, "wb") as f:
+        for m in pool.imap(_bgzf_member, (data[a:a + 65280] for a in range(0, len(data), 65280)), chunksize=64):
+            f.write(m)
+        f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+    out = {"step": "bgzf", "k": args.k, "t": args.t, "warmup": args.warmup, "repeats": args.repeats, "text_bytes": len(data),
+           "file_bytes": os.path.getsize(gz), "write_s": time.perf_counter() - t0}
+    spread = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)}
+    scan, runs = [], []
+    for i in range(args.warmup + args.repeats):
+        t0 = time.perf_counter()
+        got = count.bgzf_scan(gz)
+        scan.append((time.perf_counter() - t0) * 1e3)
+    out["blocks"] = got["blocks"]
+    out["scan_ms"] = spread(scan[args.warmup:])
+    for i in range(args.warmup + args.repeats):
+        t0 = time.perf_counter()
+        text, ms = count.bgzf_inflate(gz)
+        runs.append((ms, (time.perf_counter() - t0) * 1e3))
+        assert len(text) == len(data) and (i or text == data)
+    del text
+    out["inflate_kernel_ms"] = spread([r[0] for r in runs[args.warmup:]])
+    out["inflate_wall_ms"] = spread([r[1] for r in runs[args.warmup:]])
+    tables = {}
+    for name, path in (("plain", fq), ("bgzf", gz)):
+        walls = []
+        for i in range(args.warmup + args.repeats):
+            table, hist, st = count.count_files([path], args.k, t=args.t, threads=args.threads)
+            walls.append(st["ms_wall"])
+        tables[name] = (table.packed, table.counts, hist)
+        out[f"count_{name}_wall_ms"] = spread(walls[args.warmup:])
+        out[f"count_{name}_read_ms"] = st["ms_read"]
+    out["tables_equal"] = all(np.array_equal(a, b) for a, b in zip(tables["plain"], tables["bgzf"]))
+    base = []
+    for i in range(max(1, args.repeats // 2)):
+        t0 = time.perf_counter()
+        if sh.which("gzip"):
+            with open(back, "wb") as f:
+                subprocess.run(["gzip", "-dc", gz], stdout=f, check=True)
+            out["baseline_tool"] = "gzip -dc"
+        else:
+            import gzip
+            with gzip.open(gz, "rb") as g, open(back, "wb") as f:
+                sh.copyfileobj(g, f, 1 << 22)
+            out["baseline_tool"] = "python gzip"
+        t1 = time.perf_counter()
+        _, _, st = count.count_files([back], args.k, t=args.t, threads=args.threads)
+        base.append(((t1 - t0) * 1e3, st["ms_wall"]))
+    out["baseline_decompress_ms"] = spread([b[0] for b in base])
+    out["baseline_total_ms"] = spread([b[0] + b[1] for b in base])
+    try:
+        import torch
+        h = torch.empty(len(data), dtype=torch.uint8).pin_memory()
+        d = torch.empty(len(data), dtype=torch.uint8, device="cuda")
+        trips = []
+        for i in range(args.warmup + args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            h.copy_(d); d.copy_(h)
+            torch.cuda.synchronize()
+            trips.append((time.perf_counter() - t0) * 1e3)
+        out["text_trip_ms"] = spread(trips[args.warmup:])
+    except Exception as e:                                            # (no torch, no device: the figure is left out)
+        out["text_trip_ms"] = None
+        out["text_trip_error"] = str(e)
+    print(json.dumps(out))
+
+
+def summarise_bgzf(b):
+    f = lambda v: f"{v['median']:.1f} ({v['min']:.1f} - {v['max']:.1f})"
+    n = b["text_bytes"]
+    lines = [f"\n### bgzf: {n:.3e} text bytes in {b['blocks']} blocks, {b['file_bytes']:.3e} bytes of file, {b['repeats']} runs after "
+             f"{b['warmup']} warm-up; ms as median (min - max)\n",
+             "| what | ms | text bytes/s at the median |", "|---|---|---|",
+             f"| survey (bgzf_scan) | {f(b['scan_ms'])} | {b['scan_ms']['median'] / b['blocks'] * 1e6:.0f} ms per million blocks |",
+             f"| bgzf_inflate, kernel | {f(b['inflate_kernel_ms'])} | {n / b['inflate_kernel_ms']['median'] * 1e3:.3e} |",
+             f"| bgzf_inflate, wall | {f(b['inflate_wall_ms'])} | {n / b['inflate_wall_ms']['median'] * 1e3:.3e} |",
+             f"| count_files, plain file, wall | {f(b['count_plain_wall_ms'])} | {n / b['count_plain_wall_ms']['median'] * 1e3:.3e} |",
+             f"| count_files, BGZF file, wall | {f(b['count_bgzf_wall_ms'])} | {n / b['count_bgzf_wall_ms']['median'] * 1e3:.3e} |",
+             f"| baseline: {b['baseline_tool']} to a plain file | {f(b['baseline_decompress_ms'])} | {n / b['baseline_decompress_ms']['median'] * 1e3:.3e} |",
+             f"| baseline: that and the plain run | {f(b['baseline_total_ms'])} | {n / b['baseline_total_ms']['median'] * 1e3:.3e} |"]
+    if b.get("text_trip_ms"):
+        lines.append(f"| the text to pinned host memory and back | {f(b['text_trip_ms'])} | "
+                     f"{b['text_trip_ms']['median'] / b['count_bgzf_wall_ms']['median']:.2f} of the BGZF run's wall time |")
+    lines.append(f"\ntables of the plain and the BGZF run equal: {b['tables_equal']}")
+    return "\n".join(lines)
+
+
 def summarise(res):
-    lines = []
+    lines = [summarise_bgzf(res["bgzf"])] if "bgzf" in res else []
     for what in ("bases", "files"):
         for parts, got in res.get(what, {}).get("by_partitions", {}).items():
             if "refused" in got:
@@ -163,7 +272,7 @@ def summarise(res):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", nargs="?", default="all", choices=["all", "gen", "bases", "files"])
+    ap.add_argument("step", nargs="?", default="all", choices=["all", "gen", "bases", "files", "bgzf"])
     ap.add_argument("--bases", type=float, default=2e9)
     ap.add_argument("--genome", type=float, default=5e7)
     ap.add_argument("--k", type=int, default=31)
@@ -183,6 +292,8 @@ def main():
         return gen(args)
     if args.step in ("bases", "files"):
         return timed(args, args.step)
+    if args.step == "bgzf":
+        return bgzf(args)
     own = args.dir is None
     d = args.dir or tempfile.mkdtemp(prefix="count_time_")
     res = {}
