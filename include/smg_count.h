@@ -5,6 +5,13 @@
  *     file of independent members of at most 64 KiB, found by the BC subfield of its first header), every file of a call
  *     routed by its own header; the members of a BGZF file are inflated on the device and their CRC-32 checked there;
  *     any other gzip file is refused (SMG_EINVAL: recompress it with bgzip, or decompress it);
+ *   - input: unaligned BAM (what PacBio HiFi reads are delivered in: a BGZF file whose text begins BAM\1), found by those
+ *     four bytes; its records are framed on the host and their 4-bit sequences unpacked on the device.  Its stripped stream:
+ *     in file order every record whose FLAG has neither 0x100 nor 0x800 set gives its l_seq bases, each code mapped through
+ *     "=ACMGRSVTWYHKDBN", one SMG_COUNT_SEPARATOR between two such records -- the stream of a FASTA file of the same reads.
+ *     The size of a BAM file bounds its bases as that of any BGZF file does, by the sum of its ISIZE fields: an over-estimate
+ *     by 1.5 or more, so a large BAM may be counted by key range where one pass would have done; the result is the same
+ *     whichever way it is counted.  CRAM is not gzip and is refused like any file that is neither FASTA nor FASTQ;
  *   - bases ACGTacgt code to 0..3, every other byte ends the current stretch, no k-mer spans two records;
  *   - every window of k bases counts once for the smaller of the k-mer and its reverse complement
  *     (left-aligned big-endian words, the order of the FastK table);
@@ -14,7 +21,8 @@
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
  * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
- * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan and smg_count_version need no device.
+ * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text and smg_count_version
+ * need no device.
  */
 #ifndef SMG_COUNT_H
 #define SMG_COUNT_H
@@ -48,6 +56,7 @@ extern "C" {
 #define SMG_COUNT_FINE_BINS  (1 << SMG_COUNT_FINE_BITS)   /* the ends of a range are values of the leading 24 bits  */
 #define SMG_COUNT_BGZF_CHUNK (16 << 20)  /* compressed bytes of a BGZF file that one launch of the inflate kernel takes (whole
                                             members; a reader thread holds one such buffer and 4 x as much for their text) */
+#define SMG_COUNT_BAM_TILE   4096      /* stripped bytes of a BAM file that one workgroup of the unpack kernel writes */
 
 typedef struct smg_count_opts
 { int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
@@ -175,6 +184,29 @@ int smg_count_bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, 
    smg_count_bgzf_scan, and SMG_EFORMAT "<path>: BGZF block at offset <o>: <reason>" for the first member that does not
    inflate to ISIZE bytes with the CRC-32 of its trailer.  SMG_ENODEV without a device.                                  */
 int smg_count_bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen);
+
+/* host only: the stripped stream (see the top of this file) of inflated BAM text, fed to the framer of the counting calls
+   in pieces of `piece` bytes (0: one piece), every record unpacked by the host routine that serves the records a piece
+   boundary cuts.  *seq is malloc'ed (smg_count_free), *nseq its bytes.  SMG_EFORMAT, "<text>: BAM header: <reason>" or
+   "<text>: BAM record at text offset <o>: <reason>" (o: where its block_size stands), for a negative l_text, n_ref, l_name
+   or l_seq, a block_size smaller than 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq, and a text that ends inside
+   the header or inside a record.                                                                                        */
+int smg_count_bam_text(const uint8_t *text, int64_t n, int64_t piece, uint8_t **seq, int64_t *nseq, char *errbuf, size_t errlen);
+
+/* the stripped stream of a whole BAM file by the route the counting calls take: inflated on `device`, framed on the host,
+   unpacked on the device, the records a boundary between two inflate calls cuts from the host.  *seq is malloc'ed
+   (smg_count_free), *nseq its bytes, *records (may be NULL) the contributing records, *ms_kernel (may be NULL) the sum of the
+   HIP-event times of the unpack kernel alone.  SMG_EINVAL for a file that is not BAM, the errors of smg_count_bgzf_inflate
+   with the path in place of <text> those of smg_count_bam_text.  SMG_ENODEV without a device.                            */
+int smg_count_bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t *nseq, int64_t *records, double *ms_kernel,
+                        char *errbuf, size_t errlen);
+
+/* host only: what the last call of this process that reads BAM (smg_count_files*, smg_count_bam_strip) read from the BAM
+   file it was given as `path`: its contributing records, their bases, and in ms[4] (may be NULL) the milliseconds its reader
+   thread spent on it: framing on the host (host clock), the inflate kernel, the unpack kernel (HIP events, summed over the
+   launches), the copies of the stripped bytes to the host (host clock).  SMG_EINVAL where that call read no such BAM file to
+   its end.                                                                                                              */
+int smg_count_bam_report(const char *path, int64_t *records, int64_t *bases, double *ms);
 
 void smg_count_free(void *p);
 const char *smg_count_version(void);

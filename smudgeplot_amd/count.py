@@ -1,9 +1,13 @@
 """ctypes binding of the k-mer counter (include/smg_count.h, libsmg_count.so, built in-tree).
 
 Reads in, canonical FastK-style k-mer table out: the step in front of `hetmers`.  There is no CPU
-fallback: the counting calls raise `CountError` without a HIP device; `parse` and `bgzf_scan` need none.
+fallback: the counting calls raise `CountError` without a HIP device; `parse`, `bgzf_scan` and `bam_text` need none.
 The input files are FASTA / FASTQ, plain or block-gzipped (BGZF, what `bgzip` writes); the members of a BGZF file are
-inflated on the device.  Any other gzip file is refused.
+inflated on the device.  Any other gzip file is refused.  Unaligned BAM (PacBio HiFi reads: a BGZF file whose text begins
+BAM\\1) is read too: its records are framed on the host and their 4-bit sequences unpacked on the device; its primary
+records (FLAG without 0x100 and 0x800) give the stream of a FASTA file of the same reads.  A BAM file is bounded by its text
+like any BGZF file, 1.5 times its bases or more, so it may be counted by key range where one pass would have done, with the
+same result.
 """
 
 from __future__ import annotations
@@ -18,6 +22,7 @@ from . import ktab
 MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
 FINE_BINS = 1 << 24                       # the ends of a range are values of the leading 24 bits where a bin was split
 BGZF_CHUNK = 16 << 20                     # compressed bytes of a BGZF file that one launch of the inflate kernel takes
+BAM_TILE = 4096                           # stripped bytes of a BAM file that one workgroup of the unpack kernel writes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
@@ -26,7 +31,7 @@ BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
            "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
            "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan",
-           "smg_count_bgzf_scan", "smg_count_bgzf_inflate"]
+           "smg_count_bgzf_scan", "smg_count_bgzf_inflate", "smg_count_bam_text", "smg_count_bam_strip", "smg_count_bam_report"]
 
 
 class CountError(RuntimeError):
@@ -98,6 +103,13 @@ def load_library():
     lib.smg_count_bgzf_inflate.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_char_p,
                                            C.c_size_t]
     lib.smg_count_bgzf_inflate.restype = C.c_int
+    lib.smg_count_bam_text.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_bam_text.restype = C.c_int
+    lib.smg_count_bam_strip.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+    lib.smg_count_bam_strip.restype = C.c_int
+    lib.smg_count_bam_report.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    lib.smg_count_bam_report.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
     lib.smg_count_free.restype = None
     lib.smg_count_version.restype = C.c_char_p
@@ -362,3 +374,49 @@ def bgzf_inflate(path, device=0):
         return C.string_at(text, n.value), ms.value
     finally:
         lib.smg_count_free(text)
+
+
+def bam_text(text, piece=0) -> bytes:
+    """Host only: the stripped stream of inflated BAM text (the primary records' bases through "=ACMGRSVTWYHKDBN", one '\\n'
+    between two of them), fed to the framer of the counting calls in pieces of `piece` bytes (0: one piece) and unpacked by
+    the host routine.  Raises CountError -4, "<text>: BAM header: ..." or "<text>: BAM record at text offset <o>: ...", for a
+    negative length field, a block_size too small for its fields and a text that ends inside the header or a record."""
+    lib = load_library()
+    buf = bytes(text)
+    seq, n = C.c_void_p(), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_bam_text(C.cast(C.c_char_p(buf), C.c_void_p), len(buf), int(piece), C.byref(seq), C.byref(n), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(seq, n.value)
+    finally:
+        lib.smg_count_free(seq)
+
+
+def bam_strip(path, device=0):
+    """The stripped stream of a whole BAM file by the route of the counting calls: inflated on the device, framed on the
+    host, unpacked on the device -> (bytes, contributing records, ms_kernel: the HIP-event time of the unpack kernel alone).
+    Raises CountError -2 for a file that is not BAM, -4 as bgzf_inflate and bam_text do."""
+    lib = load_library()
+    seq, n, rec, ms = C.c_void_p(), C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_bam_strip(os.fsencode(path), int(device), C.byref(seq), C.byref(n), C.byref(rec), C.byref(ms), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(seq, n.value), rec.value, ms.value
+    finally:
+        lib.smg_count_free(seq)
+
+
+def bam_report(path) -> dict:
+    """Host only: what the last call of this process that reads BAM (count_files*, bam_strip) read from the BAM file it was
+    given as `path` -> {"records", "bases", "ms_frame" (host clock), "ms_inflate", "ms_unpack" (HIP events of the two kernels),
+    "ms_d2h" (host clock: the stripped bytes to the host)}.  Raises CountError -2 where it read no such file to its end."""
+    lib = load_library()
+    rec, bases, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+    rc = lib.smg_count_bam_report(os.fsencode(path), C.byref(rec), C.byref(bases), ms)
+    if rc != 0:
+        raise CountError(rc, f"the last call read no BAM file {path} to its end")
+    return {"records": rec.value, "bases": bases.value, "ms_frame": ms[0], "ms_inflate": ms[1], "ms_unpack": ms[2], "ms_d2h": ms[3]}

@@ -3,7 +3,8 @@
  *  smg_count -- count the canonical k-mers of FASTA / FASTQ reads on the GPU and write them as a FastK
  *               k-mer table (format F: stub + one hidden part file, 3-byte prefix index), plus the
  *               k-mer count histogram that `smudgeplot cutoff` reads.  The reads are plain or block-gzipped (BGZF, what
- *               bgzip writes: inflated on the device); any other gzip file is refused.
+ *               bgzip writes: inflated on the device), or unaligned BAM (PacBio HiFi reads: the bases of its primary
+ *               records, unpacked on the device); any other gzip file is refused.
  *
  *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.  With -e it is
  *  that step and `hetmers` in one process: the counted table stays in device memory and is trimmed, closed under reverse
@@ -40,12 +41,14 @@ static void usage(void)
   fprintf(stderr, "            default is root of the first <reads> argument\n");
   fprintf(stderr, "      -v: verbose mode\n");
   fprintf(stderr, "      -T: number of reader threads (one input file each)\n");
+  fprintf(stderr, "\n");
+  fprintf(stderr, "      <reads>: FASTA or FASTQ, plain or block-gzipped (BGZF), or unaligned BAM (the bases of its primary records)\n");
   exit(1);
 }
 
-/* the first input without its directory-independent suffix: reads.fq -> reads, reads.fq.gz -> reads */
+/* the first input without its directory-independent suffix: reads.fq -> reads, reads.fq.gz -> reads, reads.bam -> reads */
 static char *default_root(const char *name)
-{ static const char *suffix[] = { ".fastq", ".fasta", ".fq", ".fa", ".fna", ".fas", NULL };
+{ static const char *suffix[] = { ".fastq", ".fasta", ".fq", ".fa", ".fna", ".fas", ".bam", NULL };
   static const char *packed[] = { ".gz", ".bgz", NULL };
   int i, len = (int) strlen(name);
   for (i = 0; packed[i] != NULL; i++)
@@ -144,7 +147,10 @@ int main(int argc, char *argv[])
   memset(&hst, 0, sizeof(hst));
   if (ethresh == 0)
     { if (smg_count_files_parts((const char *const *) (argv + 1), j - 1, &opts, &parts, &keys, &cnt, &n, &W, hist, &st, errbuf, sizeof(errbuf)) != SMG_OK)
-        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed"); exit(1); }
+        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed");
+          if (verbose) fprintf(stderr, "  nothing was written under the root name %s\n", root);
+          exit(1);
+        }
     }
   else
     { /* the table stays where it was counted; everything is computed before the first file is written */
@@ -153,7 +159,10 @@ int main(int argc, char *argv[])
       smg_opts ho;
       int rc;
       if (smg_count_files_device((const char *const *) (argv + 1), j - 1, &opts, &parts, &d_keys, &d_cnt, &n, &W, hist, &st, errbuf, sizeof(errbuf)) != SMG_OK)
-        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed"); exit(1); }
+        { fprintf(stderr, "%s: %s\n", Prog_Name, errbuf[0] ? errbuf : "GPU engine failed");
+          if (verbose) fprintf(stderr, "  nothing was written under the root name %s\n", root);
+          exit(1);
+        }
       plot = (int64_t *) malloc(sizeof(int64_t) * SMG_PLOT_CELLS);
       rc = plot == NULL ? SMG_ENOMEM : SMG_OK;
       if (rc == SMG_OK && !no_table)                              /* a host copy for the table file, through an engine */
@@ -215,6 +224,8 @@ int main(int argc, char *argv[])
         { int64_t blocks = 0, text = 0;
           if (smg_count_bgzf_scan(argv[i], &blocks, &text, NULL, 0) == SMG_OK)
             fprintf(stderr, "  %s: BGZF, %lld blocks, %lld text bytes, inflated on the device\n", argv[i], (long long) blocks, (long long) text);
+          if (smg_count_bam_report(argv[i], &blocks, &text, NULL) == SMG_OK)
+            fprintf(stderr, "  %s: BAM, %lld records, %lld bases, unpacked on the device\n", argv[i], (long long) blocks, (long long) text);
         }
       fprintf(stderr, "  %lld bases, %lld %d-mers, %lld distinct, %lld with count >= %d, %lld batch%s\n", (long long) st.bases,
               (long long) st.windows, kmer, (long long) st.distinct, (long long) st.kept, minval, (long long) st.batches,

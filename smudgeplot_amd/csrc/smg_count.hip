@@ -1,4 +1,4 @@
-// smg_count.hip -- k-mer counter for one MI355X (gfx950, wave64): FASTA / FASTQ in, canonical k-mer table out.
+// smg_count.hip -- k-mer counter for one MI355X (gfx950, wave64): FASTA / FASTQ / unaligned BAM in, canonical k-mer table out.
 //
 // What FastK does in front of `hetmers`, on the device (include/smg_count.h is the contract):
 //   host    reader threads (one file each) strip records to sequence bytes, one separator byte between records, into
@@ -11,6 +11,10 @@
 //   finish  kc_finish_flag (histogram, trim flag) + scan + kc_finish_compact (k-mers, uint16 counts clamped to 32767)
 //   A block-gzipped (BGZF) file goes the same way: its reader thread copies whole members to the device, inf_members
 //           inflates them one per wave and checks their CRC-32, and the text comes back to the same parser
+//   A BAM file is a BGZF file whose text begins BAM\1: the reader thread frames its records on the host (fixed fields only)
+//           and bam_unpack turns their 4-bit sequences into stripped bytes where the inflate kernel left the text; those
+//           come back into the same ring.  Its bound is that of a BGZF file (the text), an over-estimate of its bases by
+//           1.5 or more: it may be counted by key range where one pass would have done, with the same result
 // A batch boundary never loses or doubles a window: a piece that does not continue the byte in front of it in the
 // batch buffer is preceded by a separator and the last k-1 bytes of its file's stream (no whole window fits in those).
 //
@@ -36,6 +40,7 @@
 //   smg_count_reader.hpp   host only: the FASTA / FASTQ parser, the reader threads and their ring of blocks (read_files), the
 //                          members of a BGZF file (bgzf_walk, bgzf_feed) and the Inflater they are handed to
 //   smg_inflate.hpp        DEFLATE, one BGZF member per wave: inf_members and the decoder it shares with the host check
+//   smg_bam.hpp            BAM: the framer of the records (host), bam_unpack and the tile logic it shares with the host check
 //   smg_count_plan.hpp     host only: the memory plan, how buffers grow, the cuts of the key ranges
 //   smg_count_parts.hpp    the parts of the device driver, each owning its buffers: Run (what they share), Batch, Distinct,
 //                          Store, Table
@@ -48,7 +53,9 @@
 #include <rocprim/rocprim.hpp>
 
 #include <memory>
+#include <mutex>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "smg_count.h"
@@ -59,6 +66,7 @@
 #include "smg_count_plan.hpp"
 #include "smg_count_parts.hpp"
 #include "smg_inflate.hpp"
+#include "smg_bam.hpp"
 
 // where a run puts its results (the arguments of the C ABI)
 struct Out
@@ -271,6 +279,10 @@ struct Counter
 
 static_assert(sizeof(InfBlock) == sizeof(BgzfBlock) && sizeof(BgzfBlock) == 20, "the kernel reads the reader's blocks as they are");
 
+#define BAM_SLAB     ((size_t) 32 << 20)                       // output bytes of one launch of bam_unpack (a multiple of BAM_TILE)
+#define BAM_MAX_DESC (BGZF_TEXT / 36 + 1)                      // records that begin in the text of one call: 36 bytes each at least
+static_assert(BAM_SLAB % BAM_TILE == 0, "a slab is whole tiles");
+
 struct DeviceInflater : Inflater
 { int device = 0;
   hipStream_t stream = nullptr;
@@ -280,6 +292,14 @@ struct DeviceInflater : Inflater
   InfBlock *d_blk = nullptr;
   double ms_kernel = 0;
   int64_t launches = 0;
+  // the second step, for BAM: set up by the first piece that needs it (a file shows that it is BAM only in its text)
+  size_t text_n = 0;                                           // text bytes of the last inflate call
+  BamDesc *h_desc = nullptr, *d_desc = nullptr;
+  uint8_t *h_out = nullptr, *d_out = nullptr;
+  double ms_unpack = 0, ms_out_d2h = 0;                        // bam_unpack alone (HIP events); the copies of its output (host clock)
+  struct BamNote { std::string path; int64_t records, bases; double ms[4]; };     // ms: as smg_count_bam_report gives them
+  std::vector<BamNote> bam_files;
+  double mark_inflate = 0, mark_unpack = 0, mark_d2h = 0;
 
   // pinned and device memory for a chunk, its blocks, their text and statuses; 0 or the HIP error
   hipError_t init(int dev)
@@ -298,7 +318,8 @@ struct DeviceInflater : Inflater
     return hipMalloc((void **) &d_status, sizeof(uint32_t) * BGZF_MAX_BLOCKS);
   }
   ~DeviceInflater() override
-  { (void) hipFree(d_status); (void) hipFree(d_text); (void) hipFree(d_blk); (void) hipFree(d_chunk);
+  { (void) hipFree(d_out); (void) hipFree(d_desc); (void) hipHostFree(h_out); (void) hipHostFree(h_desc);
+    (void) hipFree(d_status); (void) hipFree(d_text); (void) hipFree(d_blk); (void) hipFree(d_chunk);
     (void) hipHostFree(h_status); (void) hipHostFree(h_text); (void) hipHostFree(blk); (void) hipHostFree(chunk);
     if (ev0) (void) hipEventDestroy(ev0);
     if (ev1) (void) hipEventDestroy(ev1);
@@ -332,13 +353,54 @@ struct DeviceInflater : Inflater
     if (out_end) ICHK(hipMemcpyAsync(h_text, d_text, out_end, hipMemcpyDeviceToHost, stream));
     ICHK(hipStreamSynchronize(stream));
     ICHK(hipEventElapsedTime(&ms, ev0, ev1));
-#undef ICHK
     ms_kernel += ms; launches++;
+    text_n = 0;
     for (int i = 0; i < n; i++)
       if (h_status[i] != INF_OK) { *bad = i; return h_status[i] < INF_NSTATUS ? (int) h_status[i] : INF_NSTATUS; }
     *text = h_text;
+    text_n = out_end;
     return 0;
   }
+
+  void mark() override { mark_inflate = ms_kernel; mark_unpack = ms_unpack; mark_d2h = ms_out_d2h; }
+  void note_bam(const char *path, const BamFramer &fr) override
+  { bam_files.push_back(BamNote{ path, fr.records, fr.bases, { fr.ms_feed, ms_kernel - mark_inflate, ms_unpack - mark_unpack, ms_out_d2h - mark_d2h } }); }
+
+  // H2D of the descriptors, then BAM_SLAB bytes of output at a time: bam_unpack over their tiles, D2H into pinned memory,
+  // the sink.  The descriptors are checked against the text and the output here, and the kernel stays inside both anyway.
+  int unpack(const BamDesc *d, size_t nd, size_t out_len, Sink &sink, char *errbuf, size_t errlen) override
+  { if (nd > BAM_MAX_DESC || out_len > 0xFFFFFFFFu - 2 * BAM_SLAB || !bam_desc_ok(d, nd, text_n, out_len))
+      return fail(errbuf, errlen, SMG_EINVAL, "internal error: %zu BAM records with %zu bases do not describe a text of %zu bytes", nd, out_len, text_n);
+    if (out_len == 0) return 0;
+    ICHK(hipSetDevice(device));
+    if (!d_out)
+      { ICHK(hipHostMalloc((void **) &h_desc, sizeof(BamDesc) * BAM_MAX_DESC, hipHostMallocDefault));
+        ICHK(hipHostMalloc((void **) &h_out, BAM_SLAB, hipHostMallocDefault));
+        ICHK(hipMalloc((void **) &d_desc, sizeof(BamDesc) * BAM_MAX_DESC));
+        ICHK(hipMalloc((void **) &d_out, BAM_SLAB));
+      }
+    memcpy(h_desc, d, sizeof(BamDesc) * nd);
+    ICHK(hipMemcpyAsync(d_desc, h_desc, sizeof(BamDesc) * nd, hipMemcpyHostToDevice, stream));
+    for (size_t base = 0; base < out_len; base += BAM_SLAB)
+      { const size_t len = out_len - base < BAM_SLAB ? out_len - base : BAM_SLAB;
+        float ms = 0;
+        ICHK(hipEventRecord(ev0, stream));
+        hipLaunchKernelGGL(bam_unpack, dim3((unsigned) ((len + BAM_TILE - 1) / BAM_TILE)), dim3(BAM_LANES), 0, stream, d_text, (uint32_t) text_n,
+                           d_desc, (uint32_t) nd, d_out, (uint32_t) base, (uint32_t) len);
+        ICHK(hipGetLastError());
+        ICHK(hipEventRecord(ev1, stream));
+        ICHK(hipStreamSynchronize(stream));
+        ICHK(hipEventElapsedTime(&ms, ev0, ev1));
+        ms_unpack += ms;
+        const double t0 = now_ms();
+        ICHK(hipMemcpyAsync(h_out, d_out, len, hipMemcpyDeviceToHost, stream));
+        ICHK(hipStreamSynchronize(stream));
+        ms_out_d2h += now_ms() - t0;
+        if (!sink.put(h_out, len)) return 1;
+      }
+    return 0;
+  }
+#undef ICHK
 };
 
 // a device inflater, or the error: the device is checked as Counter::init checks it
@@ -391,11 +453,25 @@ static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, i
 
 #define RING_BLOCK ((size_t) 8 << 20)
 
+// what the last call of this process that reads BAM (a counting call or smg_count_bam_strip) read from its BAM files, for the
+// report of the executable and of tools/count_time.py (smg_count_bam_report)
+static std::mutex bam_seen_m;
+static std::vector<DeviceInflater::BamNote> bam_seen;
+
 // (the inflaters of the reader threads that meet a BGZF file are set up by the survey, before Counter::init reads the
 //  free device memory, so that the plan sees what is left)
 static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
 { std::vector<std::unique_ptr<DeviceInflater>> own;
   std::vector<Inflater *> infl;
+  struct Seen                                                  // (the BAM files of this call, for smg_count_bam_report)
+  { std::vector<std::unique_ptr<DeviceInflater>> &own;
+    ~Seen()
+    { std::lock_guard<std::mutex> lk(bam_seen_m);
+      bam_seen.clear();
+      try { for (auto &i : own) if (i) bam_seen.insert(bam_seen.end(), i->bam_files.begin(), i->bam_files.end()); }
+      catch (...) { bam_seen.clear(); }                        // (out of memory: no report)
+    }
+  } seen{ own };
   return count_run(opts, io, paths && npaths >= 1, npaths,
     [&](int64_t *bound)
       { std::vector<char> bgzf;
@@ -476,6 +552,71 @@ static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_
   return 0;
 }
 
+// the stripped stream of inflated BAM text, every record by the host routine; pieces of `piece` bytes (0: one piece)
+static int bam_text(const uint8_t *text, int64_t n, int64_t piece, uint8_t **seq, int64_t *nseq, char *errbuf, size_t errlen)
+{ if (n < 0 || (n && !text) || piece < 0 || !seq || !nseq) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  BamFramer fr;
+  fr.all_host = true;
+  GrowSink sink;
+  const int64_t step = piece ? piece : (n < (int64_t) BAM_MAX_PIECE ? n : (int64_t) BAM_MAX_PIECE);
+  for (int64_t o = 0; o < n; o += step)
+    { RCHK(fr.feed(text + o, (size_t) (n - o < step ? n - o : step), "<text>", errbuf, errlen));
+      if (!fr.head.empty()) sink.put(fr.head.data(), fr.head.size());
+    }
+  RCHK(fr.finish("<text>", errbuf, errlen));
+  if (!sink.p) sink.p = (uint8_t *) malloc(1);
+  if (!sink.p) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
+  *seq = sink.p; *nseq = (int64_t) sink.len;
+  sink.p = nullptr;
+  return 0;
+}
+
+// the stripped stream of a BAM file by the route of the counting calls
+static int bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t *nseq, int64_t *records, double *ms_kernel, char *errbuf, size_t errlen)
+{ if (!seq || !nseq) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  int64_t blocks = 0, bytes = 0;
+  RCHK(bgzf_scan(path, &blocks, &bytes, errbuf, errlen));
+  std::unique_ptr<DeviceInflater> infl;
+  RCHK(new_inflater(device, infl, errbuf, errlen));
+  struct Fd { int fd; ~Fd() { if (fd >= 0) close(fd); } } f{ open(path, O_RDONLY) };
+  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  GrowSink sink;
+  BamFramer fr;
+  bool any = false;
+  infl->mark();
+  RCHK(bgzf_feed(f.fd, path, *infl, [&](const uint8_t *t, size_t m)
+    { if (!any && m)
+        { if (!is_bam_text(t, m)) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BAM: its text does not begin with the magic BAM\\1", path);
+          any = true;
+        }
+      return bam_piece(fr, t, m, path, *infl, sink, errbuf, errlen);
+    }, errbuf, errlen));
+  if (!any) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BAM: it has no text", path);
+  RCHK(fr.finish(path, errbuf, errlen));
+  if (!sink.p) sink.p = (uint8_t *) malloc(1);
+  if (!sink.p) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
+  *seq = sink.p; *nseq = (int64_t) sink.len;
+  sink.p = nullptr;
+  if (records) *records = fr.records;
+  if (ms_kernel) *ms_kernel = infl->ms_unpack;
+  infl->note_bam(path, fr);
+  std::lock_guard<std::mutex> lk(bam_seen_m);
+  bam_seen = infl->bam_files;
+  return 0;
+}
+
+static int bam_report(const char *path, int64_t *records, int64_t *bases, double *ms)
+{ if (!path || !records || !bases) return SMG_EINVAL;
+  std::lock_guard<std::mutex> lk(bam_seen_m);
+  for (const DeviceInflater::BamNote &b : bam_seen)
+    if (b.path == path)
+      { *records = b.records; *bases = b.bases;
+        if (ms) memcpy(ms, b.ms, sizeof(b.ms));
+        return 0;
+      }
+  return SMG_EINVAL;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 //  C ABI: no C++ exception crosses it
 // ---------------------------------------------------------------------------------------------------------------
@@ -529,6 +670,16 @@ extern "C" int smg_count_bgzf_scan(const char *path, int64_t *blocks, int64_t *t
 
 extern "C" int smg_count_bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen)
 { GUARD(bgzf_inflate(path, device, text, n, ms_kernel, errbuf, errlen)) }
+
+extern "C" int smg_count_bam_text(const uint8_t *text, int64_t n, int64_t piece, uint8_t **seq, int64_t *nseq, char *errbuf, size_t errlen)
+{ GUARD(bam_text(text, n, piece, seq, nseq, errbuf, errlen)) }
+
+extern "C" int smg_count_bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t *nseq, int64_t *records, double *ms_kernel,
+                                   char *errbuf, size_t errlen)
+{ GUARD(bam_strip(path, device, seq, nseq, records, ms_kernel, errbuf, errlen)) }
+
+extern "C" int smg_count_bam_report(const char *path, int64_t *records, int64_t *bases, double *ms)
+{ try { return bam_report(path, records, bases, ms); } catch (...) { return SMG_ENOMEM; } }
 
 extern "C" void smg_count_free(void *p) { free(p); }
 

@@ -6,6 +6,13 @@
 // each with its length in its header (the BC subfield) and its CRC-32 and text length in its trailer.  This file finds
 // the members; their text comes from an Inflater, which the counter implements on the device (smg_inflate.hpp) and a
 // reader without one refuses.  Any other gzip file is refused as it always was.
+//
+// BGZF text that begins with the four bytes BAM\1 is a BAM file (smg_bam.hpp): its reader thread frames the records of
+// every piece of text (BamFramer) and hands their descriptors back to the Inflater, whose second step unpacks the 4-bit
+// sequences where the text lies; the one record a piece boundary cuts is unpacked here.  The survey does not look inside:
+// the bound of a BAM file is the sum of its ISIZE fields like that of any BGZF file, at least 1.5 times its bases (a base
+// takes half a byte and its quality one), so a large BAM may be counted by key range where one pass would have done; the
+// result is the same whichever way it is counted.
 
 #pragma once
 #include <fcntl.h>
@@ -25,6 +32,7 @@
 
 #include "smg_count.h"
 #include "smg_count_err.hpp"
+#include "smg_bam.hpp"
 
 static inline double now_ms()
 { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -115,6 +123,13 @@ struct Inflater
   BgzfBlock *blk = nullptr;                                    // BGZF_MAX_BLOCKS
   virtual int inflate(int n, const uint8_t **text, int *bad, char *errbuf, size_t errlen) = 0;
   virtual const char *reason(int status) const = 0;
+  // The second step, for BAM: d[0 .. nd) describe packed sequences in the text of the last inflate call (bam_desc_ok holds
+  // for them and out_len); their out_len stripped bytes go to the sink in order.  0, 1: the consumer gave up, < 0: an error
+  // code, with message.  An inflater without this step refuses.
+  virtual int unpack(const BamDesc *, size_t, size_t, Sink &, char *errbuf, size_t errlen)
+  { return fail(errbuf, errlen, SMG_EINVAL, "internal error: this inflater cannot unpack BAM sequences%s", ""); }
+  virtual void mark() {}                                       // a BGZF file begins: what note_bam reports is counted from here
+  virtual void note_bam(const char *, const BamFramer &) {}    // that file was BAM and has been read to its end
   virtual ~Inflater() {}
 };
 
@@ -270,7 +285,20 @@ static inline int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases,
   return 0;
 }
 
-// one file to the sink, routed by its own header: BGZF through the inflater, anything else as it is
+static inline bool is_bam_text(const uint8_t *t, size_t n) { return n >= 4 && memcmp(t, "BAM\1", 4) == 0; }
+
+// one piece of the text of a BAM file to the sink: the record the last boundary cut, then what the inflater unpacks
+static inline int bam_piece(BamFramer &fr, const uint8_t *t, size_t n, const char *path, Inflater &infl, Sink &sink, char *errbuf, size_t errlen)
+{ const double t0 = now_ms();
+  const int rc = fr.feed(t, n, path, errbuf, errlen);
+  fr.ms_feed += now_ms() - t0;
+  if (rc) return rc;
+  if (!fr.head.empty() && !sink.put(fr.head.data(), fr.head.size())) return 1;
+  return fr.out_len ? infl.unpack(fr.desc.data(), fr.desc.size(), fr.out_len, sink, errbuf, errlen) : 0;
+}
+
+// one file to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
+// the framer, anything else through the parser), anything else as it is
 static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, int64_t *bases, char *errbuf, size_t errlen)
 { const int z = bgzf_probe(fd, path, errbuf, errlen);
   if (z < 0) return z;
@@ -279,9 +307,17 @@ static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *inf
     return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
                 "use smg_count_bgzf_inflate or one of the counting calls", path);
   Parser ps(sink);
-  const int rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n) { return ps.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+  BamFramer bam;
+  infl->mark();
+  int route = 0;                                               // 1 FASTA / FASTQ, 2 BAM: by the first text there is
+  int rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n)
+    { if (route == 0 && n) route = is_bam_text(t, n) ? 2 : 1;
+      return route == 2 ? bam_piece(bam, t, n, path, *infl, sink, errbuf, errlen) : ps.feed(t, n, path, errbuf, errlen);
+    }, errbuf, errlen);
+  if (rc == 0 && route == 2) rc = bam.finish(path, errbuf, errlen);
   if (rc) return rc;
-  if (bases) *bases = ps.bases;
+  if (route == 2) infl->note_bam(path, bam);
+  if (bases) *bases = route == 2 ? bam.bases : ps.bases;
   return 0;
 }
 

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """count_time.py -- stage times of the k-mer counter (libsmg_count.so) on seeded reads; the source of profiles/count_reads.md
-profiles/count_partitioned.md and profiles/count_bgzf.md.
+profiles/count_partitioned.md, profiles/count_bgzf.md and profiles/count_bam.md.
 
   python tools/count_time.py [--bases 2e9] [--k 31] [--repeats 5] [--warmup 1] [--dir DIR]
-                             [--partitions 1,2,4,8,16] [--max-entries N] [--random] [--steps gen,bases]
+                             [--partitions 1,2,4,8,16] [--max-entries N] [--random] [--steps gen,bases] [--read 150]
 
 The driver runs three steps, each a child process of its own under `timeout -k 10 <seconds>`, and stops at the first that
 fails:  gen    reads of 150 bases from both strands of a seeded random genome (0.5 % substitutions), written to DIR as a
@@ -16,6 +16,13 @@ fails:  gen    reads of 150 bases from both strands of a seeded random genome (0
                used to cost: one zlib thread (`gzip -dc`, or Python's gzip where there is none) to a plain file, then the plain
                run; and, where torch is there, the copy of the text to pinned host memory and back, which the route pays for
                parsing on the host
+        bam    (only where --steps names it) the reads of reads.seq written as unaligned BAM (reads.bam: one record a read, FLAG 4,
+               qualities 40; BGZF at level 6, members of 65280 bytes) and, where it is not there yet, as BGZF FASTQ; then
+               smg_count_bam_strip (the unpack and the inflate kernel's time, the framer's host time, the copy of the stripped
+               bytes to the host: smg_count_bam_report), smg_count_files on reads.bam next to reads.fq.gz with the two tables
+               compared in every run, and, where torch is there, the copy of the stripped bytes from pinned memory to the device,
+               which the ring pays
+--read is the length of the reads (gen, and every step that reads what it wrote).
 Stage times are the library's own (HIP events around extract, sort, reduce+merge, finish; host clock for read and wall).
 Printed: one JSON line per step and a markdown table of medians with the min-max spread.
 --partitions runs every timed step once per listed number of key ranges (0 = automatic); --max-entries is the library's test
@@ -53,7 +60,7 @@ def gen(args):
         torch, dev = None, "cpu"
     seq = np.empty((nreads, READ + 1), dtype=np.uint8)
     seq[:, READ] = ord("\n")
-    step = 1 << 20
+    step = min(1 << 20, max(1, (1 << 28) // READ))               # reads made at a time
     if torch is not None:
         g = torch.Generator(device=dev); g.manual_seed(args.seed)
         genome = torch.randint(0, 4, (G,), generator=g, device=dev, dtype=torch.uint8)
@@ -90,7 +97,7 @@ def gen(args):
     # FASTQ with fixed-width records: @<10 digits>\n <read>\n +\n <quality>\n
     rec = np.empty((step, 12 + READ + 1 + 2 + READ + 1), dtype=np.uint8)
     with open(os.path.join(args.dir, "reads.fq"), "wb") as f:
-        for a in range(0, nreads if {"files", "bgzf"} & set(args.steps.split(",")) else 0, step):
+        for a in range(0, nreads if {"files", "bgzf", "bam"} & set(args.steps.split(",")) else 0, step):
             n = min(step, nreads - a)
             r = rec[:n]
             r[:, 0] = ord("@")
@@ -240,8 +247,127 @@ def summarise_bgzf(b):
     return "\n".join(lines)
 
 
+def _bam_records(seq, first):
+    """[n, READ + 1] sequence bytes (the last column the newline) -> [n, record size] uint8: the BAM records of these reads"""
+    import struct
+    n, L = seq.shape[0], seq.shape[1] - 1
+    packed = (L + 1) // 2
+    size = 4 + 32 + 11 + packed + L
+    rec = np.zeros((n, size), dtype=np.uint8)
+    fixed = struct.pack("<iiiBBHHHiiii", size - 4, -1, -1, 11, 0, 4680, 0, 4, L, -1, -1, 0)
+    rec[:, :36] = np.frombuffer(fixed, np.uint8)
+    ids = np.arange(first, first + n, dtype=np.int64)
+    for d in range(10):
+        rec[:, 36 + 9 - d] = ord("0") + (ids // 10 ** d) % 10
+    lut = np.full(256, 15, np.uint8)
+    for code, c in enumerate(b"=ACMGRSVTWYHKDBN"):
+        lut[c] = code
+    codes = np.zeros((n, 2 * packed), dtype=np.uint8)
+    codes[:, :L] = lut[seq[:, :L]]
+    rec[:, 47:47 + packed] = codes[:, 0::2] << 4 | codes[:, 1::2]
+    rec[:, 47 + packed:] = 40
+    return rec
+
+
+def _bgzf_file(pool, path, pieces):
+    with open(path, "wb") as f:
+        for m in pool.imap(_bgzf_member, pieces, chunksize=64):
+            f.write(m)
+        f.write(bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000"))
+
+
+def bam(args):
+    import multiprocessing
+    from smudgeplot_amd import count
+    seqp, fq, gz, bamp = (os.path.join(args.dir, n) for n in ("reads.seq", "reads.fq", "reads.fq.gz", "reads.bam"))
+    seq = np.fromfile(seqp, dtype=np.uint8).reshape(-1, READ + 1)
+    sam = b"@HD\tVN:1.6\tSO:unknown\n"
+    head = b"BAM\1" + len(sam).to_bytes(4, "little") + sam + (0).to_bytes(4, "little")
+    t0 = time.perf_counter()
+    step = max(1, (1 << 27) // (2 * READ))
+    text = head + b"".join(_bam_records(seq[a:a + step], a).tobytes() for a in range(0, len(seq), step))
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        _bgzf_file(pool, bamp, (text[a:a + 65280] for a in range(0, len(text), 65280)))
+        if not os.path.exists(gz):
+            data = open(fq, "rb").read()
+            _bgzf_file(pool, gz, (data[a:a + 65280] for a in range(0, len(data), 65280)))
+            del data
+    out = {"step": "bam", "k": args.k, "t": args.t, "warmup": args.warmup, "repeats": args.repeats, "reads": len(seq), "read": READ,
+           "text_bytes": len(text), "file_bytes": os.path.getsize(bamp), "fastq_text_bytes": os.path.getsize(fq),
+           "fastq_file_bytes": os.path.getsize(gz), "write_s": time.perf_counter() - t0}
+    del text
+    spread = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v)}
+    runs = []
+    for i in range(args.warmup + args.repeats):
+        t0 = time.perf_counter()
+        got, records, ms = count.bam_strip(bamp)
+        wall = (time.perf_counter() - t0) * 1e3
+        rep = count.bam_report(bamp)
+        assert records == len(seq) and len(got) == seq.size - 1 and abs(rep["ms_unpack"] - ms) < 1e-6
+        if i == 0:                                                    # the stream is the file gen wrote, less its last newline
+            assert np.array_equal(np.frombuffer(got, np.uint8), seq.reshape(-1)[:-1])
+        runs.append(dict(rep, wall=wall))
+        del got
+    out["stripped_bytes"] = int(seq.size - 1)
+    for key in ("ms_unpack", "ms_inflate", "ms_frame", "ms_d2h", "wall"):
+        out["strip_" + key] = spread([r[key] for r in runs[args.warmup:]])
+    walls, tables = {"bam": [], "fastq": []}, {}
+    for i in range(args.warmup + args.repeats):
+        for name, path in (("bam", bamp), ("fastq", gz)):
+            table, hist, st = count.count_files([path], args.k, t=args.t, threads=args.threads)
+            walls[name].append(st["ms_wall"])
+            tables[name] = (table.packed, table.counts, hist)
+            if name == "bam":
+                out["count_bam_report"] = count.bam_report(bamp)
+        assert all(np.array_equal(a, b) for a, b in zip(tables["bam"], tables["fastq"])), "the BAM and the FASTQ tables differ"
+    out["tables_equal_in_every_run"] = True
+    out["count_bam_wall_ms"] = spread(walls["bam"][args.warmup:])
+    out["count_fastq_wall_ms"] = spread(walls["fastq"][args.warmup:])
+    try:
+        import torch
+        h = torch.empty(seq.size, dtype=torch.uint8).pin_memory()
+        d = torch.empty(seq.size, dtype=torch.uint8, device="cuda")
+        trips = []
+        for i in range(args.warmup + args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            d.copy_(h)
+            torch.cuda.synchronize()
+            trips.append((time.perf_counter() - t0) * 1e3)
+        out["ring_h2d_ms"] = spread(trips[args.warmup:])
+    except Exception as e:                                            # (no torch, no device: the figure is left out)
+        out["ring_h2d_ms"] = None
+        out["ring_h2d_error"] = str(e)
+    print(json.dumps(out))
+
+
+def summarise_bam(b):
+    f = lambda v: f"{v['median']:.1f} ({v['min']:.1f} - {v['max']:.1f})"
+    n, s = b["text_bytes"], b["stripped_bytes"]
+    per = lambda v, m: f"{m / v['median'] * 1e3:.3e}"
+    lines = [f"\n### bam: {b['reads']} reads of {b['read']} bases, {n:.3e} bytes of BAM text in {b['file_bytes']:.3e} bytes of file, "
+             f"{s:.3e} stripped bytes; {b['repeats']} runs after {b['warmup']} warm-up; ms as median (min - max)\n",
+             "| what | ms | bytes/s at the median |", "|---|---|---|",
+             f"| bam_unpack, kernel (bam_strip) | {f(b['strip_ms_unpack'])} | {per(b['strip_ms_unpack'], s)} stripped |",
+             f"| inf_members, kernel, same file | {f(b['strip_ms_inflate'])} | {per(b['strip_ms_inflate'], n)} text |",
+             f"| the framer, host | {f(b['strip_ms_frame'])} | {per(b['strip_ms_frame'], n)} text |",
+             f"| the stripped bytes to the host (D2H) | {f(b['strip_ms_d2h'])} | {per(b['strip_ms_d2h'], s)} stripped |",
+             f"| bam_strip, wall | {f(b['strip_wall'])} | {per(b['strip_wall'], s)} stripped |",
+             f"| count_files, BAM, wall | {f(b['count_bam_wall_ms'])} | {per(b['count_bam_wall_ms'], s)} stripped |",
+             f"| count_files, BGZF FASTQ of the same reads, wall | {f(b['count_fastq_wall_ms'])} | {per(b['count_fastq_wall_ms'], s)} stripped |"]
+    if b.get("ring_h2d_ms"):
+        lines.append(f"| the stripped bytes from pinned memory to the device (what the ring pays) | {f(b['ring_h2d_ms'])} | {per(b['ring_h2d_ms'], s)} stripped |")
+    r = b["count_bam_report"]
+    lines.append(f"\nin the last counting run the reader thread spent on the BAM file: framing {r['ms_frame']:.1f} ms, inflate kernel "
+                 f"{r['ms_inflate']:.1f} ms, unpack kernel {r['ms_unpack']:.1f} ms, D2H of the stripped bytes {r['ms_d2h']:.1f} ms")
+    lines.append(f"tables of the BAM and the BGZF FASTQ run equal in every run: {b['tables_equal_in_every_run']}")
+    return "\n".join(lines)
+
+
 def summarise(res):
     lines = [summarise_bgzf(res["bgzf"])] if "bgzf" in res else []
+    if "bam" in res:
+        lines.append(summarise_bam(res["bam"]))
     for what in ("bases", "files"):
         for parts, got in res.get(what, {}).get("by_partitions", {}).items():
             if "refused" in got:
@@ -272,7 +398,8 @@ def summarise(res):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", nargs="?", default="all", choices=["all", "gen", "bases", "files", "bgzf"])
+    ap.add_argument("step", nargs="?", default="all", choices=["all", "gen", "bases", "files", "bgzf", "bam"])
+    ap.add_argument("--read", type=int, default=150, help="bases of a read")
     ap.add_argument("--bases", type=float, default=2e9)
     ap.add_argument("--genome", type=float, default=5e7)
     ap.add_argument("--k", type=int, default=31)
@@ -288,6 +415,10 @@ def main():
     ap.add_argument("--random", action="store_true", help="independent random reads instead of reads of a genome")
     ap.add_argument("--steps", default="gen,bases,files")
     args = ap.parse_args()
+    global READ
+    READ = args.read
+    if args.step == "bam":
+        return bam(args)
     if args.step == "gen":
         return gen(args)
     if args.step in ("bases", "files"):
@@ -301,7 +432,7 @@ def main():
         for step in args.steps.split(","):
             cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), step, "--dir", d,
                    "--bases", str(args.bases), "--genome", str(args.genome), "--k", str(args.k), "--t", str(args.t),
-                   "--threads", str(args.threads), "--repeats", str(args.repeats), "--warmup", str(args.warmup), "--seed", str(args.seed),
+                   "--threads", str(args.threads), "--read", str(args.read), "--repeats", str(args.repeats), "--warmup", str(args.warmup), "--seed", str(args.seed),
                    "--partitions", args.partitions, "--max-entries", str(args.max_entries), "--steps", args.steps] + (["--random"] if args.random else [])
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
