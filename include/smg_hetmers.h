@@ -441,6 +441,22 @@ void    smg_engine_pass1_limits(int32_t out[4]);
    first step of its gallop to the block's bounds.  Test hook SMG_FILTER_GRID=<g> (>= 1): kf_filter with at most g workgroups. */
 void    smg_engine_wide_limits(int32_t out[8]);
 
+/* where the list route between pass 1 and pass 2 changes regime (read-only, needs no device; for tests): out[0] records from
+   which a list with a count/flag word, or of k-mers wider than one word, is index-sorted, and the floor of the two hooks below,
+   [1] records from which a key-only list of one-word k-mers is sorted before its look-ups (test hook SMG_APPLY_SORT_MIN=<n>
+   moves it), [2] chunk slots from which such a list is bucketed in front of the request filter (k < 32, no look-up chain; test
+   hook SMG_FILTER_SORT_MIN=<n> moves it), [3] records per request chunk.                                                  */
+void    smg_engine_list_limits(int32_t out[4]);
+
+/* the list route of the last smg_engine_apply / smg_engine_apply_own / smg_engine_run of this engine (plain host fields, set
+   where the branch is taken, reset by every pass 1; for tests): out[0] the look-up kernel: 0 none (nothing to look up, or the
+   look-up chain ran: smg_engine_lookup_state), 1 kf_apply, 2 kf_apply_indexed, 3 kf_apply_sorted, [1] the list (or its index)
+   was sorted first, [2] the holes of the chunk list: 0 a flat list, 1 filled with sentinel words (kf_fill_holes), 2 squeezed
+   out (kf_compact), [3] records -- or, with sentinels, chunk slots -- the kernel walked, [4] the look-ups read signatures,
+   [5] the request list in front of the filter: 0 not looked at, 1 bucketed on its leading 8 bits, 2 left as it is,
+   3 partitioned for the look-up chain.                                                                                     */
+int     smg_engine_apply_state(smg_engine *e, int64_t out[6]);
+
 /* where the record decoder and the piece-wise ingest change regime (read-only, needs no device; for tests): out[0] entries
    a workgroup of k_decode decodes (a tile), [1] entries per thread, [2] the buckets of the prefix index a tile may span and
    still walk its slice of the index in LDS (a tile that spans more bisects the whole index per entry), [3] KiB per piece

@@ -59,7 +59,10 @@
 //                       smg_engine_lookup_limits and smg_engine_lookup_state);
 //                       SMG_FILTER_GRID=<g> (>= 1) launches kf_filter with at most g workgroups, so that one workgroup takes several
 //                       chunks and splits its survivors across output chunks on a table of 1e4 entries
-//                       (tests/test_wide_fast_path_gpu.py, with smg_engine_wide_limits).
+//                       (tests/test_wide_fast_path_gpu.py, with smg_engine_wide_limits);
+//                       SMG_APPLY_SORT_MIN=<n> (>= SORT_MIN) sorts a key-only list of one-word k-mers from n records on, so that a
+//                       list of a few thousand records -- sentinel words among them -- takes the sort branch of apply_sorted
+//                       (tests/test_list_lookups_gpu.py, with smg_engine_list_limits and smg_engine_apply_state).
 static inline const char *test_hook(const char *name) { return getenv(name); }
 
 // host: f(std::true_type) or f(std::false_type) -- with_words (smg_device.hpp) for a template argument that is a bool
@@ -136,6 +139,16 @@ enum RunKind { RUN_NONE, RUN_FAST, RUN_COUNTED, RUN_GENERAL };    // k <= 85 / k
 // req2 holds it partitioned into the buckets of the look-up chain
 enum Presort { PRESORT_NONE, PRESORT_BUCKETED, PRESORT_ASIS, PRESORT_CHAIN };
 enum ProbeForm { PROBE_NONE = 0, PROBE_FUSED = 1, PROBE_X = 2, PROBE_LIST = 3 };   // kl_probe fused / kl_probe_x / kl_probe to a list (exported)
+// the list route of the last apply (smg_engine_apply_state): the look-up kernel, what became of the holes of the chunk list
+enum ApplyKernel { APPLY_NONE = 0, APPLY_PLAIN = 1, APPLY_INDEXED = 2, APPLY_SORTED = 3 };      // none / kf_apply / kf_apply_indexed / kf_apply_sorted
+enum ApplyHoles { HOLES_NONE = 0, HOLES_SENTINELS = 1, HOLES_COMPACTED = 2 };                   // a flat list / kf_fill_holes / kf_compact
+struct ApplyState
+{ ApplyKernel kernel;
+  bool        sorted;           // the list, or its (key, record number) pairs, went through a radix sort first
+  ApplyHoles  holes;
+  int64_t     covered;          // records (flat and compacted lists) or chunk slots (sentinels) the look-up kernel walked
+  bool        sig;              // the look-ups bisected signatures (FastArgs::sig != NULL)
+};
 
 struct RunState
 { RunKind   kind;             // the path of the pass 1 that ran last on this table
@@ -149,6 +162,7 @@ struct RunState
   Dir       dir;  bool dir_preset;      // the directory; it is the table's own index (ixdir): pass 1 writes none
   bool      filtered;         // the request list has been filtered
   Presort   presorted;
+  ApplyState ap;              // the list route of the last apply (fast_apply resets it)
   ProbeForm probe_form;  unsigned probe_part;   // the probe kernel of the filter / look-up, requests per ticket of kl_probe_x (else 0)
   bool      far_listed;       // biglist[0 .. st.nbig) holds pass 1's deferred entries: pass 2 finishes the far partners from it
   bool      lookup_pending;   // look-ups of received requests were queued without a host wait (their time is read later)
@@ -743,6 +757,8 @@ static int fast_pass1(smg_engine *e, int emit_all, int with_meta, int want_fp, c
 // ROCm 7.2, so Onesweep is forced (MergeSortLimit = 0) and small batches are not sorted at all
 // (their look-ups are too few to matter).  SMG_VERIFY_SORT=1 checks every sort (order + checksums).
 #define SORT_MIN 4096
+#define APPLY_SORT_MIN  (1 << 21)     // apply_sorted: key-only lists of one-word k-mers are sorted from here on (SMG_APPLY_SORT_MIN)
+#define FILTER_SORT_MIN (1 << 22)     // filter_presort: chunk slots from which a key-only list is bucketed first (SMG_FILTER_SORT_MIN)
 typedef rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                    rocprim::default_config, 0> smg_sort_config;
 
@@ -755,7 +771,9 @@ static int apply_sorted(smg_engine *e, const u64 *keys_in, int64_t nsort, int ho
   const u64 *src = keys_in;
   // (a short list -- what one rank of eight receives -- is looked up as it comes: the sort is eight launches, ~90 us, to put
   //  a few hundred thousand look-ups in order, which take 70 us either way)
-  const int64_t sort_min = 1 << 21;
+  int64_t sort_min = APPLY_SORT_MIN;
+  { const char *v = test_hook("SMG_APPLY_SORT_MIN"); if (v) sort_min = atoll(v); if (sort_min < SORT_MIN) sort_min = SORT_MIN; }
+  e->run.ap.kernel = APPLY_SORTED; e->run.ap.sorted = nsort >= sort_min; e->run.ap.covered = nsort; e->run.ap.sig = a.sig != NULL;
   if (nsort >= sort_min)
     { HIPCHK(e->req2.reserve(nsort * (int64_t) sizeof(u64)));
       const unsigned lobit = 40;             // sort on bits [lobit, 64) of the k-mer
@@ -784,12 +802,14 @@ static int apply_indexed(smg_engine *e, const u64 *rec, int64_t n, int check_cou
   FastArgs a = make_fast(e);
   int64_t nb = (n + F_TPB - 1) / F_TPB;
   if (nb > 16384) nb = 16384;
+  e->run.ap.covered = n; e->run.ap.sig = a.sig != NULL;
   if (n < SORT_MIN || n >= 0xFFFFFFF0ll)
-    {
+    { e->run.ap.kernel = APPLY_PLAIN; e->run.ap.sorted = false;
       with_words<3>(e->tab.W, [&](auto w) { hipLaunchKernelGGL(kf_apply<w()>, dim3((unsigned) (nb > 8192 ? 8192 : nb)), dim3(F_TPB), 0, e->stream, a, rec,
           (const uint32_t *) NULL, n, check_count, &e->ctrl->fast, e->run.rw); });
       return SMG_OK;
     }
+  e->run.ap.kernel = APPLY_INDEXED; e->run.ap.sorted = true;
   for (int q = 0; q < 2; q++)
     { HIPCHK(e->skey[q].reserve(n * 4 + 16));
       HIPCHK(e->sidx[q].reserve(n * 4 + 16));
@@ -827,7 +847,7 @@ static int filter_presort(smg_engine *e, char *errbuf, size_t errlen)
     }
   e->run.presorted = PRESORT_ASIS;
   const int64_t nslots = (int64_t) e->run.n_chunks * F_CH;
-  int64_t sort_min = 1 << 22;               // below this the probes are too few to matter
+  int64_t sort_min = FILTER_SORT_MIN;       // below this the probes are too few to matter
   { const char *v = test_hook("SMG_FILTER_SORT_MIN"); if (v) sort_min = atoll(v); if (sort_min < SORT_MIN) sort_min = SORT_MIN; }
   if (!(e->run.rw == 1 && nslots >= sort_min && e->tab.kmer < 32)) return SMG_OK;
   hipLaunchKernelGGL(kf_fill_holes, dim3(e->run.n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
@@ -977,6 +997,7 @@ static int compact_chunks(smg_engine *e, int64_t nreq, char *errbuf, size_t errl
 static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_count, int64_t *missing,
                       char *errbuf, size_t errlen)
 { int rc = SMG_OK;
+  e->run.ap = ApplyState{};
   if (!flat && e->run.lg.nb && e->run.bm_bits && !e->run.filtered)
     { // own requests, own map: partition, then filter and look-ups in one kernel (no survivor list, no sort)
       if (e->run.n_chunks == 0 || e->st.nrequests == 0) { if (missing) *missing = 0; return SMG_OK; }
@@ -1006,12 +1027,14 @@ static int fast_apply(smg_engine *e, const u64 *flat, int64_t nflat, int check_c
           // holes as sentinels behind the requests, instead of compacting it first
           hipLaunchKernelGGL(kf_fill_holes, dim3(e->run.n_chunks), dim3(F_TPB), 0, e->stream, e->req, e->chunk_fill);
           rc = apply_sorted(e, e->req, nslots, 1, errbuf, errlen);
+          e->run.ap.holes = HOLES_SENTINELS;
         }
       else
         { // ragged chunks, k = 32 (the all-T k-mer equals the sentinel) or records with a count/flag word
           // (W > 1, exact proof): compact, then sorted (keys) or index-sorted (records) look-ups
           if ((rc = compact_chunks(e, nreq, errbuf, errlen))) return rc;
           rc = keys_only ? apply_sorted(e, e->dense, nreq, 0, errbuf, errlen) : apply_indexed(e, e->dense, nreq, check_count, errbuf, errlen);
+          e->run.ap.holes = HOLES_COMPACTED;
         }
     }
   if (rc) return rc;
@@ -1529,6 +1552,18 @@ extern "C" void smg_engine_pass1_limits(int32_t out[4])
 extern "C" void smg_engine_wide_limits(int32_t out[8])
 { const int32_t v[8] = { F_TILE, F_HALO, F_CH, F_FSTAGE, SORT_MIN, CODE_REACH, BB_LIN, BB_STEP };
   memcpy(out, v, sizeof(v));
+}
+
+extern "C" void smg_engine_list_limits(int32_t out[4])
+{ const int32_t v[4] = { SORT_MIN, APPLY_SORT_MIN, FILTER_SORT_MIN, F_CH };
+  memcpy(out, v, sizeof(v));
+}
+
+extern "C" int smg_engine_apply_state(smg_engine *e, int64_t out[6])
+{ if (!e || !out) return SMG_EINVAL;
+  const ApplyState &ap = e->run.ap;
+  out[0] = ap.kernel; out[1] = ap.sorted; out[2] = ap.holes; out[3] = ap.covered; out[4] = ap.sig; out[5] = e->run.presorted;
+  return SMG_OK;
 }
 
 extern "C" int smg_engine_lookup_state(smg_engine *e, int64_t out[10])

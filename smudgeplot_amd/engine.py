@@ -73,6 +73,7 @@ EXPORTS = [
     "smg_engine_pass1_plan", "smg_hetmers_run_mode", "smg_engine_decode_at", "smg_engine_decode_limits",
     "smg_engine_ingest_readers", "smg_engine_wide_limits",
     "smg_engine_close_canonical_range", "smg_engine_close_canonical_range_cap", "smg_hetmers_run_device_mode",
+    "smg_engine_list_limits", "smg_engine_apply_state",
 ]
 
 _lib = None
@@ -131,6 +132,10 @@ def load_library():
     if hasattr(lib, "smg_engine_wide_limits"):
         lib.smg_engine_wide_limits.argtypes = [C.POINTER(C.c_int32)]
         lib.smg_engine_wide_limits.restype = None
+    if hasattr(lib, "smg_engine_list_limits"):
+        lib.smg_engine_list_limits.argtypes = [C.POINTER(C.c_int32)]
+        lib.smg_engine_list_limits.restype = None
+        lib.smg_engine_apply_state.argtypes = [vp, C.POINTER(i64)]
     lib.smg_engine_bind.argtypes = [vp, i32, i64, vp, vp, *err]
     lib.smg_engine_set_prefix_index.argtypes = [vp, vp, i32, i64, *err]
     lib.smg_engine_condition.argtypes = [vp, i32, i32, i32, C.POINTER(i64), *err]
@@ -294,6 +299,19 @@ def wide_limits() -> dict:
     out = (C.c_int32 * 8)()
     load_library().smg_engine_wide_limits(out)
     return dict(zip(WIDE_LIMITS, (int(v) for v in out)))
+
+
+LIST_LIMITS = ("SORT_MIN", "APPLY_SORT_MIN", "FILTER_SORT_MIN", "F_CH")
+
+
+def list_limits() -> dict:
+    """where the list route between pass 1 and pass 2 changes regime (smg_engine_list_limits; no device needed): the list length
+    from which records with a count word, or of wider k-mers, are index-sorted -- the floor of the hooks SMG_APPLY_SORT_MIN and
+    SMG_FILTER_SORT_MIN as well --, the length from which key-only lists of one-word k-mers are sorted, the chunk slots from which
+    such a list is bucketed in front of the filter, records per request chunk"""
+    out = (C.c_int32 * 4)()
+    load_library().smg_engine_list_limits(out)
+    return dict(zip(LIST_LIMITS, (int(v) for v in out)))
 
 
 DECODE_LIMITS = ("DEC_TILE", "DEC_EPT", "DEC_IX", "ING_CHUNK_KIB")
@@ -685,6 +703,28 @@ class Engine:
         if rc != 0:
             raise EngineError(rc, "lookup_state")
         return dict(zip(self.LOOKUP_STATE, (int(v) for v in out)))
+
+    APPLY_STATE = ("kernel", "sorted", "holes", "covered", "sig", "presorted")
+    APPLY_KERNELS = (None, "kf_apply", "kf_apply_indexed", "kf_apply_sorted")
+    APPLY_HOLES = (None, "sentinels", "compacted")
+    PRESORTED = (None, "bucketed", "as it is", "chain")
+
+    def apply_state(self) -> dict:
+        """the list route of this engine's last apply / apply_own / run (smg_engine_apply_state; reset by every pass 1): the look-up
+        kernel ("kf_apply", "kf_apply_indexed", "kf_apply_sorted"; None: nothing to look up, or the look-up chain ran), whether
+        the list was sorted first, the holes of the chunk list ("sentinels": kf_fill_holes, "compacted": kf_compact, None: a flat
+        list), the records or chunk slots the kernel walked, whether signatures were read, the request list in front of the
+        filter (None, "bucketed", "as it is", "chain")"""
+        out = (C.c_int64 * 6)()
+        rc = self.lib.smg_engine_apply_state(self.h, out)
+        if rc != 0:
+            raise EngineError(rc, "apply_state")
+        d = dict(zip(self.APPLY_STATE, (int(v) for v in out)))
+        d["kernel"] = self.APPLY_KERNELS[d["kernel"]]
+        d["holes"] = self.APPLY_HOLES[d["holes"]]
+        d["presorted"] = self.PRESORTED[d["presorted"]]
+        d["sorted"], d["sig"] = bool(d["sorted"]), bool(d["sig"])
+        return d
 
     PASS1_FORM = ("var", "w", "rw", "inner_only")
 

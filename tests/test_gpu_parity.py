@@ -175,9 +175,10 @@ def test_medium_table_vs_c_oracle(tmp_path):
 
 
 def test_large_table_sorted_lookup_path_vs_reference_binary(tmp_path, monkeypatch):
-    """~7.6e6 entries: the request list is long enough for the radix-sorted look-up path; compare the
-    engine with the REFERENCE binary (oracle/_ref, prebuilt) on the same table, and let the engine
-    self-check every sort (SMG_VERIFY_SORT)."""
+    """~7.6e6 entries: the unfiltered request list goes through the radix-sorted look-up path (asserted from apply_state; the
+    list of a table this size is shorter than the real threshold, which tests/test_list_lookups_gpu.py crosses, so the hook
+    SMG_APPLY_SORT_MIN lowers it to its floor here); compare the engine with the REFERENCE binary (oracle/_ref, prebuilt) on
+    the same table, and let the engine self-check every sort (SMG_VERIFY_SORT)."""
     import torch
     from conftest import REF_BIN
     from smudgeplot_amd import synth_device
@@ -196,10 +197,14 @@ def test_large_table_sorted_lookup_path_vs_reference_binary(tmp_path, monkeypatc
     for mode in ("hash", "exact", "hash-unfiltered"):
         if mode == "hash-unfiltered":            # (on a table this sparse the request filter leaves too few
             monkeypatch.setenv("SMG_NO_FILTER", "1")     #  requests for the sorted path: run it without as well)
+            monkeypatch.setenv("SMG_APPLY_SORT_MIN", str(engine.list_limits()["SORT_MIN"]))
         st = e.run(plot.data_ptr(), mode.split("-")[0])
         torch.cuda.synchronize()
         assert st["path"] == 1 and st["nemitted"] > 100000
         assert mode == "hash" or st["nrequests"] > 100000
+        if mode == "hash-unfiltered":
+            ap = e.apply_state()
+            assert ap["kernel"] == "kf_apply_sorted" and ap["sorted"] and ap["covered"] >= st["nrequests"], ap
         texts[mode] = engine.smu_text(plot.cpu().numpy().reshape(1001, 501))
     assert texts["hash"] == texts["exact"] == texts["hash-unfiltered"]
     synth.write_u64_table(str(tmp_path / "t"), keys, cnt, k, ibyte=2, nparts=3)
