@@ -3,6 +3,11 @@
 // they were delivered, against Parser run over the whole file in one piece; and the three ways a run is given up.
 // Built once with -fsanitize=address,undefined and once with -fsanitize=thread, run under a time limit: a hang is a
 // failure (`make reader_check`).  Host only; no device code.
+//
+// The same for the seam to the device stage of compressed input: BGZF and BAM files crafted here (stored-block members) go
+// through bgzf_feed, the routing of parse_file and bam_piece with a HostInflater in the place of the device's, whose
+// inflate is the host twin of the kernel (inflate_member_host) and whose unpack is the host routine (bam_unpack_host), its
+// buffers malloc'ed at their exact sizes.
 
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +16,7 @@
 #include <vector>
 
 #include "smg_count_reader.hpp"
+#include "smg_inflate.hpp"
 
 typedef std::vector<uint8_t> Bytes;
 
@@ -72,27 +78,163 @@ struct Blocks                                                  // malloc'ed, eac
   ~Blocks() { for (uint8_t *q : p) free(q); }
 };
 
-// what read_files returned, and what its consumer saw
-struct Got { int rc; std::string err; std::vector<Bytes> per_file; int64_t bases; int blocks; };
+// ---------------------------------------------------------------------------------------------------------------
+//  BGZF and BAM files made here, and the Inflater of the host
+// ---------------------------------------------------------------------------------------------------------------
 
-// fail_at > 0: the consumer returns `code` for its fail_at-th block (and must not be called again)
-static Got run(const std::vector<std::string> &paths, int threads, int nblocks, size_t block, int fail_at = 0, int code = 0)
+static uint32_t crc32_of(const uint8_t *p, size_t n)
+{ static uint32_t tab[256];
+  if (!tab[1]) for (uint32_t c = 0; c < 256; c++) tab[c] = crc_byte(0, (uint8_t) c);
+  uint32_t r = 0xffffffffu;
+  for (size_t i = 0; i < n; i++) r = tab[(r ^ p[i]) & 0xffu] ^ (r >> 8);
+  return r ^ 0xffffffffu;
+}
+
+static void le(std::string &s, uint32_t v, int bytes) { for (int i = 0; i < bytes; i++) s += (char) (v >> (8 * i) & 0xffu); }
+
+// one member: the 18-byte header with the BC subfield, the text as one stored block, CRC-32 and ISIZE
+static std::string bgzf_member(const std::string &text, uint32_t crc_xor = 0)
+{ const uint32_t n = (uint32_t) text.size();
+  std::string m("\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0", 16);
+  le(m, 18 + 5 + n + 8 - 1, 2);
+  m += '\x01'; le(m, n, 2); le(m, ~n & 0xffffu, 2);
+  m += text;
+  le(m, crc32_of((const uint8_t *) text.data(), n) ^ crc_xor, 4); le(m, n, 4);
+  return m;
+}
+
+// the text in members of `isize` bytes (0: of 1 .. 5000 bytes, by rng), then the empty member bgzip ends a file with;
+// bad_member >= 0: that member gets a wrong CRC-32, *bad_at = its offset in the file
+static std::string bgzf_file(const std::string &text, size_t isize, std::mt19937_64 &rng, int bad_member = -1, size_t *bad_at = nullptr)
+{ std::string f;
+  int m = 0;
+  for (size_t o = 0; o < text.size(); m++)
+    { const size_t n = std::min(text.size() - o, isize ? isize : 1 + (size_t) (rng() % 5000));
+      if (m == bad_member && bad_at) *bad_at = f.size();
+      f += bgzf_member(text.substr(o, n), m == bad_member ? 0x5a5a5a5au : 0u);
+      o += n;
+    }
+  return f + std::string("\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0\x1b\0\x03\0\0\0\0\0\0\0\0\0", 28);
+}
+
+struct BamRec { std::string name, seq; uint32_t flag; };       // seq: letters of "=ACMGRSVTWYHKDBN"
+
+static std::string bam_letters(std::mt19937_64 &rng, size_t n)
+{ std::string s(n, '=');
+  for (char &c : s) c = "=ACMGRSVTWYHKDBN"[rng() % 16];
+  return s;
+}
+
+// block_size < 0: what the fields give
+static std::string bam_record(const BamRec &r, int32_t block_size = -1)
+{ std::string b;
+  le(b, 0xffffffffu, 4); le(b, 0xffffffffu, 4);
+  le(b, (uint32_t) r.name.size() + 1, 1); le(b, 0, 1); le(b, 4680, 2); le(b, 0, 2); le(b, r.flag, 2);
+  le(b, (uint32_t) r.seq.size(), 4); le(b, 0xffffffffu, 4); le(b, 0xffffffffu, 4); le(b, 0, 4);
+  b += r.name; b += '\0';
+  for (size_t j = 0; j < r.seq.size(); j += 2)
+    { const uint32_t hi = (uint32_t) (strchr("=ACMGRSVTWYHKDBN", r.seq[j]) - "=ACMGRSVTWYHKDBN");
+      const uint32_t lo = j + 1 < r.seq.size() ? (uint32_t) (strchr("=ACMGRSVTWYHKDBN", r.seq[j + 1]) - "=ACMGRSVTWYHKDBN") : 0u;
+      b += (char) (hi << 4 | lo);
+    }
+  b += std::string(r.seq.size(), '\xff');
+  std::string out;
+  le(out, block_size < 0 ? (uint32_t) b.size() : (uint32_t) block_size, 4);
+  return out + b;
+}
+
+static std::string bam_header()
+{ std::string h("BAM\1", 4);
+  const std::string text = "@HD\tVN:1.6\tSO:unknown\n";
+  le(h, (uint32_t) text.size(), 4); h += text; le(h, 1, 4);
+  le(h, 5, 4); h += std::string("chr1\0", 5); le(h, 1000, 4);
+  return h;
+}
+
+// the one-pass reference of a BAM file: the bases of its primary records, one separator between two of them
+static Bytes bam_stripped(const std::vector<BamRec> &recs, int64_t *records, int64_t *nbases)
+{ Bytes v;
+  *records = 0; *nbases = 0;
+  for (const BamRec &r : recs)
+    if ((r.flag & 0x900u) == 0)
+      { if ((*records)++) v.push_back(SMG_COUNT_SEPARATOR);
+        v.insert(v.end(), r.seq.begin(), r.seq.end());
+        *nbases += (int64_t) r.seq.size();
+      }
+  return v;
+}
+
+// The Inflater on the host.  chunk and blk have the sizes the reader may fill, the text that of the call and the
+// unpacked bytes that of the descriptors: a byte too many, read or written, is reported.
+struct HostInflater : Inflater
+{ uint8_t *text = nullptr;
+  size_t text_n = 0;
+  int calls = 0, unpacks = 0;
+  HostInflater()
+  { chunk = (uint8_t *) malloc(SMG_COUNT_BGZF_CHUNK);
+    blk = (BgzfBlock *) malloc(sizeof(BgzfBlock) * BGZF_MAX_BLOCKS);
+    if (!chunk || !blk) exit(1);
+  }
+  HostInflater(const HostInflater &) = delete;
+  ~HostInflater() override { free(chunk); free(blk); free(text); }
+  const char *reason(int status) const override { return inflate_reason(status); }
+  int inflate(int n, const uint8_t **out, int *bad_block, char *, size_t) override
+  { size_t end = 0;
+    for (int i = 0; i < n; i++) end = std::max(end, (size_t) blk[i].out_off + blk[i].isize);
+    free(text);
+    text = (uint8_t *) malloc(end ? end : 1);
+    if (!text) exit(1);
+    text_n = 0; calls++;
+    for (int i = 0; i < n; i++)
+      { const int st = inflate_member_host(chunk + blk[i].in_off, blk[i].clen, text + blk[i].out_off, blk[i].isize, blk[i].crc);
+        if (st != INF_OK) { *bad_block = i; return st; }
+      }
+    *out = text; text_n = end;
+    return 0;
+  }
+  int unpack(const BamDesc *d, size_t nd, size_t out_len, Sink &sink, char *errbuf, size_t errlen) override
+  { if (!bam_desc_ok(d, nd, text_n, out_len)) return fail(errbuf, errlen, SMG_EINVAL, "internal error: %zu descriptors do not describe the text", nd);
+    uint8_t *out = (uint8_t *) malloc(out_len ? out_len : 1);
+    if (!out) exit(1);
+    for (size_t i = 0; i < nd; i++)
+      { if (d[i].out_off) out[d[i].out_off - 1] = SMG_COUNT_SEPARATOR;
+        bam_unpack_host(text + d[i].seq_off, d[i].l_seq, out + d[i].out_off);
+      }
+    unpacks++;
+    const bool ok = sink.put(out, out_len);
+    free(out);
+    return ok ? 0 : 1;
+  }
+};
+
+// what read_files returned, and what its consumer saw
+struct Got { int rc; std::string err; std::vector<Bytes> per_file; int64_t bases; int blocks; std::vector<FileRead> files; int calls, unpacks; };
+
+// fail_at > 0: the consumer returns `code` for its fail_at-th block (and must not be called again); inflaters: every reader
+// thread has a HostInflater (without one a BGZF file is refused)
+static Got run(const std::vector<std::string> &paths, int threads, int nblocks, size_t block, int fail_at = 0, int code = 0, bool inflaters = false)
 { std::vector<const char *> cp;
   for (const std::string &p : paths) cp.push_back(p.c_str());
   Blocks blocks(nblocks, block);
-  Got g{ 0, "", std::vector<Bytes>(paths.size()), -1, 0 };
+  Got g{ 0, "", std::vector<Bytes>(paths.size()), -1, 0, {}, 0, 0 };
   double t_last = 0;
   char eb[512]; eb[0] = 0;
   bool after_failure = false;
-  g.rc = read_files(cp.data(), (int) cp.size(), reader_threads(threads, (int) cp.size()), blocks.p.data(), nblocks, block,
+  const int nthr = reader_threads(threads, (int) cp.size());
+  std::vector<HostInflater> own((size_t) (inflaters ? nthr : 0));
+  std::vector<Inflater *> infl;
+  for (HostInflater &h : own) infl.push_back(&h);
+  g.rc = read_files(cp.data(), (int) cp.size(), nthr, blocks.p.data(), nblocks, block,
                     [&](const uint8_t *p, int64_t n, int file)
                       { if (g.blocks >= fail_at && fail_at > 0) after_failure = true;
                         g.blocks++;
                         if (n < 1 || (size_t) n > block) { printf("FAILED  a block of %lld bytes\n", (long long) n); bad++; }
                         g.per_file[(size_t) file].insert(g.per_file[(size_t) file].end(), p, p + n);
                         return g.blocks == fail_at ? code : 0;
-                      }, &g.bases, &t_last, eb, sizeof(eb));
+                      }, &g.bases, &t_last, &g.files, eb, sizeof(eb), inflaters ? infl.data() : nullptr);
   g.err = eb;
+  for (const HostInflater &h : own) { g.calls += h.calls; g.unpacks += h.unpacks; }
+  expect(g.files.size() == paths.size(), "one record per file", std::to_string(g.files.size()));
   expect(!after_failure, "no block is consumed after the consumer failed", std::to_string(g.blocks));
   return g;
 }
@@ -134,6 +276,8 @@ int main()
           expect(g.rc == 0, "a run succeeds", what + ": " + g.err);
           for (int f = 0; f < nfiles; f++) expect(g.per_file[(size_t) f] == want[(size_t) f], "the blocks of a file are its stripped stream", what + ", file " + std::to_string(f));
           expect(g.bases == total[nfiles], "the bases are counted", what);
+          for (int f = 0; f < nfiles; f++)
+            expect(g.files[(size_t) f].route == ROUTE_TEXT && g.files[(size_t) f].bases == total[f + 1] - total[f], "the record of a plain file", what);
           runs++;
         }
 
@@ -178,9 +322,142 @@ int main()
     expect(survey_files(cp.data(), (int) cp.size(), 21, &bound, eb, sizeof(eb)) == 0 && bound == bytes, "the bound is the sizes and k + 1 a file", std::to_string(bound));
   }
 
+  // ---- BGZF and BAM through the Inflater seam ----
+  int zruns = 0;
+  const std::string no_device = " is BGZF compressed: this call has no device to inflate it on, use smg_count_bgzf_inflate or one of the counting calls";
+  auto nbases = [](const Bytes &v) { int64_t n = 0; for (uint8_t c : v) n += c != SMG_COUNT_SEPARATOR; return n; };
+  auto check_file = [&](const Got &g, size_t f, const Bytes &stream, int route, int64_t records, int64_t nb, const std::string &what)
+    { expect(g.per_file[f] == stream, "the blocks of a compressed file are its stripped stream", what);
+      const FileRead &r = g.files[f];
+      expect(r.route == route && r.records == records && r.bases == nb, "the record of a compressed file",
+             what + ": route " + std::to_string(r.route) + ", " + std::to_string(r.records) + " records, " + std::to_string(r.bases) + " bases");
+    };
+
+  // a BGZF FASTQ in members of 1 .. 5000 bytes
+  const std::string fq_text = make_text(rng, true, 300, 400, false, true);
+  const Bytes fq_want = parse_whole(fq_text);
+  int64_t fq_records = 1;
+  for (uint8_t c : fq_want) fq_records += c == SMG_COUNT_SEPARATOR;
+  const std::string fqz = write_file(dir, 20, bgzf_file(fq_text, 0, rng));
+
+  // a BAM: a few primary records, a secondary and a supplementary one that are skipped, an empty one; members of 37 bytes
+  const std::vector<BamRec> small = { { "r0", bam_letters(rng, 150), 4 }, { "r1", bam_letters(rng, 31), 0x100 }, { "r2", "", 4 },
+                                      { "r3", bam_letters(rng, 4097), 16 }, { "r4", bam_letters(rng, 77), 0x800 | 16 }, { "r5", bam_letters(rng, 1), 0 } };
+  std::string small_text = bam_header();
+  for (const BamRec &r : small) small_text += bam_record(r);
+  int64_t small_records = 0, small_bases = 0;
+  const Bytes small_want = bam_stripped(small, &small_records, &small_bases);
+  const std::string bam = write_file(dir, 21, bgzf_file(small_text, 37, rng));
+  expect(small_records == 4 && small_bases == 150 + 4097 + 1, "the small BAM is what it was made to be", std::to_string(small_records));
+
+  // a BAM whose members exceed one chunk of the reader: members of 60000 bytes (60031 in the file, which do not divide the
+  // chunk: one is cut by its end), and a record of 20000 bases placed so that the text of the first call ends inside its
+  // seq field
+  const size_t member = 60000, first_call = (size_t) SMG_COUNT_BGZF_CHUNK / (member + 31) * member;       // text bytes of the first inflate call
+  std::vector<BamRec> large;
+  std::string large_text = bam_header();
+  bool placed = false;
+  while (large_text.size() < first_call + 2 * member)
+    { const bool now = !placed && large_text.size() + 5000 > first_call;
+      large.push_back(BamRec{ "m" + std::to_string(large.size()), bam_letters(rng, now ? 20000 : rng() % 600), rng() % 23 == 0 ? 0x900u : 4u });
+      if (now)
+        { const size_t seq_at = large_text.size() + 36 + large.back().name.size() + 1;
+          large.back().flag = 4;
+          placed = seq_at < first_call && first_call < seq_at + 10000;
+          expect(placed, "the chunk seam lies in a seq field", std::to_string(seq_at));
+        }
+      large_text += bam_record(large.back());
+    }
+  int64_t large_records = 0, large_bases = 0;
+  const Bytes large_want = bam_stripped(large, &large_records, &large_bases);
+  const std::string large_file = bgzf_file(large_text, member, rng);
+  const std::string big = write_file(dir, 22, large_file);
+  expect(placed && large_file.size() > (size_t) SMG_COUNT_BGZF_CHUNK && (size_t) SMG_COUNT_BGZF_CHUNK % (member + 31) != 0,
+         "the large BAM exceeds one chunk and a member is cut by its end", std::to_string(large_file.size()));
+
+  // each alone, one reader
+  for (size_t block : { (size_t) 4096, (size_t) 8 << 20 })
+    { Got g = run({ fqz }, 1, 4, block, 0, 0, true);
+      expect(g.rc == 0 && g.calls == 1 && g.unpacks == 0, "a BGZF FASTQ is read", g.err);
+      check_file(g, 0, fq_want, ROUTE_TEXT, fq_records, nbases(fq_want), "BGZF FASTQ");
+      g = run({ bam }, 1, 4, block, 0, 0, true);
+      expect(g.rc == 0 && g.calls == 1 && g.unpacks == 1, "a BAM is read", g.err);
+      check_file(g, 0, small_want, ROUTE_BAM, small_records, small_bases, "small BAM");
+      expect(g.bases == small_bases, "the bases of a BAM are counted", std::to_string(g.bases));
+      zruns += 2;
+    }
+  { const Got g = run({ big }, 1, 4, (size_t) 8 << 20, 0, 0, true);
+    expect(g.rc == 0 && g.calls == 2 && g.unpacks == 2, "a BAM of two chunks is read in two calls", g.err + " " + std::to_string(g.calls));
+    check_file(g, 0, large_want, ROUTE_BAM, large_records, large_bases, "large BAM");
+    zruns++;
+  }
+
+  // in a mixed list with plain files, one inflater per reader thread
+  for (int threads : { 1, 3 })
+    { const std::vector<std::string> some = { paths[0], fqz, paths[1], bam, big, paths[3], fqz };
+      const Got g = run(some, threads, 2 * threads + 2, (size_t) 1 << 20, 0, 0, true);
+      const std::string what = "mixed list, " + std::to_string(threads) + " threads";
+      expect(g.rc == 0, "a mixed list is read", what + ": " + g.err);
+      for (size_t f : { (size_t) 0, (size_t) 2, (size_t) 5 })
+        { const size_t i = f == 0 ? 0 : f == 2 ? 1 : 3;
+          expect(g.per_file[f] == want[i] && g.files[f].route == ROUTE_TEXT && g.files[f].bases == total[i + 1] - total[i], "a plain file of a mixed list", what);
+        }
+      check_file(g, 1, fq_want, ROUTE_TEXT, fq_records, nbases(fq_want), what);
+      check_file(g, 6, fq_want, ROUTE_TEXT, fq_records, nbases(fq_want), what);
+      check_file(g, 3, small_want, ROUTE_BAM, small_records, small_bases, what);
+      check_file(g, 4, large_want, ROUTE_BAM, large_records, large_bases, what);
+      std::vector<const char *> cp;
+      for (const std::string &p : some) cp.push_back(p.c_str());
+      std::vector<char> is_bgzf;
+      int64_t bound = 0, text_bytes = (int64_t) (2 * fq_text.size() + small_text.size() + large_text.size() + texts[0].size() + texts[1].size() + texts[3].size());
+      char eb[512]; eb[0] = 0;
+      expect(survey_files(cp.data(), (int) cp.size(), 21, &bound, eb, sizeof(eb), &is_bgzf) == 0 && bound == text_bytes + 7 * 22 &&
+             is_bgzf == std::vector<char>({ 0, 1, 0, 1, 1, 0, 1 }), "the survey bounds a BGZF file by its text", eb);
+      zruns++;
+    }
+
+  // without an inflater a BGZF file is refused, and so is a reader thread that has none
+  for (int threads : { 1, 3 })
+    { const Got g = run({ paths[0], paths[1], bam }, threads, 2 * threads + 2, 4096);
+      expect(g.rc == SMG_EINVAL && g.err == bam + no_device, "a BGZF file without an inflater is refused", g.err);
+      expect(g.files[2].route == ROUTE_NONE, "a refused file has no record", std::to_string(g.files[2].route));
+      zruns++;
+    }
+
+  // a bad member and a bad record end the run with their message; every thread is joined
+  { size_t bad_at = 0;
+    const std::string bad_crc = write_file(dir, 23, bgzf_file(small_text, 37, rng, 5, &bad_at));
+    std::string short_text = bam_header() + bam_record(small[0]);
+    const size_t rec_at = short_text.size();
+    short_text += bam_record(small[3], 10) ;
+    const std::string bad_rec = write_file(dir, 24, bgzf_file(short_text, 37, rng));
+    for (int threads : { 1, 3 })
+      { Got g = run({ paths[0], bam, bad_crc, paths[1], fqz }, threads, 2 * threads + 2, 4096, 0, 0, true);
+        expect(g.rc == SMG_EFORMAT && g.err == bad_crc + ": BGZF block at offset " + std::to_string(bad_at) + ": " + inflate_reason(INF_BAD_CRC),
+               "a bad member ends the run", g.err);
+        expect(g.files[2].route == ROUTE_NONE, "a file with a bad member has no record", "");
+        g = run({ paths[0], bam, bad_rec, paths[1], fqz }, threads, 2 * threads + 2, 4096, 0, 0, true);
+        expect(g.rc == SMG_EFORMAT && g.err == bad_rec + ": BAM record at text offset " + std::to_string(rec_at) +
+               ": block_size is smaller than the 32 bytes of the fixed fields", "a bad record ends the run", g.err);
+        expect(g.files[2].route == ROUTE_NONE, "a file with a bad record has no record", "");
+        if (threads == 1) check_file(g, 1, small_want, ROUTE_BAM, small_records, small_bases, "the BAM read before the bad one");
+        zruns += 2;
+      }
+    remove(bad_crc.c_str()); remove(bad_rec.c_str());
+  }
+  // the scan, as the survey classifies
+  { int64_t nb = 0, nt = 0;
+    char eb[512]; eb[0] = 0;
+    expect(bgzf_scan(big.c_str(), &nb, &nt, eb, sizeof(eb)) == 0 && nt == (int64_t) large_text.size() && nb == (int64_t) ((large_text.size() + member - 1) / member) + 1,
+           "the scan of a BGZF file", eb);
+    expect(bgzf_scan(paths[0].c_str(), &nb, &nt, eb, sizeof(eb)) == SMG_EINVAL && eb == paths[0] + " is not BGZF: it does not begin with a gzip header", "the scan of a plain file", eb);
+    expect(bgzf_scan(gz.c_str(), &nb, &nt, eb, sizeof(eb)) == SMG_EINVAL && eb == gz + " is gzip compressed: compressed input is not supported, decompress it first", "the scan of a gzip file", eb);
+  }
+  remove(fqz.c_str()); remove(bam.c_str()); remove(big.c_str());
+
   for (const std::string &p : paths) remove(p.c_str());
   remove(gz.c_str());
   rmdir(dir.c_str());
-  printf("%s (%d runs)\n", bad ? "reader_check: FAILED" : "reader_check: every run delivered the parser's stream or its error", runs);
+  printf("%s (%d runs, %d of them over BGZF and BAM files)\n", bad ? "reader_check: FAILED" : "reader_check: every run delivered the parser's stream or its error", runs + zruns, zruns);
   return bad ? 1 : 0;
 }

@@ -37,14 +37,18 @@
 //   smg_count_kernels.hpp  all kc_* device code.  Earlier records (profiles/*.md) name kernels that have since been merged:
 //                          kc_extract_packed<W> is kc_extract_store<W, 12>, kc_extract_fine<W> is kc_extract_store<W, 24>,
 //                          kc_bins is kc_bins<false>, kc_subbins is kc_bins<true>, kc_bin / kc_bin24 are kc_bin<12> / kc_bin<24>
-//   smg_count_reader.hpp   host only: the FASTA / FASTQ parser, the reader threads and their ring of blocks (read_files), the
-//                          members of a BGZF file (bgzf_walk, bgzf_feed) and the Inflater they are handed to
+//   smg_count_reader.hpp   host only: the FASTA / FASTQ parser, what a file is by its first bytes (file_kind), the members of
+//                          a BGZF file (bgzf_walk, bgzf_feed) and the Inflater they are handed to, the routing of one file
+//                          (parse_file) and what it gives back (FileRead), the reader threads and their ring (read_files)
 //   smg_inflate.hpp        DEFLATE, one BGZF member per wave: inf_members and the decoder it shares with the host check
 //   smg_bam.hpp            BAM: the framer of the records (host), bam_unpack and the tile logic it shares with the host check
 //   smg_count_plan.hpp     host only: the memory plan, how buffers grow, the cuts of the key ranges
 //   smg_count_parts.hpp    the parts of the device driver, each owning its buffers: Run (what they share), Batch, Distinct,
-//                          Store, Table
-//   this file              the driver itself (Counter: set-up, flush, the ranges, finish), the entry points and the C ABI
+//                          Store, Table; the one HIP check (DCHK), the device check, pinned memory that frees itself
+//   smg_count_inflater.hpp the device stage of compressed input, a part like those: DeviceInflater (inflate, unpack), one per
+//                          reader thread, and the BGZF file a one-file route opens for an inflater of its own
+//   this file              the driver itself (Counter: set-up, flush, the ranges, finish), the entry points (count_files,
+//                          count_bases, the one-file routes, the report of the BAM files of the last call) and the C ABI
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,8 +69,7 @@
 #include "smg_count_reader.hpp"
 #include "smg_count_plan.hpp"
 #include "smg_count_parts.hpp"
-#include "smg_inflate.hpp"
-#include "smg_bam.hpp"
+#include "smg_count_inflater.hpp"
 
 // where a run puts its results (the arguments of the C ABI)
 struct Out
@@ -95,10 +98,7 @@ struct Counter
       }
     x.pt.used = 1;
     x.k = o->kmer; x.t = o->minval; x.W = count_words(x.k);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-      return fail(errbuf, errlen, SMG_ENODEV, "no HIP device: the k-mer counter has no CPU fallback%s", "");
-    if (o->device < 0 || o->device >= ndev) return fail(errbuf, errlen, SMG_EINVAL, "device %d of %d", o->device, ndev);
+    RCHK(check_device(o->device, errbuf, errlen));
     DCHK(hipSetDevice(o->device));
     size_t free_b = 0;
     RCHK(x.free_bytes(&free_b));
@@ -274,149 +274,6 @@ struct Counter
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-//  the Inflater of the device: one per reader thread, on a stream of its own
-// ---------------------------------------------------------------------------------------------------------------
-
-static_assert(sizeof(InfBlock) == sizeof(BgzfBlock) && sizeof(BgzfBlock) == 20, "the kernel reads the reader's blocks as they are");
-
-#define BAM_SLAB     ((size_t) 32 << 20)                       // output bytes of one launch of bam_unpack (a multiple of BAM_TILE)
-#define BAM_MAX_DESC (BGZF_TEXT / 36 + 1)                      // records that begin in the text of one call: 36 bytes each at least
-static_assert(BAM_SLAB % BAM_TILE == 0, "a slab is whole tiles");
-
-struct DeviceInflater : Inflater
-{ int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint8_t *h_text = nullptr, *d_chunk = nullptr, *d_text = nullptr;
-  uint32_t *h_status = nullptr, *d_status = nullptr;
-  InfBlock *d_blk = nullptr;
-  double ms_kernel = 0;
-  int64_t launches = 0;
-  // the second step, for BAM: set up by the first piece that needs it (a file shows that it is BAM only in its text)
-  size_t text_n = 0;                                           // text bytes of the last inflate call
-  BamDesc *h_desc = nullptr, *d_desc = nullptr;
-  uint8_t *h_out = nullptr, *d_out = nullptr;
-  double ms_unpack = 0, ms_out_d2h = 0;                        // bam_unpack alone (HIP events); the copies of its output (host clock)
-  struct BamNote { std::string path; int64_t records, bases; double ms[4]; };     // ms: as smg_count_bam_report gives them
-  std::vector<BamNote> bam_files;
-  double mark_inflate = 0, mark_unpack = 0, mark_d2h = 0;
-
-  // pinned and device memory for a chunk, its blocks, their text and statuses; 0 or the HIP error
-  hipError_t init(int dev)
-  { device = dev;
-    hipError_t e;
-    if ((e = hipSetDevice(dev)) != hipSuccess) return e;
-    if ((e = hipStreamCreate(&stream)) != hipSuccess) return e;
-    if ((e = hipEventCreate(&ev0)) != hipSuccess || (e = hipEventCreate(&ev1)) != hipSuccess) return e;
-    if ((e = hipHostMalloc((void **) &chunk, SMG_COUNT_BGZF_CHUNK, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipHostMalloc((void **) &blk, sizeof(BgzfBlock) * BGZF_MAX_BLOCKS, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipHostMalloc((void **) &h_text, BGZF_TEXT, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipHostMalloc((void **) &h_status, sizeof(uint32_t) * BGZF_MAX_BLOCKS, hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **) &d_chunk, SMG_COUNT_BGZF_CHUNK)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **) &d_blk, sizeof(InfBlock) * BGZF_MAX_BLOCKS)) != hipSuccess) return e;
-    if ((e = hipMalloc((void **) &d_text, BGZF_TEXT)) != hipSuccess) return e;
-    return hipMalloc((void **) &d_status, sizeof(uint32_t) * BGZF_MAX_BLOCKS);
-  }
-  ~DeviceInflater() override
-  { (void) hipFree(d_out); (void) hipFree(d_desc); (void) hipHostFree(h_out); (void) hipHostFree(h_desc);
-    (void) hipFree(d_status); (void) hipFree(d_text); (void) hipFree(d_blk); (void) hipFree(d_chunk);
-    (void) hipHostFree(h_status); (void) hipHostFree(h_text); (void) hipHostFree(blk); (void) hipHostFree(chunk);
-    if (ev0) (void) hipEventDestroy(ev0);
-    if (ev1) (void) hipEventDestroy(ev1);
-    if (stream) (void) hipStreamDestroy(stream);
-  }
-
-  const char *reason(int status) const override { return inflate_reason(status); }
-
-  // H2D of the members, the kernel, D2H of statuses and text.  The reader has bounded every block: its payload lies
-  // in the chunk, its text in BGZF_TEXT bytes, and the kernel stays inside both whatever the payload says.
-  int inflate(int n, const uint8_t **text, int *bad, char *errbuf, size_t errlen) override
-  { size_t in_end = 0, out_end = 0;
-    for (int i = 0; i < n; i++)
-      { const size_t ie = (size_t) blk[i].in_off + blk[i].clen, oe = (size_t) blk[i].out_off + blk[i].isize;
-        if (ie > in_end) in_end = ie;
-        if (oe > out_end) out_end = oe;
-      }
-    if (n < 1 || n > BGZF_MAX_BLOCKS || in_end > (size_t) SMG_COUNT_BGZF_CHUNK || out_end > BGZF_TEXT)
-      return fail(errbuf, errlen, SMG_EINVAL, "internal error: %d BGZF blocks of %zu bytes with %zu bytes of text in one launch", n, in_end, out_end);
-#define ICHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) \
-      return fail(errbuf, errlen, _e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (%s)", hipGetErrorString(_e), #call); } while (0)
-    float ms = 0;
-    ICHK(hipSetDevice(device));                                // (a reader thread has not chosen its device yet)
-    ICHK(hipMemcpyAsync(d_chunk, chunk, in_end, hipMemcpyHostToDevice, stream));
-    ICHK(hipMemcpyAsync(d_blk, blk, sizeof(InfBlock) * (size_t) n, hipMemcpyHostToDevice, stream));
-    ICHK(hipEventRecord(ev0, stream));
-    hipLaunchKernelGGL(inf_members, dim3((unsigned) n), dim3(64), 0, stream, d_chunk, d_blk, n, d_text, d_status);
-    ICHK(hipGetLastError());
-    ICHK(hipEventRecord(ev1, stream));
-    ICHK(hipMemcpyAsync(h_status, d_status, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost, stream));
-    if (out_end) ICHK(hipMemcpyAsync(h_text, d_text, out_end, hipMemcpyDeviceToHost, stream));
-    ICHK(hipStreamSynchronize(stream));
-    ICHK(hipEventElapsedTime(&ms, ev0, ev1));
-    ms_kernel += ms; launches++;
-    text_n = 0;
-    for (int i = 0; i < n; i++)
-      if (h_status[i] != INF_OK) { *bad = i; return h_status[i] < INF_NSTATUS ? (int) h_status[i] : INF_NSTATUS; }
-    *text = h_text;
-    text_n = out_end;
-    return 0;
-  }
-
-  void mark() override { mark_inflate = ms_kernel; mark_unpack = ms_unpack; mark_d2h = ms_out_d2h; }
-  void note_bam(const char *path, const BamFramer &fr) override
-  { bam_files.push_back(BamNote{ path, fr.records, fr.bases, { fr.ms_feed, ms_kernel - mark_inflate, ms_unpack - mark_unpack, ms_out_d2h - mark_d2h } }); }
-
-  // H2D of the descriptors, then BAM_SLAB bytes of output at a time: bam_unpack over their tiles, D2H into pinned memory,
-  // the sink.  The descriptors are checked against the text and the output here, and the kernel stays inside both anyway.
-  int unpack(const BamDesc *d, size_t nd, size_t out_len, Sink &sink, char *errbuf, size_t errlen) override
-  { if (nd > BAM_MAX_DESC || out_len > 0xFFFFFFFFu - 2 * BAM_SLAB || !bam_desc_ok(d, nd, text_n, out_len))
-      return fail(errbuf, errlen, SMG_EINVAL, "internal error: %zu BAM records with %zu bases do not describe a text of %zu bytes", nd, out_len, text_n);
-    if (out_len == 0) return 0;
-    ICHK(hipSetDevice(device));
-    if (!d_out)
-      { ICHK(hipHostMalloc((void **) &h_desc, sizeof(BamDesc) * BAM_MAX_DESC, hipHostMallocDefault));
-        ICHK(hipHostMalloc((void **) &h_out, BAM_SLAB, hipHostMallocDefault));
-        ICHK(hipMalloc((void **) &d_desc, sizeof(BamDesc) * BAM_MAX_DESC));
-        ICHK(hipMalloc((void **) &d_out, BAM_SLAB));
-      }
-    memcpy(h_desc, d, sizeof(BamDesc) * nd);
-    ICHK(hipMemcpyAsync(d_desc, h_desc, sizeof(BamDesc) * nd, hipMemcpyHostToDevice, stream));
-    for (size_t base = 0; base < out_len; base += BAM_SLAB)
-      { const size_t len = out_len - base < BAM_SLAB ? out_len - base : BAM_SLAB;
-        float ms = 0;
-        ICHK(hipEventRecord(ev0, stream));
-        hipLaunchKernelGGL(bam_unpack, dim3((unsigned) ((len + BAM_TILE - 1) / BAM_TILE)), dim3(BAM_LANES), 0, stream, d_text, (uint32_t) text_n,
-                           d_desc, (uint32_t) nd, d_out, (uint32_t) base, (uint32_t) len);
-        ICHK(hipGetLastError());
-        ICHK(hipEventRecord(ev1, stream));
-        ICHK(hipStreamSynchronize(stream));
-        ICHK(hipEventElapsedTime(&ms, ev0, ev1));
-        ms_unpack += ms;
-        const double t0 = now_ms();
-        ICHK(hipMemcpyAsync(h_out, d_out, len, hipMemcpyDeviceToHost, stream));
-        ICHK(hipStreamSynchronize(stream));
-        ms_out_d2h += now_ms() - t0;
-        if (!sink.put(h_out, len)) return 1;
-      }
-    return 0;
-  }
-#undef ICHK
-};
-
-// a device inflater, or the error: the device is checked as Counter::init checks it
-static int new_inflater(int device, std::unique_ptr<DeviceInflater> &out, char *errbuf, size_t errlen)
-{ int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-    return fail(errbuf, errlen, SMG_ENODEV, "no HIP device: the k-mer counter has no CPU fallback%s", "");
-  if (device < 0 || device >= ndev) return fail(errbuf, errlen, SMG_EINVAL, "device %d of %d", device, ndev);
-  out.reset(new DeviceInflater());
-  const hipError_t e = out->init(device);
-  if (e != hipSuccess)
-    return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "cannot set up the BGZF inflater: %s", hipGetErrorString(e));
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 //  entry points
 // ---------------------------------------------------------------------------------------------------------------
 
@@ -453,30 +310,48 @@ static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, i
 
 #define RING_BLOCK ((size_t) 8 << 20)
 
-// what the last call of this process that reads BAM (a counting call or smg_count_bam_strip) read from its BAM files, for the
-// report of the executable and of tools/count_time.py (smg_count_bam_report)
+// What the last call of this process that reads BAM (a counting call over files or smg_count_bam_strip) read from the BAM
+// files it read to their end, for the report of the executable and of tools/count_time.py (smg_count_bam_report).
+struct BamSeen { std::string path; FileRead read; };
 static std::mutex bam_seen_m;
-static std::vector<DeviceInflater::BamNote> bam_seen;
+static std::vector<BamSeen> bam_seen;
+
+// the one way that table is written: the BAM files among paths[f] with files[f], thread by thread as nthr readers took them
+static void publish_bam(const char *const *paths, const std::vector<FileRead> &files, int nthr)
+{ std::lock_guard<std::mutex> lk(bam_seen_m);
+  bam_seen.clear();
+  try
+    { for (int j = 0; j < nthr; j++)
+        for (size_t f = (size_t) j; f < files.size(); f += (size_t) nthr)
+          if (files[f].route == ROUTE_BAM) bam_seen.push_back(BamSeen{ paths[f], files[f] });
+    }
+  catch (...) { bam_seen.clear(); }                            // (out of memory: no report)
+}
+
+static int bam_report(const char *path, int64_t *records, int64_t *bases, double *ms)
+{ if (!path || !records || !bases) return SMG_EINVAL;
+  std::lock_guard<std::mutex> lk(bam_seen_m);
+  for (const BamSeen &b : bam_seen)
+    if (b.path == path)
+      { *records = b.read.records; *bases = b.read.bases;
+        if (ms) { ms[0] = b.read.ms_frame; ms[1] = b.read.dev.inflate; ms[2] = b.read.dev.unpack; ms[3] = b.read.dev.d2h; }
+        return 0;
+      }
+  return SMG_EINVAL;
+}
 
 // (the inflaters of the reader threads that meet a BGZF file are set up by the survey, before Counter::init reads the
 //  free device memory, so that the plan sees what is left)
 static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
 { std::vector<std::unique_ptr<DeviceInflater>> own;
   std::vector<Inflater *> infl;
-  struct Seen                                                  // (the BAM files of this call, for smg_count_bam_report)
-  { std::vector<std::unique_ptr<DeviceInflater>> &own;
-    ~Seen()
-    { std::lock_guard<std::mutex> lk(bam_seen_m);
-      bam_seen.clear();
-      try { for (auto &i : own) if (i) bam_seen.insert(bam_seen.end(), i->bam_files.begin(), i->bam_files.end()); }
-      catch (...) { bam_seen.clear(); }                        // (out of memory: no report)
-    }
-  } seen{ own };
+  int nthr = 1;
+  publish_bam(paths, std::vector<FileRead>(), 1);              // (whatever becomes of this call, the report of an earlier one is gone)
   return count_run(opts, io, paths && npaths >= 1, npaths,
     [&](int64_t *bound)
       { std::vector<char> bgzf;
         RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf));
-        const int nthr = reader_threads(opts->host_threads, npaths);
+        nthr = reader_threads(opts->host_threads, npaths);
         own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
         for (int f = 0; f < npaths; f++)
           if (bgzf[(size_t) f] && !own[(size_t) (f % nthr)])
@@ -486,19 +361,18 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         return 0;
       },
     [&](Counter &c, double *t_read)
-      { const int nthr = reader_threads(opts->host_threads, npaths);
-        std::vector<uint8_t *> pinned;
-        struct Unpin { std::vector<uint8_t *> &v; ~Unpin() { for (uint8_t *p : v) (void) hipHostFree(p); } } unpin{ pinned };
-        pinned.reserve((size_t) (2 * nthr + 2));
-        for (int b = 0; b < 2 * nthr + 2; b++)
-          { uint8_t *p = nullptr;
-            if (hipHostMalloc((void **) &p, RING_BLOCK, hipHostMallocDefault) != hipSuccess)
-              return fail(errbuf, errlen, SMG_ENOMEM, "cannot pin %zu bytes of host memory", RING_BLOCK);
-            pinned.push_back(p);
+      { std::vector<Pinned<uint8_t>> pinned((size_t) (2 * nthr + 2));
+        std::vector<uint8_t *> blocks;
+        for (Pinned<uint8_t> &b : pinned)
+          { if (b.alloc(RING_BLOCK) != hipSuccess) return fail(errbuf, errlen, SMG_ENOMEM, "cannot pin %zu bytes of host memory", RING_BLOCK);
+            blocks.push_back(b);
           }
-        return read_files(paths, npaths, nthr, pinned.data(), (int) pinned.size(), RING_BLOCK,
-                          [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, errbuf, errlen,
-                          infl.data());
+        std::vector<FileRead> files;
+        const int rc = read_files(paths, npaths, nthr, blocks.data(), (int) blocks.size(), RING_BLOCK,
+                                  [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, &files,
+                                  errbuf, errlen, infl.data());
+        publish_bam(paths, files, nthr);                       // (after an error too: the files read to their end before it)
+        return rc;
       }, errbuf, errlen);
 }
 
@@ -514,42 +388,20 @@ static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts
       }, errbuf, errlen);
 }
 
-// members and text bytes of a BGZF file; what is not BGZF is refused with the words of the counting calls
-static int bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen)
-{ if (!path || !blocks || !text_bytes) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
-  uint8_t magic[2] = { 0, 0 };
-  const ssize_t got = pread(fd, magic, 2, 0);
-  int rc = bgzf_probe(fd, path, errbuf, errlen);
-  if (rc == 1)
-    rc = got == 2 && magic[0] == 0x1f && magic[1] == 0x8b
-           ? fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path)
-           : fail(errbuf, errlen, SMG_EINVAL, "%s is not BGZF: it does not begin with a gzip header", path);
-  else if (rc == 0) rc = bgzf_walk(fd, path, blocks, text_bytes, errbuf, errlen);
-  close(fd);
-  return rc;
-}
-
+// the text of a whole BGZF file, inflated as the counting calls inflate it
 static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen)
 { if (!text || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
-  int64_t blocks = 0, bytes = 0;
-  RCHK(bgzf_scan(path, &blocks, &bytes, errbuf, errlen));
-  std::unique_ptr<DeviceInflater> infl;
-  RCHK(new_inflater(device, infl, errbuf, errlen));
-  struct Fd { int fd; ~Fd() { if (fd >= 0) close(fd); } } f{ open(path, O_RDONLY) };
-  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
-  std::unique_ptr<uint8_t, void (*)(void *)> buf((uint8_t *) malloc((size_t) bytes + 1), free);
-  if (!buf) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
-  int64_t have = 0;
-  RCHK(bgzf_feed(f.fd, path, *infl, [&](const uint8_t *t, size_t m)
-    { if (have + (int64_t) m > bytes) return fail(errbuf, errlen, SMG_EFORMAT, "%s changed while it was read", path);
-      memcpy(buf.get() + have, t, m); have += (int64_t) m;
+  BgzfInput in;
+  RCHK(in.open(path, device, errbuf, errlen));
+  GrowSink sink;
+  sink.reserve((size_t) in.text_bytes + 1);
+  RCHK(bgzf_feed(in.file->fd, path, *in.infl, [&](const uint8_t *t, size_t m)
+    { if ((int64_t) (sink.len + m) > in.text_bytes) return fail(errbuf, errlen, SMG_EFORMAT, "%s changed while it was read", path);
+      sink.put(t, m);
       return 0;
     }, errbuf, errlen));
-  *text = buf.release(); *n = have;
-  if (ms_kernel) *ms_kernel = infl->ms_kernel;
-  return 0;
+  if (ms_kernel) *ms_kernel = in.infl->ms.inflate;
+  return sink.hand_over(text, n, errbuf, errlen);
 }
 
 // the stripped stream of inflated BAM text, every record by the host routine; pieces of `piece` bytes (0: one piece)
@@ -564,57 +416,31 @@ static int bam_text(const uint8_t *text, int64_t n, int64_t piece, uint8_t **seq
       if (!fr.head.empty()) sink.put(fr.head.data(), fr.head.size());
     }
   RCHK(fr.finish("<text>", errbuf, errlen));
-  if (!sink.p) sink.p = (uint8_t *) malloc(1);
-  if (!sink.p) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
-  *seq = sink.p; *nseq = (int64_t) sink.len;
-  sink.p = nullptr;
-  return 0;
+  return sink.hand_over(seq, nseq, errbuf, errlen);
 }
 
 // the stripped stream of a BAM file by the route of the counting calls
 static int bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t *nseq, int64_t *records, double *ms_kernel, char *errbuf, size_t errlen)
 { if (!seq || !nseq) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
-  int64_t blocks = 0, bytes = 0;
-  RCHK(bgzf_scan(path, &blocks, &bytes, errbuf, errlen));
-  std::unique_ptr<DeviceInflater> infl;
-  RCHK(new_inflater(device, infl, errbuf, errlen));
-  struct Fd { int fd; ~Fd() { if (fd >= 0) close(fd); } } f{ open(path, O_RDONLY) };
-  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  BgzfInput in;
+  RCHK(in.open(path, device, errbuf, errlen));
   GrowSink sink;
   BamFramer fr;
   bool any = false;
-  infl->mark();
-  RCHK(bgzf_feed(f.fd, path, *infl, [&](const uint8_t *t, size_t m)
+  RCHK(bgzf_feed(in.file->fd, path, *in.infl, [&](const uint8_t *t, size_t m)
     { if (!any && m)
         { if (!is_bam_text(t, m)) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BAM: its text does not begin with the magic BAM\\1", path);
           any = true;
         }
-      return bam_piece(fr, t, m, path, *infl, sink, errbuf, errlen);
+      return bam_piece(fr, t, m, path, *in.infl, sink, errbuf, errlen);
     }, errbuf, errlen));
   if (!any) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BAM: it has no text", path);
   RCHK(fr.finish(path, errbuf, errlen));
-  if (!sink.p) sink.p = (uint8_t *) malloc(1);
-  if (!sink.p) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
-  *seq = sink.p; *nseq = (int64_t) sink.len;
-  sink.p = nullptr;
+  RCHK(sink.hand_over(seq, nseq, errbuf, errlen));
   if (records) *records = fr.records;
-  if (ms_kernel) *ms_kernel = infl->ms_unpack;
-  infl->note_bam(path, fr);
-  std::lock_guard<std::mutex> lk(bam_seen_m);
-  bam_seen = infl->bam_files;
+  if (ms_kernel) *ms_kernel = in.infl->ms.unpack;
+  publish_bam(&path, { bam_read(fr, in.infl->times()) }, 1);
   return 0;
-}
-
-static int bam_report(const char *path, int64_t *records, int64_t *bases, double *ms)
-{ if (!path || !records || !bases) return SMG_EINVAL;
-  std::lock_guard<std::mutex> lk(bam_seen_m);
-  for (const DeviceInflater::BamNote &b : bam_seen)
-    if (b.path == path)
-      { *records = b.records; *bases = b.bases;
-        if (ms) memcpy(ms, b.ms, sizeof(b.ms));
-        return 0;
-      }
-  return SMG_EINVAL;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@
 
 static_assert(CP_TILE == KC_TILE, "the store is sized in tiles of the kernels that read it");
 
-// (x: the Run of the part that checks)
+// the one check of a HIP call in the counter (x: the Run of the part that checks, or the Errors of a call outside a run)
 #define DCHK(call) do { const hipError_t _e = (call); if (_e != hipSuccess) return x.hip_error(_e, #call); } while (0)
 #define RCHK(call) do { const int _rc = (call); if (_rc) return _rc; } while (0)
 
@@ -31,11 +31,38 @@ static_assert(CP_TILE == KC_TILE, "the store is sized in tiles of the kernels th
 static unsigned nblk(int64_t n) { return (unsigned) ((n + KC_TPB - 1) / KC_TPB); }
 static unsigned ngrid(int64_t ntiles) { return (unsigned) (ntiles < 2048 ? ntiles : 2048); }      // grid-stride kernels
 
+// where the errors of a call go, and the one code and message of a HIP error
+struct Errors
+{ char *errbuf = nullptr; size_t errlen = 0;
+  int hip_error(hipError_t e, const char *call) const
+  { return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (%s)", hipGetErrorString(e), call); }
+};
+
+// there is a device, and `device` names one
+static int check_device(int device, char *errbuf, size_t errlen)
+{ int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(errbuf, errlen, SMG_ENODEV, "no HIP device: the k-mer counter has no CPU fallback%s", "");
+  if (device < 0 || device >= ndev) return fail(errbuf, errlen, SMG_EINVAL, "device %d of %d", device, ndev);
+  return 0;
+}
+
+// pinned host memory that frees itself: what DevBuf (smg_keysort.hpp) is for device memory
+template <class T> struct Pinned
+{ T *p = nullptr;
+  Pinned() = default;
+  Pinned(const Pinned &) = delete;
+  Pinned &operator=(const Pinned &) = delete;
+  Pinned(Pinned &&o) : p(o.p) { o.p = nullptr; }
+  ~Pinned() { if (p) (void) hipHostFree(p); }
+  hipError_t alloc(size_t bytes) { return hipHostMalloc((void **) &p, bytes, hipHostMallocDefault); }
+  operator T *() const { return p; }
+};
+
 // What the parts of a run share: k, where errors go, the stream with its two timing events, rocPRIM's grow-only scratch,
 // the statistics.
-struct Run
+struct Run : Errors
 { int k = 0, W = 1, t = 1;
-  char *errbuf = nullptr; size_t errlen = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   Dev tmp;
@@ -48,9 +75,6 @@ struct Run
     if (ev1) (void) hipEventDestroy(ev1);
     if (stream) (void) hipStreamDestroy(stream);
   }
-
-  int hip_error(hipError_t e, const char *call) const
-  { return fail(errbuf, errlen, e == hipErrorOutOfMemory ? SMG_ENOMEM : SMG_ENODEV, "HIP error: %s (%s)", hipGetErrorString(e), call); }
 
   int alloc(Dev &d, size_t bytes) const
   { const hipError_t e = d.alloc(bytes);

@@ -13,6 +13,9 @@
 // the bound of a BAM file is the sum of its ISIZE fields like that of any BGZF file, at least 1.5 times its bases (a base
 // takes half a byte and its quality one), so a large BAM may be counted by key range where one pass would have done; the
 // result is the same whichever way it is counted.
+//
+// What a reader learns about a file on the way (its route, records, bases, the times spent on it) is a FileRead, a plain
+// value that parse_file hands back and read_files collects per file; nothing of it goes through the Inflater.
 
 #pragma once
 #include <fcntl.h>
@@ -42,17 +45,26 @@ struct Sink
   virtual ~Sink() {}
 };
 
+// a file opened for reading, closed when it goes out of scope (fd < 0: it could not be opened)
+struct Fd
+{ const int fd;
+  explicit Fd(const char *path) : fd(open(path, O_RDONLY)) {}
+  Fd(const Fd &) = delete;
+  Fd &operator=(const Fd &) = delete;
+  ~Fd() { if (fd >= 0) close(fd); }
+};
+
 // Line-wise state machine over the bytes of one file, fed in arbitrary pieces.  A '\r' is dropped only in front of a
 // '\n' or at the end of the file; anywhere else it is a byte like any other (and ends a stretch).
 struct Parser
 { Sink &out;
   int fmt = 0, phase = 0, kind = 0;                           // fmt 1 FASTA, 2 FASTQ; kind 0 skip, 1 sequence, 2 blank
   bool bol = true, first = true, pending_cr = false, started = false;
-  int64_t bases = 0;
+  int64_t bases = 0, records = 0;
   explicit Parser(Sink &s) : out(s) {}
 
   bool emit(const uint8_t *p, size_t n) { bases += (int64_t) n; return n == 0 || out.put(p, n); }
-  bool record() { const uint8_t sep = SMG_COUNT_SEPARATOR; const bool ok = first || out.put(&sep, 1); first = false; return ok; }
+  bool record() { const uint8_t sep = SMG_COUNT_SEPARATOR; const bool ok = first || out.put(&sep, 1); first = false; records++; return ok; }
 
   // 0 ok, 1 the consumer gave up, SMG_EINVAL with a message
   int feed(const uint8_t *p, size_t n, const char *path, char *errbuf, size_t errlen)
@@ -115,6 +127,12 @@ struct Parser
 // one member for the inflater: its DEFLATE payload at chunk[in_off .. in_off + clen), its text at text[out_off .. + isize)
 struct BgzfBlock { uint32_t in_off, clen, out_off, isize, crc; };
 
+// the cumulative times of an inflater in ms: its two kernels, and the copies of the unpacked bytes to the host
+struct InflaterTimes
+{ double inflate = 0, unpack = 0, d2h = 0;
+  InflaterTimes operator-(const InflaterTimes &o) const { return InflaterTimes{ inflate - o.inflate, unpack - o.unpack, d2h - o.d2h }; }
+};
+
 // "These whole blocks of this buffer" -> "their text, or the first bad block and why".  The reader fills chunk (pinned
 // where the inflater is the device's) and blk[0 .. n) and calls inflate: 0 and *text (valid until the next call), or
 // > 0: the status (smg_inflate.hpp) of the first block that is not ok, *bad its index, or < 0: an error code, with message.
@@ -128,9 +146,18 @@ struct Inflater
   // code, with message.  An inflater without this step refuses.
   virtual int unpack(const BamDesc *, size_t, size_t, Sink &, char *errbuf, size_t errlen)
   { return fail(errbuf, errlen, SMG_EINVAL, "internal error: this inflater cannot unpack BAM sequences%s", ""); }
-  virtual void mark() {}                                       // a BGZF file begins: what note_bam reports is counted from here
-  virtual void note_bam(const char *, const BamFramer &) {}    // that file was BAM and has been read to its end
+  virtual InflaterTimes times() const { return InflaterTimes(); }      // of all calls so far
   virtual ~Inflater() {}
+};
+
+// What reading one file to its end gave: the route it took, its records (of a BAM file: the contributing ones) and their
+// bases, the host time of the BAM framer, and what the inflater spent on it.
+enum { ROUTE_NONE = 0, ROUTE_TEXT = 1, ROUTE_BAM = 2 };         // not read to its end; FASTA / FASTQ; BAM
+struct FileRead
+{ int route = ROUTE_NONE;
+  int64_t records = 0, bases = 0;
+  double ms_frame = 0;
+  InflaterTimes dev;
 };
 
 // The header of a member in p[0 .. avail): 0 BGZF (*blen bytes in all, *hlen of them header), 1 not BGZF, 2 more bytes
@@ -170,16 +197,22 @@ static inline int bgzf_member(const uint8_t *p, size_t avail, const char *path, 
   return 0;
 }
 
-// is the file BGZF by its first member?  0 yes, 1 no, SMG_EINVAL read error
-static inline int bgzf_probe(int fd, const char *path, char *errbuf, size_t errlen)
+// What a file is by its first bytes: FILE_PLAIN (no gzip magic: the parser says what it is), FILE_BGZF (by the header of its
+// first member; a header cut by the end of the file counts, the walk says where), or SMG_EINVAL with message: the file
+// cannot be read, or it is gzip and not BGZF.  The one place that decides this, for the survey, the scan and the readers.
+enum { FILE_PLAIN = 0, FILE_BGZF = 1 };
+static inline int file_kind(int fd, const char *path, char *errbuf, size_t errlen)
 { std::vector<uint8_t> h(32);
   for (;;)
     { const ssize_t got = pread(fd, h.data(), h.size(), 0);
       if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
       int64_t blen = 0; int hlen = 0;
       const int rc = got == 0 ? 1 : bgzf_header(h.data(), (size_t) got, &blen, &hlen);
-      if (rc != 2 || (size_t) got < h.size()) return rc == 0 ? 0 : rc == 2 && got >= 4 ? 0 : 1;      // (a cut header: the walk says where)
-      h.resize(12 + 65536);
+      if (rc == 2 && (size_t) got == h.size()) { h.resize(12 + 65536); continue; }
+      if (rc == 0 || (rc == 2 && got >= 4)) return FILE_BGZF;
+      if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b)
+        return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
+      return FILE_PLAIN;
     }
 }
 
@@ -271,7 +304,19 @@ static inline int bgzf_feed(int fd, const char *path, Inflater &infl, Consume &&
   return 0;
 }
 
-static inline int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases, char *errbuf, size_t errlen)
+// what a FASTA / FASTQ file (dev: what its inflater spent on it) and a BAM file gave, once read to their end
+static inline FileRead text_read(const Parser &ps, const InflaterTimes &dev)
+{ FileRead r;
+  r.route = ROUTE_TEXT; r.records = ps.records; r.bases = ps.bases; r.dev = dev;
+  return r;
+}
+static inline FileRead bam_read(const BamFramer &bam, const InflaterTimes &dev)
+{ FileRead r;
+  r.route = ROUTE_BAM; r.records = bam.records; r.bases = bam.bases; r.ms_frame = bam.ms_feed; r.dev = dev;
+  return r;
+}
+
+static inline int parse_fd(int fd, const char *path, Sink &sink, FileRead *fr, char *errbuf, size_t errlen)
 { std::vector<uint8_t> buf((size_t) 4 << 20);
   Parser ps(sink);
   for (;;)
@@ -281,7 +326,7 @@ static inline int parse_fd(int fd, const char *path, Sink &sink, int64_t *bases,
       const int rc = ps.feed(buf.data(), (size_t) got, path, errbuf, errlen);
       if (rc) return rc;
     }
-  if (bases) *bases = ps.bases;
+  *fr = text_read(ps, InflaterTimes());
   return 0;
 }
 
@@ -298,60 +343,66 @@ static inline int bam_piece(BamFramer &fr, const uint8_t *t, size_t n, const cha
 }
 
 // one file to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
-// the framer, anything else through the parser), anything else as it is
-static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, int64_t *bases, char *errbuf, size_t errlen)
-{ const int z = bgzf_probe(fd, path, errbuf, errlen);
-  if (z < 0) return z;
-  if (z == 1) return parse_fd(fd, path, sink, bases, errbuf, errlen);
+// the framer, anything else through the parser), anything else as it is.  *fr: what it gave, where it was read to its end
+static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
+{ const int kind = file_kind(fd, path, errbuf, errlen);
+  if (kind < 0) return kind;
+  if (kind == FILE_PLAIN) return parse_fd(fd, path, sink, fr, errbuf, errlen);
   if (!infl)
     return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
                 "use smg_count_bgzf_inflate or one of the counting calls", path);
   Parser ps(sink);
   BamFramer bam;
-  infl->mark();
-  int route = 0;                                               // 1 FASTA / FASTQ, 2 BAM: by the first text there is
+  const InflaterTimes before = infl->times();
+  int route = ROUTE_NONE;                                      // by the first text there is
   int rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n)
-    { if (route == 0 && n) route = is_bam_text(t, n) ? 2 : 1;
-      return route == 2 ? bam_piece(bam, t, n, path, *infl, sink, errbuf, errlen) : ps.feed(t, n, path, errbuf, errlen);
+    { if (route == ROUTE_NONE && n) route = is_bam_text(t, n) ? ROUTE_BAM : ROUTE_TEXT;
+      return route == ROUTE_BAM ? bam_piece(bam, t, n, path, *infl, sink, errbuf, errlen) : ps.feed(t, n, path, errbuf, errlen);
     }, errbuf, errlen);
-  if (rc == 0 && route == 2) rc = bam.finish(path, errbuf, errlen);
+  if (rc == 0 && route == ROUTE_BAM) rc = bam.finish(path, errbuf, errlen);
   if (rc) return rc;
-  if (route == 2) infl->note_bam(path, bam);
-  if (bases) *bases = route == 2 ? bam.bases : ps.bases;
+  const InflaterTimes dev = infl->times() - before;
+  *fr = route == ROUTE_BAM ? bam_read(bam, dev) : text_read(ps, dev);
   return 0;
 }
 
 struct GrowSink : Sink
 { uint8_t *p = nullptr; size_t len = 0, cap = 0;
+  void reserve(size_t n)
+  { if (n <= cap) return;
+    uint8_t *q = (uint8_t *) realloc(p, n);
+    if (!q) throw std::bad_alloc();
+    p = q; cap = n;
+  }
   bool put(const uint8_t *s, size_t n) override
   { if (len + n > cap)
       { size_t nc = cap ? cap * 2 : (size_t) 1 << 16;
         while (nc < len + n) nc *= 2;
-        uint8_t *q = (uint8_t *) realloc(p, nc);
-        if (!q) throw std::bad_alloc();
-        p = q; cap = nc;
+        reserve(nc);
       }
     memcpy(p + len, s, n); len += n;
     return true;
   }
+  // the grown stream goes to the caller as a malloc'ed array (one byte where it is empty)
+  int hand_over(uint8_t **out, int64_t *n, char *errbuf, size_t errlen)
+  { if (!p) p = (uint8_t *) malloc(1);
+    if (!p) return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", "");
+    *out = p; *n = (int64_t) len;
+    p = nullptr; len = cap = 0;
+    return 0;
+  }
   ~GrowSink() override { free(p); }
 };
 
-// the stripped stream of one file as a malloc'ed array (one byte where it is empty)
+// the stripped stream of one file as a malloc'ed array
 static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { if (!path || !seq || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
-  const int fd = open(path, O_RDONLY);
-  if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  const Fd f(path);
+  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
   GrowSink sink;
-  int rc;
-  try { rc = parse_file(fd, path, sink, nullptr, nullptr, errbuf, errlen); }
-  catch (...) { close(fd); throw; }
-  close(fd);
-  if (rc) return rc;
-  if (!sink.p) sink.p = (uint8_t *) malloc(1);
-  *seq = sink.p; *n = (int64_t) sink.len;
-  sink.p = nullptr;
-  return 0;
+  FileRead read;
+  const int rc = parse_file(f.fd, path, sink, nullptr, &read, errbuf, errlen);
+  return rc ? rc : sink.hand_over(seq, n, errbuf, errlen);
 }
 
 // Refuse what cannot be read before anything is set up for it.  *bound = the most sequence the files can hold: their
@@ -362,27 +413,30 @@ static inline int survey_files(const char *const *paths, int npaths, int k, int6
 { *bound = 0;
   if (bgzf) bgzf->assign((size_t) npaths, 0);
   for (int f = 0; f < npaths; f++)
-    { uint8_t magic[2] = { 0, 0 };
-      const int fd = open(paths[f], O_RDONLY);
-      if (fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
-      const ssize_t got = read(fd, magic, 2);
-      int64_t size = (int64_t) lseek(fd, 0, SEEK_END);
-      int rc = 0;
-      if (got < 0 || size < 0) rc = fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
-      else if (got == 2 && magic[0] == 0x1f && magic[1] == 0x8b)
-        { int64_t blocks = 0;
-          rc = bgzf_probe(fd, paths[f], errbuf, errlen);
-          if (rc == 1) rc = fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", paths[f]);
-          else if (rc == 0)
-            { rc = bgzf_walk(fd, paths[f], &blocks, &size, errbuf, errlen);
-              if (bgzf) (*bgzf)[(size_t) f] = 1;
-            }
+    { const Fd fd(paths[f]);
+      if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
+      int64_t size = (int64_t) lseek(fd.fd, 0, SEEK_END), blocks = 0;
+      if (size < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
+      int rc = file_kind(fd.fd, paths[f], errbuf, errlen);
+      if (rc == FILE_BGZF)
+        { rc = bgzf_walk(fd.fd, paths[f], &blocks, &size, errbuf, errlen);
+          if (bgzf) (*bgzf)[(size_t) f] = 1;
         }
-      close(fd);
       if (rc) return rc;
       *bound += size + k + 1;
     }
   return 0;
+}
+
+// members and text bytes of a BGZF file; what is not BGZF is refused with the words of the counting calls
+static inline int bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen)
+{ if (!path || !blocks || !text_bytes) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  const Fd f(path);
+  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  const int kind = file_kind(f.fd, path, errbuf, errlen);
+  if (kind < 0) return kind;
+  if (kind == FILE_PLAIN) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BGZF: it does not begin with a gzip header", path);
+  return bgzf_walk(f.fd, path, blocks, text_bytes, errbuf, errlen);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -403,6 +457,7 @@ struct Ring
   char err[512] = { 0 };
   int64_t bases = 0;
   double t_last = 0;
+  std::vector<FileRead> files;                                 // per file: what reading it to its end gave
 };
 
 struct RingSink : Sink
@@ -441,20 +496,18 @@ static inline void reader_main(Ring *r, const char *const *paths, int npaths, in
 { for (int f = first; f < npaths; f += step)
     { char eb[512]; eb[0] = 0;
       int rc = 0;
-      int64_t bases = 0;
+      FileRead read;
       try
         { RingSink sink(*r, f);
-          const int fd = open(paths[f], O_RDONLY);
-          if (fd < 0) rc = fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f]);
-          else
-            { rc = parse_file(fd, paths[f], sink, infl, &bases, eb, sizeof(eb));
-              close(fd);
-            }
+          const Fd fd(paths[f]);
+          rc = fd.fd < 0 ? fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f])
+                         : parse_file(fd.fd, paths[f], sink, infl, &read, eb, sizeof(eb));
           if (rc == 0) sink.done();
         }
       catch (...) { rc = fail(eb, sizeof(eb), SMG_ENOMEM, "out of host memory while reading %s", paths[f]); }
       std::unique_lock<std::mutex> lk(r->m);
-      r->bases += bases;
+      r->bases += read.bases;
+      r->files[(size_t) f] = read;
       if (rc < 0 && !r->rc) { r->rc = rc; memcpy(r->err, eb, sizeof(eb)); r->abort = true; r->cv_free.notify_all(); }
       if (rc != 0 || r->abort) break;
     }
@@ -476,12 +529,15 @@ static inline int reader_threads(int want, int npaths)
 // After the first error, a reader's or the consumer's, nothing more is consumed; the blocks in flight are drained and
 // every thread is joined before this returns.  A reader's error (code and message) goes in front of the consumer's, whose
 // message is its own business.  *bases = sequence bytes read, *t_last = now_ms() when the last reader was done.
+// *files = per file what reading it gave (route ROUTE_NONE: it was not read to its end), after an error as well.
 // infl (may be null: BGZF files are refused): the inflater of thread j, or null where none of its files is BGZF.
 template <class Consume>
 static inline int read_files(const char *const *paths, int npaths, int nthr, uint8_t *const *blocks, int nblocks, size_t block, Consume &&consume,
-                             int64_t *bases, double *t_last, char *errbuf, size_t errlen, Inflater *const *infl = nullptr)
+                             int64_t *bases, double *t_last, std::vector<FileRead> *files, char *errbuf, size_t errlen,
+                             Inflater *const *infl = nullptr)
 { Ring ring;
   ring.block = block;
+  ring.files.assign((size_t) npaths, FileRead());
   ring.idle.assign(blocks, blocks + nblocks);
   std::vector<std::thread> thr;
   thr.reserve((size_t) nthr);
@@ -511,6 +567,7 @@ static inline int read_files(const char *const *paths, int npaths, int nthr, uin
       ring.cv_free.notify_all();
     }
   for (std::thread &th : thr) th.join();
+  files->swap(ring.files);
   if (ring.rc) return fail(errbuf, errlen, ring.rc, "%s", ring.err);
   if (rc) return rc;
   *bases = ring.bases;

@@ -270,3 +270,65 @@ def test_a_bad_bam_file_is_refused_and_a_later_run_succeeds(name, inputs, tmp_pa
     assert got == bc.stripped(recs) and records == len(recs)
     keys, cnts, _ = count_oracle.kmer_counts(count_oracle.pad_reads([r[1] for r in recs]), 21)
     same(count.count_files(str(ok), 21, t=1, threads=1), *count_oracle.table(keys, cnts, 21, 1))
+
+
+# ---- 6. the report of the last call that read BAM -------------------------------------------------------------------------
+
+def report_files(d):
+    """two small BAM files with different records (one of b's is secondary: not counted) and a FASTQ"""
+    rng = np.random.default_rng(12)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    a = [(b"a%d" % i, bases(rng, 40 + i, acgt)) for i in range(3)]
+    b = [(b"b%d" % i, bases(rng, 55 + 2 * i, acgt), 0x100 if i == 1 else 4) for i in range(4)]
+    fq = d / "reads.fq"
+    fq.write_bytes(b"@r\n%s\n+\n%s\n" % (bases(rng, 60, acgt), b"I" * 60))
+    paths = {"a": bc.write(d / "a.bam", bc.bam_text(bc.header(), a)), "b": bc.write(d / "b.bam", bc.bam_text(bc.header(), b)), "fq": str(fq)}
+    want = {n: {"records": sum(1 for r in rs if len(r) < 3 or r[2] & 0x900 == 0), "bases": len(bc.stripped(rs).replace(bc.SEPARATOR, b""))}
+            for n, rs in (("a", a), ("b", b))}
+    assert want == {"a": {"records": 3, "bases": 123}, "b": {"records": 3, "bases": 175}}
+    return paths, want
+
+
+def reported(path, want):
+    r = count.bam_report(path)
+    assert {n: r[n] for n in ("records", "bases")} == want, r
+    times = [r[n] for n in ("ms_frame", "ms_inflate", "ms_unpack", "ms_d2h")]
+    assert all(isinstance(t, float) and t >= 0 for t in times), r
+
+
+def not_reported(path):
+    with pytest.raises(count.CountError) as e:
+        count.bam_report(path)
+    assert e.value.code == -2
+
+
+def test_bam_report_after_bam_strip(tmp_path):
+    paths, want = report_files(tmp_path)
+    count.bam_strip(paths["a"])
+    reported(paths["a"], want["a"])
+    not_reported(paths["b"])
+    not_reported(str(tmp_path / "never_read.bam"))
+    count.bam_strip(paths["b"])                                   # the last call alone is reported
+    reported(paths["b"], want["b"])
+    not_reported(paths["a"])
+
+
+def test_bam_report_after_counting_calls(tmp_path):
+    paths, want = report_files(tmp_path)
+    count.count_files([paths["a"], paths["fq"], paths["b"]], 21, t=1, threads=2)
+    reported(paths["a"], want["a"])
+    reported(paths["b"], want["b"])
+    not_reported(paths["fq"])
+    count.count_files([paths["fq"]], 21, t=1, threads=1)          # a call that read no BAM: the report is gone
+    not_reported(paths["a"])
+    not_reported(paths["b"])
+
+
+def test_bam_report_keeps_the_files_read_before_a_failure(tmp_path):
+    paths, want = report_files(tmp_path)
+    bad = bc.write(tmp_path / "bad.bam", bc.bam_text(bc.header(), [bc.record(b"r0", b"ACGT"), bc.record(b"r1", b"ACGT", block_size=10)]))
+    with pytest.raises(count.CountError) as e:
+        count.count_files([paths["a"], bad], 21, t=1, threads=1)
+    assert e.value.code == -4 and "block_size is smaller" in str(e.value)
+    reported(paths["a"], want["a"])
+    not_reported(bad)
