@@ -493,6 +493,31 @@ int     smg_engine_pass1_form(smg_engine *e, int32_t out[4]);
 int     smg_engine_pass1_plan(int kmer, int64_t nels, int symcheck, int own_lookups, int have_index, int bm_cap, int no_filter,
                               int32_t out[12]);
 
+/* what the stage between pass 1 and pass 2 of the fast path WOULD decide (read-only, needs no engine and no device; for tests:
+   the functions the engine itself calls).  One call answers five questions, each from the inputs it names.
+   in[0] k, [1] words per request record, [2] bucket bits of the look-up chain (0: no chain), [3] chunks of the request list in use,
+   [4] requests in them, [5] compute units of the device, [6] chunks the filter of the recorded step filled (-1: not a replayed
+   step), [7] the probe writes a survivor list (1) or looks the survivors up at once (0), [8] one-way requests, [9] deferred
+   entries of pass 1, [10] requests pass 1 emitted, [11] table entries, [12] the look-ups take a flat array of received records (1)
+   or this engine's own chunks (0), [13] records the look-ups see, [14] the list has been filtered, [15] id bits of this engine's
+   map (0: none), [16] pass 1: records its request list is to hold, [17] its workgroups (SMG_P1_GRID lowers them), [18] chunks
+   the list's allocation already holds.
+   The test hooks SMG_FILTER_SORT_MIN, SMG_FILTER_GRID, SMG_PROBE_X, SMG_PX_ONE_XCC and SMG_APPLY_SORT_MIN are read as the
+   engine reads them.
+   out[0] list capacity of pass 1 in chunks (from in[2], [16..18]);
+   [1] presort (smg_engine_apply_state's out[5]; from in[0..3]);
+   [2] workgroups of kf_filter, [3] chunks the kept list may fill (from in[2..6]);
+   [4] the probe kernel, [5] requests per ticket of kl_probe_x, [6] its workgroups all claim XCD 0, [7] workgroups of the probe
+   (smg_engine_lookup_state's out[8], [9]; from in[2], [5], [7..11]; all 0 without the chain);
+   [8] the route of the look-ups: 0 nothing to look up, 1 probe and look-ups fused in the chain, 2 the chunk array with sentinels in
+   its holes, 3 the chunks compacted, 4 the flat array; [9] the look-up kernel, [10] sorted, [11] holes, [12] records or chunk slots
+   covered (smg_engine_apply_state's out[0..3]); [13] the list is filtered first and the question asked again with in[14] = 1
+   and the list the filter kept (from in[0..4], [12..15]).
+   SMG_EINVAL for what no engine produces: k outside 1 .. 85, a record that is neither the k-mer nor the k-mer and a count word,
+   a chain without a map of >= 12 id bits or without key-only records of k <= 64, one-way requests of even k, negative counts,
+   a grid outside 1 .. 4096, flags other than 0 and 1.                                                                        */
+int     smg_engine_lookup_plan(const int64_t in[19], int64_t out[14]);
+
 /* library / build identification, e.g. "smudgeplot_amd 0.1 gfx950" */
 const char *smg_version(void);
 

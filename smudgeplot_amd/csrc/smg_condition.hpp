@@ -1,6 +1,6 @@
 // smg_condition.hpp -- table conditioning of the hetmers engine on the device: trim and symmetrise a bound table, close a
 // canonical one by merge, symmetrise a table that is cut into shards, and hand the table out.  Included by
-// smg_hetmers.hip behind route_records; no state of its own.
+// smg_hetmers.hip behind route_records (smg_phase.hpp); no state of its own.
 
 #pragma once
 
@@ -398,7 +398,7 @@ extern "C" int smg_engine_symm_route(smg_engine *e, const uint64_t *splitters, i
   hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, fill.as<uint32_t>(), nc, (uint32_t) F_CH,
                      (uint32_t) (n2 - (nc - 1) * F_CH));
   if (hipGetLastError() != hipSuccess) rc = fail(errbuf, errlen, SMG_ENODEV, "symm_route: launch failed%s");
-  if (rc == SMG_OK) rc = route_records(e, rec.as<u64>(), fill.as<uint32_t>(), (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, errbuf, errlen);
+  if (rc == SMG_OK) rc = route_records(e, rec.as<u64>(), fill.as<uint32_t>(), (unsigned) nc, rw, splitters, nranks, d_send, capacity, counts, NULL, errbuf, errlen);
   hipStreamSynchronize(e->stream);                     // (the records are freed on return)
   return rc;
 }

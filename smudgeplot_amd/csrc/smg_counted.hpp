@@ -523,14 +523,14 @@ template <bool SYM> static int launch_pass2(smg_engine *e, int64_t *d_plot, cons
 }
 
 // Pass 1 of the symmetric half-scan = k_pass1<W, true>: S_all into deg[], records (rc(x), count | S_hi << 16) from the
-// owners of a hi-side pair (emit_all: from every entry) into the flat list e->req, which holds `cap` records at first and,
+// owners of a hi-side pair (emit_all: from every entry) into the flat list e->lists.cur.rec, which holds `cap` records at first and,
 // where pass 1 counted more, that many on the second attempt.
 static int counted_pass1(smg_engine *e, int emit_all, int symcheck, int64_t cap, char *errbuf, size_t errlen)
 { int rc;
   if ((rc = counted_prepare(e, RUN_COUNTED, errbuf, errlen))) return rc;
   for (int attempt = 0; attempt < 2; attempt++)
-    { HIPCHK(e->req.reserve(cap * (int64_t) sizeof(u64) * (e->tab.W + 1)));
-      launch_pass1<true>(e, emit_all, symcheck == SMG_SYM_HASH, e->req, cap, NULL);
+    { HIPCHK(e->lists.reserve_flat(cap, e->tab.W + 1));
+      launch_pass1<true>(e, emit_all, symcheck == SMG_SYM_HASH, e->lists.cur.rec, cap, NULL);
       if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
       if (e->h_ctrl->unsorted)
         return fail(errbuf, errlen, SMG_EFORMAT, "table entries are not strictly increasing%s");
@@ -549,7 +549,7 @@ static int counted_symmetric(smg_engine *e, int symcheck, int64_t *d_plot, bool 
                              char *errbuf, size_t errlen)
 { int rc;
   if ((rc = counted_pass1(e, 0, symcheck, e->tab.n / 4 + 1024, errbuf, errlen))) return rc;
-  launch_apply(e, e->req, e->st.nrequests, symcheck == SMG_SYM_EXACT);
+  launch_apply(e, e->lists.cur.rec, e->st.nrequests, symcheck == SMG_SYM_EXACT);
   if ((rc = read_ctrl(e, errbuf, errlen))) return rc;
   e->st.ms_rclookup = ms_between(e, EV_LOOKUP_BEG, EV_LOOKUP_END);
   *symmetric = e->h_ctrl->missing == 0;
@@ -576,9 +576,9 @@ static int counted_phase_pass1(smg_engine *e, int symcheck, char *errbuf, size_t
   for (int i = 0; i < 4; i++) e->run.fp[i] = e->h_ctrl->fp[i];
   const int64_t nc = (nreq + F_CH - 1) / F_CH;
   if (nc >= 0x7FFFFFFFll) return fail(errbuf, errlen, SMG_EINVAL, "shard too large%s");
-  HIPCHK(e->chunk_fill.reserve(nc * 4 + 4));
+  HIPCHK(e->lists.reserve_fills(nc));
   if (nc > 0)
-    hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->chunk_fill, nc, (uint32_t) F_CH,
+    hipLaunchKernelGGL(kc_fill_u32, dim3((unsigned) ((nc + TPB - 1) / TPB)), dim3(TPB), 0, e->stream, e->lists.cur.fill, nc, (uint32_t) F_CH,
                        (uint32_t) (nreq - (nc - 1) * F_CH));
   HIPCHK(hipGetLastError());
   e->run.n_chunks = (unsigned) nc;

@@ -73,7 +73,7 @@ EXPORTS = [
     "smg_engine_pass1_plan", "smg_hetmers_run_mode", "smg_engine_decode_at", "smg_engine_decode_limits",
     "smg_engine_ingest_readers", "smg_engine_wide_limits",
     "smg_engine_close_canonical_range", "smg_engine_close_canonical_range_cap", "smg_hetmers_run_device_mode",
-    "smg_engine_list_limits", "smg_engine_apply_state",
+    "smg_engine_list_limits", "smg_engine_apply_state", "smg_engine_lookup_plan",
 ]
 
 _lib = None
@@ -153,6 +153,8 @@ def load_library():
         lib.smg_engine_pass1_limits.restype = None
     if hasattr(lib, "smg_engine_pass1_plan"):
         lib.smg_engine_pass1_plan.argtypes = [i32, i64, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]
+    if hasattr(lib, "smg_engine_lookup_plan"):
+        lib.smg_engine_lookup_plan.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     if hasattr(lib, "smg_hetmers_run_mode"):
         lib.smg_hetmers_run_mode.argtypes = [i32, i64, C.POINTER(Opts), C.c_double, C.POINTER(C.c_int32), *err]
     lib.smg_hetmers_run_device.argtypes = [i32, i64, vp, vp, C.POINTER(Opts), vp, C.POINTER(Stats), *err]
@@ -364,6 +366,35 @@ def pass1_plan(k: int, nels: int, symcheck: str = "hash", own_lookups: bool = Tr
     if rc:
         raise EngineError(rc, "pass1_plan")
     return dict(zip(PASS1_PLAN, (int(v) for v in out)))
+
+
+LOOKUP_PLAN_IN = {"k": 0, "rw": 0, "nb": 0, "n_chunks": 0, "nrequests": 0, "cus": 256, "seen_chunks": -1, "list": 0, "one_way": 0,
+                  "nbig": 0, "nemitted": 0, "n": 0, "flat": 0, "nrec": 0, "filtered": 0, "bm_bits": 0, "want_rec": 0, "grid": 1,
+                  "have_chunks": 0}
+LOOKUP_PLAN = ("max_chunks", "presort", "filter_grid", "maxout", "probe_form", "probe_part", "one_xcd", "probe_grid", "route",
+               "kernel", "sorted", "holes", "covered", "filter_first")
+PRESORTS = ("none", "bucketed", "asis", "chain")
+APPLY_ROUTES = ("none", "fused", "sentinels", "compacted", "flat")
+
+
+def lookup_plan(k: int, **inputs) -> dict:
+    """what the stage between pass 1 and pass 2 of the fast path would decide (smg_engine_lookup_plan; no engine, no device: the
+    functions the engine calls).  inputs: the names of LOOKUP_PLAN_IN with their defaults there (rw: the words of the k-mer) --
+    each of the five plans reads its own, see smg_hetmers.h.  Returns the names of LOOKUP_PLAN: the list capacity of pass 1; the
+    presort (index into PRESORTS); grid and kept chunks of the filter; the probe kernel (lookup_state's "probe_form"), its ticket,
+    the one-XCD flag and its grid; the route of the look-ups (index into APPLY_ROUTES) with apply_state's kernel, sorted, holes
+    and covered, and whether the list is filtered first."""
+    unknown = set(inputs) - set(LOOKUP_PLAN_IN)
+    if unknown:
+        raise TypeError(f"lookup_plan: unknown inputs {sorted(unknown)}")
+    vals = dict(LOOKUP_PLAN_IN, k=k, rw=(k + 31) // 32)
+    vals.update({a: int(b) for a, b in inputs.items()})
+    inp = (C.c_int64 * len(LOOKUP_PLAN_IN))(*(vals[a] for a in LOOKUP_PLAN_IN))
+    out = (C.c_int64 * len(LOOKUP_PLAN))()
+    rc = load_library().smg_engine_lookup_plan(inp, out)
+    if rc:
+        raise EngineError(rc, "lookup_plan")
+    return dict(zip(LOOKUP_PLAN, (int(v) for v in out)))
 
 
 RUN_MODES = ("core", "virtual", "sequential", "multi", "one_rank_forced")

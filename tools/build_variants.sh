@@ -1,5 +1,6 @@
 #!/bin/bash
 # build_variants.sh tag1="-DFLAGS" tag2="..." : tuning builds of the engine into build/var/libsmg_<tag>.so (parallel)
+# (one translation unit: smg_hetmers.hip includes smg_fast_host.hpp, smg_fast_lookup.hpp, smg_phase.hpp and the other headers)
 cd "$(dirname "$0")/../smudgeplot_amd/csrc"
 mkdir -p ../../build/var
 for spec in "$@"; do
