@@ -4,7 +4,17 @@
  *   - input: FASTA / FASTQ (first byte '>' or '@'), plain or block-gzipped (BGZF, what bgzip and htslib write: a gzip
  *     file of independent members of at most 64 KiB, found by the BC subfield of its first header), every file of a call
  *     routed by its own header; the members of a BGZF file are inflated on the device and their CRC-32 checked there;
- *     any other gzip file is refused (SMG_EINVAL: recompress it with bgzip, or decompress it);
+ *     any other gzip file is refused (SMG_EINVAL: recompress it with bgzip, or decompress it) -- unless the call opts in:
+ *   - input: plain gzip (what gzip, pigz and a sequencer write: reads_1.fastq.gz), only where smg_count_opts.gzip is set.  The
+ *     refusal above is a tested contract of this library and of smg_count (its message, and -z staying illegal), so reading
+ *     such files is an option (smg_count -g) and not the default; it changes nothing for the plain, BGZF and BAM files of the
+ *     same call.  A member is one DEFLATE stream; it is inflated in parallel all the same: the file is cut into spans, a
+ *     wavefront finds a block start in each and decodes from there with the 32 KiB in front of it unknown, the spans are
+ *     chained (what does not chain is decoded again from the known end in front of it), and a second pass decodes exactly
+ *     between the restart points that the first one left, where the file is read (smg_gzip.hpp).  Every member's CRC-32 and
+ *     ISIZE are checked; FEXTRA, FNAME, FCOMMENT, FHCRC, several members and trailing zero bytes are accepted.  One
+ *     refusal (SMG_EINVAL, offset named): a single deflate block larger than one piece of the first pass (256 spans) or
+ *     inflating to more than the text of one call (4 x SMG_COUNT_BGZF_CHUNK);
  *   - input: unaligned BAM (what PacBio HiFi reads are delivered in: a BGZF file whose text begins BAM\1), found by those
  *     four bytes; its records are framed on the host and their 4-bit sequences unpacked on the device.  Its stripped stream:
  *     in file order every record whose FLAG has neither 0x100 nor 0x800 set gives its l_seq bases, each code mapped through
@@ -21,8 +31,8 @@
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
  * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
- * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text and smg_count_version
- * need no device.
+ * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text, smg_count_gzip_text_host and
+ * smg_count_version need no device.
  */
 #ifndef SMG_COUNT_H
 #define SMG_COUNT_H
@@ -64,6 +74,7 @@ typedef struct smg_count_opts
   int32_t device;        /* HIP device ordinal                                   */
   int32_t host_threads;  /* reader threads, one file each, at most 16 are used  */
   int32_t verbose;
+  int32_t gzip;          /* 0: a gzip file that is not BGZF is refused, as always; 1: it is read (see the top of this file) */
 } smg_count_opts;
 
 typedef struct smg_count_stats
@@ -207,6 +218,29 @@ int smg_count_bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t
    launches), the copies of the stripped bytes to the host (host clock).  SMG_EINVAL where that call read no such BAM file to
    its end.                                                                                                              */
 int smg_count_bam_report(const char *path, int64_t *records, int64_t *bases, double *ms);
+
+/* the text of a whole gzip file (plain gzip, or BGZF read as such) by the route the counting calls take with the option on:
+   the index of its restart points on `device`, then the exact decoder over it.  span_bytes: compressed bytes of a span,
+   1024 .. 1048576, 0 for the default of 262144 (or the test hook SMG_COUNT_GZIP_SPAN).  *text is malloc'ed (smg_count_free),
+   *n its bytes, ms_kernel[3] (may be NULL) the HIP-event times of the block finder with the marker decoder, of the resolver
+   and of the exact decoder, summed over the launches.  SMG_EINVAL for a file that is not gzip and for the one refusal;
+   SMG_EFORMAT "<path>: gzip member at offset <o>: <reason>" (header, trailer, CRC-32, ISIZE, truncation, trailing bytes that
+   are neither zeros nor a member) or "<path>: deflate block at offset <o>: <reason>".  SMG_ENODEV without a device.     */
+int smg_count_gzip_inflate(const char *path, int32_t device, int64_t span_bytes, uint8_t **text, int64_t *n, double *ms_kernel,
+                           char *errbuf, size_t errlen);
+
+/* host only: the same text by the same finder, marker decoder, chain, resolver and exact decoder, run as one lane on the host.
+   A test twin like smg_count_bam_text, not a fallback of the counting calls.  Errors as smg_count_gzip_inflate.            */
+int smg_count_gzip_text_host(const char *path, int64_t span_bytes, uint8_t **text, int64_t *n, char *errbuf, size_t errlen);
+
+/* host only: what the last call of this process that reads plain gzip (a counting call with the option on,
+   smg_count_gzip_inflate, smg_count_gzip_text_host) read of the file it was given as `path`: its members, its text bytes, the
+   spans its pieces were cut into, how many decodes were linked (a span whose candidate is where the decode in front of it
+   ended, the first of a piece included) and how many repaired (decoded again from a known end); every byte of text comes
+   from one or the other.  ms[3] (may be NULL): as ms_kernel above (the twin: zeros).  Both routes give the same counts for
+   the same file and span size.  SMG_EINVAL where that call read no such file.                                            */
+int smg_count_gzip_report(const char *path, int64_t *members, int64_t *text_bytes, int64_t *spans, int64_t *linked, int64_t *repaired,
+                          double *ms);
 
 void smg_count_free(void *p);
 const char *smg_count_version(void);

@@ -3,7 +3,10 @@
 Reads in, canonical FastK-style k-mer table out: the step in front of `hetmers`.  There is no CPU
 fallback: the counting calls raise `CountError` without a HIP device; `parse`, `bgzf_scan` and `bam_text` need none.
 The input files are FASTA / FASTQ, plain or block-gzipped (BGZF, what `bgzip` writes); the members of a BGZF file are
-inflated on the device.  Any other gzip file is refused.  Unaligned BAM (PacBio HiFi reads: a BGZF file whose text begins
+inflated on the device.  Any other gzip file is refused -- that refusal is a tested contract, so reading plain gzip (what
+`gzip`, `pigz` and a sequencer write) is opt-in: `count_files(..., gzip=True)` inflates such files on the device in parallel
+(block finder, decode with an unknown window, chained spans, an exact second pass; csrc/smg_gzip.hpp) and changes nothing for
+the plain, BGZF and BAM files of the same call.  Unaligned BAM (PacBio HiFi reads: a BGZF file whose text begins
 BAM\\1) is read too: its records are framed on the host and their 4-bit sequences unpacked on the device; its primary
 records (FLAG without 0x100 and 0x800) give the stream of a FASTA file of the same reads.  A BAM file is bounded by its text
 like any BGZF file, 1.5 times its bases or more, so it may be counted by key range where one pass would have done, with the
@@ -23,6 +26,7 @@ MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
 FINE_BINS = 1 << 24                       # the ends of a range are values of the leading 24 bits where a bin was split
 BGZF_CHUNK = 16 << 20                     # compressed bytes of a BGZF file that one launch of the inflate kernel takes
 BAM_TILE = 4096                           # stripped bytes of a BAM file that one workgroup of the unpack kernel writes
+GZIP_SPAN = 256 << 10                     # compressed bytes of a span of a plain gzip file (1 KiB .. 1 MiB can be asked for)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsmg_count.so")
@@ -31,7 +35,8 @@ BIN_PATH = os.path.join(_HERE, "bin", "smg_count")
 EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_count_bases_parts", "smg_count_plan",
            "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
            "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan",
-           "smg_count_bgzf_scan", "smg_count_bgzf_inflate", "smg_count_bam_text", "smg_count_bam_strip", "smg_count_bam_report"]
+           "smg_count_bgzf_scan", "smg_count_bgzf_inflate", "smg_count_bam_text", "smg_count_bam_strip", "smg_count_bam_report",
+           "smg_count_gzip_inflate", "smg_count_gzip_text_host", "smg_count_gzip_report"]
 
 
 class CountError(RuntimeError):
@@ -42,7 +47,7 @@ class CountError(RuntimeError):
 
 class Opts(C.Structure):
     _fields_ = [("kmer", C.c_int32), ("minval", C.c_int32), ("device", C.c_int32),
-                ("host_threads", C.c_int32), ("verbose", C.c_int32)]
+                ("host_threads", C.c_int32), ("verbose", C.c_int32), ("gzip", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -110,6 +115,13 @@ def load_library():
     lib.smg_count_bam_strip.restype = C.c_int
     lib.smg_count_bam_report.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     lib.smg_count_bam_report.restype = C.c_int
+    lib.smg_count_gzip_inflate.argtypes = [C.c_char_p, C.c_int32, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                           C.c_char_p, C.c_size_t]
+    lib.smg_count_gzip_inflate.restype = C.c_int
+    lib.smg_count_gzip_text_host.argtypes = [C.c_char_p, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_gzip_text_host.restype = C.c_int
+    lib.smg_count_gzip_report.argtypes = [C.c_char_p] + [C.POINTER(C.c_int64)] * 5 + [C.POINTER(C.c_double)]
+    lib.smg_count_gzip_report.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
     lib.smg_count_free.restype = None
     lib.smg_count_version.restype = C.c_char_p
@@ -137,9 +149,9 @@ def _table(k, t, keys, counts):
     return ktab.KTable(k, 3, 1, t, packed, counts, index, np.array([len(counts)], np.int64))
 
 
-def _run(call, k, t, device, threads, partitions, max_entries):
+def _run(call, k, t, device, threads, partitions, max_entries, gzip=False):
     lib = load_library()
-    opts = Opts(int(k), int(t), int(device), int(threads), 0)
+    opts = Opts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)))
     parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
     keys, cnt = C.c_void_p(), C.c_void_p()
     nels, words = C.c_int64(0), C.c_int(0)
@@ -162,16 +174,17 @@ def _run(call, k, t, device, threads, partitions, max_entries):
     return _table(int(k), int(t), k64, c16), hist, stats
 
 
-def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
+def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False):
     """-> (ktab.KTable of the canonical k-mers with count >= t, hist uint64[32768], stats dict)
 
     partitions: 0 lets the library count by key range where one pass is not guaranteed to fit, 1 is one pass,
     2 .. 4096 that many ranges; max_entries (test hook) plans as if one merge held only that many entries.
     The stats carry `used` (ranges), `store_bytes`, `ms_pack` and `ms_plan` of a partitioned run, and `split`: the bins of
-    the leading 12 bits that held more windows than one merge and were split on their next 12 bits (automatic mode only)."""
+    the leading 12 bits that held more windows than one merge and were split on their next 12 bits (automatic mode only).
+    gzip: read plain gzip files too (off: they are refused, as always); gzip_report says what was read of each."""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
-    return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries)
+    return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries, gzip)
 
 
 def count_bases(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
@@ -216,9 +229,9 @@ class DeviceTable:
             e.close()
 
 
-def _run_device(call, k, t, device, threads, partitions, max_entries):
+def _run_device(call, k, t, device, threads, partitions, max_entries, gzip=False):
     lib = load_library()
-    opts = Opts(int(k), int(t), int(device), int(threads), 0)
+    opts = Opts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)))
     parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
     keys, cnt = C.c_void_p(), C.c_void_p()
     nels, words = C.c_int64(0), C.c_int(0)
@@ -239,11 +252,12 @@ def _as_bases(seq):
                                 dtype=np.uint8)
 
 
-def count_files_device(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
+def count_files_device(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False):
     """count_files with the table left on the device -> (DeviceTable, hist uint64[32768], stats dict)"""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
-    return _run_device(lambda lib, *a: lib.smg_count_files_device(arr, len(paths), *a), k, t, device, threads, partitions, max_entries)
+    return _run_device(lambda lib, *a: lib.smg_count_files_device(arr, len(paths), *a), k, t, device, threads, partitions, max_entries,
+                       gzip)
 
 
 def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
@@ -253,12 +267,13 @@ def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entri
                        partitions, max_entries)
 
 
-def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash"):
+def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash", gzip=False):
     """Reads to the het-mer plot in one process: count on the device (k-mers with count >= t), hand the table over where
     it lies, trim at e, close under reverse complement, run -> (plot int64[1001, 501], hist uint64[32768], stats dict).
     The closed table runs in core, or, where it is beyond one engine or the memory, in prefix shards one after the other
     (engine.run_device_mode says which).
     paths_or_bases: sequence bytes (bytes, bytearray, memoryview or a uint8 array) or one path or a list of paths.
+    gzip: read plain gzip files too, as count_files does.
     e < t cannot be honoured (the entries below t are gone) and raises ValueError.  The stats are the counter's, with the
     engine's under "hetmers"."""
     from . import engine
@@ -267,7 +282,7 @@ def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, ma
     if isinstance(paths_or_bases, (bytes, bytearray, memoryview, np.ndarray)):
         got = count_bases_device(paths_or_bases, k, t, device, threads, partitions, max_entries)
     else:
-        got = count_files_device(paths_or_bases, k, t, device, threads, partitions, max_entries)
+        got = count_files_device(paths_or_bases, k, t, device, threads, partitions, max_entries, gzip)
     table, hist, stats = got
     with table:
         plot, est = engine.hetmers_run_device(k, table.nels, table.keys_ptr, table.counts_ptr, device=device, symcheck=symcheck,
@@ -374,6 +389,52 @@ def bgzf_inflate(path, device=0):
         return C.string_at(text, n.value), ms.value
     finally:
         lib.smg_count_free(text)
+
+
+def gzip_inflate(path, span_bytes=0, device=0):
+    """The text of a whole gzip file by the route of the counting calls with gzip=True: the index of its restart points on the
+    device, then the exact decoder over it -> (bytes, (ms finder + marker decoder, ms resolver, ms exact decoder): HIP events).
+    span_bytes: compressed bytes of a span, 1024 .. 1048576, 0 for the default.  Raises CountError -2 for a file that is not
+    gzip, -4 "<path>: gzip member at offset <o>: ..." or "<path>: deflate block at offset <o>: ..." for one that is damaged."""
+    lib = load_library()
+    text, n, ms = C.c_void_p(), C.c_int64(0), (C.c_double * 3)()
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_gzip_inflate(os.fsencode(path), int(device), int(span_bytes), C.byref(text), C.byref(n), ms, err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(text, n.value), tuple(ms)
+    finally:
+        lib.smg_count_free(text)
+
+
+def gzip_text_host(path, span_bytes=0) -> bytes:
+    """Host only: the same text by the same block finder, marker decoder, chain, resolver and exact decoder, run as one lane
+    on the host.  A test twin, not a fallback of the counting calls.  Errors as gzip_inflate."""
+    lib = load_library()
+    text, n = C.c_void_p(), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_gzip_text_host(os.fsencode(path), int(span_bytes), C.byref(text), C.byref(n), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        return C.string_at(text, n.value)
+    finally:
+        lib.smg_count_free(text)
+
+
+def gzip_report(path) -> dict:
+    """Host only: what the last call of this process that reads plain gzip (count_files* with gzip=True, gzip_inflate,
+    gzip_text_host) read of the file it was given as `path` -> {"members", "text_bytes", "spans", "linked", "repaired",
+    "ms_marker", "ms_resolve", "ms_exact"}.  Raises CountError -2 where it read no such file."""
+    lib = load_library()
+    v = [C.c_int64(0) for _ in range(5)]
+    ms = (C.c_double * 3)()
+    rc = lib.smg_count_gzip_report(os.fsencode(path), *[C.byref(x) for x in v], ms)
+    if rc != 0:
+        raise CountError(rc, f"the last call read no gzip file {path}")
+    return {"members": v[0].value, "text_bytes": v[1].value, "spans": v[2].value, "linked": v[3].value, "repaired": v[4].value,
+            "ms_marker": ms[0], "ms_resolve": ms[1], "ms_exact": ms[2]}
 
 
 def bam_text(text, piece=0) -> bytes:

@@ -4,20 +4,23 @@
  *               k-mer table (format F: stub + one hidden part file, 3-byte prefix index), plus the
  *               k-mer count histogram that `smudgeplot cutoff` reads.  The reads are plain or block-gzipped (BGZF, what
  *               bgzip writes: inflated on the device), or unaligned BAM (PacBio HiFi reads: the bases of its primary
- *               records, unpacked on the device); any other gzip file is refused.
+ *               records, unpacked on the device); any other gzip file is refused unless -g is given: that refusal is a
+ *               tested contract of this program, so plain gzip (what gzip, pigz and a sequencer write) is read on request
+ *               only, inflated on the device in parallel; -g changes nothing for plain, BGZF and BAM inputs of the same call.
  *
  *  The step in front of `hetmers`: where a smudgeplot run starts from reads, this stands in for FastK.  With -e it is
  *  that step and `hetmers` in one process: the counted table stays in device memory and is trimmed, closed under reverse
  *  complement and scanned for het-mer pairs there (smg_hetmers_run_device: in core, or in prefix shards of the closed table one
  *  after the other where it is too large for that), and <output>.smu is written as `hetmers -e` writes it from the table on disk.
  *
- *  Usage: smg_count [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
+ *  Usage: smg_count [-v] [-g] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
  *           -k: k-mer length, 13 .. 128          -t: keep the k-mers with count >= t
  *           -H: also write <output>.hist.txt     -T: reader threads (one input file each, at most 16)
  *           -o: root name of the table; default is the root of the first input
  *           -p: key ranges to count in: 0 as many as the data need, 1 one pass, 2 .. 4096 that many
  *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device
  *           -n: write no table (with -e or -H only)
+ *           -g: read plain gzip inputs too (SMG_COUNT_GZIP_SPAN, test hook: the compressed bytes of a span)
  *
  *  SMUDGEPLOT_GPU picks the device; SMG_COUNT_MAX_ENTRIES (test hook) is max_entries of smg_count_parts.  No CPU fallback.
  *  A failed run leaves no table, histogram or .smu file behind.
@@ -28,7 +31,7 @@
 #include "smg_count.h"
 
 static void usage(void)
-{ fprintf(stderr, "\nUsage: %s [-v] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...\n", Prog_Name);
+{ fprintf(stderr, "\nUsage: %s [-v] [-g] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...\n", Prog_Name);
   fprintf(stderr, "\n");
   fprintf(stderr, "      -k: k-mer length (13 .. %d)\n", SMG_MAX_KMER);
   fprintf(stderr, "      -t: keep the k-mers that occur at least t times\n");
@@ -37,6 +40,8 @@ static void usage(void)
   fprintf(stderr, "      -e: write the het-mer pairs of the k-mers that occur at least e times to <output>.smu (e >= t),\n");
   fprintf(stderr, "            from the table in device memory: what hetmers -e writes from the table file\n");
   fprintf(stderr, "      -n: write no table (with -e or -H)\n");
+  fprintf(stderr, "      -g: read plain gzip <reads> too (reads.fastq.gz as gzip or pigz write it), inflated on the device;\n");
+  fprintf(stderr, "            without it such a file is refused, as always; plain, BGZF and BAM inputs are read the same either way\n");
   fprintf(stderr, "      -o: root name for the output table\n");
   fprintf(stderr, "            default is root of the first <reads> argument\n");
   fprintf(stderr, "      -v: verbose mode\n");
@@ -70,7 +75,7 @@ static void remove_outputs(const char *root, int table, const char *hname, const
 }
 
 int main(int argc, char *argv[])
-{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0, ethresh = 0, no_table = 0;
+{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0, ethresh = 0, no_table = 0, gzip = 0;
   char *out = NULL, *root, *hname = NULL, *sname = NULL;
   int64_t *plot = NULL;
   smg_stats hst;
@@ -92,6 +97,7 @@ int main(int argc, char *argv[])
       { case 'v': verbose = 1; break;
         case 'H': do_hist = 1; break;
         case 'n': no_table = 1; break;
+        case 'g': gzip = 1; break;
         case 'e': ethresh = arg_positive(argv[i], "Error-mer threshold"); break;
         case 'k': kmer = arg_positive(argv[i], "K-mer length"); break;
         case 'p':
@@ -139,7 +145,7 @@ int main(int argc, char *argv[])
 
   memset(&opts, 0, sizeof(opts));
   { const char *g = getenv("SMUDGEPLOT_GPU"); opts.device = g ? atoi(g) : 0; }
-  opts.kmer = kmer; opts.minval = minval; opts.host_threads = nthreads; opts.verbose = verbose;
+  opts.kmer = kmer; opts.minval = minval; opts.host_threads = nthreads; opts.verbose = verbose; opts.gzip = gzip;
   memset(&parts, 0, sizeof(parts));
   parts.partitions = nparts;
   { const char *m = getenv("SMG_COUNT_MAX_ENTRIES"); if (m != NULL && atoll(m) > 0) parts.max_entries = atoll(m); }   /* (test hook) */
@@ -221,7 +227,10 @@ int main(int argc, char *argv[])
     }
   if (verbose)
     { for (i = 1; i < j; i++)
-        { int64_t blocks = 0, text = 0;
+        { int64_t blocks = 0, text = 0, spans = 0, linked = 0, repaired = 0;
+          if (smg_count_gzip_report(argv[i], &blocks, &text, &spans, &linked, &repaired, NULL) == SMG_OK)
+            fprintf(stderr, "  %s: gzip, %lld members, %lld text bytes, %lld of %lld spans linked, %lld repaired, inflated on the device\n", argv[i],
+                    (long long) blocks, (long long) text, (long long) linked, (long long) spans, (long long) repaired);
           if (smg_count_bgzf_scan(argv[i], &blocks, &text, NULL, 0) == SMG_OK)
             fprintf(stderr, "  %s: BGZF, %lld blocks, %lld text bytes, inflated on the device\n", argv[i], (long long) blocks, (long long) text);
           if (smg_count_bam_report(argv[i], &blocks, &text, NULL) == SMG_OK)

@@ -41,12 +41,15 @@
 //                          a BGZF file (bgzf_walk, bgzf_feed) and the Inflater they are handed to, the routing of one file
 //                          (parse_file) and what it gives back (FileRead), the reader threads and their ring (read_files)
 //   smg_inflate.hpp        DEFLATE, one BGZF member per wave: inf_members and the decoder it shares with the host check
+//   smg_gzip.hpp           plain gzip, for a call that opted in: block finder, marker decoder, resolver and exact decoder (one text
+//                          for the kernels and the host twin), the chain that builds the index of a file and the pass over it
 //   smg_bam.hpp            BAM: the framer of the records (host), bam_unpack and the tile logic it shares with the host check
 //   smg_count_plan.hpp     host only: the memory plan, how buffers grow, the cuts of the key ranges
 //   smg_count_parts.hpp    the parts of the device driver, each owning its buffers: Run (what they share), Batch, Distinct,
 //                          Store, Table; the one HIP check (DCHK), the device check, pinned memory that frees itself
 //   smg_count_inflater.hpp the device stage of compressed input, a part like those: DeviceInflater (inflate, unpack), one per
-//                          reader thread, and the BGZF file a one-file route opens for an inflater of its own
+//                          reader thread (with the gzip engine and the indexes of its gzip files), and the BGZF file a one-file
+//                          route opens for an inflater of its own
 //   this file              the driver itself (Counter: set-up, flush, the ranges, finish), the entry points (count_files,
 //                          count_bases, the one-file routes, the report of the BAM files of the last call) and the C ABI
 
@@ -340,23 +343,62 @@ static int bam_report(const char *path, int64_t *records, int64_t *bases, double
   return SMG_EINVAL;
 }
 
+// What the last call of this process that reads plain gzip read of every such file (smg_count_gzip_report): a counting call
+// that opted in, smg_count_gzip_inflate, smg_count_gzip_text_host.
+struct GzSeen { std::string path; int64_t members, text, spans, linked, repaired; double ms[3]; };
+static std::mutex gz_seen_m;
+static std::vector<GzSeen> gz_seen;
+
+static void publish_gzip(const char *path, const GzIndex *ix, bool more = false)
+{ std::lock_guard<std::mutex> lk(gz_seen_m);
+  if (!more) gz_seen.clear();
+  try { if (ix) gz_seen.push_back(GzSeen{ path, (int64_t) ix->mem.size(), ix->text, ix->spans, ix->linked, ix->repaired, { ix->ms[0], ix->ms[1], ix->ms[2] } }); }
+  catch (...) { gz_seen.clear(); }
+}
+
+static int gzip_report(const char *path, int64_t *members, int64_t *text_bytes, int64_t *spans, int64_t *linked, int64_t *repaired, double *ms)
+{ if (!path || !members || !text_bytes || !spans || !linked || !repaired) return SMG_EINVAL;
+  std::lock_guard<std::mutex> lk(gz_seen_m);
+  for (const GzSeen &g : gz_seen)
+    if (g.path == path)
+      { *members = g.members; *text_bytes = g.text; *spans = g.spans; *linked = g.linked; *repaired = g.repaired;
+        if (ms) { ms[0] = g.ms[0]; ms[1] = g.ms[1]; ms[2] = g.ms[2]; }
+        return 0;
+      }
+  return SMG_EINVAL;
+}
+
 // (the inflaters of the reader threads that meet a BGZF file are set up by the survey, before Counter::init reads the
-//  free device memory, so that the plan sees what is left)
+//  free device memory, so that the plan sees what is left; the indexes of the plain gzip files of a call that opted in are
+//  built there too, once every file of the call has been looked at: they give the text bytes the bound needs)
 static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
 { std::vector<std::unique_ptr<DeviceInflater>> own;
   std::vector<Inflater *> infl;
   int nthr = 1;
   publish_bam(paths, std::vector<FileRead>(), 1);              // (whatever becomes of this call, the report of an earlier one is gone)
-  return count_run(opts, io, paths && npaths >= 1, npaths,
+  publish_gzip(nullptr, nullptr);
+  const auto report_gzip = [&]
+    { for (const std::unique_ptr<DeviceInflater> &d : own)
+        if (d) for (const auto &g : d->gz_index) publish_gzip(g.first.c_str(), &g.second, true);
+    };
+  const int rc = count_run(opts, io, paths && npaths >= 1, npaths,
     [&](int64_t *bound)
       { std::vector<char> bgzf;
-        RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf));
+        RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf, opts->gzip != 0));
         nthr = reader_threads(opts->host_threads, npaths);
         own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
         for (int f = 0; f < npaths; f++)
           if (bgzf[(size_t) f] && !own[(size_t) (f % nthr)])
             { RCHK(new_inflater(opts->device, own[(size_t) (f % nthr)], errbuf, errlen));
               infl[(size_t) (f % nthr)] = own[(size_t) (f % nthr)].get();
+            }
+        for (int f = 0; f < npaths; f++)
+          if (bgzf[(size_t) f] == FILE_GZIP)
+            { const Fd fd(paths[f]);
+              int64_t text = 0;
+              if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
+              RCHK(own[(size_t) (f % nthr)]->gzip_survey(fd.fd, paths[f], 0, &text, errbuf, errlen));
+              *bound += text;
             }
         return 0;
       },
@@ -374,6 +416,8 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         publish_bam(paths, files, nthr);                       // (after an error too: the files read to their end before it)
         return rc;
       }, errbuf, errlen);
+  report_gzip();
+  return rc;
 }
 
 static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
@@ -401,6 +445,59 @@ static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_
       return 0;
     }, errbuf, errlen));
   if (ms_kernel) *ms_kernel = in.infl->ms.inflate;
+  return sink.hand_over(text, n, errbuf, errlen);
+}
+
+// what a one-file gzip route is given: a gzip file (BGZF is one), opened
+static int gzip_open(const char *path, std::unique_ptr<Fd> &file, char *errbuf, size_t errlen)
+{ if (!path) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  file.reset(new Fd(path));
+  if (file->fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  const int kind = file_kind(file->fd, path, errbuf, errlen, true);
+  if (kind < 0) return kind;
+  if (kind == FILE_PLAIN) return fail(errbuf, errlen, SMG_EINVAL, "%s is not gzip: it does not begin with a gzip header", path);
+  return 0;
+}
+
+// the text of a whole gzip file by the route of the counting calls: the index, then the exact decoder over it
+static int gzip_inflate(const char *path, int32_t device, int64_t span_bytes, uint8_t **text, int64_t *n, double *ms_kernel, char *errbuf, size_t errlen)
+{ if (!text || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  publish_gzip(nullptr, nullptr);
+  std::unique_ptr<Fd> file;
+  RCHK(gzip_open(path, file, errbuf, errlen));
+  std::unique_ptr<DeviceInflater> infl;
+  RCHK(new_inflater(device, infl, errbuf, errlen));
+  int64_t bytes = 0;
+  RCHK(infl->gzip_survey(file->fd, path, span_bytes, &bytes, errbuf, errlen));
+  GrowSink sink;
+  sink.reserve((size_t) bytes + 1);
+  RCHK(infl->gzip_text(file->fd, path, [&](const uint8_t *t, size_t m)
+    { if ((int64_t) (sink.len + m) > bytes) return fail(errbuf, errlen, SMG_EFORMAT, "%s changed while it was read", path);
+      sink.put(t, m);
+      return 0;
+    }, errbuf, errlen));
+  const GzIndex &ix = infl->gz_index[path];
+  if (ms_kernel) { ms_kernel[0] = ix.ms[0]; ms_kernel[1] = ix.ms[1]; ms_kernel[2] = ix.ms[2]; }
+  publish_gzip(path, &ix);
+  return sink.hand_over(text, n, errbuf, errlen);
+}
+
+// the same by the host twin: finder, marker decoder, chain, resolver and exact decoder as one lane (a test twin, no fallback)
+static int gzip_text_host(const char *path, int64_t span_bytes, uint8_t **text, int64_t *n, char *errbuf, size_t errlen)
+{ if (!text || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  publish_gzip(nullptr, nullptr);
+  std::unique_ptr<Fd> file;
+  RCHK(gzip_open(path, file, errbuf, errlen));
+  uint32_t span = 0;
+  RCHK(gz_span(span_bytes, &span, errbuf, errlen));
+  GzHostEngine e;
+  GzIndex ix;
+  std::vector<uint8_t> bytes;
+  RCHK(gz_text_host(file->fd, path, span, BGZF_TEXT, GZ_MAX_PIECE, e, ix, bytes, errbuf, errlen));
+  GrowSink sink;
+  sink.reserve(bytes.size() + 1);
+  sink.put(bytes.data(), bytes.size());
+  publish_gzip(path, &ix);
   return sink.hand_over(text, n, errbuf, errlen);
 }
 
@@ -506,6 +603,17 @@ extern "C" int smg_count_bam_strip(const char *path, int32_t device, uint8_t **s
 
 extern "C" int smg_count_bam_report(const char *path, int64_t *records, int64_t *bases, double *ms)
 { try { return bam_report(path, records, bases, ms); } catch (...) { return SMG_ENOMEM; } }
+
+extern "C" int smg_count_gzip_inflate(const char *path, int32_t device, int64_t span_bytes, uint8_t **text, int64_t *n, double *ms_kernel,
+                                      char *errbuf, size_t errlen)
+{ GUARD(gzip_inflate(path, device, span_bytes, text, n, ms_kernel, errbuf, errlen)) }
+
+extern "C" int smg_count_gzip_text_host(const char *path, int64_t span_bytes, uint8_t **text, int64_t *n, char *errbuf, size_t errlen)
+{ GUARD(gzip_text_host(path, span_bytes, text, n, errbuf, errlen)) }
+
+extern "C" int smg_count_gzip_report(const char *path, int64_t *members, int64_t *text_bytes, int64_t *spans, int64_t *linked, int64_t *repaired,
+                                     double *ms)
+{ try { return gzip_report(path, members, text_bytes, spans, linked, repaired, ms); } catch (...) { return SMG_ENOMEM; } }
 
 extern "C" void smg_count_free(void *p) { free(p); }
 

@@ -5,7 +5,8 @@
 // A file may be block-gzipped (BGZF, what bgzip and htslib write): a gzip file of independent members of at most 64 KiB,
 // each with its length in its header (the BC subfield) and its CRC-32 and text length in its trailer.  This file finds
 // the members; their text comes from an Inflater, which the counter implements on the device (smg_inflate.hpp) and a
-// reader without one refuses.  Any other gzip file is refused as it always was.
+// reader without one refuses.  Any other gzip file is refused as it always was, unless the call opted in (smg_count_opts.gzip)
+// and the survey left the index of the file with the thread's Inflater (smg_gzip.hpp), which then gives its text too.
 //
 // BGZF text that begins with the four bytes BAM\1 is a BAM file (smg_bam.hpp): its reader thread frames the records of
 // every piece of text (BamFramer) and hands their descriptors back to the Inflater, whose second step unpacks the 4-bit
@@ -28,6 +29,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -147,6 +149,11 @@ struct Inflater
   virtual int unpack(const BamDesc *, size_t, size_t, Sink &, char *errbuf, size_t errlen)
   { return fail(errbuf, errlen, SMG_EINVAL, "internal error: this inflater cannot unpack BAM sequences%s", ""); }
   virtual InflaterTimes times() const { return InflaterTimes(); }      // of all calls so far
+  // Plain gzip: does this inflater hold the index of the file (the survey of a call that opted in built it)?  Then its text,
+  // piece after piece, to put(text, n) -> 0 or what ends the run; 0, or that, or an error code with message.
+  virtual bool has_gzip(const char *) const { return false; }
+  virtual int gzip_text(int, const char *path, const std::function<int(const uint8_t *, size_t)> &, char *errbuf, size_t errlen)
+  { return fail(errbuf, errlen, SMG_EINVAL, "internal error: this inflater holds no gzip index of %s", path); }
   virtual ~Inflater() {}
 };
 
@@ -199,9 +206,10 @@ static inline int bgzf_member(const uint8_t *p, size_t avail, const char *path, 
 
 // What a file is by its first bytes: FILE_PLAIN (no gzip magic: the parser says what it is), FILE_BGZF (by the header of its
 // first member; a header cut by the end of the file counts, the walk says where), or SMG_EINVAL with message: the file
-// cannot be read, or it is gzip and not BGZF.  The one place that decides this, for the survey, the scan and the readers.
-enum { FILE_PLAIN = 0, FILE_BGZF = 1 };
-static inline int file_kind(int fd, const char *path, char *errbuf, size_t errlen)
+// cannot be read, or it is gzip and not BGZF -- FILE_GZIP instead where the caller reads that (gzip_ok: the call opted in).
+// The one place that decides this, for the survey, the scan and the readers.
+enum { FILE_PLAIN = 0, FILE_BGZF = 1, FILE_GZIP = 2 };
+static inline int file_kind(int fd, const char *path, char *errbuf, size_t errlen, bool gzip_ok = false)
 { std::vector<uint8_t> h(32);
   for (;;)
     { const ssize_t got = pread(fd, h.data(), h.size(), 0);
@@ -211,7 +219,8 @@ static inline int file_kind(int fd, const char *path, char *errbuf, size_t errle
       if (rc == 2 && (size_t) got == h.size()) { h.resize(12 + 65536); continue; }
       if (rc == 0 || (rc == 2 && got >= 4)) return FILE_BGZF;
       if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b)
-        return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
+        return gzip_ok ? (int) FILE_GZIP
+                       : fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
       return FILE_PLAIN;
     }
 }
@@ -345,9 +354,17 @@ static inline int bam_piece(BamFramer &fr, const uint8_t *t, size_t n, const cha
 // one file to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
 // the framer, anything else through the parser), anything else as it is.  *fr: what it gave, where it was read to its end
 static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
-{ const int kind = file_kind(fd, path, errbuf, errlen);
+{ const int kind = file_kind(fd, path, errbuf, errlen, infl && infl->has_gzip(path));
   if (kind < 0) return kind;
   if (kind == FILE_PLAIN) return parse_fd(fd, path, sink, fr, errbuf, errlen);
+  if (kind == FILE_GZIP)
+    { Parser ps(sink);
+      const InflaterTimes before = infl->times();
+      const int rc = infl->gzip_text(fd, path, [&](const uint8_t *t, size_t n) { return ps.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+      if (rc) return rc;
+      *fr = text_read(ps, infl->times() - before);
+      return 0;
+    }
   if (!infl)
     return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
                 "use smg_count_bgzf_inflate or one of the counting calls", path);
@@ -407,9 +424,10 @@ static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *
 
 // Refuse what cannot be read before anything is set up for it.  *bound = the most sequence the files can hold: their
 // sizes (of a BGZF file: the text its members announce), and k + 1 bytes per file for the separator and the tail a batch
-// boundary puts in front of a piece.  bgzf (may be null): per file, is it BGZF?
+// boundary puts in front of a piece.  bgzf (may be null): per file, is it BGZF (1)?  gzip_ok: the call reads plain gzip; such
+// a file is FILE_GZIP in bgzf and adds only its k + 1 bytes: its text is known once its index is built.
 static inline int survey_files(const char *const *paths, int npaths, int k, int64_t *bound, char *errbuf, size_t errlen,
-                               std::vector<char> *bgzf = nullptr)
+                               std::vector<char> *bgzf = nullptr, bool gzip_ok = false)
 { *bound = 0;
   if (bgzf) bgzf->assign((size_t) npaths, 0);
   for (int f = 0; f < npaths; f++)
@@ -417,10 +435,14 @@ static inline int survey_files(const char *const *paths, int npaths, int k, int6
       if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
       int64_t size = (int64_t) lseek(fd.fd, 0, SEEK_END), blocks = 0;
       if (size < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
-      int rc = file_kind(fd.fd, paths[f], errbuf, errlen);
+      int rc = file_kind(fd.fd, paths[f], errbuf, errlen, gzip_ok);
       if (rc == FILE_BGZF)
         { rc = bgzf_walk(fd.fd, paths[f], &blocks, &size, errbuf, errlen);
-          if (bgzf) (*bgzf)[(size_t) f] = 1;
+          if (bgzf) (*bgzf)[(size_t) f] = FILE_BGZF;
+        }
+      else if (rc == FILE_GZIP)
+        { rc = 0; size = 0;
+          if (bgzf) (*bgzf)[(size_t) f] = FILE_GZIP;
         }
       if (rc) return rc;
       *bound += size + k + 1;

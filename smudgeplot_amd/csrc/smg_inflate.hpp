@@ -207,14 +207,13 @@ template <class Io> INF_HD int inf_dynamic(Io &io, InfBits &b, const InfTables &
   return INF_OK;
 }
 
-// One member: io.clen payload bytes -> exactly io.isize bytes of text with the CRC-32 io.crc, or the first reason why not.
-template <class Io> INF_HD int inflate_member(Io &io, const InfTables &t)
-{ InfBits b{ 0, 0, 0 };
-  uint32_t pos = 0, v, last;
-  do
+// One block from its header on: text from `pos` on (Pos: the type of io.isize, 32 bits for a member, 64 for a stream of any
+// length, smg_gzip.hpp), *last = its BFINAL.  Reads payload bytes below io.clen and writes text below io.isize only.
+template <class Io, class Pos> INF_HD int inf_block(Io &io, const InfTables &t, InfBits &b, Pos &pos, uint32_t *last)
+{ uint32_t v;
     { inf_refill(io, b);
       INF_BITS(3, v);
-      last = v & 1u;
+      *last = v & 1u;
       const uint32_t type = v >> 1;
       if (type == 3) return INF_BAD_TYPE;
       if (type == 0)
@@ -234,7 +233,7 @@ template <class Io> INF_HD int inflate_member(Io &io, const InfTables &t)
             }
           if (len > io.clen - b.ip) return INF_EXHAUSTED;
           if (len) { io.stored(pos, b.ip, len); pos += len; b.ip += len; }
-          continue;
+          return INF_OK;
         }
       int nlit = INF_NLIT, ndist = INF_NDIST;
       if (type == 1)
@@ -275,6 +274,14 @@ template <class Io> INF_HD int inflate_member(Io &io, const InfTables &t)
           pos += len;
         }
     }
+  return INF_OK;
+}
+
+// One member: io.clen payload bytes -> exactly io.isize bytes of text with the CRC-32 io.crc, or the first reason why not.
+template <class Io> INF_HD int inflate_member(Io &io, const InfTables &t)
+{ InfBits b{ 0, 0, 0 };
+  uint32_t pos = 0, last;
+  do INF_TRY(inf_block(io, t, b, pos, &last));
   while (!last);
   if (pos != io.isize) return INF_TOO_SHORT;
   if (io.clen - b.ip + (uint32_t) (b.cnt >> 3) != 0) return INF_LEFT_OVER;
