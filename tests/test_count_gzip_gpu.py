@@ -1,7 +1,9 @@
 """Plain gzip in front of the k-mer counter on the GPU: the four kernels byte by byte through count.gzip_inflate at the smallest
 spans (the oracle is gzip.decompress; tests/test_count_gzip_host.py holds the same streams against the host twin, and
 `make gzip_check` has held the twin against zlib on the CPU), their report against the twin's, counting with gzip=True against
-the plain run, the executable with -g, and a damaged member."""
+the plain run, the executable with -g, and a damaged member.  Every stream here is some 300 KB at ordinary ratios, so hardly
+one of the fixed sizes of the code is reached: tests/test_count_gzip_seams_gpu.py has the files that fill a piece, the ring
+slots of a decode, a slab of windows, and the intervals and the text of one call, and the refusal of the resolver."""
 import gzip
 import os
 import subprocess

@@ -2,7 +2,10 @@
 block finder, marker decoder, chain, resolver and exact decoder as the kernels, run as one lane) against Python's gzip over the
 streams of tests/gzip_craft.py at every span size, what its report says, the refusals with their offsets, and that nothing
 changes without the opt-in.  (`make gzip_check` holds the same twin against zlib under the sanitizers over mutated files; it
-takes a compiler and a minute and is run by hand; profiles/count_gzip.md keeps its output.)"""
+takes a compiler and a minute and is run by hand; profiles/count_gzip.md keeps its output.)  The streams here are some 300 KB
+at ordinary ratios; tests/test_count_gzip_seams_host.py holds the twin against files that reach the fixed sizes of the code --
+the spans of a piece, the ring slots of a decode, the intervals and the text of one call -- and has the refusals of the resolver
+and of a block above the text of one call."""
 import gzip
 import os
 import re
