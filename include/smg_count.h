@@ -22,6 +22,24 @@
  *     The size of a BAM file bounds its bases as that of any BGZF file does, by the sum of its ISIZE fields: an over-estimate
  *     by 1.5 or more, so a large BAM may be counted by key range where one pass would have done; the result is the same
  *     whichever way it is counted.  CRAM is not gzip and is refused like any file that is neither FASTA nor FASTQ;
+ *   - input: k-mers that another tool has counted already, only where smg_count_opts.dump is set (smg_count -d): the text
+ *     that kmc_dump, `jellyfish dump -c` and `meryl print` write, one line per k-mer.  The refusal of a file that begins ACGT
+ *     is a tested contract like that of plain gzip, hence the option; with it EVERY file of the call is a dump, its text routed
+ *     by its own header as above (plain; BGZF; with gzip also set, plain gzip).  A file whose text begins with '>', '@', BAM\1
+ *     or any byte outside ACGTacgt is SMG_EINVAL: the message names it and says that a call with the dump option reads dumps
+ *     only.  The grammar of a line is strict: k bases ACGTacgt, exactly one ' ' or '\t', 1 .. 20 decimal digits, an optional
+ *     '\r', '\n' (the last line may end with the text instead), at most SMG_COUNT_DUMP_LINE bytes.  The value saturates at
+ *     2^32 - 1, leading zeros are fine, 0 is an error (hist[0] is 0).  The lines are decoded on the device.  Anything else is
+ *     SMG_EFORMAT, "<path>: dump line at offset <o>: <reason>", o the offset of the first byte of the first bad line of that
+ *     file in its (inflated) text, the reason one of
+ *         is not <k> bases and a separator (is k right?)  |  has no count  |  count is 0  |  count is not followed by a line end
+ *     Every line adds its count to the smaller of its k-mer and its reverse complement; the sums saturate (never wrap) and
+ *     clamp at 32767 in the table.  A dump of both strands, repeated k-mers and several dumps in one call just add up.
+ *     stats.windows is the number of lines, stats.bases k times that.  One pass only (the packed store is a store of reads):
+ *     partitions must be 0 or 1, and where the sizes of the files (a line has k + 3 bytes at least) do not guarantee that one
+ *     merge holds the lines -- 2^32 - 16 entries, or the memory a merge is priced at -- the call is refused with SMG_ENOMEM
+ *     before its first allocation, the figures in the message.  SMG_COUNT_BATCH_BASES (test hook) is the batch in text bytes
+ *     here, raised to SMG_COUNT_DUMP_LINE where it is smaller;
  *   - bases ACGTacgt code to 0..3, every other byte ends the current stretch, no k-mer spans two records;
  *   - every window of k bases counts once for the smaller of the k-mer and its reverse complement
  *     (left-aligned big-endian words, the order of the FastK table);
@@ -31,7 +49,7 @@
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
  * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
- * return SMG_ENODEV; smg_count_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text, smg_count_gzip_text_host and
+ * return SMG_ENODEV; smg_count_parse and smg_count_dump_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text, smg_count_gzip_text_host and
  * smg_count_version need no device.
  */
 #ifndef SMG_COUNT_H
@@ -67,6 +85,7 @@ extern "C" {
 #define SMG_COUNT_BGZF_CHUNK (16 << 20)  /* compressed bytes of a BGZF file that one launch of the inflate kernel takes (whole
                                             members; a reader thread holds one such buffer and 4 x as much for their text) */
 #define SMG_COUNT_BAM_TILE   4096      /* stripped bytes of a BAM file that one workgroup of the unpack kernel writes */
+#define SMG_COUNT_DUMP_LINE  151       /* the longest legal line of a k-mer dump: 128 bases, a separator, 20 digits, \r\n */
 
 typedef struct smg_count_opts
 { int32_t kmer;          /* 13 .. SMG_MAX_KMER                                   */
@@ -75,6 +94,7 @@ typedef struct smg_count_opts
   int32_t host_threads;  /* reader threads, one file each, at most 16 are used  */
   int32_t verbose;
   int32_t gzip;          /* 0: a gzip file that is not BGZF is refused, as always; 1: it is read (see the top of this file) */
+  int32_t dump;          /* 0: the files are reads, as always; 1: every file is a k-mer dump (see the top of this file)      */
 } smg_count_opts;
 
 typedef struct smg_count_stats
@@ -241,6 +261,20 @@ int smg_count_gzip_text_host(const char *path, int64_t span_bytes, uint8_t **tex
    the same file and span size.  SMG_EINVAL where that call read no such file.                                            */
 int smg_count_gzip_report(const char *path, int64_t *members, int64_t *text_bytes, int64_t *spans, int64_t *linked, int64_t *repaired,
                           double *ms);
+
+/* host only, plain files only: the records of a k-mer dump (see the top of this file) by the line decoder the kernel compiles,
+   run on the host: per line, in line order, the canonical k-mer (*key_words left-aligned words) and the count saturated at
+   2^32 - 1.  *keys (uint64[*n * *key_words]) and *counts (uint32[*n]) are malloc'ed (smg_count_free).  The errors of the
+   counting calls with the dump option: SMG_EINVAL for a text that does not begin with a base, SMG_EFORMAT for the first bad
+   line.  A test twin like smg_count_gzip_text_host, not a fallback.                                                       */
+int smg_count_dump_parse(const char *path, int32_t kmer, uint64_t **keys, uint32_t **counts, int64_t *n, int *key_words,
+                         char *errbuf, size_t errlen);
+
+/* the same records as the kernel of the counting calls emits them, by the route those calls take (plain; BGZF; with gzip != 0
+   plain gzip): in no particular order.  *ms_kernel (may be NULL): the sum of the HIP-event times of the line kernel.  Same
+   errors.  SMG_ENODEV without a device.                                                                                */
+int smg_count_dump_records(const char *path, int32_t kmer, int32_t device, int32_t gzip, uint64_t **keys, uint32_t **counts, int64_t *n,
+                           int *key_words, double *ms_kernel, char *errbuf, size_t errlen);
 
 void smg_count_free(void *p);
 const char *smg_count_version(void);

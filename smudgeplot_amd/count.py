@@ -11,6 +11,14 @@ BAM\\1) is read too: its records are framed on the host and their 4-bit sequence
 records (FLAG without 0x100 and 0x800) give the stream of a FASTA file of the same reads.  A BAM file is bounded by its text
 like any BGZF file, 1.5 times its bases or more, so it may be counted by key range where one pass would have done, with the
 same result.
+
+K-mers that another tool has counted already are read too, again opt-in (`count_files(..., dump=True)`): the text dumps of
+`kmc_dump`, `jellyfish dump -c` and `meryl print`, one line `<k-mer><space or tab><count>` per k-mer, plain, BGZF or (with
+gzip=True) plain gzip.  With the option every file of the call is a dump; the lines are decoded on the device, every line adds
+its count to the smaller of its k-mer and its reverse complement, and the sums saturate.  `dump_parse` is the host twin of
+that decoder, `dump_records` its records as the kernel emits them.
+`smg_count_opts` grew by one trailing field for it: `Opts` is the struct up to `gzip`, as it was, and `DumpOpts(Opts)` the whole
+struct, which is what this module hands to the library.
 """
 
 from __future__ import annotations
@@ -26,6 +34,7 @@ MIN_KMER, MAX_KMER, MAX_COUNT, HIST, BINS = 13, 128, 32767, 32768, 4096
 FINE_BINS = 1 << 24                       # the ends of a range are values of the leading 24 bits where a bin was split
 BGZF_CHUNK = 16 << 20                     # compressed bytes of a BGZF file that one launch of the inflate kernel takes
 BAM_TILE = 4096                           # stripped bytes of a BAM file that one workgroup of the unpack kernel writes
+DUMP_LINE = 151                           # the longest legal line of a k-mer dump: 128 bases, a separator, 20 digits, \r\n
 GZIP_SPAN = 256 << 10                     # compressed bytes of a span of a plain gzip file (1 KiB .. 1 MiB can be asked for)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,7 +45,8 @@ EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_c
            "smg_count_plan_fine", "smg_count_parse", "smg_count_free", "smg_count_version",
            "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan",
            "smg_count_bgzf_scan", "smg_count_bgzf_inflate", "smg_count_bam_text", "smg_count_bam_strip", "smg_count_bam_report",
-           "smg_count_gzip_inflate", "smg_count_gzip_text_host", "smg_count_gzip_report"]
+           "smg_count_gzip_inflate", "smg_count_gzip_text_host", "smg_count_gzip_report",
+           "smg_count_dump_parse", "smg_count_dump_records"]
 
 
 class CountError(RuntimeError):
@@ -48,6 +58,12 @@ class CountError(RuntimeError):
 class Opts(C.Structure):
     _fields_ = [("kmer", C.c_int32), ("minval", C.c_int32), ("device", C.c_int32),
                 ("host_threads", C.c_int32), ("verbose", C.c_int32), ("gzip", C.c_int32)]
+
+
+class DumpOpts(Opts):
+    """The whole smg_count_opts: the fields of Opts and the one the struct grew by behind them.  This is what every call of
+    this module hands to the library, which reads all seven fields; Opts alone is the struct as it was before `dump`."""
+    _fields_ = [("dump", C.c_int32)]
 
 
 class Stats(C.Structure):
@@ -77,7 +93,7 @@ def load_library():
     _share_torch_hip_runtime()
     lib = C.CDLL(LIB_PATH)
     vp = C.c_void_p
-    tail = [C.POINTER(Opts), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), vp,
+    tail = [C.POINTER(DumpOpts), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int), vp,
             C.POINTER(Stats), C.c_char_p, C.c_size_t]
     lib.smg_count_files.argtypes = [C.POINTER(C.c_char_p), C.c_int] + tail
     lib.smg_count_files.restype = C.c_int
@@ -122,6 +138,12 @@ def load_library():
     lib.smg_count_gzip_text_host.restype = C.c_int
     lib.smg_count_gzip_report.argtypes = [C.c_char_p] + [C.POINTER(C.c_int64)] * 5 + [C.POINTER(C.c_double)]
     lib.smg_count_gzip_report.restype = C.c_int
+    lib.smg_count_dump_parse.argtypes = [C.c_char_p, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                         C.c_char_p, C.c_size_t]
+    lib.smg_count_dump_parse.restype = C.c_int
+    lib.smg_count_dump_records.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+    lib.smg_count_dump_records.restype = C.c_int
     lib.smg_count_free.argtypes = [vp]
     lib.smg_count_free.restype = None
     lib.smg_count_version.restype = C.c_char_p
@@ -149,9 +171,9 @@ def _table(k, t, keys, counts):
     return ktab.KTable(k, 3, 1, t, packed, counts, index, np.array([len(counts)], np.int64))
 
 
-def _run(call, k, t, device, threads, partitions, max_entries, gzip=False):
+def _run(call, k, t, device, threads, partitions, max_entries, gzip=False, dump=False):
     lib = load_library()
-    opts = Opts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)))
+    opts = DumpOpts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)), int(bool(dump)))
     parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
     keys, cnt = C.c_void_p(), C.c_void_p()
     nels, words = C.c_int64(0), C.c_int(0)
@@ -174,17 +196,19 @@ def _run(call, k, t, device, threads, partitions, max_entries, gzip=False):
     return _table(int(k), int(t), k64, c16), hist, stats
 
 
-def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False):
+def count_files(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False, dump=False):
     """-> (ktab.KTable of the canonical k-mers with count >= t, hist uint64[32768], stats dict)
 
     partitions: 0 lets the library count by key range where one pass is not guaranteed to fit, 1 is one pass,
     2 .. 4096 that many ranges; max_entries (test hook) plans as if one merge held only that many entries.
     The stats carry `used` (ranges), `store_bytes`, `ms_pack` and `ms_plan` of a partitioned run, and `split`: the bins of
     the leading 12 bits that held more windows than one merge and were split on their next 12 bits (automatic mode only).
-    gzip: read plain gzip files too (off: they are refused, as always); gzip_report says what was read of each."""
+    gzip: read plain gzip files too (off: they are refused, as always); gzip_report says what was read of each.
+    dump: every file is a k-mer dump (see the top of this module); partitions must then be 0 or 1, stats["windows"] is the
+    number of lines and stats["bases"] k times that."""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
-    return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries, gzip)
+    return _run(lambda lib, *a: lib.smg_count_files_parts(arr, len(paths), *a), k, t, device, threads, partitions, max_entries, gzip, dump)
 
 
 def count_bases(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
@@ -229,9 +253,9 @@ class DeviceTable:
             e.close()
 
 
-def _run_device(call, k, t, device, threads, partitions, max_entries, gzip=False):
+def _run_device(call, k, t, device, threads, partitions, max_entries, gzip=False, dump=False):
     lib = load_library()
-    opts = Opts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)))
+    opts = DumpOpts(int(k), int(t), int(device), int(threads), 0, int(bool(gzip)), int(bool(dump)))
     parts = Parts(int(partitions), int(max_entries), 0, 0, 0.0, 0.0)
     keys, cnt = C.c_void_p(), C.c_void_p()
     nels, words = C.c_int64(0), C.c_int(0)
@@ -252,12 +276,12 @@ def _as_bases(seq):
                                 dtype=np.uint8)
 
 
-def count_files_device(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False):
+def count_files_device(paths, k, t=4, device=0, threads=4, partitions=0, max_entries=0, gzip=False, dump=False):
     """count_files with the table left on the device -> (DeviceTable, hist uint64[32768], stats dict)"""
     paths = [os.fsencode(p) for p in ([paths] if isinstance(paths, (str, bytes, os.PathLike)) else paths)]
     arr = (C.c_char_p * len(paths))(*paths)
     return _run_device(lambda lib, *a: lib.smg_count_files_device(arr, len(paths), *a), k, t, device, threads, partitions, max_entries,
-                       gzip)
+                       gzip, dump)
 
 
 def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entries=0):
@@ -267,22 +291,24 @@ def count_bases_device(seq, k, t=4, device=0, threads=4, partitions=0, max_entri
                        partitions, max_entries)
 
 
-def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash", gzip=False):
+def reads_to_plot(paths_or_bases, k, t, e, device=0, threads=4, partitions=0, max_entries=0, symcheck="hash", gzip=False, dump=False):
     """Reads to the het-mer plot in one process: count on the device (k-mers with count >= t), hand the table over where
     it lies, trim at e, close under reverse complement, run -> (plot int64[1001, 501], hist uint64[32768], stats dict).
     The closed table runs in core, or, where it is beyond one engine or the memory, in prefix shards one after the other
     (engine.run_device_mode says which).
     paths_or_bases: sequence bytes (bytes, bytearray, memoryview or a uint8 array) or one path or a list of paths.
-    gzip: read plain gzip files too, as count_files does.
+    gzip: read plain gzip files too, as count_files does.  dump: the files are k-mer dumps, as count_files reads them.
     e < t cannot be honoured (the entries below t are gone) and raises ValueError.  The stats are the counter's, with the
     engine's under "hetmers"."""
     from . import engine
     if int(e) < int(t):
         raise ValueError(f"e = {e} is below t = {t}: the k-mers with a count below t are not in the table")
     if isinstance(paths_or_bases, (bytes, bytearray, memoryview, np.ndarray)):
+        if dump:
+            raise ValueError("dump=True reads files: a buffer of sequence bytes is no k-mer dump")
         got = count_bases_device(paths_or_bases, k, t, device, threads, partitions, max_entries)
     else:
-        got = count_files_device(paths_or_bases, k, t, device, threads, partitions, max_entries, gzip)
+        got = count_files_device(paths_or_bases, k, t, device, threads, partitions, max_entries, gzip, dump)
     table, hist, stats = got
     with table:
         plot, est = engine.hetmers_run_device(k, table.nels, table.keys_ptr, table.counts_ptr, device=device, symcheck=symcheck,
@@ -435,6 +461,40 @@ def gzip_report(path) -> dict:
         raise CountError(rc, f"the last call read no gzip file {path}")
     return {"members": v[0].value, "text_bytes": v[1].value, "spans": v[2].value, "linked": v[3].value, "repaired": v[4].value,
             "ms_marker": ms[0], "ms_resolve": ms[1], "ms_exact": ms[2]}
+
+
+def _dump_call(call, n_ms=0):
+    lib = load_library()
+    keys, cnt, n, words = C.c_void_p(), C.c_void_p(), C.c_int64(0), C.c_int(0)
+    ms = C.c_double(0.0)
+    err = C.create_string_buffer(1024)
+    rc = call(lib, C.byref(keys), C.byref(cnt), C.byref(n), C.byref(words), *([C.byref(ms)] if n_ms else []), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    try:
+        m, w = n.value, words.value
+        k64 = np.ctypeslib.as_array(C.cast(keys, C.POINTER(C.c_uint64)), shape=(max(m, 1) * w,))[: m * w].copy().reshape(m, w)
+        c32 = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint32)), shape=(max(m, 1),))[:m].copy()
+    finally:
+        lib.smg_count_free(keys)
+        lib.smg_count_free(cnt)
+    return k64, c32, ms.value
+
+
+def dump_parse(path, k):
+    """Host only, plain files only: the records of a k-mer dump by the line decoder the kernel compiles, run on the host ->
+    (k-mers uint64[n, words], canonical, left aligned; counts uint32[n], saturated at 2^32 - 1), in line order.  A test twin,
+    not a fallback.  Raises CountError -2 for a text that does not begin with a base, -4 "<path>: dump line at offset <o>:
+    <reason>" for the first bad line."""
+    k64, c32, _ = _dump_call(lambda lib, *a: lib.smg_count_dump_parse(os.fsencode(path), int(k), *a))
+    return k64, c32
+
+
+def dump_records(path, k, device=0, gzip=False):
+    """The same records as the kernel of the counting calls emits them, by the route those calls take (plain, BGZF, with
+    gzip=True plain gzip), in no particular order -> (k-mers, counts, ms_kernel: the HIP-event time of the line kernel).
+    Errors as dump_parse."""
+    return _dump_call(lambda lib, *a: lib.smg_count_dump_records(os.fsencode(path), int(k), int(device), int(bool(gzip)), *a), n_ms=1)
 
 
 def bam_text(text, piece=0) -> bytes:

@@ -13,7 +13,12 @@
  *  complement and scanned for het-mer pairs there (smg_hetmers_run_device: in core, or in prefix shards of the closed table one
  *  after the other where it is too large for that), and <output>.smu is written as `hetmers -e` writes it from the table on disk.
  *
- *  Usage: smg_count [-v] [-g] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
+ *  With -d the inputs are k-mers that another tool has counted already: the text dumps of kmc_dump, `jellyfish dump -c` and
+ *  `meryl print`, one line <k-mer><space or tab><count> per k-mer, plain, BGZF or (with -g) plain gzip; every line adds its count
+ *  to the smaller of its k-mer and its reverse complement.  An option for the reason -g is one: a file that begins ACGT is
+ *  refused without it, and that is tested.  -t, -H, -o, -n and -e mean what they mean for reads; -p must be 0 or 1.
+ *
+ *  Usage: smg_count [-v] [-g] [-d] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
  *           -k: k-mer length, 13 .. 128          -t: keep the k-mers with count >= t
  *           -H: also write <output>.hist.txt     -T: reader threads (one input file each, at most 16)
  *           -o: root name of the table; default is the root of the first input
@@ -21,6 +26,7 @@
  *           -e: also write <output>.smu, the het-mer pairs of the k-mers with count >= e (e >= t); one device
  *           -n: write no table (with -e or -H only)
  *           -g: read plain gzip inputs too (SMG_COUNT_GZIP_SPAN, test hook: the compressed bytes of a span)
+ *           -d: the inputs are k-mer dumps (k-mer, separator, count per line), not reads
  *
  *  SMUDGEPLOT_GPU picks the device; SMG_COUNT_MAX_ENTRIES (test hook) is max_entries of smg_count_parts.  No CPU fallback.
  *  A failed run leaves no table, histogram or .smu file behind.
@@ -31,7 +37,7 @@
 #include "smg_count.h"
 
 static void usage(void)
-{ fprintf(stderr, "\nUsage: %s [-v] [-g] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...\n", Prog_Name);
+{ fprintf(stderr, "\nUsage: %s [-v] [-g] [-d] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...\n", Prog_Name);
   fprintf(stderr, "\n");
   fprintf(stderr, "      -k: k-mer length (13 .. %d)\n", SMG_MAX_KMER);
   fprintf(stderr, "      -t: keep the k-mers that occur at least t times\n");
@@ -42,6 +48,8 @@ static void usage(void)
   fprintf(stderr, "      -n: write no table (with -e or -H)\n");
   fprintf(stderr, "      -g: read plain gzip <reads> too (reads.fastq.gz as gzip or pigz write it), inflated on the device;\n");
   fprintf(stderr, "            without it such a file is refused, as always; plain, BGZF and BAM inputs are read the same either way\n");
+  fprintf(stderr, "      -d: the inputs are k-mer dumps, not reads: text lines <k-mer><space or tab><count> as kmc_dump, jellyfish dump -c\n");
+  fprintf(stderr, "            and meryl print write them (plain, BGZF, with -g plain gzip); -k must be their k, -p 0 or 1\n");
   fprintf(stderr, "      -o: root name for the output table\n");
   fprintf(stderr, "            default is root of the first <reads> argument\n");
   fprintf(stderr, "      -v: verbose mode\n");
@@ -75,7 +83,7 @@ static void remove_outputs(const char *root, int table, const char *hname, const
 }
 
 int main(int argc, char *argv[])
-{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0, ethresh = 0, no_table = 0, gzip = 0;
+{ int verbose = 0, nthreads = 4, kmer = 31, minval = 4, do_hist = 0, nparts = 0, ethresh = 0, no_table = 0, gzip = 0, dump = 0;
   char *out = NULL, *root, *hname = NULL, *sname = NULL;
   int64_t *plot = NULL;
   smg_stats hst;
@@ -98,6 +106,7 @@ int main(int argc, char *argv[])
         case 'H': do_hist = 1; break;
         case 'n': no_table = 1; break;
         case 'g': gzip = 1; break;
+        case 'd': dump = 1; break;
         case 'e': ethresh = arg_positive(argv[i], "Error-mer threshold"); break;
         case 'k': kmer = arg_positive(argv[i], "K-mer length"); break;
         case 'p':
@@ -145,7 +154,7 @@ int main(int argc, char *argv[])
 
   memset(&opts, 0, sizeof(opts));
   { const char *g = getenv("SMUDGEPLOT_GPU"); opts.device = g ? atoi(g) : 0; }
-  opts.kmer = kmer; opts.minval = minval; opts.host_threads = nthreads; opts.verbose = verbose; opts.gzip = gzip;
+  opts.kmer = kmer; opts.minval = minval; opts.host_threads = nthreads; opts.verbose = verbose; opts.gzip = gzip; opts.dump = dump;
   memset(&parts, 0, sizeof(parts));
   parts.partitions = nparts;
   { const char *m = getenv("SMG_COUNT_MAX_ENTRIES"); if (m != NULL && atoll(m) > 0) parts.max_entries = atoll(m); }   /* (test hook) */
@@ -236,6 +245,7 @@ int main(int argc, char *argv[])
           if (smg_count_bam_report(argv[i], &blocks, &text, NULL) == SMG_OK)
             fprintf(stderr, "  %s: BAM, %lld records, %lld bases, unpacked on the device\n", argv[i], (long long) blocks, (long long) text);
         }
+      if (dump) fprintf(stderr, "  k-mer dumps: %lld lines, decoded on the device\n", (long long) st.windows);
       fprintf(stderr, "  %lld bases, %lld %d-mers, %lld distinct, %lld with count >= %d, %lld batch%s\n", (long long) st.bases,
               (long long) st.windows, kmer, (long long) st.distinct, (long long) st.kept, minval, (long long) st.batches,
               st.batches == 1 ? "" : "es");

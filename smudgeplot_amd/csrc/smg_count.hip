@@ -30,6 +30,12 @@
 //           (kc_extract_store<W, 24>: the same for a range with an end inside a split bin, its filter on 24 bits)
 // Every instance of a k-mer lies in one range, so ranges in ascending order give the sorted table.
 //
+// A call that opted in (smg_count_opts.dump) reads k-mers that another tool has counted: text dumps, one line per k-mer.
+//   host    the reader threads route the text as above and cut it into blocks of whole lines (DumpCutter, smg_dump.hpp)
+//   batch   kd_lines<W>  the lines of the batch -> (canonical k-mer, uint32 count), the first bad line by atomicMin
+//           pair sort, kc_flag_heads + scan, kd_run_sums + kd_run_clamp: one saturating sum per distinct k-mer of the batch
+//   merge, finish  as above.  One pass only: the packed store is a store of reads
+//
 // The output table is host arrays, or (the _device entries) two whole allocations in device memory, which the caller
 // hands to smg_engine_bind / smg_hetmers_run_device and frees; the kept entries of every range are appended to it.
 //
@@ -50,6 +56,9 @@
 //   smg_count_inflater.hpp the device stage of compressed input, a part like those: DeviceInflater (inflate, unpack), one per
 //                          reader thread (with the gzip engine and the indexes of its gzip files), and the BGZF file a one-file
 //                          route opens for an inflater of its own
+//   smg_dump.hpp           k-mer dumps, host and device: the line decoder (one text for kd_lines and the host twin), the cutter
+//                          that hands whole lines on, the twin itself
+//   smg_count_dump.hpp     kd_lines, kd_run_sums, kd_run_clamp and the part that runs them: DumpFeed
 //   this file              the driver itself (Counter: set-up, flush, the ranges, finish), the entry points (count_files,
 //                          count_bases, the one-file routes, the report of the BAM files of the last call) and the C ABI
 
@@ -73,6 +82,7 @@
 #include "smg_count_plan.hpp"
 #include "smg_count_parts.hpp"
 #include "smg_count_inflater.hpp"
+#include "smg_count_dump.hpp"
 
 // where a run puts its results (the arguments of the C ABI)
 struct Out
@@ -85,14 +95,20 @@ struct Counter
   Batch batch{ x };
   Distinct list{ x };
   Store store{ x };
+  DumpFeed dump{ x, batch };                                   // (allocates only in a run over dumps)
+  bool dumps = false;                                          // the input is k-mer dumps: lines, not windows
   std::unique_ptr<Table> table;
   DevBuf<unsigned long long> dh;                               // the histogram of the counts, summed over the ranges
   bool parted = false;                                         // the batches are packed and counted by key range in finish()
   int req_parts = 0;
 
   // argument checks, the device, the memory plan (smg_count_plan.hpp), then the allocations it asks for
-  int init(const smg_count_opts *o, const Out &io, int64_t bound, int nfiles, char *errbuf, size_t errlen)
+  int init(const smg_count_opts *o, const Out &io, int64_t bound, int nfiles, char *errbuf, size_t errlen, const char *const *dump_paths = nullptr)
   { x.errbuf = errbuf; x.errlen = errlen;
+    dumps = dump_paths != nullptr;
+    if (dumps && io.parts && io.parts->partitions > 1)
+      return fail(errbuf, errlen, SMG_EINVAL, "partitions = %d with the dump option: k-mer dumps are counted in one pass (the packed store "
+                  "is a store of reads), partitions must be 0 or 1", io.parts->partitions);
     if (io.parts)
       { if (io.parts->partitions < 0 || io.parts->partitions > SMG_COUNT_BINS)
           return fail(errbuf, errlen, SMG_EINVAL, "partitions = %d is out of range 0 .. %d", io.parts->partitions, SMG_COUNT_BINS);
@@ -108,23 +124,56 @@ struct Counter
     const char *hook = getenv("SMG_COUNT_BATCH_BASES");
     int64_t cap = 0, store_cap = 0;
     int32_t ranges = 0;
-    RCHK(memory_plan(x.k, free_b, bound, req_parts, list.max_entries, hook ? atoll(hook) : 0, &cap, &ranges, &store_cap, errbuf, errlen));
+    if (dumps) RCHK(dump_plan(free_b, bound, nfiles, hook ? atoll(hook) : 0, &cap));
+    else RCHK(memory_plan(x.k, free_b, bound, req_parts, list.max_entries, hook ? atoll(hook) : 0, &cap, &ranges, &store_cap, errbuf, errlen));
     parted = ranges != 0;
     DCHK(hipStreamCreate(&x.stream));
     DCHK(hipEventCreate(&x.ev0));
     DCHK(hipEventCreate(&x.ev1));
     RCHK(batch.init(cap, nfiles));
     if (parted) RCHK(store.init(store_cap));
+    if (dumps) RCHK(dump.init(dump_paths, nfiles));
     if (io.dev_out) table.reset(new DeviceTable(x)); else table.reset(new HostTable(x));
     return 0;
   }
 
-  int add(const uint8_t *p, int64_t n, int file) { return batch.add(p, n, file, [&] { return flush(); }); }
+  // The plan of a run over dumps, before the first allocation.  bound: the text bytes of the files at most, so lines =
+  // bound / (k + 3) + one per file bounds the lines, the records and every merge.  The batch is what smg_count_memory_plan
+  // gives a single pass over that many bytes (the hook: text bytes), at least one longest line; then the one merge that may
+  // hold every line must fit next to it, or the call is refused here.
+  int dump_plan(size_t free_b, int64_t bound, int nfiles, int64_t hook, int64_t *cap)
+  { int32_t ranges = 0;
+    int64_t store_cap = 0;
+    RCHK(memory_plan(x.k, free_b, bound, 1, 0, hook, cap, &ranges, &store_cap, x.errbuf, x.errlen));
+    if (*cap < SMG_COUNT_DUMP_LINE) *cap = SMG_COUNT_DUMP_LINE;
+    const int64_t lines = bound / (x.k + 3) + nfiles;
+    if (lines >= 0xFFFFFFF0ll)
+      return fail(x.errbuf, x.errlen, SMG_ENOMEM, "dumps of %lld text bytes may hold %lld lines of %d bases, one merge holds 2^32 - 16 entries: "
+                  "k-mer dumps are counted in one pass", (long long) bound, (long long) lines, x.k);
+    const size_t want = (size_t) (*cap * batch_price(x.W)) + dump_price(*cap, x.k) + (size_t) lines * merge_price(x.W) + CP_RESERVE;
+    if (want > free_b)
+      return fail(x.errbuf, x.errlen, SMG_ENOMEM, "dumps of %lld text bytes may hold %lld lines of %d bases: a batch of %lld bytes and one merge "
+                  "of that many entries need %.3f GB, %.3f GB of device memory are free, and k-mer dumps are counted in one pass",
+                  (long long) bound, (long long) lines, x.k, (long long) *cap, (double) want * 1e-9, (double) free_b * 1e-9);
+    return 0;
+  }
+
+  int add(const uint8_t *p, int64_t n, int file)
+  { if (dumps) return dump.add(p, n, file, [&] { return flush(); });
+    return batch.add(p, n, file, [&] { return flush(); });
+  }
 
   // the batch buffer -> (k-mer, count) runs -> merged into the distinct list (a partitioned run packs it instead)
   int flush()
   { if (parted) return store.pack(batch);
     const int64_t n = batch.take();
+    if (dumps)
+      { int64_t nl = 0;
+        if (n == 0) return 0;
+        x.st.batches++;
+        RCHK(dump.extract(n, &nl));
+        return nl ? dump.count(list, nl) : 0;
+      }
     if (n < x.k) return 0;
     x.st.batches++;
     int64_t nwin = 0;
@@ -259,6 +308,7 @@ struct Counter
   // the last batch, then histogram, clamp, trim; the table goes to the caller
   int finish(const Out &io)
   { RCHK(flush());
+    if (dumps) x.st.bases = x.st.windows * x.k;
     batch.seq.reset();
     RCHK(x.alloc(dh, sizeof(uint64_t) * SMG_COUNT_HIST));
     DCHK(hipMemsetAsync(dh.p, 0, sizeof(uint64_t) * SMG_COUNT_HIST, x.stream));
@@ -294,14 +344,15 @@ static int check_opts(const smg_count_opts *o, char *errbuf, size_t errlen)
 // device is touched and bounds the sequence bytes of the input; feed(counter, &t_read): adds all of it, sets st.bases and
 // the time (now_ms) at which the last of it was read.
 template <class Survey, class Feed>
-static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, int nfiles, Survey &&survey, Feed &&feed, char *errbuf, size_t errlen)
+static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, int nfiles, Survey &&survey, Feed &&feed, char *errbuf, size_t errlen,
+                     const char *const *dump_paths = nullptr)
 { const double t0 = now_ms();
   RCHK(check_opts(opts, errbuf, errlen));
   if (!input_ok || !io.keys || !io.counts || !io.nels || !io.key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
   int64_t bound = 0;
   RCHK(survey(&bound));
   Counter c;
-  RCHK(c.init(opts, io, bound, nfiles, errbuf, errlen));
+  RCHK(c.init(opts, io, bound, nfiles, errbuf, errlen, dump_paths));
   double t_read = t0;
   RCHK(feed(c, &t_read));
   c.x.st.ms_read = t_read - t0;
@@ -371,10 +422,49 @@ static int gzip_report(const char *path, int64_t *members, int64_t *text_bytes, 
 // (the inflaters of the reader threads that meet a BGZF file are set up by the survey, before Counter::init reads the
 //  free device memory, so that the plan sees what is left; the indexes of the plain gzip files of a call that opted in are
 //  built there too, once every file of the call has been looked at: they give the text bytes the bound needs)
-static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
+struct Inputs
 { std::vector<std::unique_ptr<DeviceInflater>> own;
   std::vector<Inflater *> infl;
   int nthr = 1;
+
+  // what survey_files refuses and bounds; then the reader threads, an inflater for each that meets a compressed file, and the
+  // indexes of the plain gzip files.  A call over dumps: a plain file that does not begin with a base is refused here too,
+  // before the device is touched (the text of a compressed one is first seen by its reader thread, which says the same).
+  int survey(const char *const *paths, int npaths, const smg_count_opts *opts, int64_t *bound, char *errbuf, size_t errlen)
+  { std::vector<char> bgzf;
+    RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf, opts->gzip != 0));
+    for (int f = 0; f < npaths && opts->dump; f++)
+      if (bgzf[(size_t) f] == FILE_PLAIN)
+        { const Fd fd(paths[f]);
+          uint8_t first = 0;
+          struct NoSink { bool put(const uint8_t *, size_t) { return true; } size_t room() const { return (size_t) -1; } bool cut() { return true; } } none;
+          if (fd.fd >= 0 && pread(fd.fd, &first, 1, 0) == 1) RCHK(DumpCutter<NoSink>(none).feed(&first, 1, paths[f], errbuf, errlen));
+        }
+    nthr = reader_threads(opts->host_threads, npaths);
+    own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
+    for (int f = 0; f < npaths; f++)
+      if (bgzf[(size_t) f] && !own[(size_t) (f % nthr)])
+        { RCHK(new_inflater(opts->device, own[(size_t) (f % nthr)], errbuf, errlen));
+          infl[(size_t) (f % nthr)] = own[(size_t) (f % nthr)].get();
+        }
+    for (int f = 0; f < npaths; f++)
+      if (bgzf[(size_t) f] == FILE_GZIP)
+        { const Fd fd(paths[f]);
+          int64_t text = 0;
+          if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
+          RCHK(own[(size_t) (f % nthr)]->gzip_survey(fd.fd, paths[f], 0, &text, errbuf, errlen));
+          *bound += text;
+        }
+    return 0;
+  }
+};
+
+static int count_files(const char *const *paths, int npaths, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
+{ Inputs in;
+  std::vector<std::unique_ptr<DeviceInflater>> &own = in.own;
+  std::vector<Inflater *> &infl = in.infl;
+  int &nthr = in.nthr;
+  const bool dumps = opts && opts->dump != 0;
   publish_bam(paths, std::vector<FileRead>(), 1);              // (whatever becomes of this call, the report of an earlier one is gone)
   publish_gzip(nullptr, nullptr);
   const auto report_gzip = [&]
@@ -382,26 +472,7 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         if (d) for (const auto &g : d->gz_index) publish_gzip(g.first.c_str(), &g.second, true);
     };
   const int rc = count_run(opts, io, paths && npaths >= 1, npaths,
-    [&](int64_t *bound)
-      { std::vector<char> bgzf;
-        RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf, opts->gzip != 0));
-        nthr = reader_threads(opts->host_threads, npaths);
-        own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
-        for (int f = 0; f < npaths; f++)
-          if (bgzf[(size_t) f] && !own[(size_t) (f % nthr)])
-            { RCHK(new_inflater(opts->device, own[(size_t) (f % nthr)], errbuf, errlen));
-              infl[(size_t) (f % nthr)] = own[(size_t) (f % nthr)].get();
-            }
-        for (int f = 0; f < npaths; f++)
-          if (bgzf[(size_t) f] == FILE_GZIP)
-            { const Fd fd(paths[f]);
-              int64_t text = 0;
-              if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
-              RCHK(own[(size_t) (f % nthr)]->gzip_survey(fd.fd, paths[f], 0, &text, errbuf, errlen));
-              *bound += text;
-            }
-        return 0;
-      },
+    [&](int64_t *bound) { return in.survey(paths, npaths, opts, bound, errbuf, errlen); },
     [&](Counter &c, double *t_read)
       { std::vector<Pinned<uint8_t>> pinned((size_t) (2 * nthr + 2));
         std::vector<uint8_t *> blocks;
@@ -412,16 +483,17 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         std::vector<FileRead> files;
         const int rc = read_files(paths, npaths, nthr, blocks.data(), (int) blocks.size(), RING_BLOCK,
                                   [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, &files,
-                                  errbuf, errlen, infl.data());
+                                  errbuf, errlen, infl.data(), dumps);
         publish_bam(paths, files, nthr);                       // (after an error too: the files read to their end before it)
         return rc;
-      }, errbuf, errlen);
+      }, errbuf, errlen, dumps ? paths : nullptr);
   report_gzip();
   return rc;
 }
 
 static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
-{ return count_run(opts, io, n >= 0 && (n == 0 || seq), 1,
+{ if (opts && opts->dump) return fail(errbuf, errlen, SMG_EINVAL, "the dump option reads files: a buffer of sequence bytes is no k-mer dump%s", "");
+  return count_run(opts, io, n >= 0 && (n == 0 || seq), 1,
     [&](int64_t *bound) { *bound = n; return 0; },
     [&](Counter &c, double *t_read)
       { const int64_t piece = (int64_t) 256 << 20;
@@ -499,6 +571,101 @@ static int gzip_text_host(const char *path, int64_t span_bytes, uint8_t **text, 
   sink.put(bytes.data(), bytes.size());
   publish_gzip(path, &ix);
   return sink.hand_over(text, n, errbuf, errlen);
+}
+
+// the records of a dump go to the caller as malloc'ed arrays (one element where there is none)
+static int dump_hand_over(const std::vector<uint64_t> &k, const std::vector<uint32_t> &c, int W, uint64_t **keys, uint32_t **counts, int64_t *n,
+                          int *key_words, char *errbuf, size_t errlen)
+{ uint64_t *ok = (uint64_t *) malloc(sizeof(uint64_t) * (k.empty() ? 1 : k.size()));
+  uint32_t *oc = (uint32_t *) malloc(sizeof(uint32_t) * (c.empty() ? 1 : c.size()));
+  if (!ok || !oc) { free(ok); free(oc); return fail(errbuf, errlen, SMG_ENOMEM, "out of host memory%s", ""); }
+  if (!k.empty()) memcpy(ok, k.data(), sizeof(uint64_t) * k.size());
+  if (!c.empty()) memcpy(oc, c.data(), sizeof(uint32_t) * c.size());
+  *keys = ok; *counts = oc; *n = (int64_t) c.size(); *key_words = W;
+  return 0;
+}
+
+static int dump_args(const char *path, int32_t kmer, const void *keys, const void *counts, const void *n, const void *key_words,
+                     char *errbuf, size_t errlen)
+{ if (!path || !keys || !counts || !n || !key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  smg_count_opts o;
+  memset(&o, 0, sizeof(o));
+  o.kmer = kmer; o.minval = 1;
+  return check_opts(&o, errbuf, errlen);
+}
+
+// the records of a plain dump by the host twin (DumpHost, smg_dump.hpp): cutter and line decoder, no device
+static int dump_parse(const char *path, int32_t kmer, uint64_t **keys, uint32_t **counts, int64_t *n, int *key_words, char *errbuf, size_t errlen)
+{ RCHK(dump_args(path, kmer, keys, counts, n, key_words, errbuf, errlen));
+  const Fd f(path);
+  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  const int kind = file_kind(f.fd, path, errbuf, errlen);
+  if (kind < 0) return kind;
+  if (kind != FILE_PLAIN)
+    return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, use one of the counting calls "
+                "or smg_count_dump_records", path);
+  DumpHost host(kmer);
+  DumpCutter<DumpHost> cut(host);
+  std::vector<uint8_t> buf((size_t) 4 << 20);
+  int rc = 0;
+  for (;;)
+    { const ssize_t got = read(f.fd, buf.data(), buf.size());
+      if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+      if (got == 0) { rc = cut.finish(); break; }
+      if ((rc = cut.feed(buf.data(), (size_t) got, path, errbuf, errlen)) != 0) break;
+    }
+  if (rc < 0) return rc;
+  if (host.bad) return dump_bad_line(errbuf, errlen, path, host.bad_off, host.bad, kmer);
+  return dump_hand_over(host.keys, host.counts, host.W, keys, counts, n, key_words, errbuf, errlen);
+}
+
+// the same records as kd_lines emits them, by the route of the counting calls: survey, reader thread, ring, feeder, batches
+static int dump_records(const char *path, int32_t kmer, int32_t device, int32_t gzip, uint64_t **keys, uint32_t **counts, int64_t *n,
+                        int *key_words, double *ms_kernel, char *errbuf, size_t errlen)
+{ RCHK(dump_args(path, kmer, keys, counts, n, key_words, errbuf, errlen));
+  publish_gzip(nullptr, nullptr);
+  smg_count_opts o;
+  memset(&o, 0, sizeof(o));
+  o.kmer = kmer; o.minval = 1; o.device = device; o.host_threads = 1; o.gzip = gzip; o.dump = 1;
+  Inputs in;
+  int64_t bound = 0;
+  RCHK(in.survey(&path, 1, &o, &bound, errbuf, errlen));
+  Counter c;                                                   // (its batch and feeder; nothing is sorted or merged)
+  const Out none{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false };
+  RCHK(c.init(&o, none, bound, 1, errbuf, errlen, &path));
+  Run &x = c.x;
+  std::vector<uint64_t> hk;
+  std::vector<uint32_t> hc;
+  const auto flush = [&]
+    { const int64_t len = c.batch.take();
+      int64_t nl = 0;
+      if (len == 0) return 0;
+      RCHK(c.dump.extract(len, &nl));
+      const size_t at = hc.size();
+      hk.resize((at + (size_t) nl) * (size_t) x.W); hc.resize(at + (size_t) nl);
+      if (nl)
+        { DCHK(hipMemcpy(hk.data() + at * (size_t) x.W, c.batch.ka.p, sizeof(uint64_t) * (size_t) nl * (size_t) x.W, hipMemcpyDeviceToHost));
+          DCHK(hipMemcpy(hc.data() + at, c.dump.ca.p, sizeof(uint32_t) * (size_t) nl, hipMemcpyDeviceToHost));
+        }
+      return 0;
+    };
+  std::vector<Pinned<uint8_t>> pinned(4);
+  std::vector<uint8_t *> blocks;
+  for (Pinned<uint8_t> &b : pinned)
+    { if (b.alloc(RING_BLOCK) != hipSuccess) return fail(errbuf, errlen, SMG_ENOMEM, "cannot pin %zu bytes of host memory", RING_BLOCK);
+      blocks.push_back(b);
+    }
+  std::vector<FileRead> files;
+  int64_t bases = 0;
+  double t_read = 0;
+  RCHK(read_files(&path, 1, 1, blocks.data(), (int) blocks.size(), RING_BLOCK,
+                  [&](const uint8_t *p, int64_t m, int file) { return c.dump.add(p, m, file, flush); }, &bases, &t_read, &files, errbuf, errlen,
+                  in.infl.data(), true));
+  RCHK(flush());
+  for (const std::unique_ptr<DeviceInflater> &d : in.own)
+    if (d) for (const auto &g : d->gz_index) publish_gzip(g.first.c_str(), &g.second, true);
+  if (ms_kernel) *ms_kernel = c.dump.ms_lines;
+  return dump_hand_over(hk, hc, x.W, keys, counts, n, key_words, errbuf, errlen);
 }
 
 // the stripped stream of inflated BAM text, every record by the host routine; pieces of `piece` bytes (0: one piece)
@@ -614,6 +781,14 @@ extern "C" int smg_count_gzip_text_host(const char *path, int64_t span_bytes, ui
 extern "C" int smg_count_gzip_report(const char *path, int64_t *members, int64_t *text_bytes, int64_t *spans, int64_t *linked, int64_t *repaired,
                                      double *ms)
 { try { return gzip_report(path, members, text_bytes, spans, linked, repaired, ms); } catch (...) { return SMG_ENOMEM; } }
+
+extern "C" int smg_count_dump_parse(const char *path, int32_t kmer, uint64_t **keys, uint32_t **counts, int64_t *n, int *key_words,
+                                    char *errbuf, size_t errlen)
+{ GUARD(dump_parse(path, kmer, keys, counts, n, key_words, errbuf, errlen)) }
+
+extern "C" int smg_count_dump_records(const char *path, int32_t kmer, int32_t device, int32_t gzip, uint64_t **keys, uint32_t **counts, int64_t *n,
+                                      int *key_words, double *ms_kernel, char *errbuf, size_t errlen)
+{ GUARD(dump_records(path, kmer, device, gzip, keys, counts, n, key_words, ms_kernel, errbuf, errlen)) }
 
 extern "C" void smg_count_free(void *p) { free(p); }
 

@@ -38,12 +38,17 @@
 #include "smg_count.h"
 #include "smg_count_err.hpp"
 #include "smg_bam.hpp"
+#include "smg_dump.hpp"
 
 static inline double now_ms()
 { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Sink
 { virtual bool put(const uint8_t *p, size_t n) = 0;          // false: the consumer gave up
+  // for the cutter of a dump (smg_dump.hpp), whose blocks end with a line: the bytes that still go into the block being
+  // filled, and "begin a new block" (false: the consumer gave up); a sink without blocks takes anything
+  virtual size_t room() const { return (size_t) -1; }
+  virtual bool cut() { return true; }
   virtual ~Sink() {}
 };
 
@@ -158,8 +163,9 @@ struct Inflater
 };
 
 // What reading one file to its end gave: the route it took, its records (of a BAM file: the contributing ones) and their
-// bases, the host time of the BAM framer, and what the inflater spent on it.
-enum { ROUTE_NONE = 0, ROUTE_TEXT = 1, ROUTE_BAM = 2 };         // not read to its end; FASTA / FASTQ; BAM
+// bases, the host time of the BAM framer, and what the inflater spent on it.  (Of a dump the host knows neither lines nor
+// bases: its lines are first looked at on the device.)
+enum { ROUTE_NONE = 0, ROUTE_TEXT = 1, ROUTE_BAM = 2, ROUTE_DUMP = 3 };      // not read to its end; FASTA / FASTQ; BAM; k-mer dump
 struct FileRead
 { int route = ROUTE_NONE;
   int64_t records = 0, bases = 0;
@@ -351,11 +357,41 @@ static inline int bam_piece(BamFramer &fr, const uint8_t *t, size_t n, const cha
   return fr.out_len ? infl.unpack(fr.desc.data(), fr.desc.size(), fr.out_len, sink, errbuf, errlen) : 0;
 }
 
+// One k-mer dump to the sink in chunks of whole lines (DumpCutter, smg_dump.hpp), its text routed by the header of the file
+// as that of reads is: plain, BGZF, or plain gzip where the inflater holds its index.
+static inline int parse_dump_file(int fd, int kind, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
+{ DumpCutter<Sink> cut(sink);
+  const InflaterTimes before = infl ? infl->times() : InflaterTimes();
+  int rc = 0;
+  if (kind == FILE_PLAIN)
+    { std::vector<uint8_t> buf((size_t) 4 << 20);
+      for (;;)
+        { const ssize_t got = read(fd, buf.data(), buf.size());
+          if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+          if (got == 0) break;
+          if ((rc = cut.feed(buf.data(), (size_t) got, path, errbuf, errlen)) != 0) return rc;
+        }
+    }
+  else if (kind == FILE_GZIP)
+    rc = infl->gzip_text(fd, path, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+  else if (!infl)
+    return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
+                "use one of the counting calls or smg_count_dump_records", path);
+  else rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+  if (rc == 0) rc = cut.finish();
+  if (rc) return rc;
+  fr->route = ROUTE_DUMP;
+  if (infl) fr->dev = infl->times() - before;
+  return 0;
+}
+
 // one file to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
-// the framer, anything else through the parser), anything else as it is.  *fr: what it gave, where it was read to its end
-static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
+// the framer, anything else through the parser), anything else as it is.  *fr: what it gave, where it was read to its end.
+// dump: the call reads k-mer dumps, whose text goes to the cutter instead
+static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen, bool dump = false)
 { const int kind = file_kind(fd, path, errbuf, errlen, infl && infl->has_gzip(path));
   if (kind < 0) return kind;
+  if (dump) return parse_dump_file(fd, kind, path, sink, infl, fr, errbuf, errlen);
   if (kind == FILE_PLAIN) return parse_fd(fd, path, sink, fr, errbuf, errlen);
   if (kind == FILE_GZIP)
     { Parser ps(sink);
@@ -508,13 +544,15 @@ struct RingSink : Sink
       }
     return true;
   }
+  size_t room() const override { return r.block - len; }
+  bool cut() override { return !(cur && len) || push(); }
   void done()
   { if (cur && len) push();
     else if (cur) { std::unique_lock<std::mutex> lk(r.m); r.idle.push_back(cur); cur = nullptr; r.cv_free.notify_one(); }
   }
 };
 
-static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step, Inflater *infl)
+static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step, Inflater *infl, bool dump)
 { for (int f = first; f < npaths; f += step)
     { char eb[512]; eb[0] = 0;
       int rc = 0;
@@ -523,7 +561,7 @@ static inline void reader_main(Ring *r, const char *const *paths, int npaths, in
         { RingSink sink(*r, f);
           const Fd fd(paths[f]);
           rc = fd.fd < 0 ? fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f])
-                         : parse_file(fd.fd, paths[f], sink, infl, &read, eb, sizeof(eb));
+                         : parse_file(fd.fd, paths[f], sink, infl, &read, eb, sizeof(eb), dump);
           if (rc == 0) sink.done();
         }
       catch (...) { rc = fail(eb, sizeof(eb), SMG_ENOMEM, "out of host memory while reading %s", paths[f]); }
@@ -553,10 +591,11 @@ static inline int reader_threads(int want, int npaths)
 // message is its own business.  *bases = sequence bytes read, *t_last = now_ms() when the last reader was done.
 // *files = per file what reading it gave (route ROUTE_NONE: it was not read to its end), after an error as well.
 // infl (may be null: BGZF files are refused): the inflater of thread j, or null where none of its files is BGZF.
+// dump: the files are k-mer dumps; every block then holds whole lines of one file.
 template <class Consume>
 static inline int read_files(const char *const *paths, int npaths, int nthr, uint8_t *const *blocks, int nblocks, size_t block, Consume &&consume,
                              int64_t *bases, double *t_last, std::vector<FileRead> *files, char *errbuf, size_t errlen,
-                             Inflater *const *infl = nullptr)
+                             Inflater *const *infl = nullptr, bool dump = false)
 { Ring ring;
   ring.block = block;
   ring.files.assign((size_t) npaths, FileRead());
@@ -567,7 +606,7 @@ static inline int read_files(const char *const *paths, int npaths, int nthr, uin
   for (int j = 0; j < nthr && rc == 0; j++)
     { try
         { { std::unique_lock<std::mutex> lk(ring.m); ring.live++; }
-          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr, infl ? infl[j] : nullptr);
+          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr, infl ? infl[j] : nullptr, dump);
         }
       catch (...)
         { std::unique_lock<std::mutex> lk(ring.m);
