@@ -21,7 +21,19 @@
  *     "=ACMGRSVTWYHKDBN", one SMG_COUNT_SEPARATOR between two such records -- the stream of a FASTA file of the same reads.
  *     The size of a BAM file bounds its bases as that of any BGZF file does, by the sum of its ISIZE fields: an over-estimate
  *     by 1.5 or more, so a large BAM may be counted by key range where one pass would have done; the result is the same
- *     whichever way it is counted.  CRAM is not gzip and is refused like any file that is neither FASTA nor FASTQ;
+ *     whichever way it is counted.  CRAM is not gzip and, given as a file, is refused like any file that is neither FASTA nor
+ *     FASTQ: it is read through a pipe (samtools fastq x.cram | smg_count ... -, or samtools view -u for BAM), see next;
+ *   - input: streams.  A path that fstat does not call a regular file -- a FIFO, a socket, /dev/stdin, the /dev/fd/N of a shell's
+ *     process substitution -- and the path "-" (standard input, at most once per call: a second one is SMG_EINVAL) is read
+ *     once and forward only: opened once, told by its first bytes as a file is (plain FASTA / FASTQ, BGZF, BAM inside BGZF, with
+ *     the dump option a dump), inflated and unpacked by the same kernels.  That is how CRAM, zstd, bzip2, xz and fasterq-dump
+ *     reach the counter without a codec each.  Plain gzip on a stream is refused with or without smg_count_opts.gzip (its
+ *     restart index reads the file twice: give the file, or decompress in the pipe).  A stream has no size, so a call with one
+ *     has no bound: smg_count_stream_plan plans it, the packed store grows as the stream goes on, and the result is that of
+ *     the same bytes read from a file.  A BGZF stream that ends inside a header or a member is SMG_EFORMAT, "<path>: BGZF
+ *     block at offset <o>: the member (the header) is cut off by the end of the stream", o counted from its first byte.  The
+ *     calls that read a file twice or seek in it (smg_count_bgzf_scan, smg_count_bgzf_inflate, smg_count_bam_strip,
+ *     smg_count_gzip_inflate, smg_count_gzip_text_host) refuse a stream: SMG_EINVAL, "<path> is a stream: this call reads a file";
  *   - input: k-mers that another tool has counted already, only where smg_count_opts.dump is set (smg_count -d): the text
  *     that kmc_dump, `jellyfish dump -c` and `meryl print` write, one line per k-mer.  The refusal of a file that begins ACGT
  *     is a tested contract like that of plain gzip, hence the option; with it EVERY file of the call is a dump, its text routed
@@ -49,8 +61,8 @@
  * The result does not depend on the number of host threads, the batch size, the order of the files or the number of
  * key ranges the run is partitioned into, nor on where their ends lie.
  * Error codes are those of smg_hetmers.h.  No CPU fallback: without a HIP device the counting calls
- * return SMG_ENODEV; smg_count_parse and smg_count_dump_parse (plain files only), smg_count_bgzf_scan, smg_count_bam_text, smg_count_gzip_text_host and
- * smg_count_version need no device.
+ * return SMG_ENODEV; smg_count_parse and smg_count_dump_parse (plain files and plain streams only), smg_count_bgzf_scan, smg_count_bam_text,
+ * smg_count_gzip_text_host, the plans and smg_count_version need no device.
  */
 #ifndef SMG_COUNT_H
 #define SMG_COUNT_H
@@ -198,8 +210,22 @@ int smg_count_plan_fine(const uint64_t *windows, const int32_t *split, int32_t n
 int smg_count_memory_plan(int32_t kmer, uint64_t free_bytes, int64_t bound, int32_t partitions, int64_t max_entries,
                           int64_t batch_bases, int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf, size_t errlen);
 
-/* host only: the stripped byte stream of one plain file, the sequence of every record with line ends removed
-   and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).  A BGZF file is
+/* host only: the plan of a call that reads at least one stream, which has no bound -- again the function the counting
+   calls use themselves.  known_bound: the most sequence bytes the REGULAR files of the call can hold; store_bases: the value
+   of the test hook SMG_COUNT_STREAM_STORE (positions the store begins with), 0 for none; the rest as above.
+   partitions == 1: one pass, *parted = 0, *store_cap = 0, and *cap is the batch of smg_count_memory_plan without its clamp
+   to the input; a distinct list that does not fit is refused by the merge that meets it (SMG_ENOMEM, its figures in the
+   message), not in advance.  Any other value, 0 included: *parted = 1, the batches are packed and counted by key range.
+   *store_cap = the positions the store BEGINS with, a multiple of 4096: store_bases rounded up, or without the hook 2^30
+   (384 MiB), or what smg_count_memory_plan gives a store for known_bound where that is more.  The store then grows by half
+   with a copy on the device; a growth that does not fit is SMG_ENOMEM, the message naming the positions packed so far, what
+   the next size needs and what is free.  With no stream in the call smg_count_memory_plan decides, as it always did.       */
+int smg_count_stream_plan(int32_t kmer, uint64_t free_bytes, int64_t known_bound, int32_t partitions, int64_t max_entries,
+                          int64_t batch_bases, int64_t store_bases, int64_t *cap, int32_t *parted, int64_t *store_cap,
+                          char *errbuf, size_t errlen);
+
+/* host only: the stripped byte stream of one plain file or stream, the sequence of every record with line ends removed
+   and one SMG_COUNT_SEPARATOR between two records.  *seq is malloc'ed (smg_count_free).  BGZF is
    SMG_EINVAL here (no device: see smg_count_bgzf_inflate).                                         */
 int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen);
 

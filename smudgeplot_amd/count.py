@@ -19,6 +19,12 @@ its count to the smaller of its k-mer and its reverse complement, and the sums s
 that decoder, `dump_records` its records as the kernel emits them.
 `smg_count_opts` grew by one trailing field for it: `Opts` is the struct up to `gzip`, as it was, and `DumpOpts(Opts)` the whole
 struct, which is what this module hands to the library.
+
+An input may be a stream: the path "-" is standard input (at most once per call), and a path that is not a regular file (a
+FIFO, /dev/stdin, /dev/fd/N) is opened once and read forward only, told by its first bytes as a file is.  `count_files`,
+`reads_to_plot`, `parse` and `dump_parse` take such paths; plain gzip on a stream is refused with or without gzip=True, and the
+calls that read a file twice (`bgzf_scan`, `bgzf_inflate`, `bam_strip`, `gzip_inflate`, `gzip_text_host`) refuse a stream.  A
+call with a stream has no bound: `stream_plan` is its plan, and the result is that of the same bytes read from a file.
 """
 
 from __future__ import annotations
@@ -46,7 +52,7 @@ EXPORTS = ["smg_count_files", "smg_count_bases", "smg_count_files_parts", "smg_c
            "smg_count_files_device", "smg_count_bases_device", "smg_count_device_free", "smg_count_memory_plan",
            "smg_count_bgzf_scan", "smg_count_bgzf_inflate", "smg_count_bam_text", "smg_count_bam_strip", "smg_count_bam_report",
            "smg_count_gzip_inflate", "smg_count_gzip_text_host", "smg_count_gzip_report",
-           "smg_count_dump_parse", "smg_count_dump_records"]
+           "smg_count_dump_parse", "smg_count_dump_records", "smg_count_stream_plan"]
 
 
 class CountError(RuntimeError):
@@ -117,6 +123,9 @@ def load_library():
     lib.smg_count_memory_plan.argtypes = [C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_memory_plan.restype = C.c_int
+    lib.smg_count_stream_plan.argtypes = [C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
+    lib.smg_count_stream_plan.restype = C.c_int
     lib.smg_count_parse.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
     lib.smg_count_parse.restype = C.c_int
     lib.smg_count_bgzf_scan.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]
@@ -373,9 +382,27 @@ def memory_plan(k, free_bytes, bound, partitions=0, max_entries=0, batch_bases=0
     return {"cap": cap.value, "parted": bool(parted.value), "store_cap": store.value}
 
 
+def stream_plan(k, free_bytes, known_bound=0, partitions=0, max_entries=0, batch_bases=0, store_bases=0):
+    """Host only: the plan of a call that reads at least one stream and so has no bound (smg_count_stream_plan; no device, no
+    environment: the function such a call uses) -> dict as memory_plan's.  known_bound covers the regular files of the call.
+    partitions == 1 is one pass (`parted` False, `store_cap` 0) with a batch that is never clamped to the input; any other
+    value packs the batches into a store that BEGINS with `store_cap` positions -- store_bases (the test hook
+    SMG_COUNT_STREAM_STORE) rounded up to whole tiles of 4096, by default 2^30 or what memory_plan gives known_bound where that
+    is more -- and grows by half from there.  With no stream in the call it is memory_plan that decides, as it always did.
+    Raises CountError (-2) for bad arguments, (-3) where the first store or the batch does not fit."""
+    lib = load_library()
+    cap, parted, store = C.c_int64(0), C.c_int32(0), C.c_int64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib.smg_count_stream_plan(int(k), int(free_bytes), int(known_bound), int(partitions), int(max_entries), int(batch_bases),
+                                   int(store_bases), C.byref(cap), C.byref(parted), C.byref(store), err, len(err))
+    if rc != 0:
+        raise CountError(rc, err.value.decode(errors="replace"))
+    return {"cap": cap.value, "parted": bool(parted.value), "store_cap": store.value}
+
+
 def parse(path) -> bytes:
-    """Host only: the stripped byte stream of one plain FASTA / FASTQ file, one '\\n' between two records.  A BGZF file is
-    refused here (CountError -2): there is no device in this call, see bgzf_inflate."""
+    """Host only: the stripped byte stream of one plain FASTA / FASTQ file or stream ("-", a FIFO, /dev/stdin), one '\\n'
+    between two records.  BGZF is refused here (CountError -2): there is no device in this call, see bgzf_inflate."""
     lib = load_library()
     seq, n = C.c_void_p(), C.c_int64(0)
     err = C.create_string_buffer(1024)
@@ -482,7 +509,7 @@ def _dump_call(call, n_ms=0):
 
 
 def dump_parse(path, k):
-    """Host only, plain files only: the records of a k-mer dump by the line decoder the kernel compiles, run on the host ->
+    """Host only, plain files and plain streams only: the records of a k-mer dump by the line decoder the kernel compiles, run on the host ->
     (k-mers uint64[n, words], canonical, left aligned; counts uint32[n], saturated at 2^32 - 1), in line order.  A test twin,
     not a fallback.  Raises CountError -2 for a text that does not begin with a base, -4 "<path>: dump line at offset <o>:
     <reason>" for the first bad line."""

@@ -18,6 +18,11 @@
  *  to the smaller of its k-mer and its reverse complement.  An option for the reason -g is one: a file that begins ACGT is
  *  refused without it, and that is tested.  -t, -H, -o, -n and -e mean what they mean for reads; -p must be 0 or 1.
  *
+ *  An input may be a stream: the argument - is standard input, and an argument that is not a regular file (a FIFO, /dev/stdin,
+ *  the /dev/fd/N of a shell's <(...)) is opened once and read forward only, told by its first bytes as a file is.  That is the way
+ *  in for CRAM (samtools fastq x.cram | smg_count -oSample -), zstd, bzip2, xz and fasterq-dump --stdout.  Plain gzip on a stream
+ *  is refused with or without -g.  A stream has no root name: -o is needed where the first input is one.
+ *
  *  Usage: smg_count [-v] [-g] [-d] [-T<int(4)>] [-k<int(31)>] [-t<int(4)>] [-p<int(0)>] [-H] [-e<int>] [-n] [-o<output>] <reads> ...
  *           -k: k-mer length, 13 .. 128          -t: keep the k-mers with count >= t
  *           -H: also write <output>.hist.txt     -T: reader threads (one input file each, at most 16)
@@ -32,6 +37,9 @@
  *  A failed run leaves no table, histogram or .smu file behind.
  *
  ********************************************************************************************/
+
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include "smg_cli.h"
 #include "smg_count.h"
@@ -55,7 +63,9 @@ static void usage(void)
   fprintf(stderr, "      -v: verbose mode\n");
   fprintf(stderr, "      -T: number of reader threads (one input file each)\n");
   fprintf(stderr, "\n");
-  fprintf(stderr, "      <reads>: FASTA or FASTQ, plain or block-gzipped (BGZF), or unaligned BAM (the bases of its primary records)\n");
+  fprintf(stderr, "      <reads>: FASTA or FASTQ, plain or block-gzipped (BGZF), or unaligned BAM (the bases of its primary records);\n");
+  fprintf(stderr, "            - is standard input, and a FIFO, /dev/stdin or <(...) is read as the stream it is, once and forward only:\n");
+  fprintf(stderr, "            samtools fastq x.cram | %s -oSample -   (-o is needed where the first input is a stream; no plain gzip)\n", Prog_Name);
   exit(1);
 }
 
@@ -73,6 +83,12 @@ static char *default_root(const char *name)
       if (epos > 0 && strncasecmp(name + epos, suffix[i], strlen(suffix[i])) == 0) return strndup(name, (size_t) epos);
     }
   return strndup(name, (size_t) len);
+}
+
+/* standard input, or whatever stat does not call a regular file: a FIFO, /dev/stdin, the /dev/fd/N of a process substitution */
+static int is_stream_arg(const char *name)
+{ struct stat sb;
+  return strcmp(name, "-") == 0 || (stat(name, &sb) == 0 && !S_ISREG(sb.st_mode));
 }
 
 /* remove what a run that fails half way has written */
@@ -143,11 +159,20 @@ int main(int argc, char *argv[])
               ethresh, minval, minval);
       exit(1);
     }
+  /* a regular file is opened and closed once, as always; a stream is not (that would end the writer of a FIFO): stat and access */
   for (i = 1; i < j; i++)
-    { FILE *f = fopen(argv[i], "rb");
-      if (f == NULL) { fprintf(stderr, "%s: Cannot open %s for reading\n", Prog_Name, argv[i]); exit(1); }
-      fclose(f);
-    }
+    if (strcmp(argv[i], "-") != 0)
+      { struct stat sb;
+        if (stat(argv[i], &sb) != 0) { fprintf(stderr, "%s: Cannot open %s for reading\n", Prog_Name, argv[i]); exit(1); }
+        if (S_ISREG(sb.st_mode))
+          { FILE *f = fopen(argv[i], "rb");
+            if (f == NULL) { fprintf(stderr, "%s: Cannot open %s for reading\n", Prog_Name, argv[i]); exit(1); }
+            fclose(f);
+          }
+        else if (access(argv[i], R_OK) != 0) { fprintf(stderr, "%s: Cannot open %s for reading\n", Prog_Name, argv[i]); exit(1); }
+      }
+  if (out == NULL && is_stream_arg(argv[1]))
+    { fprintf(stderr, "%s: -o is needed where the first input is a stream (%s)\n", Prog_Name, argv[1]); exit(1); }
   root = out != NULL ? path_n_root(out, ".ktab") : default_root(argv[1]);
   hist = (uint64_t *) calloc(SMG_COUNT_HIST, sizeof(uint64_t));
   if (root == NULL || hist == NULL) { fprintf(stderr, "%s: Out of memory\n", Prog_Name); exit(1); }

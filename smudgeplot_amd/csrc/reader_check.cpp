@@ -8,6 +8,12 @@
 // through bgzf_feed, the routing of parse_file and bam_piece with a HostInflater in the place of the device's, whose
 // inflate is the host twin of the kernel (inflate_member_host) and whose unpack is the host routine (bam_unpack_host), its
 // buffers malloc'ed at their exact sizes.
+//
+// And for streams: the same inputs (plain FASTA and FASTQ, BGZF, BAM, k-mer dumps) through a pipe(2) that a writer thread
+// fills in pieces of 1, 7, 4096 and 65 537 bytes, handed over by the survey or opened by the reader thread, each against the
+// same bytes read from a file; and streams that end inside a member, a header, a BAM record, and after no byte at all.
+
+#include <signal.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -212,7 +218,10 @@ struct Got { int rc; std::string err; std::vector<Bytes> per_file; int64_t bases
 
 // fail_at > 0: the consumer returns `code` for its fail_at-th block (and must not be called again); inflaters: every reader
 // thread has a HostInflater (without one a BGZF file is refused)
-static Got run(const std::vector<std::string> &paths, int threads, int nblocks, size_t block, int fail_at = 0, int code = 0, bool inflaters = false)
+// inputs: every reader thread has a HostInflater (without one a BGZF file is refused); dump: the files are k-mer dumps; taken:
+// what a survey opened of the paths (survey_files), or null
+static Got run(const std::vector<std::string> &paths, int threads, int nblocks, size_t block, int fail_at = 0, int code = 0, bool inflaters = false,
+               bool dump = false, const std::unique_ptr<Taken> *taken = nullptr)
 { std::vector<const char *> cp;
   for (const std::string &p : paths) cp.push_back(p.c_str());
   Blocks blocks(nblocks, block);
@@ -231,7 +240,7 @@ static Got run(const std::vector<std::string> &paths, int threads, int nblocks, 
                         if (n < 1 || (size_t) n > block) { printf("FAILED  a block of %lld bytes\n", (long long) n); bad++; }
                         g.per_file[(size_t) file].insert(g.per_file[(size_t) file].end(), p, p + n);
                         return g.blocks == fail_at ? code : 0;
-                      }, &g.bases, &t_last, &g.files, eb, sizeof(eb), inflaters ? infl.data() : nullptr);
+                      }, &g.bases, &t_last, &g.files, eb, sizeof(eb), inflaters ? infl.data() : nullptr, dump, taken);
   g.err = eb;
   for (const HostInflater &h : own) { g.calls += h.calls; g.unpacks += h.unpacks; }
   expect(g.files.size() == paths.size(), "one record per file", std::to_string(g.files.size()));
@@ -239,8 +248,74 @@ static Got run(const std::vector<std::string> &paths, int threads, int nblocks, 
   return g;
 }
 
+// A stream made here: a pipe(2) whose write end a thread fills with a copy of the bytes in pieces of `piece` bytes; the
+// reader is given the read end under its name /dev/fd/N.  done(): the read end is closed (a writer whose reader gave up
+// then sees EPIPE, SIGPIPE being ignored) and the thread joined -> it wrote everything.
+struct Piped
+{ int fd[2] = { -1, -1 };
+  std::string path;
+  std::thread writer;
+  bool all = false;
+  const std::string data;
+  Piped(const std::string &bytes, size_t piece) : data(bytes)
+  { if (pipe(fd) != 0) { printf("FAILED  no pipe\n"); exit(1); }
+    path = "/dev/fd/" + std::to_string(fd[0]);
+    const int w = fd[1];
+    writer = std::thread([this, w, piece]
+      { size_t at = 0;
+        while (at < data.size())
+          { const ssize_t r = write(w, data.data() + at, std::min(piece, data.size() - at));
+            if (r <= 0) break;
+            at += (size_t) r;
+          }
+        all = at == data.size();
+        close(w);
+      });
+  }
+  Piped(const Piped &) = delete;
+  bool done() { close(fd[0]); writer.join(); return all; }
+};
+
+// the file's message with the stream's path in the place of the file's
+static std::string renamed(const std::string &msg, const std::string &from, const std::string &to)
+{ const size_t at = msg.find(from);
+  return at == std::string::npos ? msg : msg.substr(0, at) + to + msg.substr(at + from.size());
+}
+
+// `bytes` as a stream in pieces of `piece`, read by one thread as the counter reads it -- surveyed (the survey opens it, takes
+// the bytes that tell what it is and hands it on) or opened by the reader thread itself -- against what the same bytes gave
+// as a file (`want`, read from `file`): the same stripped stream and record, or the same error under the stream's path
+static void stream_case(const std::string &what, const std::string &bytes, size_t piece, const Got &want, const std::string &file, bool inflaters,
+                        bool dump, bool surveyed)
+{ Piped p(bytes, piece);
+  const std::string name = what + " in pieces of " + std::to_string(piece) + (surveyed ? ", surveyed" : ", opened by its reader");
+  std::vector<std::unique_ptr<Taken>> taken;
+  if (surveyed)
+    { const char *cp = p.path.c_str(), *fp = file.c_str();
+      std::vector<char> kind, file_kinds;
+      int64_t bound = 0, file_bound = 0;
+      char eb[512]; eb[0] = 0;
+      const int rc = survey_files(&cp, 1, 21, &bound, eb, sizeof(eb), &kind, false, &taken);
+      expect(rc == 0 && taken.size() == 1 && taken[0] && taken[0]->src.stream && bound == 22, "the survey opens a stream and keeps it", name + ": " + eb);
+      if (want.rc == 0)
+        expect(survey_files(&fp, 1, 21, &file_bound, eb, sizeof(eb), &file_kinds) == 0 && kind == file_kinds, "a stream is told as its file is", name);
+    }
+  const Got g = run({ p.path }, 1, 4, (size_t) 1 << 20, 0, 0, inflaters, dump, surveyed ? taken.data() : nullptr);
+  taken.clear();
+  const bool all = p.done();
+  expect(g.rc == want.rc && g.err == renamed(want.err, file, p.path), "a stream ends as its file does", name + ": " + g.err + " / " + want.err);
+  if (want.rc == 0)
+    { expect(all, "the writer of a stream wrote everything", name);
+      expect(g.per_file[0] == want.per_file[0], "the blocks of a stream are the stripped stream of its file", name);
+      const FileRead &a = g.files[0], &b = want.files[0];
+      expect(a.route == b.route && a.records == b.records && a.bases == b.bases && g.bases == want.bases, "the record of a stream is that of its file", name);
+    }
+  else expect(g.files[0].route == ROUTE_NONE, "a stream that was refused has no record", name);
+}
+
 int main()
 { std::mt19937_64 rng(20261020);
+  signal(SIGPIPE, SIG_IGN);
   char tmpl[] = "/tmp/reader_check_XXXXXX";
   const char *d = mkdtemp(tmpl);
   if (!d) { printf("FAILED  no temporary directory\n"); return 1; }
@@ -338,7 +413,8 @@ int main()
   const Bytes fq_want = parse_whole(fq_text);
   int64_t fq_records = 1;
   for (uint8_t c : fq_want) fq_records += c == SMG_COUNT_SEPARATOR;
-  const std::string fqz = write_file(dir, 20, bgzf_file(fq_text, 0, rng));
+  const std::string fqz_bytes = bgzf_file(fq_text, 0, rng);
+  const std::string fqz = write_file(dir, 20, fqz_bytes);
 
   // a BAM: a few primary records, a secondary and a supplementary one that are skipped, an empty one; members of 37 bytes
   const std::vector<BamRec> small = { { "r0", bam_letters(rng, 150), 4 }, { "r1", bam_letters(rng, 31), 0x100 }, { "r2", "", 4 },
@@ -347,7 +423,8 @@ int main()
   for (const BamRec &r : small) small_text += bam_record(r);
   int64_t small_records = 0, small_bases = 0;
   const Bytes small_want = bam_stripped(small, &small_records, &small_bases);
-  const std::string bam = write_file(dir, 21, bgzf_file(small_text, 37, rng));
+  const std::string bam_bytes = bgzf_file(small_text, 37, rng);
+  const std::string bam = write_file(dir, 21, bam_bytes);
   expect(small_records == 4 && small_bases == 150 + 4097 + 1, "the small BAM is what it was made to be", std::to_string(small_records));
 
   // a BAM whose members exceed one chunk of the reader: members of 60000 bytes (60031 in the file, which do not divide the
@@ -453,11 +530,124 @@ int main()
     expect(bgzf_scan(paths[0].c_str(), &nb, &nt, eb, sizeof(eb)) == SMG_EINVAL && eb == paths[0] + " is not BGZF: it does not begin with a gzip header", "the scan of a plain file", eb);
     expect(bgzf_scan(gz.c_str(), &nb, &nt, eb, sizeof(eb)) == SMG_EINVAL && eb == gz + " is gzip compressed: compressed input is not supported, decompress it first", "the scan of a gzip file", eb);
   }
+  // ---- streams: the same bytes through a pipe, written in pieces, against the file ----
+  int sruns = 0;
+  { std::string dump_text;
+    for (int i = 0; i < 3000; i++)
+      { std::string s(31, 'A');
+        for (char &c : s) c = "ACGTacgt"[rng() % 8];
+        dump_text += s + (i % 2 ? "\t" : " ") + std::to_string(1 + rng() % 100000) + (i % 3 ? "\n" : "\r\n");
+      }
+    dump_text.resize(dump_text.size() - 1);                    // (no line end at the end of the text)
+    const std::string dump_file = write_file(dir, 30, dump_text);
+    const std::string dumpz_bytes = bgzf_file(dump_text, 0, rng);
+    const std::string dumpz = write_file(dir, 31, dumpz_bytes);
+    struct Case { const char *what; const std::string *bytes; std::string file; bool inflaters, dump, large; };
+    const std::vector<Case> cases = { { "FASTA", &texts[0], paths[0], false, false, false },
+                                      { "FASTQ, CR-LF, no final newline", &texts[1], paths[1], false, false, false },
+                                      { "long FASTA, CR-LF, no final newline", &texts[2], paths[2], false, false, true },
+                                      { "FASTQ", &texts[3], paths[3], false, false, false },
+                                      { "records without bases", &texts[4], paths[4], false, false, false },
+                                      { "BGZF FASTQ", &fqz_bytes, fqz, true, false, false },
+                                      { "BAM", &bam_bytes, bam, true, false, false },
+                                      { "BAM of two chunks", &large_file, big, true, false, true },
+                                      { "dump", &dump_text, dump_file, false, true, false },
+                                      { "BGZF dump", &dumpz_bytes, dumpz, true, true, false } };
+    for (const Case &c : cases)
+      { const Got want = run({ c.file }, 1, 4, (size_t) 1 << 20, 0, 0, c.inflaters, c.dump);
+        expect(want.rc == 0, "the file of a stream case is read", std::string(c.what) + ": " + want.err);
+        for (size_t piece : { (size_t) 1, (size_t) 7, (size_t) 4096, (size_t) 65537 })
+          { if (c.large && piece < 4096) continue;            // (some ten million writes: the small inputs cover these pieces)
+            stream_case(c.what, *c.bytes, piece, want, c.file, c.inflaters, c.dump, true);
+            sruns++;
+            if (piece == 7 || piece == 65537) { stream_case(c.what, *c.bytes, piece, want, c.file, c.inflaters, c.dump, false); sruns++; }
+          }
+      }
+    expect(large_file.size() > (size_t) SMG_COUNT_BGZF_CHUNK + 65537, "a member of the large stream is carried to the front of the chunk", "");
+
+    // two streams and a file on two reader threads, the streams handed over by the survey
+    { Piped a(fqz_bytes, 4096), b(texts[1], 7);
+      const std::vector<std::string> some = { a.path, paths[0], b.path };
+      std::vector<const char *> cp;
+      for (const std::string &p : some) cp.push_back(p.c_str());
+      std::vector<std::unique_ptr<Taken>> taken;
+      std::vector<char> kind;
+      int64_t bound = 0;
+      char eb[512]; eb[0] = 0;
+      expect(survey_files(cp.data(), 3, 21, &bound, eb, sizeof(eb), &kind, false, &taken) == 0 && taken[0] && !taken[1] && taken[2] &&
+             kind == std::vector<char>({ 1, 0, 0 }) && bound == (int64_t) texts[0].size() + 3 * 22, "the survey of streams and a file: the bound is the file's", eb);
+      const Got g = run(some, 2, 6, (size_t) 1 << 20, 0, 0, true, false, taken.data());
+      taken.clear();
+      expect(a.done() && b.done(), "the writers of two streams wrote everything", "");
+      expect(g.rc == 0 && g.per_file[0] == fq_want && g.per_file[1] == want[0] && g.per_file[2] == want[1], "two streams and a file on two threads", g.err);
+      sruns++;
+    }
+
+    // a stream that ends inside a member, inside a header, inside a BAM record, after no byte at all; gzip on a stream
+    { const std::string even = bgzf_file(fq_text, 1000, rng);   // (members of 18 + 5 + 1000 + 8 bytes)
+      for (size_t into : { (size_t) 500, (size_t) 10 })
+        { const std::string cut = even.substr(0, 3 * 1031 + into);
+          for (bool surveyed : { true, false })
+            { Got want{ SMG_EFORMAT, std::string("F: BGZF block at offset 3093: ") + (into == 500 ? "the member is cut off by the end of the stream"
+                                                                                                    : "the header is cut off by the end of the stream"),
+                        {}, 0, 0, {}, 0, 0 };
+              stream_case("a BGZF stream cut in a member", cut, 7, want, "F", true, false, surveyed);
+              sruns++;
+            }
+        }
+      std::string cut_text = bam_header() + bam_record(small[0]);
+      cut_text += bam_record(small[3]).substr(0, 1000);
+      const std::string cut_bam = bgzf_file(cut_text, 37, rng), empty;
+      const std::string cut_file = write_file(dir, 32, cut_bam), empty_file = write_file(dir, 33, empty);
+      const Got cut_want = run({ cut_file }, 1, 4, 4096, 0, 0, true), empty_want = run({ empty_file }, 1, 4, 4096, 0, 0, true);
+      expect(cut_want.rc == SMG_EFORMAT && cut_want.err.find(": BAM record at text offset ") != std::string::npos, "a BAM file that ends in a record", cut_want.err);
+      expect(empty_want.rc == 0 && empty_want.per_file[0].empty(), "an empty file", empty_want.err);
+      const Got gz_want = run({ gz }, 1, 4, 4096);
+      for (bool surveyed : { true, false })
+        { stream_case("a BAM stream cut in a record", cut_bam, 4096, cut_want, cut_file, true, false, surveyed);
+          stream_case("a stream of no bytes", empty, 7, empty_want, empty_file, true, false, surveyed);
+          sruns += 2;
+        }
+      stream_case("a gzip stream", std::string("\x1f\x8b\x08\x00", 4) + "anything", 1, gz_want, gz, false, false, false);
+      sruns++;
+      for (bool gzip_ok : { false, true })
+        { Piped p(texts[0], 4096);                              // (never read: the survey refuses the stream in front of it)
+          Piped z(fqz_bytes.substr(0, 2) + "\x08\x00 anything", 1);
+          const char *cp[2] = { z.path.c_str(), p.path.c_str() };
+          std::vector<std::unique_ptr<Taken>> taken;
+          int64_t bound = 0;
+          char eb[512]; eb[0] = 0;
+          const int rc = survey_files(cp, 2, 21, &bound, eb, sizeof(eb), nullptr, gzip_ok, &taken);
+          expect(rc == SMG_EINVAL && eb == z.path + (gzip_ok ? " is a stream of plain gzip: its restart index reads the file twice; give the file itself, or decompress it in the pipe"
+                                                              : " is gzip compressed: compressed input is not supported, decompress it first"), "gzip on a stream is refused by the survey", eb);
+          taken.clear();
+          z.done(); p.done();
+          sruns++;
+        }
+      // standard input can be named once, and a survey that hands nothing on refuses a stream
+      { const char *twice[3] = { "-", paths[0].c_str(), "-" };
+        int64_t bound = 0;
+        char eb[512]; eb[0] = 0;
+        std::vector<std::unique_ptr<Taken>> taken;
+        expect(survey_files(twice, 3, 21, &bound, eb, sizeof(eb), nullptr, false, &taken) == SMG_EINVAL && std::string(eb) == "- (standard input) is named twice: it can be read once",
+               "standard input is named twice", eb);
+        Piped p(texts[0], 4096);
+        const char *cp = p.path.c_str();
+        expect(survey_files(&cp, 1, 21, &bound, eb, sizeof(eb)) == SMG_EINVAL && eb == p.path + " is a stream: this call reads a file", "a survey without a hand-over", eb);
+        expect(bgzf_scan(cp, &bound, &bound, eb, sizeof(eb)) == SMG_EINVAL && eb == p.path + " is a stream: this call reads a file", "the scan of a stream", eb);
+        p.done();
+      }
+      remove(cut_file.c_str()); remove(empty_file.c_str());
+    }
+    remove(dump_file.c_str()); remove(dumpz.c_str());
+  }
+
   remove(fqz.c_str()); remove(bam.c_str()); remove(big.c_str());
 
   for (const std::string &p : paths) remove(p.c_str());
   remove(gz.c_str());
   rmdir(dir.c_str());
-  printf("%s (%d runs, %d of them over BGZF and BAM files)\n", bad ? "reader_check: FAILED" : "reader_check: every run delivered the parser's stream or its error", runs + zruns, zruns);
+  printf("%s (%d runs, %d of them over BGZF and BAM files, %d over streams)\n",
+         bad ? "reader_check: FAILED" : "reader_check: every run delivered the parser's stream or its error", runs + zruns + sruns, zruns, sruns);
   return bad ? 1 : 0;
 }

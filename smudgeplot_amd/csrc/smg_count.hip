@@ -36,6 +36,10 @@
 //           pair sort, kc_flag_heads + scan, kd_run_sums + kd_run_clamp: one saturating sum per distinct k-mer of the batch
 //   merge, finish  as above.  One pass only: the packed store is a store of reads
 //
+// An input may be a stream (standard input as "-", a FIFO, /dev/fd/N): opened once by the survey, told by its first bytes as a
+// file is, and read forward only by the same reader thread, inflater and kernels.  A call with a stream has no bound on its
+// input: stream_plan (smg_count_plan.hpp) plans it in the place of memory_plan, and the packed store grows as the stream goes on.
+//
 // The output table is host arrays, or (the _device entries) two whole allocations in device memory, which the caller
 // hands to smg_engine_bind / smg_hetmers_run_device and frees; the kept entries of every range are appended to it.
 //
@@ -102,8 +106,11 @@ struct Counter
   bool parted = false;                                         // the batches are packed and counted by key range in finish()
   int req_parts = 0;
 
-  // argument checks, the device, the memory plan (smg_count_plan.hpp), then the allocations it asks for
-  int init(const smg_count_opts *o, const Out &io, int64_t bound, int nfiles, char *errbuf, size_t errlen, const char *const *dump_paths = nullptr)
+  // argument checks, the device, the memory plan (smg_count_plan.hpp), then the allocations it asks for.  streams: the
+  // call reads at least one stream, so bound covers its regular files only and the plan is stream_plan's: with no stream
+  // in the call memory_plan decides, as it always did
+  int init(const smg_count_opts *o, const Out &io, int64_t bound, int nfiles, char *errbuf, size_t errlen, const char *const *dump_paths = nullptr,
+           bool streams = false)
   { x.errbuf = errbuf; x.errlen = errlen;
     dumps = dump_paths != nullptr;
     if (dumps && io.parts && io.parts->partitions > 1)
@@ -124,9 +131,14 @@ struct Counter
     const char *hook = getenv("SMG_COUNT_BATCH_BASES");
     int64_t cap = 0, store_cap = 0;
     int32_t ranges = 0;
-    if (dumps) RCHK(dump_plan(free_b, bound, nfiles, hook ? atoll(hook) : 0, &cap));
+    const char *store_hook = getenv("SMG_COUNT_STREAM_STORE");
+    if (dumps) RCHK(dump_plan(free_b, bound, nfiles, hook ? atoll(hook) : 0, streams, &cap));
+    else if (streams)
+      RCHK(stream_plan(x.k, free_b, bound, req_parts, list.max_entries, hook ? atoll(hook) : 0, store_hook && atoll(store_hook) > 0 ? atoll(store_hook) : 0,
+                       &cap, &ranges, &store_cap, errbuf, errlen));
     else RCHK(memory_plan(x.k, free_b, bound, req_parts, list.max_entries, hook ? atoll(hook) : 0, &cap, &ranges, &store_cap, errbuf, errlen));
     parted = ranges != 0;
+    store.open_ended = streams;
     DCHK(hipStreamCreate(&x.stream));
     DCHK(hipEventCreate(&x.ev0));
     DCHK(hipEventCreate(&x.ev1));
@@ -140,12 +152,15 @@ struct Counter
   // The plan of a run over dumps, before the first allocation.  bound: the text bytes of the files at most, so lines =
   // bound / (k + 3) + one per file bounds the lines, the records and every merge.  The batch is what smg_count_memory_plan
   // gives a single pass over that many bytes (the hook: text bytes), at least one longest line; then the one merge that may
-  // hold every line must fit next to it, or the call is refused here.
-  int dump_plan(size_t free_b, int64_t bound, int nfiles, int64_t hook, int64_t *cap)
+  // hold every line must fit next to it, or the call is refused here.  With a stream in the call (streams) nothing bounds the
+  // lines: the batch is that of one pass of stream_plan, and what does not fit is refused by the merge that meets it.
+  int dump_plan(size_t free_b, int64_t bound, int nfiles, int64_t hook, bool streams, int64_t *cap)
   { int32_t ranges = 0;
     int64_t store_cap = 0;
-    RCHK(memory_plan(x.k, free_b, bound, 1, 0, hook, cap, &ranges, &store_cap, x.errbuf, x.errlen));
+    if (streams) RCHK(stream_plan(x.k, free_b, bound, 1, 0, hook, 0, cap, &ranges, &store_cap, x.errbuf, x.errlen));
+    else RCHK(memory_plan(x.k, free_b, bound, 1, 0, hook, cap, &ranges, &store_cap, x.errbuf, x.errlen));
     if (*cap < SMG_COUNT_DUMP_LINE) *cap = SMG_COUNT_DUMP_LINE;
+    if (streams) return 0;
     const int64_t lines = bound / (x.k + 3) + nfiles;
     if (lines >= 0xFFFFFFF0ll)
       return fail(x.errbuf, x.errlen, SMG_ENOMEM, "dumps of %lld text bytes may hold %lld lines of %d bases, one merge holds 2^32 - 16 entries: "
@@ -340,8 +355,9 @@ static int check_opts(const smg_count_opts *o, char *errbuf, size_t errlen)
   return 0;
 }
 
-// One run.  input_ok: the caller's check of its own arguments; survey(&bound): refuses what cannot be read before the
-// device is touched and bounds the sequence bytes of the input; feed(counter, &t_read): adds all of it, sets st.bases and
+// One run.  input_ok: the caller's check of its own arguments; survey(&bound, &streams): refuses what cannot be read before
+// the device is touched and bounds the sequence bytes of the input (*streams: of its regular files only, there are streams
+// among the inputs); feed(counter, &t_read): adds all of it, sets st.bases and
 // the time (now_ms) at which the last of it was read.
 template <class Survey, class Feed>
 static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, int nfiles, Survey &&survey, Feed &&feed, char *errbuf, size_t errlen,
@@ -350,9 +366,10 @@ static int count_run(const smg_count_opts *opts, const Out &io, bool input_ok, i
   RCHK(check_opts(opts, errbuf, errlen));
   if (!input_ok || !io.keys || !io.counts || !io.nels || !io.key_words) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
   int64_t bound = 0;
-  RCHK(survey(&bound));
+  bool streams = false;
+  RCHK(survey(&bound, &streams));
   Counter c;
-  RCHK(c.init(opts, io, bound, nfiles, errbuf, errlen, dump_paths));
+  RCHK(c.init(opts, io, bound, nfiles, errbuf, errlen, dump_paths, streams));
   double t_read = t0;
   RCHK(feed(c, &t_read));
   c.x.st.ms_read = t_read - t0;
@@ -426,19 +443,31 @@ struct Inputs
 { std::vector<std::unique_ptr<DeviceInflater>> own;
   std::vector<Inflater *> infl;
   int nthr = 1;
+  std::vector<std::unique_ptr<Taken>> taken;                   // per path: the stream the survey opened, for its reader thread
+  bool streams = false;                                        // there is one: the bound is that of the regular files only
 
   // what survey_files refuses and bounds; then the reader threads, an inflater for each that meets a compressed file, and the
   // indexes of the plain gzip files.  A call over dumps: a plain file that does not begin with a base is refused here too,
   // before the device is touched (the text of a compressed one is first seen by its reader thread, which says the same).
+  // A stream is opened here, once, and told by the bytes taken from it, which decide all this as those of a file do.
   int survey(const char *const *paths, int npaths, const smg_count_opts *opts, int64_t *bound, char *errbuf, size_t errlen)
   { std::vector<char> bgzf;
-    RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf, opts->gzip != 0));
+    RCHK(survey_files(paths, npaths, opts->kmer, bound, errbuf, errlen, &bgzf, opts->gzip != 0, &taken));
+    for (const std::unique_ptr<Taken> &t : taken) streams = streams || t;
     for (int f = 0; f < npaths && opts->dump; f++)
       if (bgzf[(size_t) f] == FILE_PLAIN)
-        { const Fd fd(paths[f]);
-          uint8_t first = 0;
+        { uint8_t first = 0;
+          bool any = false;
           struct NoSink { bool put(const uint8_t *, size_t) { return true; } size_t room() const { return (size_t) -1; } bool cut() { return true; } } none;
-          if (fd.fd >= 0 && pread(fd.fd, &first, 1, 0) == 1) RCHK(DumpCutter<NoSink>(none).feed(&first, 1, paths[f], errbuf, errlen));
+          if (taken[(size_t) f])
+            { any = taken[(size_t) f]->src.take(1) >= 1;
+              if (any) first = taken[(size_t) f]->src.taken()[0];
+            }
+          else
+            { const Fd fd(paths[f]);
+              any = fd.fd >= 0 && pread(fd.fd, &first, 1, 0) == 1;
+            }
+          if (any) RCHK(DumpCutter<NoSink>(none).feed(&first, 1, paths[f], errbuf, errlen));
         }
     nthr = reader_threads(opts->host_threads, npaths);
     own.resize((size_t) nthr); infl.assign((size_t) nthr, nullptr);
@@ -472,7 +501,11 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         if (d) for (const auto &g : d->gz_index) publish_gzip(g.first.c_str(), &g.second, true);
     };
   const int rc = count_run(opts, io, paths && npaths >= 1, npaths,
-    [&](int64_t *bound) { return in.survey(paths, npaths, opts, bound, errbuf, errlen); },
+    [&](int64_t *bound, bool *streams)
+      { const int rc = in.survey(paths, npaths, opts, bound, errbuf, errlen);
+        *streams = in.streams;
+        return rc;
+      },
     [&](Counter &c, double *t_read)
       { std::vector<Pinned<uint8_t>> pinned((size_t) (2 * nthr + 2));
         std::vector<uint8_t *> blocks;
@@ -483,7 +516,7 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
         std::vector<FileRead> files;
         const int rc = read_files(paths, npaths, nthr, blocks.data(), (int) blocks.size(), RING_BLOCK,
                                   [&](const uint8_t *p, int64_t n, int file) { return c.add(p, n, file); }, &c.x.st.bases, t_read, &files,
-                                  errbuf, errlen, infl.data(), dumps);
+                                  errbuf, errlen, infl.data(), dumps, in.taken.data());
         publish_bam(paths, files, nthr);                       // (after an error too: the files read to their end before it)
         return rc;
       }, errbuf, errlen, dumps ? paths : nullptr);
@@ -494,7 +527,7 @@ static int count_files(const char *const *paths, int npaths, const smg_count_opt
 static int count_bases(const uint8_t *seq, int64_t n, const smg_count_opts *opts, const Out &io, char *errbuf, size_t errlen)
 { if (opts && opts->dump) return fail(errbuf, errlen, SMG_EINVAL, "the dump option reads files: a buffer of sequence bytes is no k-mer dump%s", "");
   return count_run(opts, io, n >= 0 && (n == 0 || seq), 1,
-    [&](int64_t *bound) { *bound = n; return 0; },
+    [&](int64_t *bound, bool *) { *bound = n; return 0; },
     [&](Counter &c, double *t_read)
       { const int64_t piece = (int64_t) 256 << 20;
         for (int64_t o = 0; o < n; o += piece) RCHK(c.add(seq + o, n - o < piece ? n - o : piece, 0));
@@ -511,7 +544,7 @@ static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_
   RCHK(in.open(path, device, errbuf, errlen));
   GrowSink sink;
   sink.reserve((size_t) in.text_bytes + 1);
-  RCHK(bgzf_feed(in.file->fd, path, *in.infl, [&](const uint8_t *t, size_t m)
+  RCHK(bgzf_feed(in.src, path, *in.infl, [&](const uint8_t *t, size_t m)
     { if ((int64_t) (sink.len + m) > in.text_bytes) return fail(errbuf, errlen, SMG_EFORMAT, "%s changed while it was read", path);
       sink.put(t, m);
       return 0;
@@ -523,9 +556,11 @@ static int bgzf_inflate(const char *path, int32_t device, uint8_t **text, int64_
 // what a one-file gzip route is given: a gzip file (BGZF is one), opened
 static int gzip_open(const char *path, std::unique_ptr<Fd> &file, char *errbuf, size_t errlen)
 { if (!path) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  RCHK(refuse_stream(path, errbuf, errlen));
   file.reset(new Fd(path));
   if (file->fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
-  const int kind = file_kind(file->fd, path, errbuf, errlen, true);
+  Source src(file->fd, false);
+  const int kind = file_kind(src, path, errbuf, errlen, true);
   if (kind < 0) return kind;
   if (kind == FILE_PLAIN) return fail(errbuf, errlen, SMG_EINVAL, "%s is not gzip: it does not begin with a gzip header", path);
   return 0;
@@ -597,9 +632,9 @@ static int dump_args(const char *path, int32_t kmer, const void *keys, const voi
 // the records of a plain dump by the host twin (DumpHost, smg_dump.hpp): cutter and line decoder, no device
 static int dump_parse(const char *path, int32_t kmer, uint64_t **keys, uint32_t **counts, int64_t *n, int *key_words, char *errbuf, size_t errlen)
 { RCHK(dump_args(path, kmer, keys, counts, n, key_words, errbuf, errlen));
-  const Fd f(path);
-  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
-  const int kind = file_kind(f.fd, path, errbuf, errlen);
+  Taken f(path);
+  if (f.file.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  const int kind = file_kind(f.src, path, errbuf, errlen);
   if (kind < 0) return kind;
   if (kind != FILE_PLAIN)
     return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, use one of the counting calls "
@@ -609,7 +644,7 @@ static int dump_parse(const char *path, int32_t kmer, uint64_t **keys, uint32_t 
   std::vector<uint8_t> buf((size_t) 4 << 20);
   int rc = 0;
   for (;;)
-    { const ssize_t got = read(f.fd, buf.data(), buf.size());
+    { const ssize_t got = f.src.get(buf.data(), buf.size());
       if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
       if (got == 0) { rc = cut.finish(); break; }
       if ((rc = cut.feed(buf.data(), (size_t) got, path, errbuf, errlen)) != 0) break;
@@ -632,7 +667,7 @@ static int dump_records(const char *path, int32_t kmer, int32_t device, int32_t 
   RCHK(in.survey(&path, 1, &o, &bound, errbuf, errlen));
   Counter c;                                                   // (its batch and feeder; nothing is sorted or merged)
   const Out none{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false };
-  RCHK(c.init(&o, none, bound, 1, errbuf, errlen, &path));
+  RCHK(c.init(&o, none, bound, 1, errbuf, errlen, &path, in.streams));
   Run &x = c.x;
   std::vector<uint64_t> hk;
   std::vector<uint32_t> hc;
@@ -660,7 +695,7 @@ static int dump_records(const char *path, int32_t kmer, int32_t device, int32_t 
   double t_read = 0;
   RCHK(read_files(&path, 1, 1, blocks.data(), (int) blocks.size(), RING_BLOCK,
                   [&](const uint8_t *p, int64_t m, int file) { return c.dump.add(p, m, file, flush); }, &bases, &t_read, &files, errbuf, errlen,
-                  in.infl.data(), true));
+                  in.infl.data(), true, in.taken.data()));
   RCHK(flush());
   for (const std::unique_ptr<DeviceInflater> &d : in.own)
     if (d) for (const auto &g : d->gz_index) publish_gzip(g.first.c_str(), &g.second, true);
@@ -691,7 +726,7 @@ static int bam_strip(const char *path, int32_t device, uint8_t **seq, int64_t *n
   GrowSink sink;
   BamFramer fr;
   bool any = false;
-  RCHK(bgzf_feed(in.file->fd, path, *in.infl, [&](const uint8_t *t, size_t m)
+  RCHK(bgzf_feed(in.src, path, *in.infl, [&](const uint8_t *t, size_t m)
     { if (!any && m)
         { if (!is_bam_text(t, m)) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BAM: its text does not begin with the magic BAM\\1", path);
           any = true;
@@ -751,6 +786,11 @@ extern "C" int smg_count_plan_fine(const uint64_t *windows, const int32_t *split
 extern "C" int smg_count_memory_plan(int32_t kmer, uint64_t free_bytes, int64_t bound, int32_t partitions, int64_t max_entries, int64_t batch_bases,
                                      int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf, size_t errlen)
 { GUARD(memory_plan(kmer, (size_t) free_bytes, bound, partitions, max_entries, batch_bases, cap, parted, store_cap, errbuf, errlen)) }
+
+extern "C" int smg_count_stream_plan(int32_t kmer, uint64_t free_bytes, int64_t known_bound, int32_t partitions, int64_t max_entries,
+                                     int64_t batch_bases, int64_t store_bases, int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf,
+                                     size_t errlen)
+{ GUARD(stream_plan(kmer, (size_t) free_bytes, known_bound, partitions, max_entries, batch_bases, store_bases, cap, parted, store_cap, errbuf, errlen)) }
 
 extern "C" int smg_count_parse(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { GUARD(parse_path(path, seq, n, errbuf, errlen)) }

@@ -367,12 +367,14 @@ struct BgzfInput
 { int64_t blocks = 0, text_bytes = 0;
   std::unique_ptr<DeviceInflater> infl;
   std::unique_ptr<Fd> file;
+  Source src;                                                  // (a file: the scan refuses a stream)
 
   int open(const char *path, int device, char *errbuf, size_t errlen)
   { RCHK(bgzf_scan(path, &blocks, &text_bytes, errbuf, errlen));
     RCHK(new_inflater(device, infl, errbuf, errlen));
     file.reset(new Fd(path));
     if (file->fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+    src = Source(file->fd, false);
     return 0;
   }
 };

@@ -305,6 +305,7 @@ struct Store
 { Run &x;
   DevBuf<u64> code, val;
   int64_t cap = 0, n = 0;
+  bool open_ended = false;
   explicit Store(Run &r) : x(r) {}
   void drop() { code.reset(); val.reset(); }
 
@@ -316,9 +317,20 @@ struct Store
 
   // room for `more` positions behind n (the size bound of the input does not count the separators and re-prefixed
   // tails that batches and interleaved files add, so the store may have to grow)
+  // open_ended (a run that reads a stream, whose store began at a size nobody could derive from the input): a growth that
+  // does not fit is refused here with its figures, the old store and the new one being there together while it is copied
   int need(int64_t more)
   { if (n + more <= cap) return 0;
     const int64_t nc = grown_cap(cap, n + more, KC_TILE);
+    if (open_ended)
+      { size_t free_b = 0;
+        RCHK(x.free_bytes(&free_b));
+        const size_t want = (size_t) nc / 8 * 3 + CP_RESERVE;
+        if (want > free_b)
+          return fail(x.errbuf, x.errlen, SMG_ENOMEM, "the packed input does not fit the device: %lld positions are packed, a store of %lld "
+                      "positions next to them needs %.3f GB, %.3f GB of device memory are free", (long long) n, (long long) nc,
+                      (double) want * 1e-9, (double) free_b * 1e-9);
+      }
     RCHK(x.regrow(code, (size_t) n / 4, (size_t) nc / 4, val, (size_t) n / 8, (size_t) nc / 8));
     cap = nc; x.pt.store_bytes = nc / 8 * 3;
     return 0;

@@ -79,6 +79,42 @@ static inline int memory_plan(int k, size_t free_b, int64_t bound, int32_t parti
   return 0;
 }
 
+// The plan of a call that reads a stream, whose length nobody knows: there is no bound.  known_bound bounds the regular
+// files of the call only.  partitions == 1 is one pass with the batch of memory_plan, never clamped to the input; what
+// memory_plan guarantees in advance is left to the check that every merge makes (it refuses, with its figures, a distinct
+// list that does not fit).  Any other value, 0 included, packs the batches into a store and counts by key range, which is
+// defined to give what one pass gives.  The store begins with store_bases positions (the test hook SMG_COUNT_STREAM_STORE)
+// or, where that is 0, CP_STREAM_STORE of them -- 2^30, 384 MiB, 0.14 % of an MI355X -- or what memory_plan
+// gives a store for known_bound where that is more; in whole tiles, as memory_plan rounds.  From there it grows by half
+// (grown_cap) as the stream goes on.  max_entries is checked and otherwise left to the merges and the plan of the ranges.
+#define CP_STREAM_STORE ((int64_t) 1 << 30)
+#define CP_NO_BOUND     (INT64_MAX - 2 * SMG_MAX_KMER)         // a bound that clamps no batch
+static inline int64_t store_tiles(int64_t positions) { return (positions + CP_TILE - 1) / CP_TILE * CP_TILE; }
+
+static inline int stream_plan(int k, size_t free_b, int64_t known_bound, int32_t partitions, int64_t max_entries, int64_t hook, int64_t store_bases,
+                              int64_t *cap, int32_t *parted, int64_t *store_cap, char *errbuf, size_t errlen)
+{ if (!cap || !parted || !store_cap || k < SMG_COUNT_MIN_KMER || k > SMG_MAX_KMER || known_bound < 0 || partitions < 0 ||
+      partitions > SMG_COUNT_BINS || max_entries < 0 || store_bases < 0 || store_bases > ((int64_t) 1 << 50))
+    return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  *cap = 0; *store_cap = 0;
+  *parted = partitions != 1;
+  if (*parted)
+    { const int64_t known = known_bound + known_bound / 32 + ((int64_t) 1 << 16);
+      *store_cap = store_tiles(store_bases ? store_bases : (known > CP_STREAM_STORE ? known : CP_STREAM_STORE));
+      const size_t need = (size_t) *store_cap / 8 * 3;
+      if (need + CP_RESERVE > free_b)
+        return fail(errbuf, errlen, SMG_ENOMEM, "the packed input does not fit the device: a first store of %lld positions needs %.3f GB, "
+                    "%.3f GB of device memory are free", (long long) *store_cap, (double) need * 1e-9, (double) free_b * 1e-9);
+      free_b -= need;
+    }
+  const int64_t c = batch_cap(free_b, k, CP_NO_BOUND, hook);
+  if (c * batch_price(count_words(k)) > (int64_t) free_b)
+    return fail(errbuf, errlen, SMG_ENOMEM, "a batch of %lld bases needs %.3f GB, %.3f GB of device memory are free",
+                (long long) c, (double) (c * batch_price(count_words(k))) * 1e-9, (double) free_b * 1e-9);
+  *cap = c;
+  return 0;
+}
+
 // ---- key ranges ---------------------------------------------------------------------------------------------------
 
 #define CP_BIN_BASES (SMG_COUNT_BIN_BITS / 2)

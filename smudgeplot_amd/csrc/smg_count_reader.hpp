@@ -15,6 +15,10 @@
 // takes half a byte and its quality one), so a large BAM may be counted by key range where one pass would have done; the
 // result is the same whichever way it is counted.
 //
+// An input may be a stream instead of a regular file (Source, Taken): it is opened once, by the survey, which takes from it the
+// bytes that tell what it is and hands it to its reader thread, and from then on it is read forward only; bgzf_feed carries the
+// member that the end of its chunk cuts to the front of the next.  A regular file is read as it always was.
+//
 // What a reader learns about a file on the way (its route, records, bases, the times spent on it) is a FileRead, a plain
 // value that parse_file hands back and read_files collects per file; nothing of it goes through the Inflater.
 
@@ -30,6 +34,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -52,14 +57,82 @@ struct Sink
   virtual ~Sink() {}
 };
 
-// a file opened for reading, closed when it goes out of scope (fd < 0: it could not be opened)
+// a file opened for reading, closed when it goes out of scope (fd < 0: it could not be opened); the path "-" is standard
+// input, a descriptor of its own (dup), so that closing it leaves descriptor 0 alone
+static inline bool is_stdin(const char *path) { return path[0] == '-' && path[1] == 0; }
 struct Fd
 { const int fd;
-  explicit Fd(const char *path) : fd(open(path, O_RDONLY)) {}
+  explicit Fd(const char *path) : fd(is_stdin(path) ? dup(0) : open(path, O_RDONLY)) {}
   Fd(const Fd &) = delete;
   Fd &operator=(const Fd &) = delete;
   ~Fd() { if (fd >= 0) close(fd); }
 };
+
+// Where the bytes of one input come from.  A regular file is read as it always was: file_kind, bgzf_walk and bgzf_feed
+// pread it, the parser and the dump route read it from its start.  A stream (whatever fstat does not call a regular file:
+// a FIFO, a socket, a character device such as /dev/stdin or /dev/fd/N) is read once and forward only: what was taken
+// from it to tell what it is (take) is handed on first (get), then what read gives.
+struct Source
+{ int fd = -1;
+  bool stream = false, ended = false;                          // ended: read has returned 0
+  std::vector<uint8_t> head;                                   // taken and not yet handed on: head[at ..)
+  size_t at = 0;
+  Source() = default;
+  Source(int f, bool s) : fd(f), stream(s) {}
+
+  // (stream only) at least `want` bytes taken, or all there is: blocks until then.  Their number, or -1 for a read error.
+  ssize_t take(size_t want)
+  { size_t have = head.size() - at;
+    if (have < want && !ended)
+      { head.erase(head.begin(), head.begin() + (long) at); at = 0;
+        head.resize(want);
+        while (have < want)
+          { const ssize_t r = read(fd, head.data() + have, want - have);
+            if (r < 0) { head.resize(have); return -1; }
+            if (r == 0) { ended = true; break; }
+            have += (size_t) r;
+          }
+        head.resize(have);
+      }
+    return (ssize_t) have;
+  }
+  const uint8_t *taken() const { return head.data() + at; }
+
+  // the next bytes, as read(2) returns them: short counts are the rule on a stream, 0 is the end
+  ssize_t get(uint8_t *p, size_t n)
+  { if (at < head.size())
+      { const size_t m = n < head.size() - at ? n : head.size() - at;
+        memcpy(p, head.data() + at, m);
+        at += m;
+        return (ssize_t) m;
+      }
+    const ssize_t r = read(fd, p, n);
+    if (r == 0) ended = true;
+    return r;
+  }
+};
+
+// Fd's companion: an input opened once, with the Source over it.  Opening a FIFO a second time, or opening and closing
+// it, ends its writer, so the survey of a call hands every stream it opened to the reader thread that gets the file.
+struct Taken
+{ Fd file;
+  Source src;
+  explicit Taken(const char *path) : file(path)
+  { struct stat sb;
+    src.fd = file.fd;
+    // (standard input is a stream whatever it is: redirected from a file it shares its offset with descriptor 0, which a
+    //  seek of the survey would move for the reader too; read forward from where it stands, a file is a stream like any)
+    src.stream = file.fd >= 0 && (is_stdin(path) || (fstat(file.fd, &sb) == 0 && !S_ISREG(sb.st_mode)));
+  }
+};
+
+// for the calls that read a file twice or seek in it: is `path` a stream?  By stat, which opens nothing.
+static inline bool names_stream(const char *path)
+{ struct stat sb;
+  return is_stdin(path) || (stat(path, &sb) == 0 && !S_ISREG(sb.st_mode));
+}
+static inline int refuse_stream(const char *path, char *errbuf, size_t errlen)
+{ return names_stream(path) ? fail(errbuf, errlen, SMG_EINVAL, "%s is a stream: this call reads a file", path) : 0; }
 
 // Line-wise state machine over the bytes of one file, fed in arbitrary pieces.  A '\r' is dropped only in front of a
 // '\n' or at the end of the file; anywhere else it is a byte like any other (and ends a stretch).
@@ -200,13 +273,17 @@ static inline int bgzf_bad(char *errbuf, size_t errlen, const char *path, int64_
 { return fail(errbuf, errlen, SMG_EFORMAT, "%s: BGZF block at offset %lld: %s", path, (long long) off, why); }
 
 // what every member is checked for before anything is inflated; p[0 .. avail) are the bytes of the file from `off` on
+// (of a stream fsize is where it ended, or BGZF_NO_END while it has not: only its end cuts a header or a member off)
+#define BGZF_NO_END ((int64_t) 1 << 62)
 static inline int bgzf_member(const uint8_t *p, size_t avail, const char *path, int64_t off, int64_t fsize, int64_t *blen, int *hlen,
-                              char *errbuf, size_t errlen)
+                              char *errbuf, size_t errlen, bool stream = false)
 { const int rc = bgzf_header(p, avail, blen, hlen);
   if (rc == 1) return bgzf_bad(errbuf, errlen, path, off, "not a BGZF member (gzip with the BC subfield)");
-  if (rc == 2) return (int64_t) avail < fsize - off ? 2 : bgzf_bad(errbuf, errlen, path, off, "the header is cut off by the end of the file");
+  if (rc == 2) return (int64_t) avail < fsize - off ? 2 : bgzf_bad(errbuf, errlen, path, off, stream ? "the header is cut off by the end of the stream"
+                                                                                                         : "the header is cut off by the end of the file");
   if (*blen < *hlen + 8) return bgzf_bad(errbuf, errlen, path, off, "BSIZE is smaller than the header and the trailer");
-  if (off + *blen > fsize) return bgzf_bad(errbuf, errlen, path, off, "BSIZE reaches past the end of the file");
+  if (off + *blen > fsize) return bgzf_bad(errbuf, errlen, path, off, stream ? "the member is cut off by the end of the stream"
+                                                                             : "BSIZE reaches past the end of the file");
   return 0;
 }
 
@@ -214,19 +291,29 @@ static inline int bgzf_member(const uint8_t *p, size_t avail, const char *path, 
 // first member; a header cut by the end of the file counts, the walk says where), or SMG_EINVAL with message: the file
 // cannot be read, or it is gzip and not BGZF -- FILE_GZIP instead where the caller reads that (gzip_ok: the call opted in).
 // The one place that decides this, for the survey, the scan and the readers.
+//
+// A stream is told by the bytes taken from it, which stay with its Source: the 18 of a BGZF header with the BC subfield
+// in front, or all there is of a shorter one; more only where bgzf_header asks for more.  Plain gzip on a stream is refused
+// either way: the index of its restart points (smg_gzip.hpp) reads the file twice.
 enum { FILE_PLAIN = 0, FILE_BGZF = 1, FILE_GZIP = 2 };
-static inline int file_kind(int fd, const char *path, char *errbuf, size_t errlen, bool gzip_ok = false)
-{ std::vector<uint8_t> h(32);
+static inline int file_kind(Source &src, const char *path, char *errbuf, size_t errlen, bool gzip_ok = false)
+{ std::vector<uint8_t> h(src.stream ? 0 : 32);
+  size_t want = src.stream ? 18 : 32;
   for (;;)
-    { const ssize_t got = pread(fd, h.data(), h.size(), 0);
+    { const ssize_t got = src.stream ? src.take(want) : pread(src.fd, h.data(), h.size(), 0);
       if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
+      const uint8_t *p = src.stream ? src.taken() : h.data();
       int64_t blen = 0; int hlen = 0;
-      const int rc = got == 0 ? 1 : bgzf_header(h.data(), (size_t) got, &blen, &hlen);
-      if (rc == 2 && (size_t) got == h.size()) { h.resize(12 + 65536); continue; }
+      const int rc = got == 0 ? 1 : bgzf_header(p, (size_t) got, &blen, &hlen);
+      if (rc == 2 && (size_t) got == want && want < 12 + 65536) { want = 12 + 65536; h.resize(src.stream ? 0 : want); continue; }
       if (rc == 0 || (rc == 2 && got >= 4)) return FILE_BGZF;
-      if (got >= 2 && h[0] == 0x1f && h[1] == 0x8b)
-        return gzip_ok ? (int) FILE_GZIP
-                       : fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
+      if (got >= 2 && p[0] == 0x1f && p[1] == 0x8b)
+        { if (!gzip_ok) return fail(errbuf, errlen, SMG_EINVAL, "%s is gzip compressed: compressed input is not supported, decompress it first", path);
+          if (src.stream)
+            return fail(errbuf, errlen, SMG_EINVAL, "%s is a stream of plain gzip: its restart index reads the file twice; give the file itself, "
+                        "or decompress it in the pipe", path);
+          return FILE_GZIP;
+        }
       return FILE_PLAIN;
     }
 }
@@ -273,9 +360,67 @@ static inline int bgzf_walk(int fd, const char *path, int64_t *blocks, int64_t *
 
 // The text of a BGZF file, chunk after chunk: whole members into infl.chunk, as many as fit it, their text to
 // consume(text, n) -> 0 or what ends the run.
+// One turn of that: the whole members among the `got` bytes of infl.chunk, which lie at `off` in a file or stream that ends
+// at fsize, inflated and consumed.  *used = the bytes of those members; what lies behind them goes on in the next turn.
 template <class Consume>
-static inline int bgzf_feed(int fd, const char *path, Inflater &infl, Consume &&consume, char *errbuf, size_t errlen)
-{ struct stat sb;
+static inline int bgzf_turn(const char *path, Inflater &infl, int64_t got, int64_t off, int64_t fsize, bool stream, std::vector<int64_t> &at,
+                            int64_t *used, Consume &&consume, char *errbuf, size_t errlen)
+{ int n = 0;
+  int64_t p = 0;
+  size_t nt = 0;
+  while (p < got && n < BGZF_MAX_BLOCKS)
+    { int64_t blen = 0; int hlen = 0;
+      const int rc = bgzf_member(infl.chunk + p, (size_t) (got - p), path, off + p, fsize, &blen, &hlen, errbuf, errlen, stream);
+      if (rc < 0) return rc;
+      if (rc == 2 || p + blen > got) break;                     // the member goes on in the next chunk
+      const uint8_t *t = infl.chunk + p + blen - 8;
+      const uint32_t crc = (uint32_t) t[0] | (uint32_t) t[1] << 8 | (uint32_t) t[2] << 16 | (uint32_t) t[3] << 24;
+      const uint32_t isize = (uint32_t) t[4] | (uint32_t) t[5] << 8 | (uint32_t) t[6] << 16 | (uint32_t) t[7] << 24;
+      if (isize > BGZF_MAX_ISIZE) return bgzf_bad(errbuf, errlen, path, off + p, "ISIZE is above 65536");
+      if (nt + isize > BGZF_TEXT) break;
+      infl.blk[n] = BgzfBlock{ (uint32_t) (p + hlen), (uint32_t) (blen - hlen - 8), (uint32_t) nt, isize, crc };
+      at[(size_t) n] = off + p;
+      n++; nt += isize; p += blen;
+    }
+  if (n == 0) return bgzf_bad(errbuf, errlen, path, off, stream ? "the member is cut off by the end of the stream"
+                                                                : "the member is cut off by the end of the file");
+  const uint8_t *text = nullptr;
+  int bad = 0;
+  const int rc = infl.inflate(n, &text, &bad, errbuf, errlen);
+  if (rc < 0) return rc;
+  if (rc > 0) return bgzf_bad(errbuf, errlen, path, at[(size_t) bad], infl.reason(rc));
+  *used = p;
+  return consume(text, nt);
+}
+
+// A stream: the chunk is filled by read until it is full or the stream ends (short reads are the rule), and the tail that
+// the last whole member leaves is moved to its front for the next turn.  Offsets count from the first byte of the stream.
+template <class Consume>
+static inline int bgzf_feed_stream(Source &src, const char *path, Inflater &infl, Consume &&consume, char *errbuf, size_t errlen)
+{ std::vector<int64_t> at((size_t) BGZF_MAX_BLOCKS);
+  int64_t off = 0, have = 0;                                   // chunk[0 .. have) are the bytes of the stream from `off` on
+  bool end = false;
+  for (;;)
+    { while (!end && have < (int64_t) SMG_COUNT_BGZF_CHUNK)
+        { const ssize_t r = src.get(infl.chunk + have, (size_t) ((int64_t) SMG_COUNT_BGZF_CHUNK - have));
+          if (r < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
+          if (r == 0) end = true;
+          have += r;
+        }
+      if (have == 0) return 0;
+      int64_t used = 0;
+      const int rc = bgzf_turn(path, infl, have, off, end ? off + have : BGZF_NO_END, true, at, &used, consume, errbuf, errlen);
+      if (rc) return rc;
+      memmove(infl.chunk, infl.chunk + used, (size_t) (have - used));
+      have -= used; off += used;
+    }
+}
+
+template <class Consume>
+static inline int bgzf_feed(Source &src, const char *path, Inflater &infl, Consume &&consume, char *errbuf, size_t errlen)
+{ if (src.stream) return bgzf_feed_stream(src, path, infl, consume, errbuf, errlen);
+  const int fd = src.fd;
+  struct stat sb;
   if (fstat(fd, &sb) != 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", path);
   const int64_t fsize = (int64_t) sb.st_size;
   std::vector<int64_t> at((size_t) BGZF_MAX_BLOCKS);
@@ -289,32 +434,10 @@ static inline int bgzf_feed(int fd, const char *path, Inflater &infl, Consume &&
           if (r == 0) break;
           got += r;
         }
-      int n = 0;
-      int64_t p = 0;
-      size_t nt = 0;
-      while (p < got && n < BGZF_MAX_BLOCKS)
-        { int64_t blen = 0; int hlen = 0;
-          const int rc = bgzf_member(infl.chunk + p, (size_t) (got - p), path, off + p, got < want ? off + got : fsize, &blen, &hlen, errbuf, errlen);
-          if (rc < 0) return rc;
-          if (rc == 2 || p + blen > got) break;                 // the member goes on in the next chunk
-          const uint8_t *t = infl.chunk + p + blen - 8;
-          const uint32_t crc = (uint32_t) t[0] | (uint32_t) t[1] << 8 | (uint32_t) t[2] << 16 | (uint32_t) t[3] << 24;
-          const uint32_t isize = (uint32_t) t[4] | (uint32_t) t[5] << 8 | (uint32_t) t[6] << 16 | (uint32_t) t[7] << 24;
-          if (isize > BGZF_MAX_ISIZE) return bgzf_bad(errbuf, errlen, path, off + p, "ISIZE is above 65536");
-          if (nt + isize > BGZF_TEXT) break;
-          infl.blk[n] = BgzfBlock{ (uint32_t) (p + hlen), (uint32_t) (blen - hlen - 8), (uint32_t) nt, isize, crc };
-          at[(size_t) n] = off + p;
-          n++; nt += isize; p += blen;
-        }
-      if (n == 0) return bgzf_bad(errbuf, errlen, path, off, "the member is cut off by the end of the file");
-      const uint8_t *text = nullptr;
-      int bad = 0;
-      const int rc = infl.inflate(n, &text, &bad, errbuf, errlen);
-      if (rc < 0) return rc;
-      if (rc > 0) return bgzf_bad(errbuf, errlen, path, at[(size_t) bad], infl.reason(rc));
-      const int crc = consume(text, nt);
-      if (crc) return crc;
-      off += p;
+      int64_t used = 0;
+      const int rc = bgzf_turn(path, infl, got, off, got < want ? off + got : fsize, false, at, &used, consume, errbuf, errlen);
+      if (rc) return rc;
+      off += used;
     }
   return 0;
 }
@@ -331,11 +454,11 @@ static inline FileRead bam_read(const BamFramer &bam, const InflaterTimes &dev)
   return r;
 }
 
-static inline int parse_fd(int fd, const char *path, Sink &sink, FileRead *fr, char *errbuf, size_t errlen)
+static inline int parse_fd(Source &src, const char *path, Sink &sink, FileRead *fr, char *errbuf, size_t errlen)
 { std::vector<uint8_t> buf((size_t) 4 << 20);
   Parser ps(sink);
   for (;;)
-    { const ssize_t got = read(fd, buf.data(), buf.size());
+    { const ssize_t got = src.get(buf.data(), buf.size());
       if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
       if (got == 0) break;
       const int rc = ps.feed(buf.data(), (size_t) got, path, errbuf, errlen);
@@ -359,25 +482,25 @@ static inline int bam_piece(BamFramer &fr, const uint8_t *t, size_t n, const cha
 
 // One k-mer dump to the sink in chunks of whole lines (DumpCutter, smg_dump.hpp), its text routed by the header of the file
 // as that of reads is: plain, BGZF, or plain gzip where the inflater holds its index.
-static inline int parse_dump_file(int fd, int kind, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
+static inline int parse_dump_file(Source &src, int kind, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen)
 { DumpCutter<Sink> cut(sink);
   const InflaterTimes before = infl ? infl->times() : InflaterTimes();
   int rc = 0;
   if (kind == FILE_PLAIN)
     { std::vector<uint8_t> buf((size_t) 4 << 20);
       for (;;)
-        { const ssize_t got = read(fd, buf.data(), buf.size());
+        { const ssize_t got = src.get(buf.data(), buf.size());
           if (got < 0) return fail(errbuf, errlen, SMG_EINVAL, "read error on %s", path);
           if (got == 0) break;
           if ((rc = cut.feed(buf.data(), (size_t) got, path, errbuf, errlen)) != 0) return rc;
         }
     }
   else if (kind == FILE_GZIP)
-    rc = infl->gzip_text(fd, path, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+    rc = infl->gzip_text(src.fd, path, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
   else if (!infl)
     return fail(errbuf, errlen, SMG_EINVAL, "%s is BGZF compressed: this call has no device to inflate it on, "
                 "use one of the counting calls or smg_count_dump_records", path);
-  else rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+  else rc = bgzf_feed(src, path, *infl, [&](const uint8_t *t, size_t n) { return cut.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
   if (rc == 0) rc = cut.finish();
   if (rc) return rc;
   fr->route = ROUTE_DUMP;
@@ -385,18 +508,18 @@ static inline int parse_dump_file(int fd, int kind, const char *path, Sink &sink
   return 0;
 }
 
-// one file to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
+// one file or stream to the sink, routed by its own header: BGZF through the inflater (and its text by its first bytes: BAM through
 // the framer, anything else through the parser), anything else as it is.  *fr: what it gave, where it was read to its end.
 // dump: the call reads k-mer dumps, whose text goes to the cutter instead
-static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen, bool dump = false)
-{ const int kind = file_kind(fd, path, errbuf, errlen, infl && infl->has_gzip(path));
+static inline int parse_file(Source &src, const char *path, Sink &sink, Inflater *infl, FileRead *fr, char *errbuf, size_t errlen, bool dump = false)
+{ const int kind = file_kind(src, path, errbuf, errlen, infl && infl->has_gzip(path));
   if (kind < 0) return kind;
-  if (dump) return parse_dump_file(fd, kind, path, sink, infl, fr, errbuf, errlen);
-  if (kind == FILE_PLAIN) return parse_fd(fd, path, sink, fr, errbuf, errlen);
+  if (dump) return parse_dump_file(src, kind, path, sink, infl, fr, errbuf, errlen);
+  if (kind == FILE_PLAIN) return parse_fd(src, path, sink, fr, errbuf, errlen);
   if (kind == FILE_GZIP)
     { Parser ps(sink);
       const InflaterTimes before = infl->times();
-      const int rc = infl->gzip_text(fd, path, [&](const uint8_t *t, size_t n) { return ps.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
+      const int rc = infl->gzip_text(src.fd, path, [&](const uint8_t *t, size_t n) { return ps.feed(t, n, path, errbuf, errlen); }, errbuf, errlen);
       if (rc) return rc;
       *fr = text_read(ps, infl->times() - before);
       return 0;
@@ -408,7 +531,7 @@ static inline int parse_file(int fd, const char *path, Sink &sink, Inflater *inf
   BamFramer bam;
   const InflaterTimes before = infl->times();
   int route = ROUTE_NONE;                                      // by the first text there is
-  int rc = bgzf_feed(fd, path, *infl, [&](const uint8_t *t, size_t n)
+  int rc = bgzf_feed(src, path, *infl, [&](const uint8_t *t, size_t n)
     { if (route == ROUTE_NONE && n) route = is_bam_text(t, n) ? ROUTE_BAM : ROUTE_TEXT;
       return route == ROUTE_BAM ? bam_piece(bam, t, n, path, *infl, sink, errbuf, errlen) : ps.feed(t, n, path, errbuf, errlen);
     }, errbuf, errlen);
@@ -447,14 +570,14 @@ struct GrowSink : Sink
   ~GrowSink() override { free(p); }
 };
 
-// the stripped stream of one file as a malloc'ed array
+// the stripped stream of one file or stream as a malloc'ed array
 static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *errbuf, size_t errlen)
 { if (!path || !seq || !n) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
-  const Fd f(path);
-  if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
+  Taken f(path);
+  if (f.file.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
   GrowSink sink;
   FileRead read;
-  const int rc = parse_file(f.fd, path, sink, nullptr, &read, errbuf, errlen);
+  const int rc = parse_file(f.src, path, sink, nullptr, &read, errbuf, errlen);
   return rc ? rc : sink.hand_over(seq, n, errbuf, errlen);
 }
 
@@ -462,16 +585,34 @@ static inline int parse_path(const char *path, uint8_t **seq, int64_t *n, char *
 // sizes (of a BGZF file: the text its members announce), and k + 1 bytes per file for the separator and the tail a batch
 // boundary puts in front of a piece.  bgzf (may be null): per file, is it BGZF (1)?  gzip_ok: the call reads plain gzip; such
 // a file is FILE_GZIP in bgzf and adds only its k + 1 bytes: its text is known once its index is built.
+// taken (a call that reads streams): per path, the stream as the survey opened it, once, with the bytes it took to tell what
+// it is, for the reader thread that gets the file; null for a regular file, which its reader opens itself.  A stream has no
+// size: it adds its k + 1 bytes, and the bound is that of the regular files of the call.  Standard input ("-") can be named
+// once.  Without `taken` a stream is refused.
 static inline int survey_files(const char *const *paths, int npaths, int k, int64_t *bound, char *errbuf, size_t errlen,
-                               std::vector<char> *bgzf = nullptr, bool gzip_ok = false)
+                               std::vector<char> *bgzf = nullptr, bool gzip_ok = false, std::vector<std::unique_ptr<Taken>> *taken = nullptr)
 { *bound = 0;
   if (bgzf) bgzf->assign((size_t) npaths, 0);
+  if (taken) { taken->clear(); taken->resize((size_t) npaths); }
+  for (int f = 0, seen = 0; f < npaths; f++)
+    if (is_stdin(paths[f]) && seen++)
+      return fail(errbuf, errlen, SMG_EINVAL, "%s (standard input) is named twice: it can be read once", paths[f]);
   for (int f = 0; f < npaths; f++)
-    { const Fd fd(paths[f]);
+    { std::unique_ptr<Taken> in(new Taken(paths[f]));
+      const Fd &fd = in->file;
       if (fd.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", paths[f]);
+      if (in->src.stream)
+        { if (!taken) return fail(errbuf, errlen, SMG_EINVAL, "%s is a stream: this call reads a file", paths[f]);
+          const int kind = file_kind(in->src, paths[f], errbuf, errlen, gzip_ok);
+          if (kind < 0) return kind;
+          if (bgzf) (*bgzf)[(size_t) f] = (char) kind;
+          (*taken)[(size_t) f] = std::move(in);
+          *bound += k + 1;
+          continue;
+        }
       int64_t size = (int64_t) lseek(fd.fd, 0, SEEK_END), blocks = 0;
       if (size < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot read %s", paths[f]);
-      int rc = file_kind(fd.fd, paths[f], errbuf, errlen, gzip_ok);
+      int rc = file_kind(in->src, paths[f], errbuf, errlen, gzip_ok);
       if (rc == FILE_BGZF)
         { rc = bgzf_walk(fd.fd, paths[f], &blocks, &size, errbuf, errlen);
           if (bgzf) (*bgzf)[(size_t) f] = FILE_BGZF;
@@ -489,9 +630,12 @@ static inline int survey_files(const char *const *paths, int npaths, int k, int6
 // members and text bytes of a BGZF file; what is not BGZF is refused with the words of the counting calls
 static inline int bgzf_scan(const char *path, int64_t *blocks, int64_t *text_bytes, char *errbuf, size_t errlen)
 { if (!path || !blocks || !text_bytes) return fail(errbuf, errlen, SMG_EINVAL, "bad arguments%s", "");
+  const int is = refuse_stream(path, errbuf, errlen);
+  if (is) return is;
   const Fd f(path);
   if (f.fd < 0) return fail(errbuf, errlen, SMG_EINVAL, "cannot open %s", path);
-  const int kind = file_kind(f.fd, path, errbuf, errlen);
+  Source src(f.fd, false);
+  const int kind = file_kind(src, path, errbuf, errlen);
   if (kind < 0) return kind;
   if (kind == FILE_PLAIN) return fail(errbuf, errlen, SMG_EINVAL, "%s is not BGZF: it does not begin with a gzip header", path);
   return bgzf_walk(f.fd, path, blocks, text_bytes, errbuf, errlen);
@@ -552,16 +696,20 @@ struct RingSink : Sink
   }
 };
 
-static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step, Inflater *infl, bool dump)
+// (taken: null, or per path what the survey opened; a path without one is opened here, a stream among them too)
+static inline void reader_main(Ring *r, const char *const *paths, int npaths, int first, int step, Inflater *infl, bool dump,
+                               const std::unique_ptr<Taken> *taken)
 { for (int f = first; f < npaths; f += step)
     { char eb[512]; eb[0] = 0;
       int rc = 0;
       FileRead read;
       try
         { RingSink sink(*r, f);
-          const Fd fd(paths[f]);
-          rc = fd.fd < 0 ? fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f])
-                         : parse_file(fd.fd, paths[f], sink, infl, &read, eb, sizeof(eb), dump);
+          std::unique_ptr<Taken> mine;
+          if (!taken || !taken[f]) mine.reset(new Taken(paths[f]));
+          Taken &in = mine ? *mine : *taken[f];
+          rc = in.file.fd < 0 ? fail(eb, sizeof(eb), SMG_EINVAL, "cannot open %s", paths[f])
+                              : parse_file(in.src, paths[f], sink, infl, &read, eb, sizeof(eb), dump);
           if (rc == 0) sink.done();
         }
       catch (...) { rc = fail(eb, sizeof(eb), SMG_ENOMEM, "out of host memory while reading %s", paths[f]); }
@@ -592,10 +740,11 @@ static inline int reader_threads(int want, int npaths)
 // *files = per file what reading it gave (route ROUTE_NONE: it was not read to its end), after an error as well.
 // infl (may be null: BGZF files are refused): the inflater of thread j, or null where none of its files is BGZF.
 // dump: the files are k-mer dumps; every block then holds whole lines of one file.
+// taken (may be null): per path, the stream the survey opened and took bytes from (survey_files), or null.
 template <class Consume>
 static inline int read_files(const char *const *paths, int npaths, int nthr, uint8_t *const *blocks, int nblocks, size_t block, Consume &&consume,
                              int64_t *bases, double *t_last, std::vector<FileRead> *files, char *errbuf, size_t errlen,
-                             Inflater *const *infl = nullptr, bool dump = false)
+                             Inflater *const *infl = nullptr, bool dump = false, const std::unique_ptr<Taken> *taken = nullptr)
 { Ring ring;
   ring.block = block;
   ring.files.assign((size_t) npaths, FileRead());
@@ -606,7 +755,7 @@ static inline int read_files(const char *const *paths, int npaths, int nthr, uin
   for (int j = 0; j < nthr && rc == 0; j++)
     { try
         { { std::unique_lock<std::mutex> lk(ring.m); ring.live++; }
-          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr, infl ? infl[j] : nullptr, dump);
+          thr.emplace_back(reader_main, &ring, paths, npaths, j, nthr, infl ? infl[j] : nullptr, dump, taken);
         }
       catch (...)
         { std::unique_lock<std::mutex> lk(ring.m);
